@@ -2,7 +2,7 @@
 """Headline benchmark: patch-pairs/sec of one ViT-ED training step (forward + backward [+ RCCL gradient all-reduce] +
 clip + AdamW) on synthetic patch pairs, bf16 MFMA path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload A-train|H-train|H-infer]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload A-train|H-train|H-infer] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -30,6 +30,12 @@ One JSON line on rank 0 (contract in the task statement).  Extra objects:
   other_workloads   (A-train, one GPU) short H-train and H-infer legs run after the headline timing: BASELINE configs 3 and 5.
   cpu_baseline  the fp32 CPU oracle (oracle/vited_oracle.py, a port - the reference itself cannot travel) on a bounded
                 sample: config A, batch 32, fwd+bwd, median of 5 steps, with the host's CPU model and thread count.
+
+``--dump-outputs DIR`` writes, after the timed steps, what the headline leg's timed path returned to its caller in the last step
+as DIR/<name>.npy (float32; float64 scalars): A-train / H-train ``loss``, ``grad_norm`` and every parameter after the update
+(``param.<name>``), H-infer the similarity matrix ``sim``.  The inputs and initial weights come from fixed seeds, so two builds
+run with the same arguments can be compared file by file.  Above DUMP_BUDGET bytes the largest arrays are cut to a fixed, seeded
+sample of their flattened elements (see ``dump_outputs``).
 """
 import argparse
 import contextlib
@@ -56,6 +62,7 @@ def _latest_pmc_csv():
 
 
 PMC_TRAFFIC_CSV = _latest_pmc_csv()       # the newest committed rocprofv3 PMC summary (profiles/collect.sh + summarize.py)
+DUMP_BUDGET = 60 * 2**20                  # --dump-outputs array bytes; with the .npy headers the directory stays under 64 MB
 
 
 def parse():
@@ -74,7 +81,32 @@ def parse():
     ap.add_argument('--no-roofline', action='store_true')
     ap.add_argument('--no-other-workloads', action='store_true', help='skip the short H-train / H-infer legs after the A-train headline')
     ap.add_argument('--compress-bf16', action='store_true', help='bf16 gradients on the wire')
-    return ap.parse_args()
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write what the headline leg's last timed step returned as DIR/<name>.npy (see the module docstring)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    return args
+
+
+def dump_outputs(dirpath, arrays, budget=DUMP_BUDGET):
+    """Write ``arrays`` (name -> tensor) as DIR/<name>.npy in float32 (float64 stays float64).  When they hold more than
+    ``budget`` bytes, the arrays are visited smallest first and each keeps at most an equal share of what is left; an array cut
+    down is stored as the elements of its flattened form at a fixed sample of positions (``randperm`` seeded with 0, sorted),
+    so the same sizes give the same positions in every run."""
+    import numpy as np
+    import torch
+    os.makedirs(dirpath, exist_ok=True)
+    items = sorted(((name, t.detach().to('cpu', torch.float64 if t.dtype == torch.float64 else torch.float32))
+                    for name, t in arrays.items()), key=lambda it: it[1].numel())
+    left = budget
+    for i, (name, t) in enumerate(items):
+        keep = min(t.numel(), left // ((len(items) - i) * t.element_size()))
+        if keep < t.numel():
+            pos = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            t = t.reshape(-1)[pos]
+        np.save(os.path.join(dirpath, f'{name}.npy'), t.numpy())
+        left -= t.numel() * t.element_size()
 
 
 # ---------------------------------------------------------------------------------------------
@@ -444,7 +476,7 @@ def _line(ctx, *, metric, what, units, unit_flops, executed_flops, elapsed, step
     return out
 
 
-def run_train(ctx, workload, *, steps, warmup, batch=None, cfg_path=None, want_roofline=True):
+def run_train(ctx, workload, *, steps, warmup, batch=None, cfg_path=None, want_roofline=True, dump_dir=None):
     """A-train / H-train: W untimed warm-up steps, then exactly K timed steps between two fences."""
     torch, V, engine, args, world, rank, dev = ctx.torch, ctx.V, ctx.engine, ctx.args, ctx.world, ctx.rank, ctx.dev
     cfg_path = cfg_path or (CFG_A if workload == 'A-train' else CFG_H)
@@ -517,6 +549,9 @@ def run_train(ctx, workload, *, steps, warmup, batch=None, cfg_path=None, want_r
     # training on one fixed batch must reduce its loss; anything else means the step is not doing its work
     if not (math.isfinite(loss_val) and math.isfinite(norm_val) and loss_val < loss_first):
         raise SystemExit(f'bench.py: the timed steps did not train (loss {loss_first:.5f} -> {loss_val:.5f}, grad norm {norm_val})')
+    if dump_dir is not None and rank == 0:
+        dump_outputs(dump_dir, {'loss': torch.tensor(loss_val, dtype=torch.float64), 'grad_norm': torch.tensor(norm_val, dtype=torch.float64),
+                                **{f'param.{n}': p for n, p in model.named_parameters()}})
     extra.update({'loss_first': round(loss_first, 5), 'loss': round(loss_val, 5), 'grad_norm': round(norm_val, 5),
                   'optimizer': 'torch.optim.AdamW(fused)' if args.torch_optim else 'vited_adamw_step (HIP, fused clip)'})
     metric = f'patch-pairs/sec fwd+bwd, {name} ViT-ED'
@@ -566,7 +601,7 @@ def run_train_hostfed(ctx, *, steps, warmup, batch=None):
                         f'side stream, depth 2) -> vited_patchify_u8; full train step, H2D inside the timed region'}
 
 
-def run_infer(ctx, *, steps, warmup, batch=None, cfg_path=None, want_roofline=True):
+def run_infer(ctx, *, steps, warmup, batch=None, cfg_path=None, want_roofline=True, dump_dir=None):
     """H-infer: pairwise similarity-matrix inference (hisfrag.py:161-302): every rank encodes its row block and streams all later
     images; one "step" = one whole similarity matrix."""
     torch, V, engine, args, world, rank, dev = ctx.torch, ctx.V, ctx.engine, ctx.args, ctx.world, ctx.rank, ctx.dev
@@ -591,7 +626,6 @@ def run_infer(ctx, *, steps, warmup, batch=None, cfg_path=None, want_roofline=Tr
         roof = roofline_of(V, run, passes=1)      # the whole matrix once, every launch bracketed: executed FLOPs are counted, not modelled
     for _ in range(max(warmup, 1)):
         run()
-    steps = max(1, min(steps, 5))
     ctx.fence()
     t0 = time.perf_counter()
     for _ in range(steps):
@@ -600,6 +634,8 @@ def run_infer(ctx, *, steps, warmup, batch=None, cfg_path=None, want_roofline=Tr
     elapsed = time.perf_counter() - t0
     if not bool(torch.isfinite(sim.float()).all()) or not torch.equal(sim, sim.t()):
         raise SystemExit('bench.py: the similarity matrix is not finite / symmetric')
+    if dump_dir is not None and rank == 0:
+        dump_outputs(dump_dir, {'sim': sim})
     units = total_pairs / world                   # _line multiplies by world again
     # reference-equivalent work: hisfrag.py:226-229 runs the whole decoder (and image 2's patch embedding) for every pair
     unit_flops = (dec_flops * total_pairs + enc_flops * n_img) / total_pairs
@@ -632,9 +668,11 @@ def main():
     torch = ctx.torch
     want_roof = not args.no_roofline
     if args.workload in ('A-train', 'H-train'):
-        out = run_train(ctx, args.workload, steps=args.steps, warmup=args.warmup, batch=args.batch, cfg_path=args.cfg, want_roofline=want_roof)
+        out = run_train(ctx, args.workload, steps=args.steps, warmup=args.warmup, batch=args.batch, cfg_path=args.cfg, want_roofline=want_roof,
+                        dump_dir=args.dump_outputs)
     else:
-        out = run_infer(ctx, steps=args.steps, warmup=args.warmup, batch=args.batch, cfg_path=args.cfg, want_roofline=want_roof)
+        out = run_infer(ctx, steps=args.steps, warmup=args.warmup, batch=args.batch, cfg_path=args.cfg, want_roofline=want_roof,
+                        dump_dir=args.dump_outputs)
     if args.workload == 'A-train' and world == 1 and not args.no_other_workloads and args.cfg is None:
         # BASELINE configs 3 and 5 on this GPU, AFTER the headline's timed region: short legs, reported beside the headline
         import gc

@@ -25,7 +25,14 @@ def _named_grads(model, flat):
     return {name_of[id(p)]: v.clone() for p, v in zip(flat.params, flat.views)}
 
 
+def _cpu_only_rank():
+    """The workers test the CPU / gloo plumbing.  On a machine with GPUs, configure_ddp would bind rank r to device r and pick
+    nccl, so the spawned ranks see no GPU, as on a CPU-only machine."""
+    torch.cuda.is_available = lambda: False
+
+
 def _worker(rank, world, port, compress, out, overlap=True, accum=1):
+    _cpu_only_rank()
     import sys
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     import vited_amd
@@ -265,6 +272,7 @@ def test_row_sharding_balances_pairs():
 
 
 def _sim_worker(rank, world, port, out):
+    _cpu_only_rank()
     import sys
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     import vited_amd
