@@ -38,6 +38,7 @@ extern "C" {
 
 #define VITED_F32 0
 #define VITED_BF16 1
+#define VITED_F16 2 /* vited_retrieval_metrics only */
 
 /* GEMM epilogues (vited_gemm) */
 #define VITED_EPI_STORE 0          /* out = T(acc + bias)                                          */
@@ -324,6 +325,26 @@ int vited_attention_bwd(const void* q, int64_t q_bs, int64_t q_ts, const void* k
                         int64_t dq_ts, void* dk, int64_t dk_bs, int64_t dk_ts, void* dv, int64_t dv_bs,
                         int64_t dv_ts, int dtype, int64_t batch, int heads, int64_t nq, int64_t nk,
                         int head_dim, float scale, void* stream);
+
+/* ---- evaluation: retrieval metrics of a distance matrix (misc/wi19_evaluate.get_metrics) ------ */
+
+/* Row records and their sums for the rows [r0, r1) of an n x n matrix D (dtype VITED_F32, VITED_BF16 or VITED_F16; row stride
+ * ld elements).  Row i ranks its n columns ascending by (D[i, j], j): ties to the lower column, NaN after +inf - what
+ * np.argsort(kind='stable') does.  With remove_self_column = 1 the first element of that order is dropped, whatever column it
+ * is (sorted_indexes[:, 1:]).  A retrieval is correct when labels[j] == labels[i].  With from_similarity = 1, D holds
+ * similarities and the row is ranked by dtype(1 - D) (fp32 subtract, one rounding): what `1 - similarity_matrix` is in the
+ * reference (hisfrag.py:296), without the n x n temporary.
+ *   labels   int32 [n], class ids in [0, num_classes)
+ *   offsets  int32 [num_classes + 1], members int32 [n]: the columns of class c are members[offsets[c], offsets[c + 1])
+ *   rows_out float64 [(r1 - r0) x 5]: sum over correct retrievals of m / rank_m (m-th correct retrieval at 1-based position
+ *            rank_m), number of correct retrievals, top-1 hit (0/1), correct retrievals in the first 10, in the first 100
+ *   sums     float64 [7]: sum of AP over rows with a correct retrieval, those rows, top-1 hits, sum of Pr@10, sum of Pr@100,
+ *            rows without a correct retrieval, rows (r1 - r0).  Pr@k = hits_k / min(correct, k) is NaN on a row without a
+ *            correct retrieval, as in the reference, and so is its sum.
+ * The sums are formed in a fixed order: identical inputs give bit-identical outputs.  No workspace. */
+int vited_retrieval_metrics(const void* D, int dtype, int64_t ld, int64_t n, int64_t r0, int64_t r1, const int* labels,
+                            const int* offsets, const int* members, int num_classes, int remove_self_column, int from_similarity,
+                            double* rows_out, double* sums, void* stream);
 
 #ifdef __cplusplus
 }

@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('VITED_LIB') or os.path.join(_HERE, 'libvited_hip.so')  # VITED_LIB: kernel-experiment builds
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'vited.h')
 
-F32, BF16 = 0, 1
+F32, BF16, F16 = 0, 1, 2
 EPI_STORE, EPI_GELU, EPI_RESIDUAL, EPI_MUL_GELU_GRAD, EPI_STORE_F32, EPI_MUL, EPI_GELU_GRAD = 0, 1, 2, 3, 4, 5, 6
 B_NK, B_KN = 0, 1
 
@@ -71,6 +71,7 @@ SIGNATURES = {
                                          _i64, _i64, _i, _f, _p]),
     'vited_attention_bwd': (_i, [_p, _i64, _i64, _p, _i64, _i64, _p, _i64, _i64, _p, _p, _i64, _i64, _p, _p,
                                  _p, _i64, _i64, _p, _i64, _i64, _p, _i64, _i64, _i, _i64, _i, _i64, _i64, _i, _f, _p]),
+    'vited_retrieval_metrics': (_i, [_p, _i, _i64, _i64, _i64, _i64, _p, _p, _p, _i, _i, _i, _p, _p, _p]),
 }
 
 _lib = None

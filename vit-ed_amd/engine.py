@@ -829,3 +829,76 @@ def pairwise_similarity(model, images, *, rank: int = 0, world: int = 1, block: 
             off += ii.numel()
         assert off == counts[r], (r, off, counts[r])
     return sim
+
+
+# ---------------------------------------------------------------------------------------------
+# retrieval metrics of the distance matrix (misc/wi19_evaluate.get_metrics, hisfrag.py:309,321)
+# ---------------------------------------------------------------------------------------------
+def class_members(labels: torch.Tensor):
+    """(class ids int32 [n] in [0, C), offsets int32 [C + 1], members int32 [n]): the columns of class c are
+    members[offsets[c]:offsets[c + 1]], in ascending order.  Equal input labels get equal ids, so 'same class' is unchanged."""
+    _, ids = torch.unique(labels, return_inverse=True)
+    members = torch.argsort(ids, stable=True)
+    counts = torch.bincount(ids)
+    offsets = torch.zeros(counts.numel() + 1, dtype=torch.int64, device=labels.device)
+    offsets[1:] = torch.cumsum(counts, 0)
+    return ids.to(torch.int32), offsets.to(torch.int32), members.to(torch.int32)
+
+
+def metrics_from_sums(sums):
+    """(mAP, top-1, Pr@10, Pr@100) from the 7 sums of vited_retrieval_metrics (after any cross-rank SUM).  mAP is NaN when
+    no row has a correct retrieval (numpy's mean of an empty array); Pr@k is NaN as soon as one row has none, as in the
+    reference."""
+    ap, valid, top1, pr10, pr100, _, rows = (float(v) for v in sums.tolist())
+    nan = float('nan')
+    return (ap / valid if valid else nan,) + ((top1 / rows, pr10 / rows, pr100 / rows) if rows else (nan, nan, nan))
+
+
+def retrieval_metrics(distance: torch.Tensor, labels, *, rows=None, remove_self_column: bool = True,
+                      from_similarity: bool = False, group=None):
+    """(mAP, top-1, Pr@10, Pr@100) of ``wi19_evaluate.get_metrics(distance, labels, remove_self_column)`` on the GPU.
+
+    ``distance``: [n, n] float16 / bfloat16 / float32 on the device (with ``from_similarity``: the similarity matrix S, ranked
+    by dtype(1 - S)).  ``labels``: int class ids [n] (a device tensor, or anything torch.as_tensor takes).  ``rows=(r0, r1)``
+    computes this rank's share of the rows (default: all); with ``group`` (a process group, e.g. ``dist.group.WORLD``) ONE
+    all-reduce (SUM, so gloo works too) combines the shares and every rank returns the metrics of all rows.  Without a group
+    the result covers ``rows`` only."""
+    from . import ops                                       # ops.retrieval_metrics_rows refuses CPU tensors: no CPU fallback
+    n = distance.shape[0]
+    labels = torch.as_tensor(labels, device=distance.device)
+    if labels.dim() != 1 or labels.numel() != n:
+        raise ValueError(f'labels must be a vector of length {n}, got shape {tuple(labels.shape)}')
+    if labels.is_floating_point() or labels.is_complex():
+        raise TypeError(f'labels must be integer class ids, got {labels.dtype}')
+    r0, r1 = (0, n) if rows is None else (int(rows[0]), int(rows[1]))
+    if not 0 <= r0 <= r1 <= n:
+        raise ValueError(f'rows ({r0}, {r1}) is not a range inside [0, {n}]')
+    if r1 > r0:
+        ids, offsets, members = class_members(labels)
+        _, sums = ops.retrieval_metrics_rows(distance, ids, offsets, members, (r0, r1), remove_self_column=remove_self_column,
+                                             from_similarity=from_similarity)
+    else:                                                   # an empty share (more ranks than rows) still joins the reduction
+        sums = torch.zeros(7, dtype=torch.float64, device=distance.device)
+    if group is not None:
+        dist.all_reduce(sums, op=dist.ReduceOp.SUM, group=group)
+    return metrics_from_sums(sums)
+
+
+@torch.no_grad()
+def hisfrag_retrieval_metrics(similarity: torch.Tensor, labels, *, rank: int = 0, world: int = 1, group=None,
+                              remove_self_column: bool = True):
+    """The evaluation step after ``pairwise_similarity``: every rank holds the [n, n] fp16 similarity, ranks the rows
+    ``shard_rows_by_pair_count(n, world)`` gives it by fp16(1 - similarity), and one all-reduce gives every rank the metrics of
+    all rows.  Replaces, on every rank (hisfrag.py:294-296,306-309):
+
+        distance_matrix = 1 - similarity_matrix
+        labels = utils.list_to_idx(img_names, lambda x: x.split('_')[0])
+        m_ap, top1, pr_k10, pr_k100 = wi19_evaluate.get_metrics(distance_matrix.numpy(), np.asarray(labels))
+
+    with ``hisfrag_retrieval_metrics(similarity, labels, rank=rank, world=world)`` (same ``labels``)."""
+    n = similarity.shape[0]
+    bounds = shard_rows_by_pair_count(n, world)
+    if world > 1 and group is None:
+        group = dist.group.WORLD
+    return retrieval_metrics(similarity, labels, rows=(bounds[rank], bounds[rank + 1]), remove_self_column=remove_self_column,
+                             from_similarity=True, group=group if world > 1 else None)

@@ -11,7 +11,8 @@ from __future__ import annotations
 import torch
 
 from . import _lib
-from ._lib import (B_KN, B_NK, BF16, EPI_GELU, EPI_GELU_GRAD, EPI_MUL, EPI_MUL_GELU_GRAD, EPI_RESIDUAL, EPI_STORE, EPI_STORE_F32, F32)
+from ._lib import (B_KN, B_NK, BF16, EPI_GELU, EPI_GELU_GRAD, EPI_MUL, EPI_MUL_GELU_GRAD, EPI_RESIDUAL, EPI_STORE, EPI_STORE_F32, F16,
+                   F32)
 
 _DT = {torch.float32: F32, torch.bfloat16: BF16}
 
@@ -622,3 +623,38 @@ def attention_bwd(q, k, v, o, do, lse, heads: int, scale: float, dq, dk, dv):
 def last_paths():
     lib = _lib.load()
     return lib.vited_last_gemm_path(), lib.vited_last_attention_path()
+
+
+# ---------------------------------------------------------------------------------------------
+# evaluation: retrieval metrics of a distance matrix (misc/wi19_evaluate.get_metrics)
+# ---------------------------------------------------------------------------------------------
+_DT_RETRIEVAL = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16}
+
+
+def retrieval_metrics_rows(matrix: torch.Tensor, labels: torch.Tensor, offsets: torch.Tensor, members: torch.Tensor,
+                           rows: tuple[int, int], *, remove_self_column: bool = True, from_similarity: bool = False):
+    """Row records (float64 [r1 - r0, 5]: AP sum, correct retrievals, top-1 hit, hits in the first 10, in the first 100) and
+    their sums (float64 [7], see include/vited.h) for the rows [r0, r1) of the [n, n] matrix.  ``labels`` int32 [n] in
+    [0, C) with the class CSR ``offsets`` int32 [C + 1] / ``members`` int32 [n] built from them (engine.class_members)."""
+    _need_gpu(matrix, labels, offsets, members)
+    if matrix.dtype not in _DT_RETRIEVAL:
+        raise TypeError(f'retrieval metrics take float32, bfloat16 or float16 matrices, got {matrix.dtype}')
+    if matrix.dim() != 2 or matrix.shape[0] != matrix.shape[1]:
+        raise ValueError(f'expected a square [n, n] matrix, got shape {tuple(matrix.shape)}')
+    ld = _rows2d(matrix)
+    n = matrix.shape[0]
+    for name, t, size in (('labels', labels, n), ('members', members, n), ('offsets', offsets, None)):
+        if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() or (size is not None and t.numel() != size):
+            raise ValueError(f'{name} must be a contiguous int32 vector{f" of length {size}" if size else ""}, '
+                             f'got {t.dtype} of shape {tuple(t.shape)}')
+        if t.device != matrix.device:
+            raise ValueError(f'{name} is on {t.device}, the matrix on {matrix.device}')
+    r0, r1 = int(rows[0]), int(rows[1])
+    if not 0 <= r0 < r1 <= n:
+        raise ValueError(f'rows ({r0}, {r1}) is not a non-empty range inside [0, {n})')
+    rows_out = torch.empty((r1 - r0, 5), dtype=torch.float64, device=matrix.device)
+    sums = torch.empty(7, dtype=torch.float64, device=matrix.device)
+    _lib.check(_lib.load().vited_retrieval_metrics(
+        _ptr(matrix), _DT_RETRIEVAL[matrix.dtype], ld, n, r0, r1, _ptr(labels), _ptr(offsets), _ptr(members), offsets.numel() - 1,
+        int(bool(remove_self_column)), int(bool(from_similarity)), _ptr(rows_out), _ptr(sums), _stream()), 'vited_retrieval_metrics')
+    return rows_out, sums
