@@ -38,7 +38,9 @@ extern "C" {
 
 #define VITED_F32 0
 #define VITED_BF16 1
-#define VITED_F16 2 /* vited_retrieval_metrics only */
+#define VITED_F16 2 /* vited_retrieval_metrics, vited_group_retrieval_metrics and vited_pair_scores_add only */
+#define VITED_I32 3 /* integer index dtypes (vited_pair_scores_add) */
+#define VITED_I64 4
 
 /* GEMM epilogues (vited_gemm) */
 #define VITED_EPI_STORE 0          /* out = T(acc + bias)                                          */
@@ -345,6 +347,51 @@ int vited_attention_bwd(const void* q, int64_t q_bs, int64_t q_ts, const void* k
 int vited_retrieval_metrics(const void* D, int dtype, int64_t ld, int64_t n, int64_t r0, int64_t r1, const int* labels,
                             const int* offsets, const int* members, int num_classes, int remove_self_column, int from_similarity,
                             double* rows_out, double* sums, void* stream);
+
+/* ---- evaluation: group mAP / Pr@k of a distance matrix (misc/metric.calc_map_prak) ------------- */
+
+/* Row records and their sums for the rows [r0, r1) of an n x n matrix D (dtype VITED_F32, VITED_BF16 or VITED_F16; row stride
+ * ld elements).  Row i has the label a = labels[i]; column j is CORRECT when labels[j] is a positive label of a.  When a negative
+ * relation is given, only the ELIGIBLE columns - labels[j] positive or negative for a - take part; otherwise every column does.
+ * The eligible columns are ranked ascending by (D[i, j], j) (ties to the lower column, NaN after +inf: a stable argsort), the
+ * first of that order is skipped whatever it is, and AP and hits_k are taken over the correct columns at the positions after it.
+ *   labels      int32 [n], label ids in [0, num_labels)
+ *   col_offsets int32 [num_labels + 1], col_members int32 [n]: the columns of label b are col_members[col_offsets[b], col_offsets[b + 1])
+ *   pos_offsets int32 [num_labels + 1], pos_labels int32: the positive labels of a are pos_labels[pos_offsets[a], pos_offsets[a + 1]),
+ *               ascending, without duplicates
+ *   neg_offsets / neg_labels: the negative relation in the same form, or both null (no filter); may overlap the positives
+ *   ks          HOST int32 [nk], 1 <= nk <= 8, every k >= 1: the Pr@k cut-offs
+ *   rows_out    float64 [(r1 - r0) x (3 + nk)]: AP (0 when the row has no correct retrieval), valid (1 when it has one),
+ *               correct retrievals, then hits_k = correct retrievals in the first k positions, for every k
+ *   sums        float64 [2 + nk]: sum of AP over valid rows, valid rows, then for every k the sum over valid rows of
+ *               hits_k / min(correct, k).  A row without a correct retrieval is left out of every sum, as in the reference.
+ * The sums are formed in a fixed order: identical inputs give bit-identical outputs.  No workspace. */
+int vited_group_retrieval_metrics(const void* D, int dtype, int64_t ld, int64_t n, int64_t r0, int64_t r1, const int* labels,
+                                  int num_labels, const int* col_offsets, const int* col_members, const int* pos_offsets,
+                                  const int* pos_labels, const int* neg_offsets, const int* neg_labels, const int* ks, int nk,
+                                  double* rows_out, double* sums, void* stream);
+
+/* ---- evaluation: pair-score aggregation (michigan.py:188-209, the distance maps of geshaem_test) ---- */
+
+/* A record (i, j, score) adds d = 1 - score (fp32) to cell (i, j) and to cell (j, i) of an n x n grid of fragments (a diagonal
+ * record adds it twice to (i, i)).  vited_pair_scores_add stores m records and counts them per cell; vited_pair_scores_finish
+ * reduces every record stored so far.  The results are bit-identical whatever the batching and order of the records.
+ *   pairs       [m, 2] fragment ids, VITED_I32 or VITED_I64, row stride pair_ld elements (column stride 1)
+ *   scores      [m], VITED_F32, VITED_BF16 or VITED_F16, contiguous
+ *   counts      int32 [n, n], zeroed by the caller before the first batch and accumulated by every add
+ *   rec_cells   int32 [m, 2], rec_values float32 [m]: where add stores this batch's records (i, j, d); ids outside [0, n) are
+ *               stored as (-1, -1), not counted, and set bit 0 of *bad (int32, device)
+ * finish takes every stored record (rec_cells / rec_values [m] now span all batches, in any order) and writes, per cell,
+ *   mean float32 [n, n] (fp64 sum / count, rounded once), min float32 [n, n], stdev float64 [n, n] (sample stdev, count > 1),
+ *   with NaN where a cell has no value (stdev: fewer than two), and
+ *   stats float64 [2]: the mean and the sample stdev of stdev over the cells with count > 1 (NaN with fewer than 1 / 2 of them).
+ * n <= 46340.  workspace >= vited_pair_scores_workspace_bytes(n, m) bytes, 256-byte aligned (-1: bad n or m). */
+int64_t vited_pair_scores_workspace_bytes(int64_t n, int64_t m);
+int vited_pair_scores_add(const void* pairs, int pair_dtype, int64_t pair_ld, const void* scores, int score_dtype, int64_t m, int64_t n,
+                          int* counts, int* rec_cells, float* rec_values, int* bad, void* stream);
+int vited_pair_scores_finish(const int* rec_cells, const float* rec_values, int64_t m, int64_t n, const int* counts, float* mean,
+                             float* minv, double* stdev, double* stats, int* bad, void* workspace, int64_t workspace_bytes,
+                             void* stream);
 
 #ifdef __cplusplus
 }

@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get('VITED_LIB') or os.path.join(_HERE, 'libvited_hip.so')
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'vited.h')
 
 F32, BF16, F16 = 0, 1, 2
+I32, I64 = 3, 4
 EPI_STORE, EPI_GELU, EPI_RESIDUAL, EPI_MUL_GELU_GRAD, EPI_STORE_F32, EPI_MUL, EPI_GELU_GRAD = 0, 1, 2, 3, 4, 5, 6
 B_NK, B_KN = 0, 1
 
@@ -72,6 +73,10 @@ SIGNATURES = {
     'vited_attention_bwd': (_i, [_p, _i64, _i64, _p, _i64, _i64, _p, _i64, _i64, _p, _p, _i64, _i64, _p, _p,
                                  _p, _i64, _i64, _p, _i64, _i64, _p, _i64, _i64, _i, _i64, _i, _i64, _i64, _i, _f, _p]),
     'vited_retrieval_metrics': (_i, [_p, _i, _i64, _i64, _i64, _i64, _p, _p, _p, _i, _i, _i, _p, _p, _p]),
+    'vited_group_retrieval_metrics': (_i, [_p, _i, _i64, _i64, _i64, _i64, _p, _i, _p, _p, _p, _p, _p, _p, _p, _i, _p, _p, _p]),
+    'vited_pair_scores_workspace_bytes': (_i64, [_i64, _i64]),
+    'vited_pair_scores_add': (_i, [_p, _i, _i64, _p, _i, _i64, _i64, _p, _p, _p, _p, _p]),
+    'vited_pair_scores_finish': (_i, [_p, _p, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _i64, _p]),
 }
 
 _lib = None

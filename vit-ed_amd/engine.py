@@ -9,6 +9,7 @@ checkpoint rotation and validation stay in the reference's ``Trainer``.
 from __future__ import annotations
 
 import os
+from typing import NamedTuple
 
 import torch
 import torch.distributed as dist
@@ -902,3 +903,160 @@ def hisfrag_retrieval_metrics(similarity: torch.Tensor, labels, *, rank: int = 0
         group = dist.group.WORLD
     return retrieval_metrics(similarity, labels, rows=(bounds[rank], bounds[rank + 1]), remove_self_column=remove_self_column,
                              from_similarity=True, group=group if world > 1 else None)
+
+
+# ---------------------------------------------------------------------------------------------
+# group mAP / Pr@k (misc/metric.calc_map_prak) and the geshaem evaluation (michigan.py:188-233)
+# ---------------------------------------------------------------------------------------------
+def _relation_csr(uniq, id_of, relation, row_ids, device):
+    """(offsets int32 [L + 1], label ids int32): for every label id a whose label is in ``row_ids``, the ascending, duplicate-free
+    ids of the labels of ``relation[label]`` that occur among the columns (others cannot match).  A missing key raises KeyError,
+    as the reference's ``positive_pairs[labels[i]]`` does; labels of rows outside the range get an empty row."""
+    offsets, flat = [0], []
+    for a, label in enumerate(uniq):
+        if a in row_ids:
+            flat.extend(sorted({id_of[b] for b in relation[label] if b in id_of}))
+        offsets.append(len(flat))
+    return (torch.tensor(offsets, dtype=torch.int32, device=device), torch.tensor(flat, dtype=torch.int32, device=device))
+
+
+def group_relations(labels, positive_pairs, negative_pairs=None, device='cuda', *, rows=None):
+    """The device form of (labels, positive_pairs, negative_pairs) that ``ops.group_retrieval_metrics_rows`` takes:
+    (label ids int32 [n], (offsets, members) of every label's columns, positive CSR, negative CSR or None), label ids numbered
+    by first appearance.  Only the labels of ``rows`` (default: all) are looked up in the mappings."""
+    labels = list(labels)
+    r0, r1 = (0, len(labels)) if rows is None else (int(rows[0]), int(rows[1]))
+    id_of = {}
+    ids = [id_of.setdefault(label, len(id_of)) for label in labels]
+    uniq = list(id_of)
+    row_ids = set(ids[r0:r1])
+    label_ids, col_off, col_mem = class_members(torch.tensor(ids, dtype=torch.int64, device=device))
+    pos = _relation_csr(uniq, id_of, positive_pairs, row_ids, device)
+    neg = None if negative_pairs is None else _relation_csr(uniq, id_of, negative_pairs, row_ids, device)
+    return label_ids, (col_off, col_mem), pos, neg
+
+
+def map_prak(distances: torch.Tensor, labels, positive_pairs, negative_pairs=None, prak=(1, 5), *, rows=None, group=None):
+    """``(m_ap, (pr@k for k in prak))`` of ``misc/metric.calc_map_prak(distances, labels, positive_pairs, negative_pairs, prak)``
+    on the GPU.
+
+    ``distances``: [n, n] float16 / bfloat16 / float32 on the device.  ``labels``: n hashables (``dist_df.columns``); row i has
+    the label ``labels[i]``.  ``positive_pairs`` / ``negative_pairs``: mappings from a label to an iterable of labels
+    (``fragment_to_group``); "correct" and "eligible" are set membership.  A row label missing from a mapping raises KeyError.
+    Each row is ordered by a STABLE argsort (ties to the lower column, NaN last; numpy's default sort may order ties otherwise),
+    its first eligible element is skipped whatever it is, and rows without a correct retrieval are left out, as in the
+    reference.  Where no row has one the reference divides by zero; here every result is then NaN.  ``prak``: up to 8 ints >= 1.
+    ``rows=(r0, r1)`` computes this rank's share of the rows (default: all); with ``group`` ONE all-reduce (SUM, so gloo works
+    too) combines the shares and every rank returns the metrics of all rows.  Without a group the result covers ``rows`` only."""
+    from . import ops                                       # ops refuses CPU tensors: no CPU fallback
+    n = distances.shape[0]
+    labels = list(labels)
+    if len(labels) != n:
+        raise ValueError(f'labels must hold {n} labels, got {len(labels)}')
+    prak = tuple(int(k) for k in prak)
+    r0, r1 = (0, n) if rows is None else (int(rows[0]), int(rows[1]))
+    if not 0 <= r0 <= r1 <= n:
+        raise ValueError(f'rows ({r0}, {r1}) is not a range inside [0, {n}]')
+    if r1 > r0:
+        rel = group_relations(labels, positive_pairs, negative_pairs, distances.device, rows=(r0, r1))
+        _, sums = ops.group_retrieval_metrics_rows(distances, *rel, prak, (r0, r1))
+    else:                                                   # an empty share (more ranks than rows) still joins the reduction
+        if not 1 <= len(prak) <= 8 or min(prak) < 1:
+            raise ValueError(f'prak must be 1 to 8 cut-offs >= 1, got {prak}')
+        sums = torch.zeros(2 + len(prak), dtype=torch.float64, device=distances.device)
+    if group is not None:
+        dist.all_reduce(sums, op=dist.ReduceOp.SUM, group=group)
+    s = [float(v) for v in sums.tolist()]
+    if s[1] == 0:
+        return float('nan'), tuple(float('nan') for _ in prak)
+    return s[0] / s[1], tuple(v / s[1] for v in s[2:])
+
+
+class PairScoreStats(NamedTuple):
+    """What ``PairScoreAggregator.finish`` returns.  mean / min float32 [n, n] of the distances 1 - score of every cell (NaN where
+    a cell has no value), count int32 [n, n], std_stats = (avg_std, std_std): the mean and the sample stdev of the per-cell
+    sample stdevs over the cells with more than one value (NaN where there are too few), std float64 [n, n] those stdevs."""
+    mean: torch.Tensor
+    min: torch.Tensor
+    count: torch.Tensor
+    std_stats: tuple
+    std: torch.Tensor
+
+
+class PairScoreAggregator:
+    """The distance maps of ``geshaem_test`` (michigan.py:188-209) on the device.  ``add(pairs, scores)`` takes a validation
+    batch's fragment-id pairs [m, 2] (int32 / int64, on the host or the device) and its scores [m] (the model's
+    ``output.view(-1)``, float32 / bfloat16 / float16, on the device: never copied to the host).  Every score adds 1 - score to
+    cell (i, j) and to cell (j, i).  ``finish()`` reduces every record added so far (PairScoreStats); its result is bit-identical
+    whatever the batching and order of the records (include/vited.h)."""
+
+    def __init__(self, n_fragments: int, device):
+        self.n = int(n_fragments)
+        self.device = torch.device(device)
+        self.counts = torch.zeros((self.n, self.n), dtype=torch.int32, device=self.device)
+        self.bad = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self.size = 0
+        self._cells = torch.empty((0, 2), dtype=torch.int32, device=self.device)
+        self._values = torch.empty(0, dtype=torch.float32, device=self.device)
+
+    def _reserve(self, extra: int):
+        need = self.size + extra
+        if need <= self._values.numel():
+            return
+        cap = max(need, 2 * self._values.numel(), 1 << 16)
+        cells = torch.empty((cap, 2), dtype=torch.int32, device=self.device)
+        values = torch.empty(cap, dtype=torch.float32, device=self.device)
+        cells[:self.size] = self._cells[:self.size]
+        values[:self.size] = self._values[:self.size]
+        self._cells, self._values = cells, values
+
+    def add(self, pairs: torch.Tensor, scores: torch.Tensor):
+        from . import ops
+        scores = scores.reshape(-1)
+        pairs = pairs.to(self.device, non_blocking=True)
+        m = pairs.shape[0]
+        if m == 0:
+            return
+        self._reserve(m)
+        ops.pair_scores_add(pairs, scores, self.n, self.counts, self._cells[self.size:self.size + m],
+                            self._values[self.size:self.size + m], self.bad)
+        self.size += m
+
+    def finish(self) -> PairScoreStats:
+        from . import ops
+        mean, minv, std, stats = ops.pair_scores_finish(self._cells[:self.size], self._values[:self.size], self.n, self.counts,
+                                                       self.bad)
+        bad = int(self.bad.item())
+        if bad & 1:
+            raise ValueError(f'a fragment id outside [0, {self.n}) was added (those records were ignored)')
+        if bad:
+            raise RuntimeError('vited_pair_scores_finish: counts and records disagree')
+        avg_std, std_std = (float(v) for v in stats.tolist())
+        return PairScoreStats(mean, minv, self.counts.clone(), (avg_std, std_std), std)
+
+
+class GeshaemMetrics(NamedTuple):
+    """``geshaem_pair_metrics``: ``mean`` / ``min`` = (m_ap, (pr@k, ...)) of calc_map_prak on the MEAN / MIN distance maps,
+    ``avg_std`` / ``std_std`` as logged by the reference, ``n_categories`` = the number of scored fragments."""
+    mean: tuple
+    min: tuple
+    avg_std: float
+    std_std: float
+    n_categories: int
+
+
+@torch.no_grad()
+def geshaem_pair_metrics(aggregator: PairScoreAggregator, fragments, fragment_to_group, prak=(1, 5, 10)) -> GeshaemMetrics:
+    """The evaluation of ``geshaem_test`` after its loop (michigan.py:211-233): the fragments that were scored, in ascending
+    fragment index (the order the reference's dicts and DataFrame get from its unshuffled loader), labelled
+    ``fragments[index]`` (``dataset.fragments``), ranked by the MEAN and by the MIN distance map with ``fragment_to_group`` as
+    the positive relation.  The reference's return value is ``1 - max(result.mean[0], result.min[0])``."""
+    res = aggregator.finish()
+    scored = torch.nonzero((res.count > 0).any(dim=1)).flatten()
+    idx = scored.tolist()
+    labels = [fragments[a] for a in idx]
+    out = []
+    for matrix in (res.mean, res.min):
+        sub = matrix.index_select(0, scored).index_select(1, scored)
+        out.append(map_prak(sub, labels, fragment_to_group, prak=prak))
+    return GeshaemMetrics(out[0], out[1], res.std_stats[0], res.std_stats[1], len(idx))

@@ -658,3 +658,98 @@ def retrieval_metrics_rows(matrix: torch.Tensor, labels: torch.Tensor, offsets: 
         _ptr(matrix), _DT_RETRIEVAL[matrix.dtype], ld, n, r0, r1, _ptr(labels), _ptr(offsets), _ptr(members), offsets.numel() - 1,
         int(bool(remove_self_column)), int(bool(from_similarity)), _ptr(rows_out), _ptr(sums), _stream()), 'vited_retrieval_metrics')
     return rows_out, sums
+
+
+# ---------------------------------------------------------------------------------------------
+# evaluation: group mAP / Pr@k (misc/metric.calc_map_prak) and pair-score aggregation (michigan.py:188-209)
+# ---------------------------------------------------------------------------------------------
+def _int32_vector(name, t, device, size=None):
+    if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() or (size is not None and t.numel() != size):
+        raise ValueError(f'{name} must be a contiguous int32 vector{f" of length {size}" if size else ""}, '
+                         f'got {t.dtype} of shape {tuple(t.shape)}')
+    if t.device != device:
+        raise ValueError(f'{name} is on {t.device}, the matrix on {device}')
+
+
+def group_retrieval_metrics_rows(matrix: torch.Tensor, labels: torch.Tensor, col_csr, pos_csr, neg_csr, ks, rows: tuple[int, int]):
+    """Row records (float64 [r1 - r0, 3 + len(ks)]: AP, valid, correct retrievals, hits_k for every k) and their sums
+    (float64 [2 + len(ks)], see include/vited.h) of calc_map_prak for the rows [r0, r1) of the [n, n] distance matrix.
+    ``labels`` int32 [n] label ids in [0, L); ``col_csr`` = (offsets int32 [L + 1], members int32 [n]) the columns of every label;
+    ``pos_csr`` / ``neg_csr`` = (offsets int32 [L + 1], label ids int32), every row ascending and without duplicates; ``neg_csr``
+    may be None.  ``ks``: 1 to 8 ints >= 1."""
+    import ctypes
+    _need_gpu(matrix, labels, *col_csr, *pos_csr, *(neg_csr or ()))
+    if matrix.dtype not in _DT_RETRIEVAL:
+        raise TypeError(f'group retrieval metrics take float32, bfloat16 or float16 matrices, got {matrix.dtype}')
+    if matrix.dim() != 2 or matrix.shape[0] != matrix.shape[1]:
+        raise ValueError(f'expected a square [n, n] matrix, got shape {tuple(matrix.shape)}')
+    ld = _rows2d(matrix)
+    n = matrix.shape[0]
+    _int32_vector('labels', labels, matrix.device, n)
+    num_labels = col_csr[0].numel() - 1
+    for name, (off, vals) in (('col', col_csr), ('pos', pos_csr)) + ((('neg', neg_csr),) if neg_csr is not None else ()):
+        _int32_vector(f'{name} offsets', off, matrix.device, num_labels + 1)
+        _int32_vector(f'{name} members', vals, matrix.device)
+    ks = [int(k) for k in ks]
+    if not 1 <= len(ks) <= 8 or min(ks) < 1:
+        raise ValueError(f'ks must be 1 to 8 cut-offs >= 1, got {ks}')
+    r0, r1 = int(rows[0]), int(rows[1])
+    if not 0 <= r0 < r1 <= n:
+        raise ValueError(f'rows ({r0}, {r1}) is not a non-empty range inside [0, {n})')
+    rows_out = torch.empty((r1 - r0, 3 + len(ks)), dtype=torch.float64, device=matrix.device)
+    sums = torch.empty(2 + len(ks), dtype=torch.float64, device=matrix.device)
+    k_host = (ctypes.c_int * len(ks))(*ks)
+    neg_off, neg_lab = neg_csr if neg_csr is not None else (None, None)
+    _lib.check(_lib.load().vited_group_retrieval_metrics(
+        _ptr(matrix), _DT_RETRIEVAL[matrix.dtype], ld, n, r0, r1, _ptr(labels), num_labels, _ptr(col_csr[0]), _ptr(col_csr[1]),
+        _ptr(pos_csr[0]), _ptr(pos_csr[1]), _ptr(neg_off), _ptr(neg_lab), ctypes.addressof(k_host), len(ks), _ptr(rows_out),
+        _ptr(sums), _stream()), 'vited_group_retrieval_metrics')
+    return rows_out, sums
+
+
+_DT_INDEX = {torch.int32: _lib.I32, torch.int64: _lib.I64}
+
+
+def pair_scores_add(pairs: torch.Tensor, scores: torch.Tensor, n: int, counts: torch.Tensor, rec_cells: torch.Tensor,
+                    rec_values: torch.Tensor, bad: torch.Tensor):
+    """Stores the records (pairs[r, 0], pairs[r, 1], 1 - scores[r]) into rec_cells int32 [m, 2] / rec_values float32 [m] and
+    counts them into counts int32 [n, n] (both cells (i, j) and (j, i)).  Ids outside [0, n) set bit 0 of bad int32 [1]."""
+    _need_gpu(pairs, scores, counts, rec_cells, rec_values, bad)
+    if pairs.dtype not in _DT_INDEX or pairs.dim() != 2 or pairs.shape[1] != 2:
+        raise ValueError(f'pairs must be int32 / int64 [m, 2], got {pairs.dtype} of shape {tuple(pairs.shape)}')
+    if pairs.stride(1) != 1:
+        pairs = pairs.contiguous()
+    if scores.dtype not in _DT_RETRIEVAL or scores.dim() != 1 or scores.numel() != pairs.shape[0]:
+        raise ValueError(f'scores must be a float32 / bfloat16 / float16 vector of {pairs.shape[0]}, '
+                         f'got {scores.dtype} of shape {tuple(scores.shape)}')
+    scores = scores.contiguous()
+    m = pairs.shape[0]
+    for name, t, dtype, shape in (('counts', counts, torch.int32, (n, n)), ('rec_cells', rec_cells, torch.int32, (m, 2)),
+                                  ('rec_values', rec_values, torch.float32, (m,)), ('bad', bad, torch.int32, (1,))):
+        if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != pairs.device:
+            raise ValueError(f'{name} must be contiguous {dtype} {shape} on {pairs.device}, got {t.dtype} {tuple(t.shape)} on {t.device}')
+    if m == 0:
+        return
+    _lib.check(_lib.load().vited_pair_scores_add(_ptr(pairs), _DT_INDEX[pairs.dtype], pairs.stride(0), _ptr(scores),
+                                                 _DT_RETRIEVAL[scores.dtype], m, n, _ptr(counts), _ptr(rec_cells), _ptr(rec_values),
+                                                 _ptr(bad), _stream()), 'vited_pair_scores_add')
+
+
+def pair_scores_finish(rec_cells: torch.Tensor, rec_values: torch.Tensor, n: int, counts: torch.Tensor, bad: torch.Tensor):
+    """(mean float32 [n, n], min float32 [n, n], stdev float64 [n, n], stats float64 [2] = (avg_std, std_std)) of every stored
+    record; see include/vited.h."""
+    _need_gpu(rec_cells, rec_values, counts, bad)
+    m = rec_values.numel()
+    lib = _lib.load()
+    ws_bytes = lib.vited_pair_scores_workspace_bytes(n, m)
+    if ws_bytes < 0:
+        raise ValueError(f'{n} fragments / {m} records is outside what vited_pair_scores_finish takes')
+    dev = counts.device
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    mean = torch.empty((n, n), dtype=torch.float32, device=dev)
+    minv = torch.empty((n, n), dtype=torch.float32, device=dev)
+    stdev = torch.empty((n, n), dtype=torch.float64, device=dev)
+    stats = torch.empty(2, dtype=torch.float64, device=dev)
+    _lib.check(lib.vited_pair_scores_finish(_ptr(rec_cells), _ptr(rec_values), m, n, _ptr(counts), _ptr(mean), _ptr(minv), _ptr(stdev),
+                                            _ptr(stats), _ptr(bad), _ptr(ws), ws_bytes, _stream()), 'vited_pair_scores_finish')
+    return mean, minv, stdev, stats
