@@ -835,6 +835,18 @@ def pairwise_similarity(model, images, *, rank: int = 0, world: int = 1, block: 
 # ---------------------------------------------------------------------------------------------
 # retrieval metrics of the distance matrix (misc/wi19_evaluate.get_metrics, hisfrag.py:309,321)
 # ---------------------------------------------------------------------------------------------
+def _summed_rows(share, n, rows, nsums, device, group):
+    """The float64 [nsums] sums ``share(r0, r1)`` returns for ``rows=(r0, r1)`` (default: all n rows), SUM all-reduced over
+    ``group`` when one is given.  An empty share (more ranks than rows) contributes zeros but still joins the reduction."""
+    r0, r1 = (0, n) if rows is None else (int(rows[0]), int(rows[1]))
+    if not 0 <= r0 <= r1 <= n:
+        raise ValueError(f'rows ({r0}, {r1}) is not a range inside [0, {n}]')
+    sums = share(r0, r1) if r1 > r0 else torch.zeros(nsums, dtype=torch.float64, device=device)
+    if group is not None:
+        dist.all_reduce(sums, op=dist.ReduceOp.SUM, group=group)
+    return sums
+
+
 def class_members(labels: torch.Tensor):
     """(class ids int32 [n] in [0, C), offsets int32 [C + 1], members int32 [n]): the columns of class c are
     members[offsets[c]:offsets[c + 1]], in ascending order.  Equal input labels get equal ids, so 'same class' is unchanged."""
@@ -871,18 +883,12 @@ def retrieval_metrics(distance: torch.Tensor, labels, *, rows=None, remove_self_
         raise ValueError(f'labels must be a vector of length {n}, got shape {tuple(labels.shape)}')
     if labels.is_floating_point() or labels.is_complex():
         raise TypeError(f'labels must be integer class ids, got {labels.dtype}')
-    r0, r1 = (0, n) if rows is None else (int(rows[0]), int(rows[1]))
-    if not 0 <= r0 <= r1 <= n:
-        raise ValueError(f'rows ({r0}, {r1}) is not a range inside [0, {n}]')
-    if r1 > r0:
+
+    def share(r0, r1):
         ids, offsets, members = class_members(labels)
-        _, sums = ops.retrieval_metrics_rows(distance, ids, offsets, members, (r0, r1), remove_self_column=remove_self_column,
-                                             from_similarity=from_similarity)
-    else:                                                   # an empty share (more ranks than rows) still joins the reduction
-        sums = torch.zeros(7, dtype=torch.float64, device=distance.device)
-    if group is not None:
-        dist.all_reduce(sums, op=dist.ReduceOp.SUM, group=group)
-    return metrics_from_sums(sums)
+        return ops.retrieval_metrics_rows(distance, ids, offsets, members, (r0, r1), remove_self_column=remove_self_column,
+                                          from_similarity=from_similarity)[1]
+    return metrics_from_sums(_summed_rows(share, n, rows, 7, distance.device, group))
 
 
 @torch.no_grad()
@@ -954,19 +960,13 @@ def map_prak(distances: torch.Tensor, labels, positive_pairs, negative_pairs=Non
     if len(labels) != n:
         raise ValueError(f'labels must hold {n} labels, got {len(labels)}')
     prak = tuple(int(k) for k in prak)
-    r0, r1 = (0, n) if rows is None else (int(rows[0]), int(rows[1]))
-    if not 0 <= r0 <= r1 <= n:
-        raise ValueError(f'rows ({r0}, {r1}) is not a range inside [0, {n}]')
-    if r1 > r0:
+    if not 1 <= len(prak) <= 8 or min(prak) < 1:
+        raise ValueError(f'prak must be 1 to 8 cut-offs >= 1, got {prak}')
+
+    def share(r0, r1):
         rel = group_relations(labels, positive_pairs, negative_pairs, distances.device, rows=(r0, r1))
-        _, sums = ops.group_retrieval_metrics_rows(distances, *rel, prak, (r0, r1))
-    else:                                                   # an empty share (more ranks than rows) still joins the reduction
-        if not 1 <= len(prak) <= 8 or min(prak) < 1:
-            raise ValueError(f'prak must be 1 to 8 cut-offs >= 1, got {prak}')
-        sums = torch.zeros(2 + len(prak), dtype=torch.float64, device=distances.device)
-    if group is not None:
-        dist.all_reduce(sums, op=dist.ReduceOp.SUM, group=group)
-    s = [float(v) for v in sums.tolist()]
+        return ops.group_retrieval_metrics_rows(distances, *rel, prak, (r0, r1))[1]
+    s = [float(v) for v in _summed_rows(share, n, rows, 2 + len(prak), distances.device, group).tolist()]
     if s[1] == 0:
         return float('nan'), tuple(float('nan') for _ in prak)
     return s[0] / s[1], tuple(v / s[1] for v in s[2:])

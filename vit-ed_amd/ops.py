@@ -631,38 +631,6 @@ def last_paths():
 _DT_RETRIEVAL = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16}
 
 
-def retrieval_metrics_rows(matrix: torch.Tensor, labels: torch.Tensor, offsets: torch.Tensor, members: torch.Tensor,
-                           rows: tuple[int, int], *, remove_self_column: bool = True, from_similarity: bool = False):
-    """Row records (float64 [r1 - r0, 5]: AP sum, correct retrievals, top-1 hit, hits in the first 10, in the first 100) and
-    their sums (float64 [7], see include/vited.h) for the rows [r0, r1) of the [n, n] matrix.  ``labels`` int32 [n] in
-    [0, C) with the class CSR ``offsets`` int32 [C + 1] / ``members`` int32 [n] built from them (engine.class_members)."""
-    _need_gpu(matrix, labels, offsets, members)
-    if matrix.dtype not in _DT_RETRIEVAL:
-        raise TypeError(f'retrieval metrics take float32, bfloat16 or float16 matrices, got {matrix.dtype}')
-    if matrix.dim() != 2 or matrix.shape[0] != matrix.shape[1]:
-        raise ValueError(f'expected a square [n, n] matrix, got shape {tuple(matrix.shape)}')
-    ld = _rows2d(matrix)
-    n = matrix.shape[0]
-    for name, t, size in (('labels', labels, n), ('members', members, n), ('offsets', offsets, None)):
-        if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() or (size is not None and t.numel() != size):
-            raise ValueError(f'{name} must be a contiguous int32 vector{f" of length {size}" if size else ""}, '
-                             f'got {t.dtype} of shape {tuple(t.shape)}')
-        if t.device != matrix.device:
-            raise ValueError(f'{name} is on {t.device}, the matrix on {matrix.device}')
-    r0, r1 = int(rows[0]), int(rows[1])
-    if not 0 <= r0 < r1 <= n:
-        raise ValueError(f'rows ({r0}, {r1}) is not a non-empty range inside [0, {n})')
-    rows_out = torch.empty((r1 - r0, 5), dtype=torch.float64, device=matrix.device)
-    sums = torch.empty(7, dtype=torch.float64, device=matrix.device)
-    _lib.check(_lib.load().vited_retrieval_metrics(
-        _ptr(matrix), _DT_RETRIEVAL[matrix.dtype], ld, n, r0, r1, _ptr(labels), _ptr(offsets), _ptr(members), offsets.numel() - 1,
-        int(bool(remove_self_column)), int(bool(from_similarity)), _ptr(rows_out), _ptr(sums), _stream()), 'vited_retrieval_metrics')
-    return rows_out, sums
-
-
-# ---------------------------------------------------------------------------------------------
-# evaluation: group mAP / Pr@k (misc/metric.calc_map_prak) and pair-score aggregation (michigan.py:188-209)
-# ---------------------------------------------------------------------------------------------
 def _int32_vector(name, t, device, size=None):
     if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() or (size is not None and t.numel() != size):
         raise ValueError(f'{name} must be a contiguous int32 vector{f" of length {size}" if size else ""}, '
@@ -671,6 +639,41 @@ def _int32_vector(name, t, device, size=None):
         raise ValueError(f'{name} is on {t.device}, the matrix on {device}')
 
 
+def _ranking_args(what, matrix, labels, rows):
+    """(dtype code, ld, n, r0, r1) of the [n, n] matrix a ranking-metrics entry takes, after the checks both entries share."""
+    if matrix.dtype not in _DT_RETRIEVAL:
+        raise TypeError(f'{what} metrics take float32, bfloat16 or float16 matrices, got {matrix.dtype}')
+    if matrix.dim() != 2 or matrix.shape[0] != matrix.shape[1]:
+        raise ValueError(f'expected a square [n, n] matrix, got shape {tuple(matrix.shape)}')
+    ld = _rows2d(matrix)
+    n = matrix.shape[0]
+    _int32_vector('labels', labels, matrix.device, n)
+    r0, r1 = int(rows[0]), int(rows[1])
+    if not 0 <= r0 < r1 <= n:
+        raise ValueError(f'rows ({r0}, {r1}) is not a non-empty range inside [0, {n})')
+    return _DT_RETRIEVAL[matrix.dtype], ld, n, r0, r1
+
+
+def retrieval_metrics_rows(matrix: torch.Tensor, labels: torch.Tensor, offsets: torch.Tensor, members: torch.Tensor,
+                           rows: tuple[int, int], *, remove_self_column: bool = True, from_similarity: bool = False):
+    """Row records (float64 [r1 - r0, 5]: AP sum, correct retrievals, top-1 hit, hits in the first 10, in the first 100) and
+    their sums (float64 [7], see include/vited.h) for the rows [r0, r1) of the [n, n] matrix.  ``labels`` int32 [n] in
+    [0, C) with the class CSR ``offsets`` int32 [C + 1] / ``members`` int32 [n] built from them (engine.class_members)."""
+    _need_gpu(matrix, labels, offsets, members)
+    dt, ld, n, r0, r1 = _ranking_args('retrieval', matrix, labels, rows)
+    _int32_vector('members', members, matrix.device, n)
+    _int32_vector('offsets', offsets, matrix.device)
+    rows_out = torch.empty((r1 - r0, 5), dtype=torch.float64, device=matrix.device)
+    sums = torch.empty(7, dtype=torch.float64, device=matrix.device)
+    _lib.check(_lib.load().vited_retrieval_metrics(
+        _ptr(matrix), dt, ld, n, r0, r1, _ptr(labels), _ptr(offsets), _ptr(members), offsets.numel() - 1,
+        int(bool(remove_self_column)), int(bool(from_similarity)), _ptr(rows_out), _ptr(sums), _stream()), 'vited_retrieval_metrics')
+    return rows_out, sums
+
+
+# ---------------------------------------------------------------------------------------------
+# evaluation: group mAP / Pr@k (misc/metric.calc_map_prak) and pair-score aggregation (michigan.py:188-209)
+# ---------------------------------------------------------------------------------------------
 def group_retrieval_metrics_rows(matrix: torch.Tensor, labels: torch.Tensor, col_csr, pos_csr, neg_csr, ks, rows: tuple[int, int]):
     """Row records (float64 [r1 - r0, 3 + len(ks)]: AP, valid, correct retrievals, hits_k for every k) and their sums
     (float64 [2 + len(ks)], see include/vited.h) of calc_map_prak for the rows [r0, r1) of the [n, n] distance matrix.
@@ -679,13 +682,7 @@ def group_retrieval_metrics_rows(matrix: torch.Tensor, labels: torch.Tensor, col
     may be None.  ``ks``: 1 to 8 ints >= 1."""
     import ctypes
     _need_gpu(matrix, labels, *col_csr, *pos_csr, *(neg_csr or ()))
-    if matrix.dtype not in _DT_RETRIEVAL:
-        raise TypeError(f'group retrieval metrics take float32, bfloat16 or float16 matrices, got {matrix.dtype}')
-    if matrix.dim() != 2 or matrix.shape[0] != matrix.shape[1]:
-        raise ValueError(f'expected a square [n, n] matrix, got shape {tuple(matrix.shape)}')
-    ld = _rows2d(matrix)
-    n = matrix.shape[0]
-    _int32_vector('labels', labels, matrix.device, n)
+    dt, ld, n, r0, r1 = _ranking_args('group retrieval', matrix, labels, rows)
     num_labels = col_csr[0].numel() - 1
     for name, (off, vals) in (('col', col_csr), ('pos', pos_csr)) + ((('neg', neg_csr),) if neg_csr is not None else ()):
         _int32_vector(f'{name} offsets', off, matrix.device, num_labels + 1)
@@ -693,15 +690,12 @@ def group_retrieval_metrics_rows(matrix: torch.Tensor, labels: torch.Tensor, col
     ks = [int(k) for k in ks]
     if not 1 <= len(ks) <= 8 or min(ks) < 1:
         raise ValueError(f'ks must be 1 to 8 cut-offs >= 1, got {ks}')
-    r0, r1 = int(rows[0]), int(rows[1])
-    if not 0 <= r0 < r1 <= n:
-        raise ValueError(f'rows ({r0}, {r1}) is not a non-empty range inside [0, {n})')
     rows_out = torch.empty((r1 - r0, 3 + len(ks)), dtype=torch.float64, device=matrix.device)
     sums = torch.empty(2 + len(ks), dtype=torch.float64, device=matrix.device)
     k_host = (ctypes.c_int * len(ks))(*ks)
     neg_off, neg_lab = neg_csr if neg_csr is not None else (None, None)
     _lib.check(_lib.load().vited_group_retrieval_metrics(
-        _ptr(matrix), _DT_RETRIEVAL[matrix.dtype], ld, n, r0, r1, _ptr(labels), num_labels, _ptr(col_csr[0]), _ptr(col_csr[1]),
+        _ptr(matrix), dt, ld, n, r0, r1, _ptr(labels), num_labels, _ptr(col_csr[0]), _ptr(col_csr[1]),
         _ptr(pos_csr[0]), _ptr(pos_csr[1]), _ptr(neg_off), _ptr(neg_lab), ctypes.addressof(k_host), len(ks), _ptr(rows_out),
         _ptr(sums), _stream()), 'vited_group_retrieval_metrics')
     return rows_out, sums
