@@ -18,67 +18,6 @@ I32, I64 = 3, 4
 EPI_STORE, EPI_GELU, EPI_RESIDUAL, EPI_MUL_GELU_GRAD, EPI_STORE_F32, EPI_MUL, EPI_GELU_GRAD = 0, 1, 2, 3, 4, 5, 6
 B_NK, B_KN = 0, 1
 
-_p, _i64, _i, _f = C.c_void_p, C.c_int64, C.c_int, C.c_float
-
-# name -> (restype, argtypes); mirrors include/vited.h one to one (tests/test_abi.py checks that the
-# header declares exactly these names and that the library exports every one of them)
-SIGNATURES = {
-    'vited_abi_version': (_i, []),
-    'vited_strerror': (C.c_char_p, [_i]),
-    'vited_last_gemm_path': (_i, []),
-    'vited_last_attention_path': (_i, []),
-    'vited_cast': (_i, [_p, _i, _p, _i, _i64, _p]),
-    'vited_cast_transpose': (_i, [_p, _p, _i, _i64, _i64, _p]),
-    'vited_cast_weights': (_i, [_p, _i, _i64, _p]),
-    'vited_patchify': (_i, [_p, _i64, _p, _p, _i, _i64, _i, _i, _i, _p]),
-    'vited_patchify_u8': (_i, [_p, _i64, _p, _p, _i, _i64, _i, _i, _i, _p, _p, _p]),
-    'vited_crop_pairs_u8': (_i, [_p, _i64, _p, _p, _p, _i64, _i, _i, _p]),
-    'vited_slice_rows_cast': (_i, [_p, _p, _i, _i64, _i64, _i64, _i64, _i64, _p]),
-    'vited_write_cls_row': (_i, [_p, _p, _p, _i64, _i64, _i64, _p]),
-    'vited_sum_rows_workspace_bytes': (_i64, [_i64, _i64]),
-    'vited_sum_rows': (_i, [_p, _i, _i64, _p, _i64, _i64, _p, _i64, _p]),
-    'vited_layernorm_fwd': (_i, [_p, _i64, _p, _p, _p, _i, _i64, _p, _p, _i64, _i64, _f, _p]),
-    'vited_layernorm_bwd_workspace_bytes': (_i64, [_i64, _i64]),
-    'vited_layernorm_bwd': (_i, [_p, _i, _i64, _p, _i64, _p, _p, _p, _p, _i64, _p, _i64, _p, _i, _i64, _p, _p, _i,
-                                 _i64, _i64, _p, _i64, _p]),
-    'vited_gemm': (_i, [_p, _i64, _p, _i64, _i, _i, _i64, _i64, _i64, _i, _p, _p, _p, _p, _p, _i64, _i64, _i64,
-                        _i64, _i, _p]),
-    'vited_linear_bwd_weight_workspace_bytes': (_i64, [_i64, _i64, _i64]),
-    'vited_linear_bwd_weight': (_i, [_p, _i64, _p, _i64, _i, _i64, _i64, _i64, _p, _p, _i, _p, _i64, _p]),
-    'vited_linear_bwd_weight_batched_supported': (_i, [_i, _p, _p, _p, _i]),
-    'vited_linear_bwd_weight_batched_workspace_bytes': (_i64, [_i, _p, _p, _p]),
-    'vited_linear_bwd_weight_batched': (_i, [_i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _p, _i64, _p]),
-    'vited_linear_layernorm_supported': (_i, [_i64, _i64, _i64]),
-    'vited_linear_residual_layernorm_fwd': (_i, [_p, _i64, _p, _i64, _p, _p, _i64, _p, _i64, _p, _p, _f, _p, _i64, _p, _p, _i64, _i64, _i64, _p]),
-    'vited_linear_layernorm_bwd_segmented': (_i, [_p, _i64, _i64, _i64, _i64, _p, _i64, _p, _i64, _p, _p, _p, _p, _i64, _p, _i64, _p, _i64, _p, _p,
-                                                  _i, _i64, _i64, _p, _i64, _p]),
-    'vited_linear_layernorm_bwd_partial_rows': (_i64, [_i64]),
-    'vited_layernorm_bwd_finish_batched': (_i, [_i, _p, _p, _p, _p, _p, _i64, _p]),
-    'vited_linear_layernorm_bwd_workspace_bytes': (_i64, [_i64, _i64]),
-    'vited_linear_layernorm_bwd': (_i, [_p, _i64, _p, _i64, _p, _i64, _p, _p, _p, _p, _i64, _p, _i64, _p, _i64, _p, _p, _i, _i64, _i64, _i64,
-                                        _p, _i64, _p]),
-    'vited_fold_context_weights': (_i, [_i, _p, _p, _p, _p, _i64, _i64, _p, _p, _p, _p]),
-    'vited_unfold_context_grads': (_i, [_i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i, _p]),
-    'vited_mlp_fwd': (_i, [_p, _i64, _p, _p, _p, _p, _p, _p, _p, _i64, _p, _p, _p, _p, _p, _i64, _i64, _i64, _f, _p]),
-    'vited_block_workspace_bytes': (_i64, [_i64, _i64, _i64, _i64, _i]),
-    'vited_block_fwd': (_i, [_p, _p, _i64, _i64, _i64, _i, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _f, _p, _i64, _p]),
-    'vited_cross_block_workspace_bytes': (_i64, [_i64, _i64, _i64, _i64, _i64, _i]),
-    'vited_cross_block_fwd': (_i, [_p, _p, _p, _i64, _i64, _i64, _i64, _i, _i64] + [_p] * 22 + [_f, _p, _i64, _p]),
-    'vited_adamw_workspace_bytes': (_i64, []),
-    'vited_adamw_step': (_i, [_p, _i, _i64, _p, _i64, _p, _f, _i, _p, _p, _i64, _p]),
-    'vited_attention_fwd': (_i, [_p, _i64, _i64, _p, _i64, _i64, _p, _i64, _i64, _p, _i64, _i64, _p, _i, _i64, _i,
-                                 _i64, _i64, _i, _f, _p]),
-    'vited_attention_fwd_indexed': (_i, [_p, _i64, _i64, _p, _i64, _i64, _p, _i64, _i64, _p, _p, _i64, _i64, _p, _i, _i64, _i,
-                                         _i64, _i64, _i, _f, _p]),
-    'vited_attention_bwd': (_i, [_p, _i64, _i64, _p, _i64, _i64, _p, _i64, _i64, _p, _p, _i64, _i64, _p, _p,
-                                 _p, _i64, _i64, _p, _i64, _i64, _p, _i64, _i64, _i, _i64, _i, _i64, _i64, _i, _f, _p]),
-    'vited_retrieval_metrics': (_i, [_p, _i, _i64, _i64, _i64, _i64, _p, _p, _p, _i, _i, _i, _p, _p, _p]),
-    'vited_group_retrieval_metrics': (_i, [_p, _i, _i64, _i64, _i64, _i64, _p, _i, _p, _p, _p, _p, _p, _p, _p, _i, _p, _p, _p]),
-    'vited_pair_scores_workspace_bytes': (_i64, [_i64, _i64]),
-    'vited_pair_scores_add': (_i, [_p, _i, _i64, _p, _i, _i64, _i64, _p, _p, _p, _p, _p]),
-    'vited_pair_scores_finish': (_i, [_p, _p, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _i64, _p]),
-}
-
 _lib = None
 
 
@@ -91,6 +30,44 @@ def header_declared_functions():
     text = open(HEADER_PATH).read()
     text = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
     return sorted(set(re.findall(r'\b(vited_[a-z0-9_]+)\s*\(', text)))
+
+
+_C_SCALARS = {'int': C.c_int, 'int64_t': C.c_int64, 'float': C.c_float}
+_PROTOTYPE = re.compile(r'(\w[\w\s*]*?)\s*\b(vited_\w+)\s*\(([^)]*)\)\s*;')
+
+
+def _ctype(decl: str, where: str):
+    """ctypes type of a C type of the header: every pointer is a c_void_p, the scalars map one to one."""
+    if '*' in decl:
+        return C.c_void_p
+    try:
+        return _C_SCALARS[' '.join(decl.split())]
+    except KeyError:
+        raise VitedLibraryError(f'include/vited.h: {where} has the C type {decl.strip()!r}, which the binding cannot express') from None
+
+
+def parse_signatures(text: str) -> dict:
+    """name -> (restype, argtypes) of every ``vited_*`` prototype in ``text`` (the source of include/vited.h)."""
+    text = re.sub(r'/\*.*?\*/|//[^\n]*', ' ', text, flags=re.S)
+    text = re.sub(r'^\s*#.*$', '', text, flags=re.M)
+    sigs = {}
+    for ret, name, params in _PROTOTYPE.findall(text):
+        ret = ' '.join(ret.replace('*', ' *').split())
+        restype = C.c_char_p if ret == 'const char *' else _ctype(ret, f'the return of {name}')
+        argtypes = []
+        if params.strip() != 'void':
+            for i, param in enumerate(params.split(',')):
+                decl = re.sub(r'\b\w+\s*$', '', param)          # drop the parameter's name
+                argtypes.append(_ctype(decl, f'parameter {i} ({" ".join(param.split())}) of {name}'))
+        sigs[name] = (restype, argtypes)
+    missed = set(re.findall(r'\b(vited_\w+)\s*\(', text)) - set(sigs)
+    if missed:
+        raise VitedLibraryError(f'include/vited.h: cannot parse the prototypes of {sorted(missed)}')
+    return sigs
+
+
+# name -> (restype, argtypes), derived from include/vited.h: the header is the only statement of each signature
+SIGNATURES = parse_signatures(open(HEADER_PATH).read())
 
 
 def load():
@@ -120,3 +97,8 @@ def check(code: int, what: str):
     if code != 0:
         msg = load().vited_strerror(code).decode()
         raise RuntimeError(f'{what} failed: {msg} (vited error {code})')
+
+
+def call(name: str, *args):
+    """Call the status-returning entry ``name`` and raise ``RuntimeError`` unless it returned VITED_OK."""
+    check(getattr(load(), name)(*args), name)

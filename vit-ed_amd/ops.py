@@ -8,20 +8,23 @@ is hipGraph-capturable.
 """
 from __future__ import annotations
 
+import ctypes as C
+
 import torch
 
 from . import _lib
 from ._lib import (B_KN, B_NK, BF16, EPI_GELU, EPI_GELU_GRAD, EPI_MUL, EPI_MUL_GELU_GRAD, EPI_RESIDUAL, EPI_STORE, EPI_STORE_F32, F16,
-                   F32)
+                   F32, I32, I64)
 
-_DT = {torch.float32: F32, torch.bfloat16: BF16}
+_DTYPE = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16, torch.int32: I32, torch.int64: I64}
+_FLOATS = (torch.float32, torch.bfloat16, torch.float16)       # what the ranking and pair-score entries take
 
 
 def _code(dtype: torch.dtype) -> int:
-    try:
-        return _DT[dtype]
-    except KeyError:
-        raise TypeError(f'vited ops support float32 and bfloat16 activations, got {dtype}') from None
+    """dtype code of an activation (fp32 or bf16)."""
+    if dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f'vited ops support float32 and bfloat16 activations, got {dtype}')
+    return _DTYPE[dtype]
 
 
 def _need_gpu(*tensors):
@@ -37,6 +40,15 @@ def _ptr(t):
 
 def _stream():
     return torch.cuda.current_stream().cuda_stream
+
+
+def _host_array(ctype, values, length=None):
+    """ctypes array of ``values`` (zero-filled up to ``length``) for an entry that reads a host array; a ``c_void_p`` array takes
+    tensors, ``None`` being null."""
+    values = list(values)
+    if ctype is C.c_void_p:
+        values = [_ptr(t) or None for t in values]
+    return (ctype * (len(values) if length is None else length))(*values)
 
 
 def _rows2d(t: torch.Tensor):
@@ -73,6 +85,12 @@ def workspace(nbytes: int, device) -> torch.Tensor:
     return buf
 
 
+def _scratch(nbytes: int, device):
+    """(pointer, size in bytes) of ``workspace(nbytes, device)``."""
+    ws = workspace(nbytes, device)
+    return ws.data_ptr(), ws.numel() * 4
+
+
 # ---------------------------------------------------------------------------------------------
 def cast(src: torch.Tensor, dtype: torch.dtype, out: torch.Tensor | None = None) -> torch.Tensor:
     _need_gpu(src, out)
@@ -80,7 +98,7 @@ def cast(src: torch.Tensor, dtype: torch.dtype, out: torch.Tensor | None = None)
     if out is None:
         out = torch.empty_like(src, dtype=dtype)
     assert out.dtype == dtype and out.numel() == src.numel() and out.is_contiguous()
-    _lib.check(_lib.load().vited_cast(_ptr(src), _code(src.dtype), _ptr(out), _code(dtype), src.numel(), _stream()), 'vited_cast')
+    _lib.call('vited_cast', _ptr(src), _code(src.dtype), _ptr(out), _code(dtype), src.numel(), _stream())
     return out
 
 
@@ -91,8 +109,7 @@ def cast_transpose(w: torch.Tensor, dtype: torch.dtype, out: torch.Tensor | None
     if out is None:
         out = torch.empty((w.shape[1], w.shape[0]), dtype=dtype, device=w.device)
     assert out.dtype == dtype and out.shape == (w.shape[1], w.shape[0]) and out.is_contiguous()
-    _lib.check(_lib.load().vited_cast_transpose(_ptr(w), _ptr(out), _code(dtype), w.shape[0], w.shape[1], _stream()),
-               'vited_cast_transpose')
+    _lib.call('vited_cast_transpose', _ptr(w), _ptr(out), _code(dtype), w.shape[0], w.shape[1], _stream())
     return out
 
 
@@ -121,7 +138,7 @@ class WeightShadowPlan:
 
     def run(self):
         if self.count:
-            _lib.check(_lib.load().vited_cast_weights(_ptr(self.table), self.count, self.total_tiles, _stream()), 'vited_cast_weights')
+            _lib.call('vited_cast_weights', _ptr(self.table), self.count, self.total_tiles, _stream())
 
 
 def patchify(img: torch.Tensor, patch: int, dtype: torch.dtype, batch_index: torch.Tensor | None = None,
@@ -143,14 +160,11 @@ def patchify(img: torch.Tensor, patch: int, dtype: torch.dtype, batch_index: tor
     g = s // patch
     out = torch.empty((nb * g * g, c * patch * patch), dtype=dtype, device=img.device)
     if u8:
-        import ctypes
-        m = (ctypes.c_float * c)(*[float(v) for v in list(mean)[:c]])
-        sd = (ctypes.c_float * c)(*[float(v) for v in list(std)[:c]])
-        _lib.check(_lib.load().vited_patchify_u8(_ptr(img), img.stride(0), _ptr(batch_index), _ptr(out), _code(dtype), nb, c, s, patch,
-                                                 ctypes.cast(m, ctypes.c_void_p), ctypes.cast(sd, ctypes.c_void_p), _stream()), 'vited_patchify_u8')
-        return out
-    _lib.check(_lib.load().vited_patchify(_ptr(img), img.stride(0), _ptr(batch_index), _ptr(out), _code(dtype), nb, c, s,
-                                          patch, _stream()), 'vited_patchify')
+        mean, std = ([float(v) for v in list(t)[:c]] for t in (mean, std))
+        _lib.call('vited_patchify_u8', _ptr(img), img.stride(0), _ptr(batch_index), _ptr(out), _code(dtype), nb, c, s, patch,
+                  _host_array(C.c_float, mean, c), _host_array(C.c_float, std, c), _stream())
+    else:
+        _lib.call('vited_patchify', _ptr(img), img.stride(0), _ptr(batch_index), _ptr(out), _code(dtype), nb, c, s, patch, _stream())
     return out
 
 
@@ -166,8 +180,7 @@ def crop_pairs_u8(regions: torch.Tensor, cells: torch.Tensor, erode: torch.Tenso
     assert cells.dtype == torch.int32 and cells.shape == (b, 2) and cells.is_contiguous()
     assert erode.dtype == torch.int32 and erode.shape == (b,) and erode.is_contiguous()
     out = torch.empty((b, 2, c, s, s), dtype=torch.uint8, device=regions.device)
-    _lib.check(_lib.load().vited_crop_pairs_u8(_ptr(regions), regions.stride(0), _ptr(cells), _ptr(erode), _ptr(out), b, c, s, _stream()),
-               'vited_crop_pairs_u8')
+    _lib.call('vited_crop_pairs_u8', _ptr(regions), regions.stride(0), _ptr(cells), _ptr(erode), _ptr(out), b, c, s, _stream())
     return out
 
 
@@ -177,8 +190,7 @@ def slice_rows_cast(x: torch.Tensor, row_offset: int, rows: int, dtype: torch.dt
     assert x.dtype == torch.float32 and x.dim() == 3 and x.is_contiguous()
     b, r, d = x.shape
     out = torch.empty((b * rows, d), dtype=dtype, device=x.device)
-    _lib.check(_lib.load().vited_slice_rows_cast(_ptr(x), _ptr(out), _code(dtype), b, r, row_offset, rows, d, _stream()),
-               'vited_slice_rows_cast')
+    _lib.call('vited_slice_rows_cast', _ptr(x), _ptr(out), _code(dtype), b, r, row_offset, rows, d, _stream())
     return out
 
 
@@ -187,7 +199,7 @@ def write_cls_row(x: torch.Tensor, cls: torch.Tensor, pos: torch.Tensor):
     _need_gpu(x, cls, pos)
     assert x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 3
     b, r, d = x.shape
-    _lib.check(_lib.load().vited_write_cls_row(_ptr(x), _ptr(cls), _ptr(pos), b, r, d, _stream()), 'vited_write_cls_row')
+    _lib.call('vited_write_cls_row', _ptr(x), _ptr(cls), _ptr(pos), b, r, d, _stream())
 
 
 def sum_rows(x: torch.Tensor) -> torch.Tensor:
@@ -195,12 +207,9 @@ def sum_rows(x: torch.Tensor) -> torch.Tensor:
     _need_gpu(x)
     ld = _rows2d(x)
     b, w = x.shape
-    lib = _lib.load()
     out = torch.empty(w, dtype=torch.float32, device=x.device)
-    nbytes = lib.vited_sum_rows_workspace_bytes(b, w)
-    ws = workspace(nbytes, x.device)
-    _lib.check(lib.vited_sum_rows(_ptr(x), _code(x.dtype), ld, _ptr(out), b, w, _ptr(ws), ws.numel() * 4, _stream()),
-               'vited_sum_rows')
+    ws = _scratch(_lib.load().vited_sum_rows_workspace_bytes(b, w), x.device)
+    _lib.call('vited_sum_rows', _ptr(x), _code(x.dtype), ld, _ptr(out), b, w, *ws, _stream())
     return out
 
 
@@ -219,8 +228,8 @@ def layernorm_fwd(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps:
         y = torch.empty((rows, dim), dtype=out_dtype, device=x.device)
         mean = torch.empty(rows, dtype=torch.float32, device=x.device)
         rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
-    _lib.check(_lib.load().vited_layernorm_fwd(_ptr(x), ld, _ptr(gamma), _ptr(beta), _ptr(y), _code(out_dtype), dim,
-                                               _ptr(mean), _ptr(rstd), rows, dim, float(eps), _stream()), 'vited_layernorm_fwd')
+    _lib.call('vited_layernorm_fwd', _ptr(x), ld, _ptr(gamma), _ptr(beta), _ptr(y), _code(out_dtype), dim, _ptr(mean), _ptr(rstd), rows,
+              dim, float(eps), _stream())
     return y, mean, rstd
 
 
@@ -235,7 +244,6 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, dx_in=None, dx_out=None, want_lp: bo
     dy_ld, x_ld = _rows2d(dy), _rows2d(x)
     rows, dim = x.shape
     assert dy.shape == x.shape and x.dtype == torch.float32
-    lib = _lib.load()
     if dx_out is None:
         dx_out = torch.empty((rows, dim), dtype=torch.float32, device=x.device)
     if want_lp and dx_lp is None:
@@ -248,13 +256,12 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, dx_in=None, dx_out=None, want_lp: bo
     else:
         dgamma = torch.empty(dim, dtype=torch.float32, device=x.device)
         dbeta = torch.empty(dim, dtype=torch.float32, device=x.device)
-    nbytes = lib.vited_layernorm_bwd_workspace_bytes(rows, dim)
-    ws = workspace(nbytes, x.device)
-    _lib.check(lib.vited_layernorm_bwd(
-        _ptr(dy), _code(dy.dtype), dy_ld, _ptr(x), x_ld, _ptr(gamma), _ptr(mean), _ptr(rstd),
-        _ptr(dx_in), _rows2d(dx_in) if dx_in is not None else 0, _ptr(dx_out), _rows2d(dx_out),
-        _ptr(dx_lp), BF16, _rows2d(dx_lp) if dx_lp is not None else 0, _ptr(dgamma), _ptr(dbeta), int(accumulate), rows, dim,
-        _ptr(ws), ws.numel() * 4, _stream()), 'vited_layernorm_bwd')
+    ws = _scratch(_lib.load().vited_layernorm_bwd_workspace_bytes(rows, dim), x.device)
+    _lib.call('vited_layernorm_bwd',
+              _ptr(dy), _code(dy.dtype), dy_ld, _ptr(x), x_ld, _ptr(gamma), _ptr(mean), _ptr(rstd),
+              _ptr(dx_in), _rows2d(dx_in) if dx_in is not None else 0, _ptr(dx_out), _rows2d(dx_out),
+              _ptr(dx_lp), BF16, _rows2d(dx_lp) if dx_lp is not None else 0, _ptr(dgamma), _ptr(dbeta), int(accumulate), rows, dim,
+              *ws, _stream())
     return dx_out, dx_lp, dgamma, dbeta
 
 
@@ -291,10 +298,8 @@ def gemm(a: torch.Tensor, b: torch.Tensor, *, b_layout: int = B_NK, epilogue: in
         assert residual.stride(-2) == ldo if residual.dim() >= 2 else True
     if bias is not None:
         assert bias.dtype == torch.float32 and bias.numel() == n
-    _lib.check(_lib.load().vited_gemm(
-        _ptr(a), lda, _ptr(b), ldb, b_layout, _code(a.dtype), m, n, k, epilogue, _ptr(bias), _ptr(aux), _ptr(residual),
-        _ptr(out), _ptr(out2), ldo, rows_per_batch, out_rows_per_batch, row_offset, int(bool(residual_bcast)), _stream()),
-        'vited_gemm')
+    _lib.call('vited_gemm', _ptr(a), lda, _ptr(b), ldb, b_layout, _code(a.dtype), m, n, k, epilogue, _ptr(bias), _ptr(aux), _ptr(residual),
+              _ptr(out), _ptr(out2), ldo, rows_per_batch, out_rows_per_batch, row_offset, int(bool(residual_bcast)), _stream())
     return (out, out2) if epilogue in (EPI_GELU, EPI_GELU_GRAD) else out
 
 
@@ -306,7 +311,6 @@ def linear_bwd_weight(dy: torch.Tensor, x: torch.Tensor, want_bias: bool = True,
     lddy, ldx = _rows2d(dy), _rows2d(x)
     m, n = dy.shape
     k = x.shape[1]
-    lib = _lib.load()
     accumulate = dw_out is not None
     if accumulate:
         assert dw_out.dtype == torch.float32 and dw_out.is_contiguous() and dw_out.numel() == n * k
@@ -315,10 +319,9 @@ def linear_bwd_weight(dy: torch.Tensor, x: torch.Tensor, want_bias: bool = True,
     else:
         dw = torch.empty((n, k), dtype=torch.float32, device=x.device)
         db = torch.empty(n, dtype=torch.float32, device=x.device) if want_bias else None
-    nbytes = lib.vited_linear_bwd_weight_workspace_bytes(m, n, k)
-    ws = workspace(nbytes, x.device)
-    _lib.check(lib.vited_linear_bwd_weight(_ptr(dy), lddy, _ptr(x), ldx, _code(x.dtype), m, n, k, _ptr(dw), _ptr(db),
-                                           int(accumulate), _ptr(ws), ws.numel() * 4, _stream()), 'vited_linear_bwd_weight')
+    ws = _scratch(_lib.load().vited_linear_bwd_weight_workspace_bytes(m, n, k), x.device)
+    _lib.call('vited_linear_bwd_weight', _ptr(dy), lddy, _ptr(x), ldx, _code(x.dtype), m, n, k, _ptr(dw), _ptr(db), int(accumulate), *ws,
+              _stream())
     return dw, db
 
 
@@ -330,7 +333,6 @@ def linear_bwd_weight_batched(items, accumulate: bool) -> bool:
     sums of dy_i for every item in ONE launch of the wide weight-gradient kernel + one slab-sum launch
     (``vited_linear_bwd_weight_batched``).  Returns False (nothing launched) when the set is not covered - the caller then issues
     ``linear_bwd_weight`` per item."""
-    import ctypes as C
     n = len(items)
     if n < 1 or n > MAX_BATCHED_WEIGHT_GRADS:
         return False
@@ -342,22 +344,17 @@ def linear_bwd_weight_batched(items, accumulate: bool) -> bool:
         assert db is None or (db.dtype == torch.float32 and db.is_contiguous() and db.numel() == dy.shape[1])
         if dw.data_ptr() % 16 or (db is not None and db.data_ptr() % 16) or dy.data_ptr() % 16 or x.data_ptr() % 16:
             return False                 # the batched kernels use 16-byte accesses throughout
-    i64, vp = C.c_int64 * n, C.c_void_p * n
-    M = i64(*[it[0].shape[0] for it in items])
-    N = i64(*[it[0].shape[1] for it in items])
-    K = i64(*[it[1].shape[1] for it in items])
+    dys, xs, dws, dbs = zip(*items)
+    M = _host_array(C.c_int64, [dy.shape[0] for dy in dys])
+    N = _host_array(C.c_int64, [dy.shape[1] for dy in dys])
+    K = _host_array(C.c_int64, [x.shape[1] for x in xs])
     lib = _lib.load()
     if not lib.vited_linear_bwd_weight_batched_supported(n, M, N, K, BF16):
         return False
-    lddy = i64(*[_rows2d(it[0]) for it in items])
-    ldx = i64(*[_rows2d(it[1]) for it in items])
-    dY = vp(*[it[0].data_ptr() for it in items])
-    X = vp(*[it[1].data_ptr() for it in items])
-    dW = vp(*[it[2].data_ptr() for it in items])
-    dB = vp(*[_ptr(it[3]) or None for it in items])
-    ws = workspace(lib.vited_linear_bwd_weight_batched_workspace_bytes(n, M, N, K), items[0][0].device)
-    _lib.check(lib.vited_linear_bwd_weight_batched(n, dY, lddy, X, ldx, M, N, K, dW, dB, BF16, int(bool(accumulate)), _ptr(ws),
-                                                   ws.numel() * 4, _stream()), 'vited_linear_bwd_weight_batched')
+    lddy, ldx = _host_array(C.c_int64, map(_rows2d, dys)), _host_array(C.c_int64, map(_rows2d, xs))
+    ws = _scratch(lib.vited_linear_bwd_weight_batched_workspace_bytes(n, M, N, K), dys[0].device)
+    _lib.call('vited_linear_bwd_weight_batched', n, _host_array(C.c_void_p, dys), lddy, _host_array(C.c_void_p, xs), ldx, M, N, K,
+              _host_array(C.c_void_p, dws), _host_array(C.c_void_p, dbs), BF16, int(bool(accumulate)), *ws, _stream())
     return True
 
 
@@ -383,9 +380,8 @@ def linear_residual_layernorm_fwd(a, w, bias, residual, gamma=None, beta=None, e
         h = torch.empty((m, n), dtype=torch.bfloat16, device=a.device)
         mean = torch.empty(m, dtype=torch.float32, device=a.device)
         rstd = torch.empty(m, dtype=torch.float32, device=a.device)
-    _lib.check(_lib.load().vited_linear_residual_layernorm_fwd(
-        _ptr(a), lda, _ptr(w), ldw, _ptr(bias), _ptr(residual), ldr, _ptr(y), _rows2d(y), _ptr(gamma), _ptr(beta), float(eps),
-        _ptr(h), n, _ptr(mean), _ptr(rstd), m, n, k, _stream()), 'vited_linear_residual_layernorm_fwd')
+    _lib.call('vited_linear_residual_layernorm_fwd', _ptr(a), lda, _ptr(w), ldw, _ptr(bias), _ptr(residual), ldr, _ptr(y), _rows2d(y),
+              _ptr(gamma), _ptr(beta), float(eps), _ptr(h), n, _ptr(mean), _ptr(rstd), m, n, k, _stream())
     return y, h, mean, rstd
 
 
@@ -422,32 +418,29 @@ def linear_layernorm_bwd(dy, wt, x, gamma, mean, rstd, dx_in=None, dx_out=None, 
         dbeta = torch.empty(n, dtype=torch.float32, device=x.device)
     if defer is not None:
         rows = int(lib.vited_linear_layernorm_bwd_partial_rows(m))
-        ws = torch.empty(rows * 2 * n, dtype=torch.float32, device=x.device)     # lives until the flush
-        defer.append((ws, rows, dgamma, dbeta, accumulate))
+        part = torch.empty(rows * 2 * n, dtype=torch.float32, device=x.device)     # lives until the flush
+        defer.append((part, rows, dgamma, dbeta, accumulate))
+        ws = (part.data_ptr(), part.numel() * 4)
     else:
-        ws = workspace(lib.vited_linear_layernorm_bwd_workspace_bytes(m, n), x.device)
+        ws = _scratch(lib.vited_linear_layernorm_bwd_workspace_bytes(m, n), x.device)
     tail = (_ptr(x), ldx, _ptr(gamma), _ptr(mean), _ptr(rstd), _ptr(dx_in), _rows2d(dx_in) if dx_in is not None else 0, _ptr(dx_out),
             _rows2d(dx_out), _ptr(dx_lp), n, 0 if defer is not None else _ptr(dgamma), 0 if defer is not None else _ptr(dbeta), int(accumulate))
     if segments > 1:
-        _lib.check(lib.vited_linear_layernorm_bwd_segmented(_ptr(dy), lddy, seg_k, seg_stride, segments, _ptr(wt), ldwt, *tail, m, n, _ptr(ws),
-                                                            ws.numel() * 4, _stream()), 'vited_linear_layernorm_bwd_segmented')
+        _lib.call('vited_linear_layernorm_bwd_segmented', _ptr(dy), lddy, seg_k, seg_stride, segments, _ptr(wt), ldwt, *tail, m, n, *ws,
+                  _stream())
     else:
-        _lib.check(lib.vited_linear_layernorm_bwd(_ptr(dy), lddy, _ptr(wt), ldwt, *tail, m, n, k, _ptr(ws), ws.numel() * 4, _stream()),
-                   'vited_linear_layernorm_bwd')
+        _lib.call('vited_linear_layernorm_bwd', _ptr(dy), lddy, _ptr(wt), ldwt, *tail, m, n, k, *ws, _stream())
     return dx_out, dx_lp, dgamma, dbeta
 
 
 def layernorm_bwd_finish(entries):
     """Finish the deferred column sums of ``linear_layernorm_bwd(..., defer=entries)``: one launch per 16 LayerNorms."""
-    import ctypes as C
-    n = len(entries)
-    if not n:
+    if not entries:
         return
-    vp, ci = C.c_void_p * n, C.c_int * n
-    dim = entries[0][2].numel()
-    _lib.check(_lib.load().vited_layernorm_bwd_finish_batched(
-        n, vp(*[e[0].data_ptr() for e in entries]), ci(*[e[1] for e in entries]), vp(*[e[2].data_ptr() for e in entries]),
-        vp(*[e[3].data_ptr() for e in entries]), ci(*[int(e[4]) for e in entries]), dim, _stream()), 'vited_layernorm_bwd_finish_batched')
+    parts, rows, dgammas, dbetas, accumulate = zip(*entries)
+    _lib.call('vited_layernorm_bwd_finish_batched', len(entries), _host_array(C.c_void_p, parts), _host_array(C.c_int, rows),
+              _host_array(C.c_void_p, dgammas), _host_array(C.c_void_p, dbetas), _host_array(C.c_int, map(int, accumulate)),
+              dgammas[0].numel(), _stream())
     entries.clear()
 
 
@@ -458,7 +451,6 @@ MAX_FOLDED_BLOCKS = 16
 def fold_context_weights(ws, biases, gammas, betas, out=None):
     """Folded kv weights of several decoder blocks: W'_l = W_l o gamma_l (bf16, stacked [L N, K] and transposed [K, L N]) and
     b'_l = b_l + W_l beta_l (fp32 [L N]) - ``vited_fold_context_weights``.  ``out`` = (w, wt, b) buffers to refresh in place."""
-    import ctypes as C
     n_blk = len(ws)
     _need_gpu(*ws, *gammas, *betas)
     n, k = ws[0].shape
@@ -466,37 +458,25 @@ def fold_context_weights(ws, biases, gammas, betas, out=None):
     if out is None:
         out = (torch.empty((n_blk * n, k), dtype=torch.bfloat16, device=dev), torch.empty((k, n_blk * n), dtype=torch.bfloat16, device=dev),
                torch.empty(n_blk * n, dtype=torch.float32, device=dev))
-    vp = C.c_void_p * n_blk
     for t in list(ws) + list(gammas) + list(betas):
         assert t.dtype == torch.float32 and t.is_contiguous()
-    _lib.check(_lib.load().vited_fold_context_weights(n_blk, vp(*[w.data_ptr() for w in ws]), vp(*[_ptr(b) or None for b in biases]),
-                                                      vp(*[g.data_ptr() for g in gammas]), vp(*[b.data_ptr() for b in betas]), n, k,
-                                                      _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _stream()), 'vited_fold_context_weights')
+    _lib.call('vited_fold_context_weights', n_blk, *(_host_array(C.c_void_p, ts) for ts in (ws, biases, gammas, betas)), n, k,
+              _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _stream())
     return out
 
 
 def unfold_context_grads(dwf, dbf, ws, gammas, betas, dws, dbiases, dgammas, dbetas, accumulate: bool):
     """Gradients of the folded weights / bias -> dW_l, db_l, dgamma_l, dbeta_l (``vited_unfold_context_grads``)."""
-    import ctypes as C
     n_blk = len(ws)
     n, k = ws[0].shape
     assert dwf.dtype == dbf.dtype == torch.float32 and dwf.is_contiguous() and dbf.is_contiguous()
     assert dwf.shape == (n_blk * n, k) and dbf.numel() == n_blk * n
-    vp = C.c_void_p * n_blk
-    _lib.check(_lib.load().vited_unfold_context_grads(n_blk, _ptr(dwf), _ptr(dbf), vp(*[w.data_ptr() for w in ws]),
-                                                      vp(*[g.data_ptr() for g in gammas]), vp(*[b.data_ptr() for b in betas]),
-                                                      vp(*[t.data_ptr() for t in dws]),
-                                                      vp(*[_ptr(t) or None for t in dbiases]), vp(*[t.data_ptr() for t in dgammas]),
-                                                      vp(*[t.data_ptr() for t in dbetas]), n, k, int(bool(accumulate)), _stream()),
-               'vited_unfold_context_grads')
+    _lib.call('vited_unfold_context_grads', n_blk, _ptr(dwf), _ptr(dbf),
+              *(_host_array(C.c_void_p, ts) for ts in (ws, gammas, betas, dws, dbiases, dgammas, dbetas)), n, k, int(bool(accumulate)),
+              _stream())
 
 
 # ---------------------------------------------------------------------------------------------
-def mlp_fused_supported(x: torch.Tensor, w1: torch.Tensor) -> bool:
-    """The fused MLP kernel covers bf16, embed dim 384, hidden 1536 (every shipped pjs config)."""
-    return w1.dtype == torch.bfloat16 and tuple(w1.shape) == (1536, 384) and x.shape[-1] == 384
-
-
 def mlp_fwd(x, gamma, beta, w1, b1, w2, b2, eps: float, save: bool = True, out=None):
     """y = x + fc2(gelu(fc1(LayerNorm(x)))) in one kernel (``vited_mlp_fwd``).  x fp32 [rows, 384]; w1 / w2 the bf16 weights.
     Returns (y, saved) with saved = (mean, rstd, h, gd, u) or None.  ``out`` = (y, mean, rstd, h, gd, u) pre-made outputs
@@ -521,10 +501,9 @@ def mlp_fwd(x, gamma, beta, w1, b1, w2, b2, eps: float, save: bool = True, out=N
             u = torch.empty((rows, hidden), dtype=torch.bfloat16, device=dev)
     if save:
         assert h.is_contiguous() and gd.is_contiguous() and u.is_contiguous() and h.shape == (rows, dim) and gd.shape == u.shape == (rows, hidden)
-    _lib.check(_lib.load().vited_mlp_fwd(_ptr(x), ldx, _ptr(gamma), _ptr(beta), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), _ptr(y), _rows2d(y),
-                                         _ptr(h) if save else 0, _ptr(gd) if save else 0, _ptr(u) if save else 0,
-                                         _ptr(mean) if save else 0, _ptr(rstd) if save else 0, rows, dim, hidden, float(eps), _stream()),
-               'vited_mlp_fwd')
+    _lib.call('vited_mlp_fwd', _ptr(x), ldx, _ptr(gamma), _ptr(beta), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), _ptr(y), _rows2d(y),
+              _ptr(h) if save else 0, _ptr(gd) if save else 0, _ptr(u) if save else 0, _ptr(mean) if save else 0, _ptr(rstd) if save else 0,
+              rows, dim, hidden, float(eps), _stream())
     return y, ((mean, rstd, h, gd, u) if save else None)
 
 
@@ -535,13 +514,12 @@ def block_fwd(x, heads: int, ln1_g, ln1_b, wqkv, bqkv, wproj, bproj, ln2_g, ln2_
     assert all(t.dtype == torch.bfloat16 and t.is_contiguous() for t in (wqkv, wproj, w1, w2))
     b, n, d = x.shape
     hidden = w1.shape[0]
-    lib = _lib.load()
     y = torch.empty_like(x)
-    ws = workspace(lib.vited_block_workspace_bytes(b, n, d, hidden, heads) + 256, x.device)
-    base = (ws.data_ptr() + 255) // 256 * 256
-    _lib.check(lib.vited_block_fwd(_ptr(x), _ptr(y), b, n, d, heads, hidden, _ptr(ln1_g), _ptr(ln1_b), _ptr(wqkv), _ptr(bqkv), _ptr(wproj),
-                                   _ptr(bproj), _ptr(ln2_g), _ptr(ln2_b), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), float(eps), base,
-                                   ws.numel() * 4 - (base - ws.data_ptr()), _stream()), 'vited_block_fwd')
+    ws, nbytes = _scratch(_lib.load().vited_block_workspace_bytes(b, n, d, hidden, heads) + 256, x.device)
+    base = (ws + 255) // 256 * 256
+    _lib.call('vited_block_fwd', _ptr(x), _ptr(y), b, n, d, heads, hidden, _ptr(ln1_g), _ptr(ln1_b), _ptr(wqkv), _ptr(bqkv), _ptr(wproj),
+              _ptr(bproj), _ptr(ln2_g), _ptr(ln2_b), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), float(eps), base, nbytes - (base - ws),
+              _stream())
     return y
 
 
@@ -556,15 +534,13 @@ def cross_block_fwd(x, context, heads: int, ln1, wqkv, bqkv, wproj, bproj, lnq, 
     nc = context.shape[1]
     assert context.shape == (b, nc, d)
     hidden = w1.shape[0]
-    lib = _lib.load()
     y = torch.empty_like(x)
-    ws = workspace(lib.vited_cross_block_workspace_bytes(b, n, nc, d, hidden, heads) + 256, x.device)
-    base = (ws.data_ptr() + 255) // 256 * 256
-    _lib.check(lib.vited_cross_block_fwd(_ptr(x), _ptr(context), _ptr(y), b, n, nc, d, heads, hidden, _ptr(ln1[0]), _ptr(ln1[1]), _ptr(wqkv),
-                                         _ptr(bqkv), _ptr(wproj), _ptr(bproj), _ptr(lnq[0]), _ptr(lnq[1]), _ptr(lnc[0]), _ptr(lnc[1]),
-                                         _ptr(wq), _ptr(bq), _ptr(wkv), _ptr(bkv), _ptr(wcproj), _ptr(bcproj), _ptr(ln2[0]), _ptr(ln2[1]),
-                                         _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), float(eps), base, ws.numel() * 4 - (base - ws.data_ptr()),
-                                         _stream()), 'vited_cross_block_fwd')
+    ws, nbytes = _scratch(_lib.load().vited_cross_block_workspace_bytes(b, n, nc, d, hidden, heads) + 256, x.device)
+    base = (ws + 255) // 256 * 256
+    _lib.call('vited_cross_block_fwd', _ptr(x), _ptr(context), _ptr(y), b, n, nc, d, heads, hidden, _ptr(ln1[0]), _ptr(ln1[1]), _ptr(wqkv),
+              _ptr(bqkv), _ptr(wproj), _ptr(bproj), _ptr(lnq[0]), _ptr(lnq[1]), _ptr(lnc[0]), _ptr(lnc[1]), _ptr(wq), _ptr(bq), _ptr(wkv),
+              _ptr(bkv), _ptr(wcproj), _ptr(bcproj), _ptr(ln2[0]), _ptr(ln2[1]), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), float(eps), base,
+              nbytes - (base - ws), _stream())
     return y
 
 
@@ -593,9 +569,8 @@ def attention_fwd(q, k, v, heads: int, scale: float, kv_index=None):
     v_bs, v_ts = _head_view(v, heads, hd)
     o = torch.empty((b, nq, d), dtype=q.dtype, device=q.device)
     lse = torch.empty((b, heads, nq), dtype=torch.float32, device=q.device)
-    _lib.check(_lib.load().vited_attention_fwd_indexed(_ptr(q), q_bs, q_ts, _ptr(k), k_bs, k_ts, _ptr(v), v_bs, v_ts, _ptr(kv_index),
-                                                       _ptr(o), nq * d, d, _ptr(lse), _code(q.dtype), b, heads, nq, nk, hd,
-                                                       float(scale), _stream()), 'vited_attention_fwd')
+    _lib.call('vited_attention_fwd_indexed', _ptr(q), q_bs, q_ts, _ptr(k), k_bs, k_ts, _ptr(v), v_bs, v_ts, _ptr(kv_index), _ptr(o), nq * d,
+              d, _ptr(lse), _code(q.dtype), b, heads, nq, nk, hd, float(scale), _stream())
     return o, lse
 
 
@@ -613,10 +588,10 @@ def attention_bwd(q, k, v, o, do, lse, heads: int, scale: float, dq, dk, dv):
     dk_bs, dk_ts = _head_view(dk, heads, hd)
     dv_bs, dv_ts = _head_view(dv, heads, hd)
     delta = torch.empty((b, heads, nq), dtype=torch.float32, device=q.device)
-    _lib.check(_lib.load().vited_attention_bwd(
-        _ptr(q), q_bs, q_ts, _ptr(k), k_bs, k_ts, _ptr(v), v_bs, v_ts, _ptr(o), _ptr(do), nq * d, d, _ptr(lse), _ptr(delta),
-        _ptr(dq), dq_bs, dq_ts, _ptr(dk), dk_bs, dk_ts, _ptr(dv), dv_bs, dv_ts, _code(q.dtype), b, heads, nq, nk, hd,
-        float(scale), _stream()), 'vited_attention_bwd')
+    _lib.call('vited_attention_bwd',
+              _ptr(q), q_bs, q_ts, _ptr(k), k_bs, k_ts, _ptr(v), v_bs, v_ts, _ptr(o), _ptr(do), nq * d, d, _ptr(lse), _ptr(delta),
+              _ptr(dq), dq_bs, dq_ts, _ptr(dk), dk_bs, dk_ts, _ptr(dv), dv_bs, dv_ts, _code(q.dtype), b, heads, nq, nk, hd,
+              float(scale), _stream())
     return dq, dk, dv
 
 
@@ -628,9 +603,6 @@ def last_paths():
 # ---------------------------------------------------------------------------------------------
 # evaluation: retrieval metrics of a distance matrix (misc/wi19_evaluate.get_metrics)
 # ---------------------------------------------------------------------------------------------
-_DT_RETRIEVAL = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16}
-
-
 def _int32_vector(name, t, device, size=None):
     if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() or (size is not None and t.numel() != size):
         raise ValueError(f'{name} must be a contiguous int32 vector{f" of length {size}" if size else ""}, '
@@ -641,7 +613,7 @@ def _int32_vector(name, t, device, size=None):
 
 def _ranking_args(what, matrix, labels, rows):
     """(dtype code, ld, n, r0, r1) of the [n, n] matrix a ranking-metrics entry takes, after the checks both entries share."""
-    if matrix.dtype not in _DT_RETRIEVAL:
+    if matrix.dtype not in _FLOATS:
         raise TypeError(f'{what} metrics take float32, bfloat16 or float16 matrices, got {matrix.dtype}')
     if matrix.dim() != 2 or matrix.shape[0] != matrix.shape[1]:
         raise ValueError(f'expected a square [n, n] matrix, got shape {tuple(matrix.shape)}')
@@ -651,7 +623,7 @@ def _ranking_args(what, matrix, labels, rows):
     r0, r1 = int(rows[0]), int(rows[1])
     if not 0 <= r0 < r1 <= n:
         raise ValueError(f'rows ({r0}, {r1}) is not a non-empty range inside [0, {n})')
-    return _DT_RETRIEVAL[matrix.dtype], ld, n, r0, r1
+    return _DTYPE[matrix.dtype], ld, n, r0, r1
 
 
 def retrieval_metrics_rows(matrix: torch.Tensor, labels: torch.Tensor, offsets: torch.Tensor, members: torch.Tensor,
@@ -665,9 +637,8 @@ def retrieval_metrics_rows(matrix: torch.Tensor, labels: torch.Tensor, offsets: 
     _int32_vector('offsets', offsets, matrix.device)
     rows_out = torch.empty((r1 - r0, 5), dtype=torch.float64, device=matrix.device)
     sums = torch.empty(7, dtype=torch.float64, device=matrix.device)
-    _lib.check(_lib.load().vited_retrieval_metrics(
-        _ptr(matrix), dt, ld, n, r0, r1, _ptr(labels), _ptr(offsets), _ptr(members), offsets.numel() - 1,
-        int(bool(remove_self_column)), int(bool(from_similarity)), _ptr(rows_out), _ptr(sums), _stream()), 'vited_retrieval_metrics')
+    _lib.call('vited_retrieval_metrics', _ptr(matrix), dt, ld, n, r0, r1, _ptr(labels), _ptr(offsets), _ptr(members), offsets.numel() - 1,
+              int(bool(remove_self_column)), int(bool(from_similarity)), _ptr(rows_out), _ptr(sums), _stream())
     return rows_out, sums
 
 
@@ -680,7 +651,6 @@ def group_retrieval_metrics_rows(matrix: torch.Tensor, labels: torch.Tensor, col
     ``labels`` int32 [n] label ids in [0, L); ``col_csr`` = (offsets int32 [L + 1], members int32 [n]) the columns of every label;
     ``pos_csr`` / ``neg_csr`` = (offsets int32 [L + 1], label ids int32), every row ascending and without duplicates; ``neg_csr``
     may be None.  ``ks``: 1 to 8 ints >= 1."""
-    import ctypes
     _need_gpu(matrix, labels, *col_csr, *pos_csr, *(neg_csr or ()))
     dt, ld, n, r0, r1 = _ranking_args('group retrieval', matrix, labels, rows)
     num_labels = col_csr[0].numel() - 1
@@ -692,16 +662,11 @@ def group_retrieval_metrics_rows(matrix: torch.Tensor, labels: torch.Tensor, col
         raise ValueError(f'ks must be 1 to 8 cut-offs >= 1, got {ks}')
     rows_out = torch.empty((r1 - r0, 3 + len(ks)), dtype=torch.float64, device=matrix.device)
     sums = torch.empty(2 + len(ks), dtype=torch.float64, device=matrix.device)
-    k_host = (ctypes.c_int * len(ks))(*ks)
     neg_off, neg_lab = neg_csr if neg_csr is not None else (None, None)
-    _lib.check(_lib.load().vited_group_retrieval_metrics(
-        _ptr(matrix), dt, ld, n, r0, r1, _ptr(labels), num_labels, _ptr(col_csr[0]), _ptr(col_csr[1]),
-        _ptr(pos_csr[0]), _ptr(pos_csr[1]), _ptr(neg_off), _ptr(neg_lab), ctypes.addressof(k_host), len(ks), _ptr(rows_out),
-        _ptr(sums), _stream()), 'vited_group_retrieval_metrics')
+    _lib.call('vited_group_retrieval_metrics', _ptr(matrix), dt, ld, n, r0, r1, _ptr(labels), num_labels, _ptr(col_csr[0]),
+              _ptr(col_csr[1]), _ptr(pos_csr[0]), _ptr(pos_csr[1]), _ptr(neg_off), _ptr(neg_lab), _host_array(C.c_int, ks), len(ks),
+              _ptr(rows_out), _ptr(sums), _stream())
     return rows_out, sums
-
-
-_DT_INDEX = {torch.int32: _lib.I32, torch.int64: _lib.I64}
 
 
 def pair_scores_add(pairs: torch.Tensor, scores: torch.Tensor, n: int, counts: torch.Tensor, rec_cells: torch.Tensor,
@@ -709,11 +674,11 @@ def pair_scores_add(pairs: torch.Tensor, scores: torch.Tensor, n: int, counts: t
     """Stores the records (pairs[r, 0], pairs[r, 1], 1 - scores[r]) into rec_cells int32 [m, 2] / rec_values float32 [m] and
     counts them into counts int32 [n, n] (both cells (i, j) and (j, i)).  Ids outside [0, n) set bit 0 of bad int32 [1]."""
     _need_gpu(pairs, scores, counts, rec_cells, rec_values, bad)
-    if pairs.dtype not in _DT_INDEX or pairs.dim() != 2 or pairs.shape[1] != 2:
+    if pairs.dtype not in (torch.int32, torch.int64) or pairs.dim() != 2 or pairs.shape[1] != 2:
         raise ValueError(f'pairs must be int32 / int64 [m, 2], got {pairs.dtype} of shape {tuple(pairs.shape)}')
     if pairs.stride(1) != 1:
         pairs = pairs.contiguous()
-    if scores.dtype not in _DT_RETRIEVAL or scores.dim() != 1 or scores.numel() != pairs.shape[0]:
+    if scores.dtype not in _FLOATS or scores.dim() != 1 or scores.numel() != pairs.shape[0]:
         raise ValueError(f'scores must be a float32 / bfloat16 / float16 vector of {pairs.shape[0]}, '
                          f'got {scores.dtype} of shape {tuple(scores.shape)}')
     scores = scores.contiguous()
@@ -724,9 +689,8 @@ def pair_scores_add(pairs: torch.Tensor, scores: torch.Tensor, n: int, counts: t
             raise ValueError(f'{name} must be contiguous {dtype} {shape} on {pairs.device}, got {t.dtype} {tuple(t.shape)} on {t.device}')
     if m == 0:
         return
-    _lib.check(_lib.load().vited_pair_scores_add(_ptr(pairs), _DT_INDEX[pairs.dtype], pairs.stride(0), _ptr(scores),
-                                                 _DT_RETRIEVAL[scores.dtype], m, n, _ptr(counts), _ptr(rec_cells), _ptr(rec_values),
-                                                 _ptr(bad), _stream()), 'vited_pair_scores_add')
+    _lib.call('vited_pair_scores_add', _ptr(pairs), _DTYPE[pairs.dtype], pairs.stride(0), _ptr(scores), _DTYPE[scores.dtype], m, n,
+              _ptr(counts), _ptr(rec_cells), _ptr(rec_values), _ptr(bad), _stream())
 
 
 def pair_scores_finish(rec_cells: torch.Tensor, rec_values: torch.Tensor, n: int, counts: torch.Tensor, bad: torch.Tensor):
@@ -734,8 +698,7 @@ def pair_scores_finish(rec_cells: torch.Tensor, rec_values: torch.Tensor, n: int
     record; see include/vited.h."""
     _need_gpu(rec_cells, rec_values, counts, bad)
     m = rec_values.numel()
-    lib = _lib.load()
-    ws_bytes = lib.vited_pair_scores_workspace_bytes(n, m)
+    ws_bytes = _lib.load().vited_pair_scores_workspace_bytes(n, m)
     if ws_bytes < 0:
         raise ValueError(f'{n} fragments / {m} records is outside what vited_pair_scores_finish takes')
     dev = counts.device
@@ -744,6 +707,6 @@ def pair_scores_finish(rec_cells: torch.Tensor, rec_values: torch.Tensor, n: int
     minv = torch.empty((n, n), dtype=torch.float32, device=dev)
     stdev = torch.empty((n, n), dtype=torch.float64, device=dev)
     stats = torch.empty(2, dtype=torch.float64, device=dev)
-    _lib.check(lib.vited_pair_scores_finish(_ptr(rec_cells), _ptr(rec_values), m, n, _ptr(counts), _ptr(mean), _ptr(minv), _ptr(stdev),
-                                            _ptr(stats), _ptr(bad), _ptr(ws), ws_bytes, _stream()), 'vited_pair_scores_finish')
+    _lib.call('vited_pair_scores_finish', _ptr(rec_cells), _ptr(rec_values), m, n, _ptr(counts), _ptr(mean), _ptr(minv), _ptr(stdev),
+              _ptr(stats), _ptr(bad), _ptr(ws), ws_bytes, _stream())
     return mean, minv, stdev, stats

@@ -123,11 +123,9 @@ class FlatAdamW(torch.optim.Optimizer):
         if not capturing:
             self.sync_hyperparameters()
         desc = self._descriptors()
-        lib = _lib.load()
-        _lib.check(lib.vited_adamw_step(desc.data_ptr(), desc.shape[0], self._tiles, self.flat.flat.data_ptr(), self.flat.flat.numel(),
-                                        self._hyper.data_ptr(), float(max_norm) if max_norm else 0.0, int(zero_grad),
-                                        self._norm.data_ptr(), self._ws.data_ptr(), self._ws.numel() * 4,
-                                        torch.cuda.current_stream().cuda_stream), 'vited_adamw_step')
+        _lib.call('vited_adamw_step', desc.data_ptr(), desc.shape[0], self._tiles, self.flat.flat.data_ptr(), self.flat.flat.numel(),
+                  self._hyper.data_ptr(), float(max_norm) if max_norm else 0.0, int(zero_grad), self._norm.data_ptr(), self._ws.data_ptr(),
+                  self._ws.numel() * 4, torch.cuda.current_stream().cuda_stream)
         if not capturing:
             self._publish_update()
         return self._norm[0]
