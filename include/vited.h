@@ -393,6 +393,36 @@ int vited_pair_scores_finish(const int* rec_cells, const float* rec_values, int6
                              float* minv, double* stdev, double* stats, int* bad, void* workspace, int64_t workspace_bytes,
                              void* stream);
 
+/* ---- puzzle solving: the Paikin-Tal compatibility stage (paikin_tal_solver/inter_piece_distance.py), type-1 puzzles ---------------
+ * n pieces (2 <= n <= 46340), sides top 0, right 1, bottom 2, left 3, s^ = (s + 2) % 4.  All arrays are contiguous device memory:
+ *   dq       int32 [4, n, n]: dq[s, i, j] = distance of side s of piece i to side s^ of piece j, >= 0 (the diagonal is not read)
+ *   min_d, second_d int64 [n, 4]; candidate, best_buddy int32 [n, 4] (a piece id or -1); compat, mutual float32 [4, n, n]
+ *   start_count int32 [n], start_total float32 [n], start_order int32 [n]; placed, changed int32 [n] (0 / 1)
+ * Every result is exact and independent of the launch split (integer reductions, elementwise fp32 / fp64, a rank count).
+ *
+ * vited_puzzle_distances_from_logits: m ordered pairs (pi[r], pj[r]) (int64, i != j, both in [0, n)) and their logits [m, 4] fp32
+ *   -> dq[s, i, j] = uint32(trunc(fp32(fp32(1 - sigmoid(logits[r, (s + 3) % 4])) * 1000))) for the 4 sides (evaluation.py:118-133).
+ *   A pair outside [0, n) or with i == j is skipped and sets bit 0 of *bad (int32, device).
+ * vited_puzzle_compat_init == InterPieceDistance.__init__: per (piece, side) min / second-best distance over j != i (second order
+ *   statistic with multiplicity, seeded (maxsize - 1, maxsize)), the unique best-buddy candidate (-1 when the minimum is held by
+ *   none or several j), compat (1 at d == 0, -maxsize at second == 0, else fp32(1 - d / second in fp64); diagonal inf), mutual
+ *   ((C[s,i,j] + C[s^,j,i]) / 2 in fp32; diagonal inf), the mutual best buddies and the start-piece ordering (stable descending
+ *   sort of (count, total)).
+ * vited_puzzle_compat_recalc == recalculate_remaining_piece_compatibilities(placed): for unplaced i, min / second over unplaced
+ *   j != i; changed[i] = 1 where one of its 8 values moved; compat of changed rows at unplaced j; mutual of every pair with a
+ *   changed piece.  Best buddies and the start ordering are left alone, as the reference leaves them.
+ * vited_puzzle_best_slot: the first maximum of mutual[(slot_side[k] + 2) % 4, p, slot_piece[k]] over unplaced p ascending (outer)
+ *   x k < slots (inner) - the scan of solver.py:456-499 over the open slots the caller lists.  *best (int64, device) receives
+ *   (key << 32) | (0xffffffff - (p * slots + k)), key the order-preserving uint32 image of the fp32 value; n * slots < 2^32. */
+int vited_puzzle_distances_from_logits(const float* logits, const int64_t* pi, const int64_t* pj, int64_t m, int64_t n, int* dq,
+                                       int* bad, void* stream);
+int vited_puzzle_compat_init(const int* dq, int64_t n, int64_t* min_d, int64_t* second_d, int* candidate, int* best_buddy,
+                             float* compat, float* mutual, int* start_count, float* start_total, int* start_order, void* stream);
+int vited_puzzle_compat_recalc(const int* dq, int64_t n, const int* placed, int64_t* min_d, int64_t* second_d, float* compat,
+                               float* mutual, int* changed, void* stream);
+int vited_puzzle_best_slot(const float* mutual, int64_t n, const int* placed, const int* slot_piece, const int* slot_side,
+                           int64_t slots, int64_t* best, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

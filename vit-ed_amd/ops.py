@@ -710,3 +710,76 @@ def pair_scores_finish(rec_cells: torch.Tensor, rec_values: torch.Tensor, n: int
     _lib.call('vited_pair_scores_finish', _ptr(rec_cells), _ptr(rec_values), m, n, _ptr(counts), _ptr(mean), _ptr(minv), _ptr(stdev),
               _ptr(stats), _ptr(bad), _ptr(ws), ws_bytes, _stream())
     return mean, minv, stdev, stats
+
+
+# ---- puzzle solving: Paikin-Tal compatibility stage (include/vited.h) ------------------------------------------------------------
+def _puzzle_check(name, t, dtype, shape, dev):
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous() or t.device != dev:
+        raise ValueError(f'{name} must be contiguous {dtype} {tuple(shape)} on {dev}, got {t.dtype} {tuple(t.shape)} on {t.device}')
+
+
+def puzzle_distances_from_logits(logits: torch.Tensor, pi: torch.Tensor, pj: torch.Tensor, dq: torch.Tensor, bad: torch.Tensor):
+    """dq[s, pi[r], pj[r]] = uint32(trunc(fp32(fp32(1 - sigmoid(logits[r, (s + 3) % 4])) * 1000))) for s = 0..3 (top, right, bottom,
+    left).  logits float32 [m, 4], pi / pj int64 [m], dq int32 [4, n, n]; a pair outside [0, n) or with i == j sets bad int32 [1]."""
+    _need_gpu(logits, pi, pj, dq, bad)
+    m, dev = pi.numel(), dq.device
+    n = dq.shape[1]
+    _puzzle_check('logits', logits, torch.float32, (m, 4), dev)
+    _puzzle_check('pi', pi, torch.int64, (m,), dev)
+    _puzzle_check('pj', pj, torch.int64, (m,), dev)
+    _puzzle_check('dq', dq, torch.int32, (4, n, n), dev)
+    _puzzle_check('bad', bad, torch.int32, (1,), dev)
+    _lib.call('vited_puzzle_distances_from_logits', _ptr(logits), _ptr(pi), _ptr(pj), m, n, _ptr(dq), _ptr(bad), _stream())
+
+
+def puzzle_compat_init(dq: torch.Tensor) -> dict:
+    """InterPieceDistance.__init__ on the device: a dict of the state tensors (min_d, second_d, candidate, best_buddy, compat,
+    mutual, start_count, start_total, start_order) of the distances dq int32 [4, n, n]."""
+    _need_gpu(dq)
+    n, dev = dq.shape[1], dq.device
+    _puzzle_check('dq', dq, torch.int32, (4, n, n), dev)
+    st = {'min_d': torch.empty((n, 4), dtype=torch.int64, device=dev), 'second_d': torch.empty((n, 4), dtype=torch.int64, device=dev),
+          'candidate': torch.empty((n, 4), dtype=torch.int32, device=dev), 'best_buddy': torch.empty((n, 4), dtype=torch.int32, device=dev),
+          'compat': torch.empty((4, n, n), dtype=torch.float32, device=dev), 'mutual': torch.empty((4, n, n), dtype=torch.float32, device=dev),
+          'start_count': torch.empty(n, dtype=torch.int32, device=dev), 'start_total': torch.empty(n, dtype=torch.float32, device=dev),
+          'start_order': torch.empty(n, dtype=torch.int32, device=dev)}
+    _lib.call('vited_puzzle_compat_init', _ptr(dq), n, *(_ptr(st[k]) for k in ('min_d', 'second_d', 'candidate', 'best_buddy', 'compat',
+                                                                                   'mutual', 'start_count', 'start_total', 'start_order')),
+              _stream())
+    return st
+
+
+def puzzle_compat_recalc(dq: torch.Tensor, placed: torch.Tensor, st: dict, changed: torch.Tensor):
+    """recalculate_remaining_piece_compatibilities(placed) on the state ``st`` of puzzle_compat_init, in place; changed int32 [n]
+    receives 1 for every piece whose min / second-best distances moved.  placed int32 [n] (0 / 1)."""
+    _need_gpu(dq, placed, changed)
+    n, dev = dq.shape[1], dq.device
+    _puzzle_check('dq', dq, torch.int32, (4, n, n), dev)
+    _puzzle_check('placed', placed, torch.int32, (n,), dev)
+    _puzzle_check('changed', changed, torch.int32, (n,), dev)
+    _lib.call('vited_puzzle_compat_recalc', _ptr(dq), n, _ptr(placed), _ptr(st['min_d']), _ptr(st['second_d']), _ptr(st['compat']),
+              _ptr(st['mutual']), _ptr(changed), _stream())
+
+
+def puzzle_best_slot(mutual: torch.Tensor, placed: torch.Tensor, slot_piece: torch.Tensor, slot_side: torch.Tensor,
+                     out: torch.Tensor | None = None) -> torch.Tensor:
+    """The packed int64 [1] word of the first maximum of mutual[(slot_side[k] + 2) % 4, p, slot_piece[k]] over unplaced p ascending
+    x slot k (see include/vited.h; decode with puzzle_unpack_slot).  placed, slot_piece, slot_side int32."""
+    _need_gpu(mutual, placed, slot_piece, slot_side)
+    n, dev, k = mutual.shape[1], mutual.device, slot_piece.numel()
+    _puzzle_check('mutual', mutual, torch.float32, (4, n, n), dev)
+    _puzzle_check('placed', placed, torch.int32, (n,), dev)
+    _puzzle_check('slot_piece', slot_piece, torch.int32, (k,), dev)
+    _puzzle_check('slot_side', slot_side, torch.int32, (k,), dev)
+    out = torch.empty(1, dtype=torch.int64, device=dev) if out is None else out
+    _lib.call('vited_puzzle_best_slot', _ptr(mutual), n, _ptr(placed), _ptr(slot_piece), _ptr(slot_side), k, _ptr(out), _stream())
+    return out
+
+
+def puzzle_unpack_slot(word: int, slots: int):
+    """(piece, slot index) of a vited_puzzle_best_slot word; None when no piece was unplaced."""
+    word &= (1 << 64) - 1
+    if word == 0:
+        return None
+    lin = 0xffffffff - (word & 0xffffffff)
+    return lin // slots, lin % slots
