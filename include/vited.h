@@ -423,6 +423,21 @@ int vited_puzzle_compat_recalc(const int* dq, int64_t n, const int* placed, int6
 int vited_puzzle_best_slot(const float* mutual, int64_t n, const int* placed, const int* slot_piece, const int* slot_side,
                            int64_t slots, int64_t* best, void* stream);
 
+/* ---- validation metrics of a multi-output binary classifier (main.py:49-132, DefaultTrainer.validate) -------------------------
+ * vited_cls_metrics_update: one validation batch of logits [batch, classes] and targets [batch, classes] (fp32, row strides
+ *   ld_logits / ld_targets >= classes, unit column stride; 1 <= classes <= 64, 1 <= batch <= INT32_MAX), one workgroup:
+ *   loss   = BCEWithLogitsLoss (mean over batch x classes): an fp32 sum in a fixed order divided by batch * classes in fp32
+ *   (an infinite or NaN element loss gives torch's inf / NaN);
+ *   per column, pred = logit > 0 (NaN and -0 give 0): acc = (correct / batch) * 100 and sklearn 1.7's macro f1 / precision /
+ *   recall (fp64) over the labels present in unique(target U pred), P = tp / npred, R = tp / ntrue (0 where the count is 0),
+ *   F1 = 2 tp / (ntrue + npred); the batch values are the column sums in column order divided by classes.
+ *   meters (fp64 [10], device): (sum, count) of loss, acc, f1, precision, recall, updated as AverageMeter.update(val, n=batch):
+ *   sum += val * batch, count += batch (loss: the fp32 mean widened).  last (fp64 [5], device) receives the batch's 5 values.
+ *   A target that is neither 0 nor 1 is not counted and sets bit 0 of *bad (int32, device).  No host sync, no allocation;
+ *   bit-identical from run to run. */
+int vited_cls_metrics_update(const float* logits, int64_t ld_logits, const float* targets, int64_t ld_targets, int64_t batch,
+                             int64_t classes, double* meters, double* last, int* bad, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

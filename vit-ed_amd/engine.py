@@ -3,8 +3,9 @@ re-plumbed for MI355X: one process per GPU, RCCL all-reduce of a single flat fp3
 over xGMI instead of c10d's 25 MB DDP buckets, bf16 autocast instead of fp16 + GradScaler, and the
 whole forward+backward replayable as one hipGraph.
 
-Only what drives the hot path is here; data loading, logging,
-checkpoint rotation and validation stay in the reference's ``Trainer``.
+Only what drives the hot path is here, with the evaluation paths
+on the device (retrieval, geshaem, puzzle, and ``validate_classifier`` for main.py's validation); data
+loading, logging and checkpoint rotation stay in the reference's ``Trainer``.
 """
 from __future__ import annotations
 
@@ -1336,3 +1337,114 @@ def puzzle_accuracy(solution: PuzzleSolution, true_locations) -> dict:
             got = int(placed_id[r, c]) if 0 <= r < g_rows and 0 <= c < g_cols else -1
             neighbors += (None if got < 0 else got) == want
     return {'Direct_Standard': standard / n, 'Direct_Modified': modified / n, 'neighbor': neighbors / (4 * n), 'perfect': standard == n}
+
+
+# ---------------------------------------------------------------------------------------------
+# validation of the multi-output binary classifier (main.py:49-132, DefaultTrainer.validate)
+# ---------------------------------------------------------------------------------------------
+_METERS = ('loss', 'acc', 'f1', 'precision', 'recall')
+
+
+class MeterValue(NamedTuple):
+    """AverageMeter's ``val`` (the last batch's value) and ``avg`` (sum / count on this rank)."""
+    val: float
+    avg: float
+
+
+class ValidationResult(NamedTuple):
+    """The averages ``DefaultTrainer.validate`` logs after its all-reduce; ``loss`` is what it returns.  ``samples``: the
+    all-reduced sample count (fp32, as the reference's meters hold it)."""
+    loss: float
+    acc: float
+    f1: float
+    precision: float
+    recall: float
+    samples: int
+
+
+class ClassificationMeters:
+    """The reference's five validation AverageMeters (loss, acc, f1, precision, recall) on the device.
+
+    ``update(logits, targets)`` is one launch of vited_cls_metrics_update per batch (no host sync): it replaces main.py:73-93, the
+    host copy of the batch and the 16 sklearn calls.  ``values()`` copies the meters to the host once, for the PRINT_FREQ log
+    lines.  ``all_reduce(group)`` replaces the six ``AverageMeter.all_reduce`` calls (main.py:113-119) with ONE fp32 SUM
+    all-reduce of every (sum, count), rounded to fp32 first as the reference rounds them (also at world size 1); the bad-target
+    flag travels in the same reduction, so every rank raises together."""
+
+    def __init__(self, num_classes: int = 4, device='cuda'):
+        self.num_classes = int(num_classes)
+        if not 1 <= self.num_classes <= 64:
+            raise ValueError(f'num_classes must be in [1, 64], got {num_classes}')
+        self.device = torch.device(device)
+        self.meters = torch.zeros(2 * len(_METERS), dtype=torch.float64, device=self.device)   # (sum, count) per meter
+        self.last = torch.zeros(len(_METERS), dtype=torch.float64, device=self.device)
+        self.bad = torch.zeros(1, dtype=torch.int32, device=self.device)
+
+    def reset(self):
+        self.meters.zero_()
+        self.last.zero_()
+        self.bad.zero_()
+
+    def update(self, logits: torch.Tensor, targets: torch.Tensor):
+        from . import ops                                   # ops refuses CPU tensors: no CPU fallback
+        if logits.dim() != 2 or logits.shape[1] != self.num_classes:
+            raise ValueError(f'logits must be [B, {self.num_classes}], got {tuple(logits.shape)}')
+        ops.cls_metrics_update(logits, targets, self.meters, self.last, self.bad)
+
+    def values(self) -> dict:
+        """name -> MeterValue(val, avg) of each meter on this rank (one device-to-host copy)."""
+        host = torch.cat([self.last, self.meters]).tolist()
+        last, state = host[:len(_METERS)], host[len(_METERS):]
+        return {name: MeterValue(last[k], state[2 * k] / state[2 * k + 1] if state[2 * k + 1] else 0.0)
+                for k, name in enumerate(_METERS)}
+
+    def all_reduce(self, group=None) -> ValidationResult:
+        """The all-reduced averages.  Raises ValueError when a target other than 0 / 1 was seen on any rank, and when no sample
+        was added on any rank.  Joins the reduction over ``group`` (None: the default group) when torch.distributed is
+        initialised; otherwise the result is this process's."""
+        state = torch.cat([self.meters.to(torch.float32), self.bad.to(torch.float32)])   # AverageMeter.all_reduce's fp32 tensor
+        if dist.is_available() and dist.is_initialized():
+            dist.all_reduce(state, op=dist.ReduceOp.SUM, group=group)
+        host = state.tolist()
+        if host[-1]:
+            raise ValueError('validation targets must be 0 or 1: vited_cls_metrics_update saw another value')
+        if not host[1]:
+            raise ValueError('no validation sample was added before all_reduce')
+        avg = [host[2 * k] / host[2 * k + 1] for k in range(len(_METERS))]
+        return ValidationResult(*avg, samples=int(host[1]))
+
+
+@torch.no_grad()
+def validate_classifier(model, data_loader, *, amp: bool = True, group=None, print_freq: int | None = None,
+                        log=None) -> ValidationResult:
+    """``DefaultTrainer.validate`` (main.py:49-132) with its metrics on the device.
+
+    ``model``: the classifier (a DDP wrapper too), run in eval mode under no_grad and bf16 autocast when ``amp``; its previous
+    mode is restored.  ``data_loader`` yields (images, targets [B, C] of 0 / 1): batches already on the model's device are used
+    as they are, host batches go through DevicePrefetcher.  ``log(idx, values)`` is called with ``ClassificationMeters.values()``
+    on every batch with idx % print_freq == 0 (the only batches that wait for the device).  One all-reduce over ``group`` at the
+    end; the result's ``loss`` is what the reference's validate() returns."""
+    import itertools
+    dev = next(model.parameters()).device
+    batches = iter(data_loader)
+    first = next(batches, None)
+    if first is None:
+        raise ValueError('the validation loader yielded no batch')
+    batches = itertools.chain([first], batches)
+    if not (torch.is_tensor(first[0]) and first[0].device == dev):
+        batches = DevicePrefetcher(batches, dev)
+    meters = None
+    was_training = model.training
+    model.eval()
+    try:
+        for idx, (images, target) in enumerate(batches):
+            with torch.autocast(dev.type, dtype=torch.bfloat16, enabled=amp):
+                output = model(images)
+            if meters is None:
+                meters = ClassificationMeters(output.shape[1], dev)
+            meters.update(output, target)
+            if log is not None and print_freq and idx % print_freq == 0:
+                log(idx, meters.values())
+    finally:
+        model.train(was_training)
+    return meters.all_reduce(group)

@@ -783,3 +783,36 @@ def puzzle_unpack_slot(word: int, slots: int):
         return None
     lin = 0xffffffff - (word & 0xffffffff)
     return lin // slots, lin % slots
+
+
+# ---- validation metrics of a multi-output binary classifier (include/vited.h) ------------------------------------------------
+def cls_metrics_update(logits: torch.Tensor, targets: torch.Tensor, meters: torch.Tensor, last: torch.Tensor, bad: torch.Tensor):
+    """One validation batch (main.py:73-93): BCE-with-logits loss, accuracy and macro f1 / precision / recall of pred = logit > 0
+    per column, averaged over the columns and added to the device meters as AverageMeter.update(val, n=B) does.
+
+    ``logits`` / ``targets`` [B, C] (1 <= C <= 64) on one device, unit column stride; bf16 / fp16 logits and non-fp32 targets are
+    cast to fp32.  ``meters`` fp64 [10]: (sum, count) of loss, acc, f1, precision, recall; ``last`` fp64 [5] receives the batch's
+    values; a target other than 0 / 1 sets ``bad`` int32 [1].  One launch, no host sync."""
+    _need_gpu(logits, targets, meters, last, bad)
+    dev = meters.device
+    if logits.dim() != 2 or tuple(targets.shape) != tuple(logits.shape):
+        raise ValueError(f'logits and targets must be [B, C] of the same shape, got {tuple(logits.shape)} and {tuple(targets.shape)}')
+    b, c = logits.shape
+    if b < 1 or not 1 <= c <= 64:
+        raise ValueError(f'need B >= 1 rows and 1 <= C <= 64 columns, got [{b}, {c}]')
+    if logits.device != dev or targets.device != dev:
+        raise ValueError(f'logits ({logits.device}) and targets ({targets.device}) must be on the meters\' device {dev}')
+    if logits.dtype not in _FLOATS:
+        raise TypeError(f'logits must be float32 / bfloat16 / float16, got {logits.dtype}')
+    if targets.dtype == torch.bool or targets.is_complex():
+        raise TypeError(f'targets must be real numbers 0 / 1, got {targets.dtype}')
+    logits, targets = logits.float(), targets.float()
+    for name, t in (('logits', logits), ('targets', targets)):
+        if (c > 1 and t.stride(1) != 1) or (b > 1 and t.stride(0) < c):
+            raise ValueError(f'{name} must have a unit column stride and a row stride >= {c}, got strides {t.stride()}')
+    _puzzle_check('meters', meters, torch.float64, (10,), dev)
+    _puzzle_check('last', last, torch.float64, (5,), dev)
+    _puzzle_check('bad', bad, torch.int32, (1,), dev)
+    ld = lambda t: t.stride(0) if b > 1 else c
+    _lib.call('vited_cls_metrics_update', _ptr(logits), ld(logits), _ptr(targets), ld(targets), b, c, _ptr(meters), _ptr(last), _ptr(bad),
+              _stream())
