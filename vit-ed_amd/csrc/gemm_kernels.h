@@ -13,6 +13,10 @@ bool gemm_nt_mfma_supported(const void* A, int64_t lda, const void* B, int64_t l
                             int epilogue, const EpiParams& ep);
 int gemm_nt_mfma(const void* A, int64_t lda, const void* B, int64_t ldb, int64_t M, int64_t N, int64_t K, int epilogue,
                  const EpiParams& ep, hipStream_t s);
+// K = 384, N % 128 == 0 with the A operand in registers (gemm_nt_k384.hip); waves = 8 (256-row panels) or 4 (128-row panels)
+bool gemm_nt_areg_supported(int64_t ldw, int64_t M, int64_t N, int64_t K, int epilogue);
+int gemm_nt_areg(const void* A, int64_t lda, const void* W, int64_t ldw, int64_t M, int64_t N, int epilogue, int waves,
+                 const EpiParams& ep, hipStream_t s);
 bool gemm_tn_mfma_supported(const void* dY, int64_t lddy, const void* X, int64_t ldx, int64_t M, int64_t N, int64_t K);
 int64_t gemm_tn_mfma_splits(int64_t M, int64_t N, int64_t K);
 int gemm_tn_mfma(const void* dY, int64_t lddy, const void* X, int64_t ldx, int64_t M, int64_t N, int64_t K, int64_t splits,

@@ -33,6 +33,7 @@ __device__ __forceinline__ void nt_stage_load(const bf16* __restrict__ A, int64_
                                               char* stage, int wave, int lane) {
     using C = NtCfg<BKT, WM>;
     const int rsub = lane / C::CHUNKS, cp = lane % C::CHUNKS;
+#ifndef NT_DBG_NO_A_DMA   // timing only: the MFMAs then read stale LDS; the bound on what removing the A staging can buy
 #pragma unroll
     for (int i = 0; i < 32 / C::ROWS_PER_DMA; ++i) {          // A: 32 rows per wave
         const int r = wave * 32 + i * C::ROWS_PER_DMA + rsub;
@@ -43,6 +44,7 @@ __device__ __forceinline__ void nt_stage_load(const bf16* __restrict__ A, int64_
         if constexpr (ASM_DMA) glds16_asm(asrc, stage + (wave * 32 + i * C::ROWS_PER_DMA) * C::ROW_BYTES);
         else glds16(asrc, stage + (wave * 32 + i * C::ROWS_PER_DMA) * C::ROW_BYTES);
     }
+#endif
     constexpr int RB = BN / (2 * WM);                         // B: 128 rows over all waves
 #pragma unroll
     for (int i = 0; i < RB / C::ROWS_PER_DMA; ++i) {
@@ -98,7 +100,11 @@ gemm_nt_mfma_kernel(const bf16* __restrict__ A, int64_t lda, const bf16* __restr
 
     using C = NtCfg<BKT, WM>;
     constexpr bool RING = STAGES >= 3;
+#ifdef NT_DBG_NO_A_DMA
+    constexpr int PER = (BN / (2 * WM)) / C::ROWS_PER_DMA;
+#else
     constexpr int PER = 32 / C::ROWS_PER_DMA + (BN / (2 * WM)) / C::ROWS_PER_DMA;   // DMA instructions per stage per wave
+#endif
     const int nk = (int)(K / BKT);
     nt_stage_load<BKT, WM, RING>(A, lda, B, ldb, m0, n0, M, N, 0, smem, wave, lane);
     if constexpr (RING) {
@@ -229,9 +235,27 @@ static int launch_nt(const bf16* a, int64_t lda, const bf16* b, int64_t ldb, int
     return VITED_OK;
 }
 
+// K = 384 shapes that take the A-in-registers kernel (gemm_nt_k384.hip): 0 = none, else its waves per workgroup.  Adopted per
+// epilogue class where the step showed a win: the dz multiply on 8-wave workgroups (-30 % isolated at
+// M = 65,536, a win at every row count probed and traced), the plain-store qkv shape (N >= 1152) on 4-wave workgroups from 65,536
+// rows (in the step 93 -> 74 us; at 24,576 rows a workgroup's share is 3-5 items, the up-front A load is not amortised and the
+// tile kernel is 13-18 % faster; kv, N = 768, traced 3 % SLOWER in the step and stays).  fc1 + GELU' stays on the tile kernel:
+// -7 % isolated on 4 waves, nothing in the step.
+template <int EPI> static inline int nt_areg_waves(int64_t ldb, int64_t M, int64_t N, int64_t K) {
+    if (!gemm_nt_areg_supported(ldb, M, N, K, EPI)) return 0;
+#ifdef VITED_TUNING   // experiment builds only: VITED_NT_AREG = 0 (never) | 4 | 8 (that geometry wherever the shape allows); read on
+                      // every call so that one process can interleave the kernels (profiles/nt_k384_probe.py)
+    if (const char* force = getenv("VITED_NT_AREG")) return atoi(force);
+#endif
+    if (EPI == VITED_EPI_MUL) return 8;
+    if (EPI == VITED_EPI_STORE && N >= 1152 && M >= 65536) return 4;
+    return 0;
+}
+
 template <int EPI>
 static int dispatch_nt(const bf16* a, int64_t lda, const bf16* b, int64_t ldb, int64_t M, int64_t N, int64_t K, const EpiParams& ep,
                        hipStream_t s) {
+    if (const int waves = nt_areg_waves<EPI>(ldb, M, N, K)) return gemm_nt_areg(a, lda, b, ldb, M, N, EPI, waves, ep, s);
     // BK = 32 (4 workgroups / CU) pays only when the grid is large: at N = 384 (1,536 tiles) BK = 64 is 9-14 % faster
     bool shallow = K <= 512 && N >= 768;
     // measured (M = 65536): the 256-row tile wins 5-10 % on plain-store K = 384 GEMMs with

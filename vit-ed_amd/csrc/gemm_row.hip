@@ -222,7 +222,7 @@ gemm_row_kernel(const RowArgs a) {
         __builtin_amdgcn_sched_barrier(0);
     };
     // The fragment reads of an L slot retire INSIDE it (under the partner group's MFMAs): the M slot then opens with its first MFMA
-    // instead of the reads' latency (compute-only loop 60 -> ?? us at K = 1536).
+    // instead of the reads' latency (ROW_DBG_LATE_LGKM leaves the wait to the compiler, in front of the M slot's first MFMA, for an A/B).
     auto landed = [&]() {
 #ifndef ROW_DBG_LATE_LGKM
         __builtin_amdgcn_s_waitcnt(0xc07f);       // lgkmcnt(0)
