@@ -75,7 +75,7 @@ def rel(a, b):
 
 
 def like(tap, ref, batch):
-    """The last decoder block of the HIP path runs on the cls rows only (functions._dec_block_fwd): compare those rows."""
+    """The last decoder block of the HIP path runs on the cls rows only (functions._dec_self_fwd): compare those rows."""
     if tap.numel() == ref.numel():
         return ref.reshape(-1)
     return ref.reshape(batch, -1, ref.shape[-1])[:, 0, :].reshape(-1)

@@ -61,6 +61,57 @@ def test_build_model_matches_reference_layout(vited, cfg, params, flops):
     assert pjs.QKV_BIAS is True
 
 
+ENC_BLOCK_KEYS = ('norm1.weight', 'norm1.bias', 'attn.qkv.weight', 'attn.qkv.bias', 'attn.proj.weight',
+                  'attn.proj.bias', 'norm2.weight', 'norm2.bias', 'mlp.fc1.weight', 'mlp.fc1.bias',
+                  'mlp.fc2.weight', 'mlp.fc2.bias')
+DEC_BLOCK_KEYS = ('norm1.weight', 'norm1.bias', 'attn.qkv.weight', 'attn.qkv.bias', 'attn.proj.weight',
+                  'attn.proj.bias', 'norm_cross.weight', 'norm_cross.bias', 'norm_context.weight',
+                  'norm_context.bias', 'cross_attn.q.weight', 'cross_attn.q.bias', 'cross_attn.kv.weight',
+                  'cross_attn.kv.bias', 'cross_attn.proj.weight', 'cross_attn.proj.bias', 'norm2.weight',
+                  'norm2.bias', 'mlp.fc1.weight', 'mlp.fc1.bias', 'mlp.fc2.weight', 'mlp.fc2.bias')
+ENC_SHARED_KEYS = ('patch_embed.proj.weight', 'patch_embed.proj.bias', 'pos_embed')
+DEC_SHARED_KEYS = ('patch_embed.proj.weight', 'patch_embed.proj.bias', 'pos_embed', 'cls_token', 'norm.weight',
+                   'norm.bias', 'head.weight', 'head.bias')
+ENC_BLOCK_FIELDS = 'g1 b1 wqkv bqkv wproj bproj g2 b2 w1 bb1 w2 bb2'.split()
+DEC_BLOCK_FIELDS = 'g1 b1 wqkv bqkv wproj bproj gc bc gx bx wq bq wkv bkv wcp bcp g2 b2 w1 bb1 w2 bb2'.split()
+ENC_SHARED_FIELDS = 'pw pb pos'.split()
+DEC_SHARED_FIELDS = 'pw pb pos cls gN bN wh bh'.split()
+
+
+@pytest.mark.parametrize('cfg', [CFG_A, CFG_H, CFG_T])
+def test_parameter_bundles_name_the_modules_parameters(vited, cfg):
+    """functions.split_params turns the flat parameter lists that the autograd Functions receive into named bundles: every field
+    IS the parameter that the paired state_dict key names on the module (no tensor is created or moved: pure Python), the flat
+    order is the key order that model.py and the checkpoints use, and flatten_params undoes the split."""
+    F_ = vited.functions
+    assert F_.ENC_BLOCK_KEYS == ENC_BLOCK_KEYS and F_.DEC_BLOCK_KEYS == DEC_BLOCK_KEYS
+    assert F_.ENC_SHARED_KEYS == ENC_SHARED_KEYS and F_.DEC_SHARED_KEYS == DEC_SHARED_KEYS
+    m = vited.build_model(vited.config_from_yaml(cfg))
+
+    def named(module, dotted):
+        for part in dotted.split('.'):
+            module = getattr(module, part)
+        return module
+
+    for flat, types, shared_pairs, block_pairs, modules in (
+            (m._encoder_params(), (F_.EncShared, F_.EncBlock), zip(ENC_SHARED_FIELDS, ENC_SHARED_KEYS), zip(ENC_BLOCK_FIELDS, ENC_BLOCK_KEYS), m.blocks),
+            (m._decoder_params(), (F_.DecShared, F_.DecBlock), zip(DEC_SHARED_FIELDS, DEC_SHARED_KEYS), zip(DEC_BLOCK_FIELDS, DEC_BLOCK_KEYS), m.cross_blocks)):
+        shared, blocks = F_.split_params(flat, *types)
+        shared_pairs, block_pairs = list(shared_pairs), list(block_pairs)
+        assert list(shared._fields) == [f for f, _ in shared_pairs] and len(blocks) == len(modules) > 0
+        for field, key in shared_pairs:
+            assert getattr(shared, field) is named(m, key), (field, key)
+        for block, module in zip(blocks, modules):
+            assert list(block._fields) == [f for f, _ in block_pairs]
+            for field, key in block_pairs:
+                assert getattr(block, field) is named(module, key), (field, key)
+        again = F_.flatten_params(shared, blocks)
+        assert len(again) == len(flat) and all(a is b for a, b in zip(again, flat))
+        with pytest.raises(ValueError):
+            F_.split_params(flat[:-1], *types)       # not a whole number of blocks
+    assert blocks[-1].wkv is m.cross_blocks[-1].cross_attn.kv.weight and shared.gN is m.norm.weight
+
+
 def test_checkpoint_roundtrip_with_oracle_weights(vited):
     s = vo.SHAPE_T
     o = vo.fill_closed_form_(vo.OracleViTED(s))

@@ -552,7 +552,8 @@ def test_mlp_no_grad_fused_head_plus_unfused_tail(vited, gpu):
     vited.ops.gemm = lambda *a, **k: (calls.append(('gemm', a[0].shape[0])), real[1](*a, **k))[1]
     try:
         with torch.no_grad():
-            y, saved, _ = F_._mlp_fwd(rt, x, gamma, beta, w1, b1, w2, b2, grad=False)
+            block = F_.EncBlock._make([None] * len(F_.EncBlock._fields))._replace(g2=gamma, b2=beta, w1=w1, bb1=b1, w2=w2, bb2=b2)
+            y, saved, _ = F_._mlp_fwd(rt, x, block, grad=False)
     finally:
         vited.ops.mlp_fwd, vited.ops.gemm = real
     assert saved is None and ('fused', head) in calls and ('gemm', rows - head) in calls, calls
@@ -747,7 +748,7 @@ def test_folded_context_kv_matches_the_per_block_form(vited, gpu):
 
 @pytest.mark.gpu
 def test_grouped_weight_gradient_launches_match_one_launch_per_block(vited, gpu):
-    """functions._DwBatch(blocks=True) sends the weight gradients of several blocks out in one launch (one row range per product
+    """functions._DwBatch sends the weight gradients of several blocks out in one launch (one row range per product
     when the tiles fill a round of workgroups) where round 3's first form launched once per block (up to 7 row ranges + a slab
     sum).  Same products, another fp32 summation order over the rows: every weight / bias gradient agrees to 1e-5 of its norm,
     everything that does not pass through a weight-gradient launch (logits, LayerNorm gradients) bit for bit."""

@@ -14,7 +14,9 @@ exact path).
 """
 from __future__ import annotations
 
+import contextlib
 import os
+from collections import namedtuple
 
 import torch
 
@@ -23,17 +25,36 @@ from ._lib import (B_KN, B_NK, EPI_GELU_GRAD, EPI_MUL, EPI_RESIDUAL, EPI_STORE, 
 
 LN_EPS = 1e-6  # partial(nn.LayerNorm, eps=1e-6), vision_transformer.py:348
 
-ENC_BLOCK_KEYS = ('norm1.weight', 'norm1.bias', 'attn.qkv.weight', 'attn.qkv.bias', 'attn.proj.weight',
-                  'attn.proj.bias', 'norm2.weight', 'norm2.bias', 'mlp.fc1.weight', 'mlp.fc1.bias',
-                  'mlp.fc2.weight', 'mlp.fc2.bias')
-DEC_BLOCK_KEYS = ('norm1.weight', 'norm1.bias', 'attn.qkv.weight', 'attn.qkv.bias', 'attn.proj.weight',
-                  'attn.proj.bias', 'norm_cross.weight', 'norm_cross.bias', 'norm_context.weight',
-                  'norm_context.bias', 'cross_attn.q.weight', 'cross_attn.q.bias', 'cross_attn.kv.weight',
-                  'cross_attn.kv.bias', 'cross_attn.proj.weight', 'cross_attn.proj.bias', 'norm2.weight',
-                  'norm2.bias', 'mlp.fc1.weight', 'mlp.fc1.bias', 'mlp.fc2.weight', 'mlp.fc2.bias')
-ENC_SHARED_KEYS = ('patch_embed.proj.weight', 'patch_embed.proj.bias', 'pos_embed')
-DEC_SHARED_KEYS = ('patch_embed.proj.weight', 'patch_embed.proj.bias', 'pos_embed', 'cls_token', 'norm.weight',
-                   'norm.bias', 'head.weight', 'head.bias')
+
+def _bundle(name, table):
+    """(namedtuple of the short names, tuple of the state_dict keys) of one ``field=key`` table, the only statement of which field
+    is which parameter and of their order: model.py and the checkpoint layout read the keys, the code below reads the fields."""
+    fields, keys = zip(*(pair.split('=') for pair in table.split()))
+    return namedtuple(name, fields), keys
+
+
+_ATTN = 'g1=norm1.weight b1=norm1.bias wqkv=attn.qkv.weight bqkv=attn.qkv.bias wproj=attn.proj.weight bproj=attn.proj.bias '
+_CROSS = ('gc=norm_cross.weight bc=norm_cross.bias gx=norm_context.weight bx=norm_context.bias wq=cross_attn.q.weight '
+          'bq=cross_attn.q.bias wkv=cross_attn.kv.weight bkv=cross_attn.kv.bias wcp=cross_attn.proj.weight bcp=cross_attn.proj.bias ')
+_MLP = 'g2=norm2.weight b2=norm2.bias w1=mlp.fc1.weight bb1=mlp.fc1.bias w2=mlp.fc2.weight bb2=mlp.fc2.bias'
+_PATCH = 'pw=patch_embed.proj.weight pb=patch_embed.proj.bias pos=pos_embed '
+EncBlock, ENC_BLOCK_KEYS = _bundle('EncBlock', _ATTN + _MLP)
+DecBlock, DEC_BLOCK_KEYS = _bundle('DecBlock', _ATTN + _CROSS + _MLP)
+EncShared, ENC_SHARED_KEYS = _bundle('EncShared', _PATCH)
+DecShared, DEC_SHARED_KEYS = _bundle('DecShared', _PATCH + 'cls=cls_token gN=norm.weight bN=norm.bias wh=head.weight bh=head.bias')
+
+
+def split_params(params, shared_type, block_type):
+    """Flat ``*params`` of a Function (model._encoder_params / _decoder_params) -> (shared bundle, [block bundle, ...])."""
+    ns, nb = len(shared_type._fields), len(block_type._fields)
+    if len(params) < ns or (len(params) - ns) % nb:
+        raise ValueError(f'{len(params)} parameters are not {ns} shared + a whole number of {nb}-parameter blocks')
+    return shared_type._make(params[:ns]), [block_type._make(params[i: i + nb]) for i in range(ns, len(params), nb)]
+
+
+def flatten_params(shared, blocks):
+    """Inverse of split_params: the flat tuple in key order (what a Function's backward returns for ``*params``)."""
+    return (*shared, *(g for block in blocks for g in block))
 
 
 _step_hook_installed = False
@@ -77,7 +98,7 @@ class Runtime:
         self.input_mean, self.input_std = (0.5, 0.5, 0.5), (0.5, 0.5, 0.5)   # Normalize() of data/transforms.py:14-18, for uint8 inputs
         self.keep_attn = False      # MODEL.PJS.KEEP_ATTN: also materialise the attention maps (visualisation slow path)
         self.attn_store = {}        # (kind, block index, 'attn' | 'cross_attn') -> {'attn': ..., 'grad': ...}
-        self.cls_tail = os.environ.get('VITED_CLS_TAIL', '1') != '0'   # last decoder block on the cls rows only (exact; see _dec_block_fwd)
+        self.cls_tail = os.environ.get('VITED_CLS_TAIL', '1') != '0'   # last decoder block on the cls rows only (exact; see _dec_self_fwd)
         self.fused_mlp = os.environ.get('VITED_FUSED_MLP', '1') != '0'   # vited_mlp_fwd on the no-grad paths
         self.fused_ln = os.environ.get('VITED_FUSED_LN', '1') != '0'     # LayerNorm inside the neighbouring Linear's kernel (gemm_row.hip)
         self.batch_dw = os.environ.get('VITED_BATCH_DW', '1') != '0'     # a block's weight gradients in one launch (vited_linear_bwd_weight_batched)
@@ -224,19 +245,17 @@ def _weight_grads(rt, dy, x_saved, w, b):
 
 
 class _DwBatch:
-    """``with _DwBatch(rt):`` around one block's backward: the weight-gradient products issued inside are collected and
-    launched together (vited_linear_bwd_weight_batched) - they only read tensors the block's backward already produced, and
-    nothing inside a backward pass consumes a weight gradient.
-
-    ``with _DwBatch(rt, blocks=True) as g:`` around a LOOP over blocks, ``with g.block():`` around each: the products of several
-    blocks go out together, flushed when another block of the same size would no longer fit one round of 256 workgroups
-    (an encoder block of the embed-384 models is 36 output tiles of 128 x 384: seven blocks = 252 tiles = ONE row range per
-    product - no split-M slabs to write and sum - where one block alone is cut into 7 row ranges)."""
+    """``with _DwBatch(rt) as g:`` around a backward's LOOP over blocks, ``with g.block():`` around each block: the weight-gradient
+    products issued inside are collected and launched together (vited_linear_bwd_weight_batched) - they only read tensors the
+    block's backward already produced, and nothing inside a backward pass consumes a weight gradient.  The products of several
+    blocks go out together (rt.group_dw), flushed when another block of the same size would no longer fit one round of 256
+    workgroups (an encoder block of the embed-384 models is 36 output tiles of 128 x 384: seven blocks = 252 tiles = ONE row range
+    per product - no split-M slabs to write and sum - where one block alone is cut into 7 row ranges)."""
 
     ROUND = 256
 
-    def __init__(self, rt, blocks=False, kind=None):
-        self.rt, self.blocks, self.kind = rt, blocks and rt.group_dw, kind
+    def __init__(self, rt, kind=None):
+        self.rt, self.blocks, self.kind = rt, rt.group_dw, kind
 
     def __enter__(self):
         self.outer = self.rt.dw_queue
@@ -244,8 +263,10 @@ class _DwBatch:
         self.mark = 0
         return self
 
+    @contextlib.contextmanager
     def block(self):
-        return _DwBlock(self)
+        yield
+        self._end_of_block()
 
     @staticmethod
     def _tiles(items):
@@ -269,19 +290,8 @@ class _DwBatch:
             return
         self.rt.dw_queue, self.mark = [], 0
         with _BlockSpan(self.rt, self.kind, len(q), 'dw'):     # (bench.py: these launches belong to the blocks queued since the last flush)
-            self._launch(q)
-
-    @staticmethod
-    def _launch(q):
-        for acc in (True, False):
-            group = [(dy, x, dw, db) for dy, x, dw, db, a in q if a == acc]
-            for i in range(0, len(group), ops.MAX_BATCHED_WEIGHT_GRADS):
-                part = group[i: i + ops.MAX_BATCHED_WEIGHT_GRADS]
-                if len(part) > 1 and ops.linear_bwd_weight_batched(part, acc):
-                    continue
-                for dy, x, dw, db in part:
-                    ops.linear_bwd_weight(dy, x, want_bias=db is not None, dw_out=dw, db_out=db) if acc else \
-                        _overwrite_weight_grad(dy, x, dw, db)
+            for acc in (True, False):
+                _launch_weight_grads([(dy, x, dw, db) for dy, x, dw, db, a in q if a == acc], acc)
 
     def __exit__(self, exc_type, *exc):
         if exc_type is None:
@@ -290,35 +300,30 @@ class _DwBatch:
         return False
 
 
-class _DwBlock:
-    def __init__(self, group):
-        self.group = group
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, exc_type, *exc):
-        if exc_type is None:
-            self.group._end_of_block()
-        return False
-
-
-def _overwrite_weight_grad(dy, x, dw, db):
-    got_w, got_b = ops.linear_bwd_weight(dy, x, want_bias=db is not None)
-    dw.copy_(got_w)
-    if db is not None:
-        db.copy_(got_b)
+def _launch_weight_grads(items, accumulate):
+    """items: [(dy, x, dW target, dbias target | None)].  One batched launch per MAX_BATCHED_WEIGHT_GRADS products where the
+    batched kernel covers them, otherwise one launch per product."""
+    for i in range(0, len(items), ops.MAX_BATCHED_WEIGHT_GRADS):
+        part = items[i: i + ops.MAX_BATCHED_WEIGHT_GRADS]
+        if len(part) > 1 and ops.linear_bwd_weight_batched(part, accumulate):
+            continue
+        for dy, x, dw, db in part:
+            if accumulate:
+                ops.linear_bwd_weight(dy, x, want_bias=db is not None, dw_out=dw, db_out=db)
+                continue
+            got_w, got_b = ops.linear_bwd_weight(dy, x, want_bias=db is not None)
+            dw.copy_(got_w)
+            if db is not None:
+                db.copy_(got_b)
 
 
-def _linear_bwd(rt, dy, x_saved, w, b=None, want_dx=True, aux=None):
-    """(dx | None, dW, db) of y = x W^T + b given dy (activation dtype)."""
-    dx = None
-    if want_dx:
-        wt, layout = rt.weight_t(w)
-        if aux is not None:
-            dx = ops.gemm(dy, wt, b_layout=layout, epilogue=EPI_MUL, aux=aux)
-        else:
-            dx = ops.gemm(dy, wt, b_layout=layout)
+def _linear_bwd(rt, dy, x_saved, w, b=None, aux=None):
+    """(dx, dW, db) of y = x W^T + b given dy (activation dtype); with ``aux`` dx is multiplied by it elementwise."""
+    wt, layout = rt.weight_t(w)
+    if aux is not None:
+        dx = ops.gemm(dy, wt, b_layout=layout, epilogue=EPI_MUL, aux=aux)
+    else:
+        dx = ops.gemm(dy, wt, b_layout=layout)
     dw, db = _weight_grads(rt, dy, x_saved, w, b)
     return dx, dw, db
 
@@ -345,7 +350,8 @@ def _res_linear(rt, a, w, bias, residual, ln=None):
 def _linear_ln_bwd(rt, dy, h_saved, w, bias, x, gamma, beta, mean, rstd, dx_in=None, dx_out=None, want_lp=True):
     """Backward of  y = LayerNorm(x; gamma, beta) W^T + bias  given dy: the input-gradient GEMM and the LayerNorm backward in
     ONE kernel when the row-complete kernel covers the shape (d(LayerNorm output) then never exists in HBM).
-    Returns (dx fp32 = dx_in + ..., dx_lp | None, dgamma, dbeta, dW, dbias) - gradients are None when accumulated in place."""
+    Returns (dx fp32 = dx_in + ..., dx_lp | None (dx itself on the exact path), dgamma, dbeta, dW, dbias) - gradients are None when
+    accumulated in place."""
     want_lp = want_lp and not rt.exact
     wt, layout = rt.weight_t(w)
     if layout == B_NK and _row_kernel_ok(rt, dy.shape[0], wt.shape[0], dy.shape[1], dy.dtype, dy, x, dx_in, dx_out):
@@ -359,7 +365,19 @@ def _linear_ln_bwd(rt, dy, h_saved, w, bias, x, gamma, beta, mean, rstd, dx_in=N
         dh = ops.gemm(dy, wt, b_layout=layout)
         dx, dx_lp, dg, db = _ln_bwd(rt, dh, x, gamma, beta, mean, rstd, dx_in=dx_in, dx_out=dx_out, want_lp=want_lp)
     dw, dbias = _weight_grads(rt, dy, h_saved, w, bias)
-    return dx, dx_lp, dg, db, dw, dbias
+    return dx, (dx if rt.exact else dx_lp), dg, db, dw, dbias
+
+
+@contextlib.contextmanager
+def _ln_sums(rt):
+    """``with _ln_sums(rt):`` around a Function's backward: the LayerNorm column sums that _linear_ln_bwd defers inside
+    (d gamma, d beta of the row-complete kernel) go out together at the end, one launch per 16 LayerNorms."""
+    rt.ln_queue = [] if not rt.exact else None
+    try:
+        yield
+        ops.layernorm_bwd_finish(rt.ln_queue)           # (nothing to do for None or an empty list)
+    finally:
+        rt.ln_queue = None
 
 
 def _keep_attention(rt, key, q, k):
@@ -424,9 +442,17 @@ def _fused_mlp_rows(rt, x, w1, grad):
     return min(tiles * FUSED_MLP_TILE, x.shape[0])
 
 
-def _mlp_fwd(rt, x, g, b, w1, b1, w2, b2, grad=True, ln=None, next_ln=None):
-    """x + fc2(gelu(fc1(LayerNorm(x)))).  ``ln`` = (h, mean, rstd) when the LayerNorm was already produced by the kernel that
-    wrote x; ``next_ln`` = (gamma, beta) of the LayerNorm that follows on the output.  Returns (y, saved | None, next | None)."""
+def _hand_over_ln(rt, x, P, grad):
+    """Whether the Linear kernels before and after this block's MLP (x: its input rows) also produce the LayerNorm that follows
+    them: always when training; on the no-grad path only when the one-kernel MLP, which does its own LayerNorm, leaves the rows."""
+    return grad or not _fused_mlp_rows(rt, x, P.w1, grad)
+
+
+def _mlp_fwd(rt, x, P, grad=True, ln=None, next_ln=None):
+    """x + fc2(gelu(fc1(LayerNorm(x)))) with the block's norm2 / mlp parameters (P: an EncBlock or a DecBlock).  ``ln`` = (h, mean,
+    rstd) when the LayerNorm was already produced by the kernel that wrote x; ``next_ln`` = (gamma, beta) of the LayerNorm that
+    follows on the output.  Returns (y, saved | None, next | None)."""
+    g, b, w1, b1, w2, b2 = P.g2, P.b2, P.w1, P.bb1, P.w2, P.bb2
     rows = _fused_mlp_rows(rt, x, w1, grad) if ln is None else 0
     if rows:
         y = torch.empty_like(x)
@@ -445,61 +471,66 @@ def _mlp_fwd(rt, x, g, b, w1, b1, w2, b2, grad=True, ln=None, next_ln=None):
     return y, (mean, rstd, h, gd, u), nxt
 
 
-def _mlp_bwd(rt, dy, dy_lp, x, g, b, w1, b1, w2, b2, saved):
+def _mlp_bwd(rt, dy, dy_lp, x, P, saved):
+    """Backward of _mlp_fwd.  Returns (dx, its low-precision copy, the six parameter gradients by field name)."""
     mean, rstd, h, gd, u = saved
-    dz, dw2, db2 = _linear_bwd(rt, dy_lp, u, w2, b2, aux=gd)
-    dx, dx_lp, dg, db, dw1, db1 = _linear_ln_bwd(rt, dz, h, w1, b1, x, g, b, mean, rstd, dx_in=dy)
-    return dx, (dx if rt.exact else dx_lp), (dg, db, dw1, db1, dw2, db2)
+    dz, dw2, dbb2 = _linear_bwd(rt, dy_lp, u, P.w2, P.bb2, aux=gd)
+    dx, dx_lp, dg2, db2, dw1, dbb1 = _linear_ln_bwd(rt, dz, h, P.w1, P.bb1, x, P.g2, P.b2, mean, rstd, dx_in=dy)
+    return dx, dx_lp, dict(g2=dg2, b2=db2, w1=dw1, bb1=dbb1, w2=dw2, bb2=dbb2)
 
 
-def _attn_branch_fwd(rt, x, g, b, wqkv, bqkv, wproj, bproj, batch, n, key=None, ln=None, next_ln=None):
-    """x + proj(attention(qkv(LayerNorm(x)))); ``ln`` / ``next_ln`` as in _mlp_fwd.  Returns (y, saved, next | None)."""
-    h, mean, rstd = ln if ln is not None else ops.layernorm_fwd(x, g, b, LN_EPS, rt.act_dtype)
-    qkv, o, lse = _self_attn_fwd(rt, h, wqkv, bqkv, batch, n, key)
-    y, nxt = _res_linear(rt, o, wproj, bproj, x, next_ln)
+def _attn_branch_fwd(rt, x, P, batch, n, key=None, ln=None, next_ln=None):
+    """x + proj(attention(qkv(LayerNorm(x)))) with the block's norm1 / attn parameters; ``ln`` / ``next_ln`` as in _mlp_fwd.
+    Returns (y, saved, next | None)."""
+    h, mean, rstd = ln if ln is not None else ops.layernorm_fwd(x, P.g1, P.b1, LN_EPS, rt.act_dtype)
+    qkv, o, lse = _self_attn_fwd(rt, h, P.wqkv, P.bqkv, batch, n, key)
+    y, nxt = _res_linear(rt, o, P.wproj, P.bproj, x, next_ln)
     return y, (mean, rstd, h, qkv, o, lse), nxt
 
 
-def _attn_branch_bwd(rt, dy, dy_lp, x, g, b, wqkv, bqkv, wproj, bproj, saved, batch, n, key=None):
+def _attn_branch_bwd(rt, dy, dy_lp, x, P, saved, batch, n, key=None):
+    """Backward of _attn_branch_fwd.  Returns (dx, its low-precision copy, the six parameter gradients by field name)."""
     mean, rstd, h, qkv, o, lse = saved
-    do, dwp, dbp = _linear_bwd(rt, dy_lp, o, wproj, bproj)
+    do, dwproj, dbproj = _linear_bwd(rt, dy_lp, o, P.wproj, P.bproj)
     dqkv = _self_attn_bwd(rt, do, qkv, o, lse, batch, n, key)
-    dx, dx_lp, dg, db, dwq, dbq = _linear_ln_bwd(rt, dqkv, h, wqkv, bqkv, x, g, b, mean, rstd, dx_in=dy)
-    return dx, (dx if rt.exact else dx_lp), (dg, db, dwq, dbq, dwp, dbp)
+    dx, dx_lp, dg1, db1, dwqkv, dbqkv = _linear_ln_bwd(rt, dqkv, h, P.wqkv, P.bqkv, x, P.g1, P.b1, mean, rstd, dx_in=dy)
+    return dx, dx_lp, dict(g1=dg1, b1=db1, wqkv=dwqkv, bqkv=dbqkv, wproj=dwproj, bproj=dbproj)
 
 
-def _patch_tokens_fwd(rt, img, pw, pb, pos, with_cls, cls=None, batch_index=None):
-    """timm PatchEmbed + pos-embed (+ cls row): returns x fp32 [B*rows, D] and the saved patch matrix."""
+def _patch_tokens_fwd(rt, img, S, with_cls, batch_index=None):
+    """timm PatchEmbed + pos-embed (+ cls row, S: a DecShared) : returns x fp32 [B*rows, D] and the saved patch matrix."""
     patches = ops.patchify(img, rt.patch_size, rt.act_dtype, batch_index, mean=rt.input_mean, std=rt.input_std)
     batch = patches.shape[0] // rt.n1
-    pos2 = pos.view(rt.n2, rt.dim)
-    rows = rt.n2 if with_cls else rt.n1
+    pos2 = S.pos.view(rt.n2, rt.dim)
+    rows, first = (rt.n2, 1) if with_cls else (rt.n1, 0)        # under a cls row the patch tokens start at row 1 of every image
+    x = ops.gemm(patches, rt.weight(S.pw), epilogue=EPI_RESIDUAL, bias=S.pb, residual=pos2[1 - first:], rows_per_batch=rt.n1,
+                 out_rows_per_batch=rows, row_offset=first, residual_bcast=True, out_rows=batch * rows)
     if with_cls:
-        x = ops.gemm(patches, rt.weight(pw), epilogue=EPI_RESIDUAL, bias=pb, residual=pos2, rows_per_batch=rt.n1,
-                     out_rows_per_batch=rt.n2, row_offset=1, residual_bcast=True, out_rows=batch * rt.n2)
-        ops.write_cls_row(x.view(batch, rt.n2, rt.dim), cls.view(-1), pos2)
-    else:
-        x = ops.gemm(patches, rt.weight(pw), epilogue=EPI_RESIDUAL, bias=pb, residual=pos2[1:], rows_per_batch=rt.n1,
-                     out_rows_per_batch=rt.n1, row_offset=0, residual_bcast=True, out_rows=batch * rt.n1)
+        ops.write_cls_row(x.view(batch, rt.n2, rt.dim), S.cls.view(-1), pos2)
     return x, patches, batch, rows
 
 
-def _patch_tokens_bwd(rt, dx, patches, pw, pb, pos, with_cls, batch):
-    """dx fp32 [B*rows, D] -> (d patch weight, d patch bias, d pos_embed, d cls | None)."""
+def _patch_tokens_bwd(rt, dx, patches, S, with_cls, batch):
+    """dx fp32 [B*rows, D] -> the gradients of pw, pb, pos (and cls) by field name."""
     rows = rt.n2 if with_cls else rt.n1
     dx3 = dx.view(batch, rows, rt.dim)
     dpos_rows = ops.sum_rows(dx3.view(batch, rows * rt.dim)).view(rows, rt.dim)
-    dpos = torch.zeros_like(pos)
-    dcls = None
+    dpos = torch.zeros_like(S.pos)
+    grads = dict(pos=dpos)
     if with_cls:
         dpos[0] = dpos_rows
-        dcls = dpos_rows[0].clone().view(1, 1, rt.dim)
+        grads['cls'] = dpos_rows[0].clone().view_as(S.cls)
         dtok = ops.slice_rows_cast(dx3, 1, rt.n1, rt.act_dtype)
     else:
         dpos[0, 1:] = dpos_rows
         dtok = dx if rt.exact else ops.cast(dx, rt.act_dtype)
-    dw, db = _weight_grads(rt, dtok, patches, pw, pb)
-    return dw, db, dpos, dcls
+    grads['pw'], grads['pb'] = _weight_grads(rt, dtok, patches, S.pw, S.pb)
+    return grads
+
+
+def _norm1_of(blocks, i):
+    """(gamma, beta) of block i's norm1, None past the last block: what the previous block's fc2 kernel is asked to produce."""
+    return (blocks[i].g1, blocks[i].b1) if i < len(blocks) else None
 
 
 # ---------------------------------------------------------------------------------------------
@@ -508,62 +539,178 @@ def _patch_tokens_bwd(rt, dx, patches, pw, pb, pos, with_cls, batch):
 class EncoderFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, rt: Runtime, img, *params):
-        pw, pb, pos = params[:3]
-        nb = len(ENC_BLOCK_KEYS)
-        blocks = [params[3 + i * nb: 3 + (i + 1) * nb] for i in range(rt.depth)]
+        shared, blocks = split_params(params, EncShared, EncBlock)
         grad = any(ctx.needs_input_grad)  # False under no_grad: nothing is saved for inference
-        x, patches, batch, n = _patch_tokens_fwd(rt, img, pw, pb, pos, with_cls=False)
+        x, patches, batch, n = _patch_tokens_fwd(rt, img, shared, with_cls=False)
         tape = []
         ln1 = None          # (h, mean, rstd) of this block's norm1 when the previous block's fc2 kernel already produced it
         for i, P in enumerate(blocks):
-            g1, b1, wqkv, bqkv, wproj, bproj, g2, b2, w1, bb1, w2, bb2 = P
-            # on the no-grad path the one-kernel MLP does its own LayerNorm: nothing to hand over
-            chain = grad or not _fused_mlp_rows(rt, x, w1, grad)
+            chain = _hand_over_ln(rt, x, P, grad)
             with _BlockSpan(rt, 'enc', i, 'fwd'):
-                xa, sa, ln2 = _attn_branch_fwd(rt, x, g1, b1, wqkv, bqkv, wproj, bproj, batch, n, key=('blocks', i, 'attn'), ln=ln1,
-                                               next_ln=(g2, b2) if chain else None)
-                nxt = (blocks[i + 1][0], blocks[i + 1][1]) if (chain and i + 1 < rt.depth) else None
-                xb, sm, ln1 = _mlp_fwd(rt, xa, g2, b2, w1, bb1, w2, bb2, grad, ln=ln2, next_ln=nxt)
+                xa, sa, ln2 = _attn_branch_fwd(rt, x, P, batch, n, key=('blocks', i, 'attn'), ln=ln1, next_ln=(P.g2, P.b2) if chain else None)
+                xb, sm, ln1 = _mlp_fwd(rt, xa, P, grad, ln=ln2, next_ln=_norm1_of(blocks, i + 1) if chain else None)
             if grad:
                 tape.append((x, sa, xa, sm))
             x = xb
             if rt.tap is not None:
                 rt.tap[f'enc.x.{len(tape) - 1 if grad else 0}'] = x.clone()
         if grad:
-            ctx.rt, ctx.tape, ctx.patches, ctx.batch, ctx.params = rt, tape, patches, batch, params
+            ctx.rt, ctx.tape, ctx.patches, ctx.batch, ctx.params = rt, tape, patches, batch, (shared, blocks)
         return x.view(batch, n, rt.dim)
 
     @staticmethod
     def backward(ctx, dout):
         rt, batch, n = ctx.rt, ctx.batch, ctx.rt.n1
-        params = ctx.params
-        pw, pb, pos = params[:3]
-        nb = len(ENC_BLOCK_KEYS)
+        shared, blocks = ctx.params
         dx = dout.contiguous().view(batch * n, rt.dim).float()
         dx_lp = _lp(rt, dx)
-        grads = [None] * len(params)
-        rt.ln_queue = [] if not rt.exact else None
-        with _DwBatch(rt, blocks=True, kind='enc') as dwg:
-            for i in reversed(range(rt.depth)):
-                g1, b1, wqkv, bqkv, wproj, bproj, g2, b2, w1, bb1, w2, bb2 = params[3 + i * nb: 3 + (i + 1) * nb]
+        gblocks = [None] * len(blocks)
+        with _ln_sums(rt), _DwBatch(rt, kind='enc') as dwg:      # the encoder's 2 x depth LayerNorm column sums
+            for i in reversed(range(len(blocks))):
                 x, sa, xa, sm = ctx.tape[i]
                 ctx.tape[i] = None
                 with _BlockSpan(rt, 'enc', i, 'bwd'), dwg.block():
-                    dx, dx_lp, (dg2, db2, dw1, dbb1, dw2, dbb2) = _mlp_bwd(rt, dx, dx_lp, xa, g2, b2, w1, bb1, w2, bb2, sm)
-                    dx, dx_lp, (dg1, db1, dwq, dbq, dwp, dbp) = _attn_branch_bwd(rt, dx, dx_lp, x, g1, b1, wqkv, bqkv, wproj, bproj, sa, batch, n,
-                                                                                 key=('blocks', i, 'attn'))
+                    dx, dx_lp, gm = _mlp_bwd(rt, dx, dx_lp, xa, blocks[i], sm)
+                    dx, dx_lp, ga = _attn_branch_bwd(rt, dx, dx_lp, x, blocks[i], sa, batch, n, key=('blocks', i, 'attn'))
                 if rt.tap is not None:
                     rt.tap[f'enc.dx.{i}'] = dx.clone()      # gradient w.r.t. the INPUT of encoder block i
-                base = 3 + i * nb
-                blk = [dg1, db1, dwq, dbq, dwp, dbp, dg2, db2, dw1, dbb1, dw2, dbb2]
-                grads[base: base + nb] = blk
-        if rt.ln_queue is not None:
-            ops.layernorm_bwd_finish(rt.ln_queue)       # the encoder's 2 x depth LayerNorm column sums: one launch per 16
-            rt.ln_queue = None
-        dpw, dpb, dpos, _ = _patch_tokens_bwd(rt, dx, ctx.patches, pw, pb, pos, with_cls=False, batch=batch)
-        grads[0], grads[1], grads[2] = dpw, dpb, dpos
+                gblocks[i] = EncBlock(**ga, **gm)
+        gshared = EncShared(**_patch_tokens_bwd(rt, dx, ctx.patches, shared, with_cls=False, batch=batch))
         ctx.tape = ctx.patches = None
-        return (None, None, *grads)
+        return (None, None, *flatten_params(gshared, gblocks))
+
+
+# ---------------------------------------------------------------------------------------------
+# one CrossBlock (vision_transformer.py:268-272) in three stages: self-attention, cross-attention, MLP (_mlp_fwd / _mlp_bwd).
+# DecoderFn (training and no_grad), decoder_cached and image2_tokens (pair-cached inference) are all built from them.
+# ---------------------------------------------------------------------------------------------
+def _dense_rows(t):
+    """[rows, D] copy with row stride D (``.contiguous()`` keeps the strides of a one-row view, and the GEMM epilogue needs ldo)."""
+    out = torch.empty(t.shape, dtype=t.dtype, device=t.device)
+    out.copy_(t)
+    return out
+
+
+def _dec_self_fwd(rt, x, P, batch, n, cls_only, key=None, ln1=None, fuse_ln=True):
+    """Self stage: x -> (xa = x + attn(norm1(x)), saved, lnq).  ``cls_only`` (the LAST decoder block): only x[:, 0] of the
+    block's output reaches the head (:400, :417 - the final norm and the head are row-wise), and within a CrossBlock the
+    token rows only mix in the self-attention, as keys / values.  So after the block's qkv projection everything runs on the
+    cls row alone: self-attention for query 0, proj, the whole cross-attention query side and the MLP - 1 row instead of
+    N2 = 65 / 1025 per pair - with identical logits and gradients (the dropped rows' outputs are dead, their gradients exactly
+    zero); xa is then [batch, D].  ``ln1`` = (h, mean, rstd) of norm1(x) when the previous block's fc2 kernel produced it.
+    ``fuse_ln``: the proj kernel also produces lnq = (h, mean, rstd) of norm_cross(xa); else lnq is None (_cross_q computes it)."""
+    next_ln = (P.gc, P.bc) if fuse_ln else None
+    if not cls_only:
+        return _attn_branch_fwd(rt, x, P, batch, n, key=key, ln=ln1, next_ln=next_ln)
+    d = rt.dim
+    h1, m1, r1 = ln1 if ln1 is not None else ops.layernorm_fwd(x, P.g1, P.b1, LN_EPS, rt.act_dtype)
+    qkv = ops.gemm(h1, rt.weight(P.wqkv), bias=P.bqkv)            # K and V of every row feed query 0
+    qkv3 = qkv.view(batch, n, 3 * d)
+    o0, lse0 = ops.attention_fwd(qkv3[:, 0:1, 0:d], qkv3[:, :, d:2 * d], qkv3[:, :, 2 * d:3 * d], rt.heads, rt.scale)
+    o0 = o0.view(batch, d)
+    x0 = _dense_rows(x.view(batch, n, d)[:, 0, :])
+    xa, lnq = _res_linear(rt, o0, P.wproj, P.bproj, x0, next_ln)
+    return xa, (m1, r1, h1, qkv, o0, lse0), lnq
+
+
+def _dec_self_bwd(rt, dx, dx_lp, x, P, saved, batch, n, cls_only, key=None):
+    """Backward of _dec_self_fwd.  dx / dx_lp: gradient w.r.t. xa (all rows, or the cls rows when cls_only).
+    Returns (d x fp32 [batch n, D], its low-precision copy, the six parameter gradients by field name)."""
+    if not cls_only:
+        return _attn_branch_bwd(rt, dx, dx_lp, x, P, saved, batch, n, key=key)
+    d = rt.dim
+    m1, r1, h1, qkv, o0, lse0 = saved
+    do0, dwproj, dbproj = _linear_bwd(rt, dx_lp, o0, P.wproj, P.bproj)
+    qkv3 = qkv.view(batch, n, 3 * d)
+    dqkv = torch.zeros_like(qkv)                 # d(q) of the rows that never queried is zero
+    dqkv3 = dqkv.view(batch, n, 3 * d)
+    ops.attention_bwd(qkv3[:, 0:1, 0:d], qkv3[:, :, d:2 * d], qkv3[:, :, 2 * d:3 * d], o0.view(batch, 1, d), do0.view(batch, 1, d),
+                      lse0, rt.heads, rt.scale, dqkv3[:, 0:1, 0:d], dqkv3[:, :, d:2 * d], dqkv3[:, :, 2 * d:3 * d])
+    dres = torch.zeros((batch * n, d), dtype=torch.float32, device=dx.device)   # the residual path carries gradient on the cls rows only
+    dres.view(batch, n, d)[:, 0, :].copy_(dx)
+    dx, dx_lp, dg1, db1, dwqkv, dbqkv = _linear_ln_bwd(rt, dqkv, h1, P.wqkv, P.bqkv, x, P.g1, P.b1, m1, r1, dx_in=dres)
+    return dx, dx_lp, dict(g1=dg1, b1=db1, wqkv=dwqkv, bqkv=dbqkv, wproj=dwproj, bproj=dbproj)
+
+
+def _cross_q(rt, xa, P, lnq=None):
+    """q = Linear_q(norm_cross(xa)) of the cross-attention (:176); ``lnq`` = (h, mean, rstd) of norm_cross(xa) when the self
+    stage's proj kernel produced it.  Returns (q in the activation dtype, (h, mean, rstd))."""
+    hq, mq, rq = lnq if lnq is not None else ops.layernorm_fwd(xa, P.gc, P.bc, LN_EPS, rt.act_dtype)
+    return ops.gemm(hq, rt.weight(P.wq), bias=P.bq), (hq, mq, rq)
+
+
+def _dec_cross_fwd(rt, xa, P, batch, lnq=None, q=None, kv3=None, ctxf=None, kv_index=None, key=None, fuse_ln=True):
+    """Cross stage (:174-200, :270): xa [batch Nq, D] -> (xb = xa + proj(attention(q, k, v)), saved, ln2) with q from the image-2
+    tokens (_cross_q, unless the pair cache hands ``q`` over) and k / v from the image-1 features: ``kv3`` [., N1, 2 D] when they
+    were computed ahead for all blocks (_context_kv_folded, context_kv; with ``kv_index`` pair p reads kv3[kv_index[p]]), else
+    Linear_kv(norm_context(ctxf)) here.  ``fuse_ln``: the cross-proj kernel also produces ln2 = (h, mean, rstd) of norm2(xb)."""
+    d, nq = rt.dim, xa.shape[0] // batch
+    hq = mq = rq = hc = mc = rc = None
+    if q is None:
+        q, (hq, mq, rq) = _cross_q(rt, xa, P, lnq)
+    kv = kv3                    # computed ahead: a view, nothing of norm_context is saved here
+    if kv3 is None:
+        hc, mc, rc = ops.layernorm_fwd(ctxf, P.gx, P.bx, LN_EPS, rt.act_dtype)
+        kv = ops.gemm(hc, rt.weight(P.wkv), bias=P.bkv)              # [Mc, 2D], columns [2][h][hd] (:178)
+        kv3 = kv.view(batch, rt.n1, 2 * d)
+    oc, lse_c = ops.attention_fwd(q.view(batch, nq, d), kv3[:, :, 0:d], kv3[:, :, d:2 * d], rt.heads, rt.scale, kv_index=kv_index)
+    if rt.keep_attn and key is not None:
+        _keep_attention(rt, key, q.view(batch, nq, d), kv3[:, :, 0:d])
+    oc = oc.view(batch * nq, d)
+    xb, ln2 = _res_linear(rt, oc, P.wcp, P.bcp, xa, (P.g2, P.b2) if fuse_ln else None)
+    return xb, (mq, rq, hq, mc, rc, hc, q, kv, oc, lse_c), ln2
+
+
+def _dec_cross_bwd(rt, dx, dx_lp, xa, P, saved, ctxf, dctx, batch, index, dkv3=None):
+    """Backward of _dec_cross_fwd.  Returns (d xa fp32, its low-precision copy, d context (accumulated in place), the ten parameter
+    gradients by field name).  When the keys / values came from _context_kv_folded, d(kv) is written into ``dkv3`` (this block's
+    view of the all-blocks tensor) and gx, bx, wkv, bkv stay None: _context_kv_folded_bwd fills them in after the last block."""
+    d, nq = rt.dim, xa.shape[0] // batch
+    mq, rq, hq, mc, rc, hc, q, kv, oc, lse_c = saved
+    doc, dwcp, dbcp = _linear_bwd(rt, dx_lp, oc, P.wcp, P.bcp)
+    dq = torch.empty_like(q)
+    folded = hc is None
+    if folded:
+        kv3, dkv = kv, dkv3                 # views of the all-blocks kv / d(kv) tensors
+    else:
+        dkv = torch.empty_like(kv)
+        kv3, dkv3 = kv.view(batch, rt.n1, 2 * d), dkv.view(batch, rt.n1, 2 * d)
+    if rt.keep_attn:
+        _keep_attention_grad(rt, ('cross_blocks', index, 'cross_attn'), doc.view(batch, nq, d), kv3[:, :, d:2 * d])
+    ops.attention_bwd(q.view(batch, nq, d), kv3[:, :, 0:d], kv3[:, :, d:2 * d], oc.view(batch, nq, d),
+                      doc.view(batch, nq, d), lse_c, rt.heads, rt.scale, dq.view(batch, nq, d), dkv3[:, :, 0:d],
+                      dkv3[:, :, d:2 * d])
+    if rt.tap is not None:
+        i = index
+        rt.tap[f'dec.doc.{i}'], rt.tap[f'dec.dq.{i}'], rt.tap[f'dec.dkv.{i}'] = doc.clone(), dq.clone(), dkv.clone()
+        rt.tap[f'dec.q.{i}'], rt.tap[f'dec.kv.{i}'], rt.tap[f'dec.oc.{i}'] = q.clone(), kv.clone(), oc.clone()
+    # q = Linear(norm_cross(x')), kv = Linear(norm_context(features)): input-gradient GEMM + LayerNorm backward fused
+    dx, dx_lp, dgc, dbc, dwq, dbq = _linear_ln_bwd(rt, dq, hq, P.wq, P.bq, xa, P.gc, P.bc, mq, rq, dx_in=dx)
+    dgx = dbx = dwkv = dbkv = None
+    if not folded:
+        # d(context) accumulates over the c_depth blocks in fp32, in place
+        dctx, _, dgx, dbx, dwkv, dbkv = _linear_ln_bwd(rt, dkv, hc, P.wkv, P.bkv, ctxf, P.gx, P.bx, mc, rc, dx_in=dctx, dx_out=dctx, want_lp=False)
+    return dx, dx_lp, dctx, dict(gc=dgc, bc=dbc, gx=dgx, bx=dbx, wq=dwq, bq=dbq, wkv=dwkv, bkv=dbkv, wcp=dwcp, bcp=dbcp)
+
+
+def _dec_block_fwd(rt, x, ctxf, P, batch, n, grad, cls_only, index=0, ln1=None, next_ln=None, kv3=None):
+    """One CrossBlock forward of DecoderFn: self + cross + MLP stage, every following LayerNorm asked of the Linear before it
+    (``next_ln`` = (gamma, beta) of the NEXT block's norm1).  Returns (block output, tape entry | None, next block's ln1 | None)."""
+    xa, sa, lnq = _dec_self_fwd(rt, x, P, batch, n, cls_only, key=('cross_blocks', index, 'attn'), ln1=ln1)
+    xb, sc, ln2 = _dec_cross_fwd(rt, xa, P, batch, lnq=lnq, kv3=kv3, ctxf=ctxf, key=('cross_blocks', index, 'cross_attn'),
+                                 fuse_ln=_hand_over_ln(rt, xa, P, grad))
+    xc, sm, nxt = _mlp_fwd(rt, xb, P, grad, ln=ln2, next_ln=next_ln)
+    return xc, ((x, sa, xa, sc, xb, sm) if grad else None), nxt
+
+
+def _dec_block_bwd(rt, dx, dx_lp, ctxf, dctx, P, entry, batch, n, cls_only, index, dkv3=None):
+    """Backward of _dec_block_fwd.  dx / dx_lp: gradient w.r.t. the block's output (all rows, or the cls rows when cls_only).
+    Returns (d input fp32, its low-precision copy, d context (accumulated in place), the parameter gradients as a DecBlock)."""
+    x, sa, xa, sc, xb, sm = entry
+    dx, dx_lp, gm = _mlp_bwd(rt, dx, dx_lp, xb, P, sm)
+    dx, dx_lp, dctx, gc = _dec_cross_bwd(rt, dx, dx_lp, xa, P, sc, ctxf, dctx, batch, index, dkv3)
+    dx, dx_lp, ga = _dec_self_bwd(rt, dx, dx_lp, x, P, sa, batch, n, cls_only, key=('cross_blocks', index, 'attn'))
+    return dx, dx_lp, dctx, DecBlock(**ga, **gc, **gm)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -574,33 +721,34 @@ class EncoderFn(torch.autograd.Function):
 #   * prepare_x2 (vision_transformer.py:390-395) depends on image j only  -> image2_tokens(), once per image;
 #   * cross-attention keys / values (:177-179) depend on image i's features only -> context_kv(), once per image-1 row block;
 # the pair batch then gathers token rows by index j and the attention kernel reads K / V by index i (vited_attention_fwd_indexed).
+# ``params`` is the decoder's flat parameter list (model._decoder_params) throughout.
 @torch.no_grad()
-def image2_tokens(rt: Runtime, img, pw, pb, pos, cls, block0=None):
+def image2_tokens(rt: Runtime, img, params):
     """Everything of the decoder that depends on image 2 ALONE, once per image:
       * x  = patch embedding + cls row + pos_embed (timm _pos_embed), the decoder's input stream;
       * x' = x + attn(norm1(x)) of the FIRST CrossBlock (its self-attention sees image 2 only: the features enter at the
              cross-attention that follows, vision_transformer.py:269-270) - unless that block is also the last one (cls-only);
       * q  = Linear_q(norm_cross(x')) of that block's cross-attention (:176), activation dtype.
     Returns (x' or x as [n, N2, D] fp32, q [n, N2, D] or None)."""
-    x, _, batch, _ = _patch_tokens_fwd(rt, img, pw, pb, pos, with_cls=True, cls=cls)
-    if block0 is None or (rt.cls_tail and rt.c_depth == 1):
+    shared, blocks = split_params(params, DecShared, DecBlock)
+    x, _, batch, _ = _patch_tokens_fwd(rt, img, shared, with_cls=True)
+    if not blocks or (rt.cls_tail and rt.c_depth == 1):
         return x.view(batch, rt.n2, rt.dim), None
-    g1, b1, wqkv, bqkv, wproj, bproj, gc, bc, gx, bx, wq, bq = block0[:12]
-    xa, _, lnq = _attn_branch_fwd(rt, x, g1, b1, wqkv, bqkv, wproj, bproj, batch, rt.n2, next_ln=(gc, bc))
-    q = ops.gemm(lnq[0], rt.weight(wq), bias=bq)
+    xa, _, lnq = _dec_self_fwd(rt, x, blocks[0], batch, rt.n2, cls_only=False)
+    q, _ = _cross_q(rt, xa, blocks[0], lnq)
     return xa.view(batch, rt.n2, rt.dim), q.view(batch, rt.n2, rt.dim)
 
 
 @torch.no_grad()
-def context_kv(rt: Runtime, feats, blocks):
+def context_kv(rt: Runtime, feats, params):
     """Per decoder block: kv = Linear_kv(norm_context(features)) as [b1, N1, 2 D] in the activation dtype (columns [2][h][hd])."""
+    _, blocks = split_params(params, DecShared, DecBlock)
     b1 = feats.shape[0]
     ctxf = feats.detach().contiguous().float().view(b1 * rt.n1, rt.dim)
     out = []
     for P in blocks:
-        gx, bx, wkv, bkv = P[8], P[9], P[12], P[13]
-        hc, _, _ = ops.layernorm_fwd(ctxf, gx, bx, LN_EPS, rt.act_dtype)
-        out.append(ops.gemm(hc, rt.weight(wkv), bias=bkv).view(b1, rt.n1, 2 * rt.dim))
+        hc, _, _ = ops.layernorm_fwd(ctxf, P.gx, P.bx, LN_EPS, rt.act_dtype)
+        out.append(ops.gemm(hc, rt.weight(P.wkv), bias=P.bkv).view(b1, rt.n1, 2 * rt.dim))
     return out
 
 
@@ -608,150 +756,33 @@ def context_kv(rt: Runtime, feats, blocks):
 def decoder_cached(rt: Runtime, tokens2, j_idx, kvs, i_idx, params, q0=None):
     """Logits [P, C] of the pairs (image-1 row i_idx[p] of the cached block, image j_idx[p]): forward_second_part + forward_head
     (vision_transformer.py:397-405,417) on cached image-2 tokens and cached cross-attention keys / values.  With ``q0`` the cache
-    already holds block 0's self-attention branch and cross-attention queries (image2_tokens with block0)."""
-    gN, bN, wh, bh = params[4:8]
-    ns, nb = 8, len(DEC_BLOCK_KEYS)
+    already holds block 0's self-attention branch and cross-attention queries (image2_tokens)."""
+    shared, blocks = split_params(params, DecShared, DecBlock)
     d, n = rt.dim, rt.n2
     batch = j_idx.numel()
     x = tokens2.index_select(0, j_idx).view(batch * n, d)
-    for l in range(rt.c_depth):
-        g1, b1, wqkv, bqkv, wproj, bproj, gc, bc, gx, bx, wq, bq, wkv, bkv, wcp, bcp, g2, b2, w1, bb1, w2, bb2 = params[ns + l * nb: ns + (l + 1) * nb]
-        cls_only = rt.cls_tail and l == rt.c_depth - 1          # see _dec_block_fwd: the last block runs on the cls row alone
-        lnq = None
+    for l, (P, kv3) in enumerate(zip(blocks, kvs)):
+        cls_only = rt.cls_tail and l == rt.c_depth - 1          # see _dec_self_fwd: the last block runs on the cls row alone
+        lnq = q = None
         if l == 0 and q0 is not None:
-            xa, nq = x, n                                         # cached: x IS x + attn(norm1(x)) of block 0
-        elif not cls_only:
-            xa, _, lnq = _attn_branch_fwd(rt, x, g1, b1, wqkv, bqkv, wproj, bproj, batch, n, next_ln=(gc, bc))
-            nq = n
+            xa, q = x, q0.index_select(0, j_idx)                  # cached: x IS x + attn(norm1(x)) of block 0
         else:
-            h1, _, _ = ops.layernorm_fwd(x, g1, b1, LN_EPS, rt.act_dtype)
-            qkv3 = ops.gemm(h1, rt.weight(wqkv), bias=bqkv).view(batch, n, 3 * d)
-            o0, _ = ops.attention_fwd(qkv3[:, 0:1, 0:d], qkv3[:, :, d:2 * d], qkv3[:, :, 2 * d:3 * d], rt.heads, rt.scale)
-            xa = ops.gemm(o0.view(batch, d), rt.weight(wproj), epilogue=EPI_RESIDUAL, bias=bproj, residual=_dense_rows(x.view(batch, n, d)[:, 0, :]))
-            nq = 1
-        if l == 0 and q0 is not None:
-            q = q0.index_select(0, j_idx)
-        else:
-            hq = lnq[0] if lnq is not None else ops.layernorm_fwd(xa, gc, bc, LN_EPS, rt.act_dtype)[0]
-            q = ops.gemm(hq, rt.weight(wq), bias=bq)
-        kv3 = kvs[l]
-        oc, _ = ops.attention_fwd(q.view(batch, nq, d), kv3[:, :, 0:d], kv3[:, :, d:2 * d], rt.heads, rt.scale, kv_index=i_idx)
-        xb = ops.gemm(oc.view(batch * nq, d), rt.weight(wcp), epilogue=EPI_RESIDUAL, bias=bcp, residual=xa)
-        x, _, _ = _mlp_fwd(rt, xb, g2, b2, w1, bb1, w2, bb2, grad=False)
+            # fuse_ln: the historical form of this path, not a measured choice - its cls-rows-only proj leaves norm_cross to a
+            # separate launch (DecoderFn fuses it), and below its cross-proj never produces norm2, its fc2 never the next norm1
+            xa, _, lnq = _dec_self_fwd(rt, x, P, batch, n, cls_only, fuse_ln=not cls_only)
+        xb, _, _ = _dec_cross_fwd(rt, xa, P, batch, lnq=lnq, q=q, kv3=kv3, kv_index=i_idx, fuse_ln=False)
+        x, _, _ = _mlp_fwd(rt, xb, P, grad=False)
     xcls = x if (rt.cls_tail and rt.c_depth > 0) else x.view(batch, n, d)[:, 0, :]
-    y, _, _ = ops.layernorm_fwd(xcls, gN, bN, LN_EPS, rt.act_dtype)
-    return ops.gemm(y, rt.weight(wh), epilogue=EPI_STORE_F32, bias=bh)
+    y, _, _ = ops.layernorm_fwd(xcls, shared.gN, shared.bN, LN_EPS, rt.act_dtype)
+    return ops.gemm(y, rt.weight(shared.wh), epilogue=EPI_STORE_F32, bias=shared.bh)
 
 
 # ---------------------------------------------------------------------------------------------
 # decoder + head: forward_second_part + forward_head (vision_transformer.py:390-405,417)
 # ---------------------------------------------------------------------------------------------
-def _dense_rows(t):
-    """[rows, D] copy with row stride D (``.contiguous()`` keeps the strides of a one-row view, and the GEMM epilogue needs ldo)."""
-    out = torch.empty(t.shape, dtype=t.dtype, device=t.device)
-    out.copy_(t)
-    return out
-
-
-def _dec_block_fwd(rt, x, ctxf, P, batch, n, grad, cls_only, index=0, ln1=None, next_ln=None, kv3=None):
-    """One CrossBlock forward (vision_transformer.py:268-272).  ``cls_only`` (the LAST decoder block): only x[:, 0] of the
-    block's output reaches the head (:400, :417 - the final norm and the head are row-wise), and within a CrossBlock the
-    token rows only mix in the self-attention, as keys / values.  So after the block's qkv projection everything runs on the
-    cls row alone: self-attention for query 0, proj, the whole cross-attention query side and the MLP - 1 row instead of
-    N2 = 65 / 1025 per pair - with identical logits and identical gradients (the dropped rows' outputs are dead, their
-    gradients exactly zero).  ``ln1`` = (h, mean, rstd) of this block's norm1 when the previous block's fc2 kernel produced it;
-    ``next_ln`` = (gamma, beta) of the NEXT block's norm1.  Returns (block output, tape entry, next block's ln1 | None)."""
-    g1, b1, wqkv, bqkv, wproj, bproj, gc, bc, gx, bx, wq, bq, wkv, bkv, wcp, bcp, g2, b2, w1, bb1, w2, bb2 = P
-    d = rt.dim
-    if not cls_only:
-        xa, sa, lnq = _attn_branch_fwd(rt, x, g1, b1, wqkv, bqkv, wproj, bproj, batch, n, key=('cross_blocks', index, 'attn'), ln=ln1,
-                                       next_ln=(gc, bc))
-        nq = n
-    else:
-        h1, m1, r1 = ln1 if ln1 is not None else ops.layernorm_fwd(x, g1, b1, LN_EPS, rt.act_dtype)
-        qkv = ops.gemm(h1, rt.weight(wqkv), bias=bqkv)            # K and V of every row feed query 0
-        qkv3 = qkv.view(batch, n, 3 * d)
-        o0, lse0 = ops.attention_fwd(qkv3[:, 0:1, 0:d], qkv3[:, :, d:2 * d], qkv3[:, :, 2 * d:3 * d], rt.heads, rt.scale)
-        o0 = o0.view(batch, d)
-        x0 = _dense_rows(x.view(batch, n, d)[:, 0, :])
-        xa, lnq = _res_linear(rt, o0, wproj, bproj, x0, (gc, bc))
-        sa = (m1, r1, h1, qkv, o0, lse0)
-        nq = 1
-    # cross attention: q from image-2 tokens, k/v from image-1 features (:174-200)
-    hq, mq, rq = lnq
-    q = ops.gemm(hq, rt.weight(wq), bias=bq)
-    if kv3 is None:
-        hc, mc, rc = ops.layernorm_fwd(ctxf, gx, bx, LN_EPS, rt.act_dtype)
-        kv = ops.gemm(hc, rt.weight(wkv), bias=bkv)                  # [Mc, 2D], columns [2][h][hd] (:178)
-        kv3 = kv.view(batch, rt.n1, 2 * d)
-    else:
-        hc = mc = rc = None     # this block's keys / values came out of the folded all-blocks GEMM (_context_kv_folded): a strided view
-        kv = kv3
-    oc, lse_c = ops.attention_fwd(q.view(batch, nq, d), kv3[:, :, 0:d], kv3[:, :, d:2 * d], rt.heads, rt.scale)
-    if rt.keep_attn:
-        _keep_attention(rt, ('cross_blocks', index, 'cross_attn'), q.view(batch, nq, d), kv3[:, :, 0:d])
-    oc = oc.view(batch * nq, d)
-    chain = grad or not _fused_mlp_rows(rt, xa, w1, grad)      # the no-grad one-kernel MLP does its own LayerNorm
-    xb, ln2 = _res_linear(rt, oc, wcp, bcp, xa, (g2, b2) if chain else None)
-    xc, sm, nxt = _mlp_fwd(rt, xb, g2, b2, w1, bb1, w2, bb2, grad, ln=ln2, next_ln=next_ln)
-    entry = (x, sa, xa, (mq, rq, hq, mc, rc, hc, q, kv, oc, lse_c), xb, sm) if grad else None
-    return xc, entry, nxt
-
-
-def _dec_block_bwd(rt, dx, dx_lp, ctxf, dctx, P, entry, batch, n, cls_only, tap_index, dkv3=None):
-    """Backward of _dec_block_fwd.  dx / dx_lp: gradient w.r.t. the block's output (all rows, or the cls rows when cls_only).
-    Returns (d input fp32, its low-precision copy, d context (accumulated in place), the 22 parameter gradients)."""
-    g1, b1, wqkv, bqkv, wproj, bproj, gc, bc, gx, bx, wq, bq, wkv, bkv, wcp, bcp, g2, b2, w1, bb1, w2, bb2 = P
-    d = rt.dim
-    x, sa, xa, sc, xb, sm = entry
-    mq, rq, hq, mc, rc, hc, q, kv, oc, lse_c = sc
-    nq = 1 if cls_only else n
-    dx, dx_lp, (dg2, db2, dw1, dbb1, dw2, dbb2) = _mlp_bwd(rt, dx, dx_lp, xb, g2, b2, w1, bb1, w2, bb2, sm)
-    # cross attention
-    doc, dwcp, dbcp = _linear_bwd(rt, dx_lp, oc, wcp, bcp)
-    dq = torch.empty_like(q)
-    folded = hc is None
-    if folded:
-        kv3, dkv = kv, dkv3                 # views of the all-blocks kv / d(kv) tensors
-    else:
-        dkv = torch.empty_like(kv)
-        kv3, dkv3 = kv.view(batch, rt.n1, 2 * d), dkv.view(batch, rt.n1, 2 * d)
-    if rt.keep_attn:
-        _keep_attention_grad(rt, ('cross_blocks', tap_index, 'cross_attn'), doc.view(batch, nq, d), kv3[:, :, d:2 * d])
-    ops.attention_bwd(q.view(batch, nq, d), kv3[:, :, 0:d], kv3[:, :, d:2 * d], oc.view(batch, nq, d),
-                      doc.view(batch, nq, d), lse_c, rt.heads, rt.scale, dq.view(batch, nq, d), dkv3[:, :, 0:d],
-                      dkv3[:, :, d:2 * d])
-    if rt.tap is not None:
-        i = tap_index
-        rt.tap[f'dec.doc.{i}'], rt.tap[f'dec.dq.{i}'], rt.tap[f'dec.dkv.{i}'] = doc.clone(), dq.clone(), dkv.clone()
-        rt.tap[f'dec.q.{i}'], rt.tap[f'dec.kv.{i}'], rt.tap[f'dec.oc.{i}'] = q.clone(), kv.clone(), oc.clone()
-    # q = Linear(norm_cross(x')), kv = Linear(norm_context(features)): input-gradient GEMM + LayerNorm backward fused
-    dx, dx_lp, dgc, dbc, dwq, dbq = _linear_ln_bwd(rt, dq, hq, wq, bq, xa, gc, bc, mq, rq, dx_in=dx)
-    if rt.exact:
-        dx_lp = dx
-    if folded:
-        dgx = dbx = dwkv = dbkv = None      # filled in by _context_kv_folded_bwd once every block has written its d(kv)
-    else:
-        # d(context) accumulates over the c_depth blocks in fp32, in place
-        dctx, _, dgx, dbx, dwkv, dbkv = _linear_ln_bwd(rt, dkv, hc, wkv, bkv, ctxf, gx, bx, mc, rc, dx_in=dctx, dx_out=dctx, want_lp=False)
-    if not cls_only:
-        dx, dx_lp, (dg1, db1, dwqkv, dbqkv, dwp, dbp) = _attn_branch_bwd(rt, dx, dx_lp, x, g1, b1, wqkv, bqkv, wproj, bproj, sa, batch, n,
-                                                                           key=('cross_blocks', tap_index, 'attn'))
-    else:
-        m1, r1, h1, qkv, o0, lse0 = sa
-        do0, dwp, dbp = _linear_bwd(rt, dx_lp, o0, wproj, bproj)
-        qkv3 = qkv.view(batch, n, 3 * d)
-        dqkv = torch.zeros_like(qkv)                 # d(q) of the rows that never queried is zero
-        dqkv3 = dqkv.view(batch, n, 3 * d)
-        ops.attention_bwd(qkv3[:, 0:1, 0:d], qkv3[:, :, d:2 * d], qkv3[:, :, 2 * d:3 * d], o0.view(batch, 1, d), do0.view(batch, 1, d),
-                          lse0, rt.heads, rt.scale, dqkv3[:, 0:1, 0:d], dqkv3[:, :, d:2 * d], dqkv3[:, :, 2 * d:3 * d])
-        dres = torch.zeros((batch * n, d), dtype=torch.float32, device=dx.device)   # the residual path carries gradient on the cls rows only
-        dres.view(batch, n, d)[:, 0, :].copy_(dx)
-        dx, dx_lp, dg1, db1, dwqkv, dbqkv = _linear_ln_bwd(rt, dqkv, h1, wqkv, bqkv, x, g1, b1, m1, r1, dx_in=dres)
-        if rt.exact:
-            dx_lp = dx
-    return dx, dx_lp, dctx, [dg1, db1, dwqkv, dbqkv, dwp, dbp, dgc, dbc, dgx, dbx, dwq, dbq, dwkv, dbkv, dwcp, dbcp,
-                             dg2, db2, dw1, dbb1, dw2, dbb2]
+def _kv_params(blocks):
+    """(kv weights, kv biases, norm_context gammas, norm_context betas) of every decoder block: what the fold works on."""
+    return [P.wkv for P in blocks], [P.bkv for P in blocks], [P.gx for P in blocks], [P.bx for P in blocks]
 
 
 def _context_kv_folded(rt, ctxf, blocks):
@@ -761,7 +792,7 @@ def _context_kv_folded(rt, ctxf, blocks):
     dev = ctxf.device
     if rt._unit_ln is None or rt._unit_ln[0].device != dev:
         rt._unit_ln = (torch.ones(rt.dim, dtype=torch.float32, device=dev), torch.zeros(rt.dim, dtype=torch.float32, device=dev))
-    ws, bs, gs, bes = [P[12] for P in blocks], [P[13] for P in blocks], [P[8] for P in blocks], [P[9] for P in blocks]
+    ws, bs, gs, bes = _kv_params(blocks)
     bufs = rt._fold_bufs
     if bufs is not None and (bufs[0].shape[0] != len(blocks) * 2 * rt.dim or bufs[0].device != dev):
         if rt.pinned:
@@ -783,7 +814,7 @@ def _context_kv_folded_bwd(rt, dkv_all, ctxf, saved, bufs, blocks):
     """Backward of _context_kv_folded once every block has written its d(kv) slice: d(features) from ONE row-complete kernel
     (input-gradient GEMM with K = L 2D + the affine-free LayerNorm's backward), the folded weights' gradient from one
     weight-gradient GEMM, unfolded into dW_kv, db_kv, d(norm_context.weight / bias) of every block.
-    Returns (d features fp32, [(dgx, dbx, dwkv, dbkv) per block] - None entries when accumulated straight into .grad)."""
+    Returns (d features fp32, per block the gradients of gx, bx, wkv, bkv by field name - None when accumulated straight into .grad)."""
     xhat, mean, rstd = saved
     ones = rt._unit_ln[0]
     nblk, mc, n2 = dkv_all.shape
@@ -796,32 +827,25 @@ def _context_kv_folded_bwd(rt, dkv_all, ctxf, saved, bufs, blocks):
         dctx, _, _, _ = ops.layernorm_bwd(dh, ctxf, ones, mean, rstd)
     dwf = torch.empty((nblk * n2, rt.dim), dtype=torch.float32, device=ctxf.device)
     dbf = torch.empty(nblk * n2, dtype=torch.float32, device=ctxf.device)
-    items = [(dkv_all[l], xhat, dwf[l * n2:(l + 1) * n2], dbf[l * n2:(l + 1) * n2]) for l in range(nblk)]
-    for i in range(0, nblk, ops.MAX_BATCHED_WEIGHT_GRADS):
-        part = items[i: i + ops.MAX_BATCHED_WEIGHT_GRADS]
-        if not (len(part) > 1 and ops.linear_bwd_weight_batched(part, False)):
-            for dy_, x_, dw_, db_ in part:
-                _overwrite_weight_grad(dy_, x_, dw_, db_)
-    ws, bs, gs, bes = [P[12] for P in blocks], [P[13] for P in blocks], [P[8] for P in blocks], [P[9] for P in blocks]
+    _launch_weight_grads([(dkv_all[l], xhat, dwf[l * n2:(l + 1) * n2], dbf[l * n2:(l + 1) * n2]) for l in range(nblk)], False)
+    ws, bs, gs, bes = _kv_params(blocks)
     targets = [(_gtarget(rt, w), _gtarget(rt, b) if b is not None else None, _gtarget(rt, g), _gtarget(rt, be)) for w, b, g, be in zip(ws, bs, gs, bes)]
-    direct = all(t[0] is not None and t[2] is not None and t[3] is not None and (b is None or t[1] is not None) for t, b in zip(targets, bs))
+    direct = all(tw is not None and tg is not None and tbe is not None and (b is None or tb is not None) for (tw, tb, tg, tbe), b in zip(targets, bs))
     if not direct:
         targets = [(torch.empty_like(w), torch.empty_like(b) if b is not None else None, torch.empty_like(g), torch.empty_like(be))
                    for w, b, g, be in zip(ws, bs, gs, bes)]
-    ops.unfold_context_grads(dwf, dbf, [w.detach() for w in ws], [g.detach() for g in gs], [b.detach() for b in bes], [t[0] for t in targets], [t[1] for t in targets],
-                             [t[2] for t in targets], [t[3] for t in targets], accumulate=direct)
-    return dctx, [(None, None, None, None) if direct else (t[2], t[3], t[0], t[1]) for t in targets]
+    ops.unfold_context_grads(dwf, dbf, [w.detach() for w in ws], [g.detach() for g in gs], [b.detach() for b in bes],
+                             [tw for tw, _, _, _ in targets], [tb for _, tb, _, _ in targets], [tg for _, _, tg, _ in targets],
+                             [tbe for _, _, _, tbe in targets], accumulate=direct)
+    return dctx, [dict.fromkeys(('gx', 'bx', 'wkv', 'bkv')) if direct else dict(gx=tg, bx=tbe, wkv=tw, bkv=tb) for tw, tb, tg, tbe in targets]
 
 
 class DecoderFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, rt: Runtime, feats, img2, img2_index, *params):
-        pw, pb, pos, cls, gN, bN, wh, bh = params[:8]
-        ns = 8
-        nb = len(DEC_BLOCK_KEYS)
-        blocks = [params[ns + i * nb: ns + (i + 1) * nb] for i in range(rt.c_depth)]
+        shared, blocks = split_params(params, DecShared, DecBlock)
         grad = any(ctx.needs_input_grad)
-        x, patches, batch, n = _patch_tokens_fwd(rt, img2, pw, pb, pos, with_cls=True, cls=cls, batch_index=img2_index)
+        x, patches, batch, n = _patch_tokens_fwd(rt, img2, shared, with_cls=True, batch_index=img2_index)
         assert feats.shape == (batch, rt.n1, rt.dim), f'features {tuple(feats.shape)} do not match {batch} image-2 samples'
         ctxf = feats.detach().contiguous().float().view(batch * rt.n1, rt.dim)
         tape = []
@@ -833,19 +857,18 @@ class DecoderFn(torch.autograd.Function):
         if fold:
             kv_all, kv_saved, fold_bufs = _context_kv_folded(rt, ctxf, blocks)
         for i, P in enumerate(blocks):
-            nxt = (blocks[i + 1][0], blocks[i + 1][1]) if i + 1 < rt.c_depth else None     # the next block's norm1
-            x, entry, ln1 = _dec_block_fwd(rt, x, ctxf, P, batch, n, grad, cls_tail and i == rt.c_depth - 1, index=i, ln1=ln1, next_ln=nxt,
-                                           kv3=kv_all[i].view(batch, rt.n1, 2 * d) if fold else None)
+            x, entry, ln1 = _dec_block_fwd(rt, x, ctxf, P, batch, n, grad, cls_tail and i == rt.c_depth - 1, index=i, ln1=ln1,
+                                           next_ln=_norm1_of(blocks, i + 1), kv3=kv_all[i].view(batch, rt.n1, 2 * d) if fold else None)
             if grad:
                 tape.append(entry)
             if rt.tap is not None:
                 rt.tap[f'dec.x.{i}'] = x.clone()
         # final norm on the cls rows only (LayerNorm is row-wise; only x[:, 0] reaches the head, :400,:417)
         xcls = x if cls_tail else x.view(batch, n, d)[:, 0, :]
-        y, mN, rN = ops.layernorm_fwd(xcls, gN, bN, LN_EPS, rt.act_dtype)
-        logits = ops.gemm(y, rt.weight(wh), epilogue=EPI_STORE_F32, bias=bh)
+        y, mN, rN = ops.layernorm_fwd(xcls, shared.gN, shared.bN, LN_EPS, rt.act_dtype)
+        logits = ops.gemm(y, rt.weight(shared.wh), epilogue=EPI_STORE_F32, bias=shared.bh)
         if grad:
-            ctx.rt, ctx.tape, ctx.patches, ctx.batch, ctx.params = rt, tape, patches, batch, params
+            ctx.rt, ctx.tape, ctx.patches, ctx.batch, ctx.params = rt, tape, patches, batch, (shared, blocks)
             ctx.ctxf, ctx.final, ctx.cls_tail = ctxf, (xcls, y, mN, rN), cls_tail
             ctx.feats_needs_grad = feats.requires_grad
             ctx.fold = (kv_all, kv_saved, fold_bufs) if fold else None
@@ -854,65 +877,47 @@ class DecoderFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dlogits):
         rt, batch, n, d = ctx.rt, ctx.batch, ctx.rt.n2, ctx.rt.dim
-        params = ctx.params
-        pw, pb, pos, cls, gN, bN, wh, bh = params[:8]
-        ns, nb = 8, len(DEC_BLOCK_KEYS)
-        grads = [None] * len(params)
+        shared, blocks = ctx.params
         xcls, y, mN, rN = ctx.final
         # head: logits = y Wh^T + bh
         dl = _lp(rt, dlogits.contiguous().float())
-        wh_act = rt.weight(wh)
+        wh_act = rt.weight(shared.wh)
         dy = ops.gemm(dl, wh_act, b_layout=B_KN)                         # [B, D]
-        dwh, dbh = _weight_grads(rt, dl, y, wh, bh)
+        dwh, dbh = _weight_grads(rt, dl, y, shared.wh, shared.bh)
         if ctx.cls_tail:
             # the last block ran on the cls rows only: so does its gradient
-            dx, dx_lp, dgN, dbN = _ln_bwd(rt, dy, xcls, gN, bN, mN, rN, want_lp=not rt.exact)
+            dx, dx_lp, dgN, dbN = _ln_bwd(rt, dy, xcls, shared.gN, shared.bN, mN, rN, want_lp=not rt.exact)
         else:
             # final LayerNorm touches the cls rows only; every other row of d(x) is zero
             dx = torch.zeros((batch * n, d), dtype=torch.float32, device=dy.device)
-            dx3 = dx.view(batch, n, d)
-            dx_lp = None
-            dx_lp3 = None
+            dx_lp = dx_lp3 = None
             if not rt.exact:
                 dx_lp = torch.zeros((batch * n, d), dtype=rt.act_dtype, device=dy.device)
                 dx_lp3 = dx_lp.view(batch, n, d)[:, 0, :]
-            _, _, dgN, dbN = _ln_bwd(rt, dy, xcls, gN, bN, mN, rN, dx_out=dx3[:, 0, :], dx_lp=dx_lp3)
+            _, _, dgN, dbN = _ln_bwd(rt, dy, xcls, shared.gN, shared.bN, mN, rN, dx_out=dx.view(batch, n, d)[:, 0, :], dx_lp=dx_lp3)
         if rt.exact:
             dx_lp = dx
-        grads[4], grads[5], grads[6], grads[7] = dgN, dbN, dwh, dbh
         dctx = None
-        rt.ln_queue = [] if not rt.exact else None
-        dkv_all3 = None
-        if ctx.fold is not None:
-            dkv_all = torch.empty_like(ctx.fold[0])
-            dkv_all3 = dkv_all
-        with _DwBatch(rt, blocks=True, kind='dec') as dwg:
-            for i in reversed(range(rt.c_depth)):
-                P = params[ns + i * nb: ns + (i + 1) * nb]
-                entry = ctx.tape[i]
-                ctx.tape[i] = None
-                with dwg.block():
-                    dx, dx_lp, dctx, blk = _dec_block_bwd(rt, dx, dx_lp, ctx.ctxf, dctx, P, entry, batch, n,
-                                                          ctx.cls_tail and i == rt.c_depth - 1, i,
-                                                          dkv3=dkv_all3[i].view(batch, rt.n1, 2 * d) if dkv_all3 is not None else None)
-                if rt.tap is not None:
-                    rt.tap[f'dec.dx.{i}'] = dx.clone()      # gradient w.r.t. the INPUT of decoder block i
-                    if dctx is not None:
-                        rt.tap[f'dec.dctx.{i}'] = dctx.clone()  # running d(features) after blocks c_depth-1 .. i
-                base = ns + i * nb
-                grads[base: base + nb] = blk
-        if ctx.fold is not None:
-            blocks = [params[ns + i * nb: ns + (i + 1) * nb] for i in range(rt.c_depth)]
-            dctx, per_block = _context_kv_folded_bwd(rt, dkv_all, ctx.ctxf, ctx.fold[1], ctx.fold[2], blocks)
-            for i, (dgx, dbx, dwkv, dbkv) in enumerate(per_block):
-                base = ns + i * nb
-                grads[base + 8], grads[base + 9], grads[base + 12], grads[base + 13] = dgx, dbx, dwkv, dbkv
-            ctx.fold = None
-        if rt.ln_queue is not None:
-            ops.layernorm_bwd_finish(rt.ln_queue)       # the decoder's 4 x c_depth LayerNorm column sums
-            rt.ln_queue = None
-        dpw, dpb, dpos, dcls = _patch_tokens_bwd(rt, dx, ctx.patches, pw, pb, pos, with_cls=True, batch=batch)
-        grads[0], grads[1], grads[2], grads[3] = dpw, dpb, dpos, dcls.view_as(cls)
+        gblocks = [None] * len(blocks)
+        dkv_all = torch.empty_like(ctx.fold[0]) if ctx.fold is not None else None       # ctx.fold: (kv_all, saved, folded buffers)
+        with _ln_sums(rt):                              # the decoder's 4 x c_depth LayerNorm column sums
+            with _DwBatch(rt, kind='dec') as dwg:
+                for i in reversed(range(len(blocks))):
+                    entry = ctx.tape[i]
+                    ctx.tape[i] = None
+                    with dwg.block():
+                        dx, dx_lp, dctx, gblocks[i] = _dec_block_bwd(rt, dx, dx_lp, ctx.ctxf, dctx, blocks[i], entry, batch, n,
+                                                                     ctx.cls_tail and i == rt.c_depth - 1, i,
+                                                                     dkv3=dkv_all[i].view(batch, rt.n1, 2 * d) if dkv_all is not None else None)
+                    if rt.tap is not None:
+                        rt.tap[f'dec.dx.{i}'] = dx.clone()      # gradient w.r.t. the INPUT of decoder block i
+                        if dctx is not None:
+                            rt.tap[f'dec.dctx.{i}'] = dctx.clone()  # running d(features) after blocks c_depth-1 .. i
+            if dkv_all is not None:
+                dctx, kv_grads = _context_kv_folded_bwd(rt, dkv_all, ctx.ctxf, ctx.fold[1], ctx.fold[2], blocks)
+                gblocks = [g._replace(**kv) for g, kv in zip(gblocks, kv_grads)]
+                ctx.fold = None
+        gshared = DecShared(**_patch_tokens_bwd(rt, dx, ctx.patches, shared, with_cls=True, batch=batch), gN=dgN, bN=dbN, wh=dwh, bh=dbh)
         dfeats = dctx.view(batch, rt.n1, d) if ctx.feats_needs_grad and dctx is not None else None
         ctx.tape = ctx.patches = ctx.ctxf = ctx.final = None
-        return (None, dfeats, None, None, *grads)
+        return (None, dfeats, None, None, *flatten_params(gshared, gblocks))

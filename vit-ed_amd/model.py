@@ -261,18 +261,12 @@ class VisionTransformerCustom(nn.Module):
         """Everything of the decoder that depends on image 2 alone, once per image: prepare_x2 (vision_transformer.py:390-395),
         the first CrossBlock's self-attention branch and its cross-attention queries.  Returns (tokens [n, N2, D] fp32, q0 | None)."""
         self._check_images(images)
-        p = self._decoder_params()
-        nb = len(DEC_BLOCK_KEYS)
-        block0 = p[8: 8 + nb] if self.c_depth else None
-        return F_.image2_tokens(self.runtime(), images, p[0], p[1], p[2], p[3], block0)
+        return F_.image2_tokens(self.runtime(), images, self._decoder_params())
 
     @torch.no_grad()
     def cache_context_kv(self, feats):
         """Cross-attention keys / values of every decoder block for a block of image-1 features (:177-179), once per block."""
-        rt = self.runtime()
-        p = self._decoder_params()
-        nb = len(DEC_BLOCK_KEYS)
-        return F_.context_kv(rt, feats, [p[8 + l * nb: 8 + (l + 1) * nb] for l in range(self.c_depth)])
+        return F_.context_kv(self.runtime(), feats, self._decoder_params())
 
     @torch.no_grad()
     def forward_pairs_cached(self, tokens2, j_idx, kvs, i_idx, q0=None):
