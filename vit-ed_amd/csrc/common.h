@@ -52,8 +52,9 @@ __device__ __forceinline__ void gelu_parts_fast(float x, float& cdf, float& e) {
     // 64 activations per lane go through this in the fc1 epilogue, so the form below is the one with the fewest instructions
     // (9 % fewer than the textbook arrangement bought 1.1 % of that kernel: vector issue is not what bounds it): v = |x| sqrt(log2(e)/2) serves both the exponent (e = 2^(-v^2) = exp(-x^2/2), one multiply
     // with a negated operand) and the rational argument (t = 1 / (1 + p v) with A&S's p rescaled); 0.5 is folded into the polynomial;
-    // the reflection cdf(x >= 0) = 1 - h, cdf(x < 0) = h is  step(x) - copysign(h, x)  with step from one clamped FMA - no compare /
-    // select through VCC, and the negative tail keeps h's relative accuracy (no 0.5 - (0.5 - h) cancellation).
+    // the reflection cdf(x >= 0) = 1 - h, cdf(x < 0) = h is  step - sg h  with sg = copysign(1, x) and step = sg clamped to [0, 1] - no
+    // compare / select through VCC, and the negative tail keeps h's relative accuracy (no 0.5 - (0.5 - h) cancellation).  Both terms
+    // follow x's sign BIT, so -0 and negative denormals reflect like every other negative x.
     const float v = fabsf(x) * 0.84932180028801907f;                       // |x| * sqrt(0.5 * log2(e))
     e = __builtin_amdgcn_exp2f(-v * v);                                     // exp(-x^2/2)
     const float t = __builtin_amdgcn_rcpf(fmaf(0.27273748087922250f, v, 1.0f));   // 0.3275911 / sqrt(log2(e)): same t as A&S 7.1.26
@@ -62,8 +63,9 @@ __device__ __forceinline__ void gelu_parts_fast(float x, float& cdf, float& e) {
     p = fmaf(t, p, -0.142248368f);
     p = fmaf(t, p, 0.127414796f);
     const float h = (p * t) * e;                                            // 0.5 * erfc(|x| / sqrt2)
-    const float step = __builtin_amdgcn_fmed3f(fmaf(x, 3.0e38f, 1.0f), 0.f, 1.f);   // 1 for x >= 0, 0 for x < 0 (clamp modifier)
-    cdf = step - __builtin_copysignf(h, x);
+    const float sg = __builtin_copysignf(1.0f, x);                          // +-1, also for +-0 and denormals
+    const float step = __builtin_amdgcn_fmed3f(sg, 0.f, 1.f);               // 1 for a clear sign bit, 0 for a set one
+    cdf = fmaf(-sg, h, step);                                               // = step - copysign(h, x): sg h is exact, one rounding
 }
 __device__ __forceinline__ float gelu_fast(float x) {
     float cdf, e;
