@@ -107,6 +107,22 @@ int vited_patchify_u8(const uint8_t* img, int64_t img_bs, const int64_t* batch_i
 int vited_crop_pairs_u8(const uint8_t* src, int64_t src_bs, const int* cells, const int* erode, uint8_t* out, int64_t batch,
                         int chans, int img_size, void* stream);
 
+/* The stage in front of vited_crop_pairs_u8 (data/datasets/div2k_patch.py:84-111: RandomHorizontalFlip, RandomVerticalFlip,
+ * A.ShiftScaleRotate, A.RGBShift, RandomCrop / CenterCrop) from images that stay on the device.  store holds n_images decoded
+ * images back to back, uint8 HWC with 3 channels: image i starts at byte img_off[i] and is img_hw[2 i] rows of img_hw[2 i + 1]
+ * pixels.  Sample b takes image[b] (clamped to [0, n_images)) and writes out[b] = uint8 [3, 2 S, 3 S] (S = img_size), the window
+ * of the augmented image whose top-left corner is crop[b] = (top, left), clamped to [0, H - 2 S] x [0, W - 3 S]:
+ *   flags[b]  bit 0 horizontal flip, bit 1 vertical flip, bit 2 warp, bit 3 colour shift
+ *   minv[b]   6 doubles, the inverse (destination -> source) affine map, row-major; read when bit 2 is set
+ *   rgb[b]    3 floats added per channel, then clamped to [0, 255] and floored (fp32); read when bit 3 is set
+ * The warp is cv2.warpAffine's linear scheme: 1/32-pixel positions from fp64 terms rounded half-even at 10 fractional bits,
+ * four taps with 15-bit integer weights, BORDER_REFLECT_101; the flips act on the tap fetch.  DESIGN.md section 16 defines
+ * every step.  All arrays are DEVICE memory; an image smaller than 2 S x 3 S is the caller's error (the window is then reflected).
+ * VITED_ERR_BAD_ARG: a null pointer, n_images <= 0, batch outside 1..65535, img_size outside 1..4096. */
+int vited_div2k_regions_u8(const uint8_t* store, const int64_t* img_off, const int* img_hw, int n_images, const int* image,
+                           const int* flags, const double* minv, const float* rgb, const int* crop, uint8_t* out, int64_t batch,
+                           int img_size, void* stream);
+
 /* out[b, r] = (out_dtype) in[b, row_offset + r] for r < rows: drops the cls row of a token-gradient
  * tensor before the patch-embed weight gradient. in is fp32 [batch, in_rows, dim]. */
 int vited_slice_rows_cast(const float* in, void* out, int out_dtype, int64_t batch, int64_t in_rows,

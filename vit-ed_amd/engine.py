@@ -612,6 +612,148 @@ def assemble_pairs(regions_u8: torch.Tensor, cells: torch.Tensor, erode: torch.T
 
 
 # ---------------------------------------------------------------------------------------------
+# the stage in front of it on the device too: resident images, augmentation and crop (div2k_patch.py:84-111)
+# ---------------------------------------------------------------------------------------------
+class Div2kImageStore:
+    """The decoded images of a DIV2K split, resident on ``device``: ``images`` (HWC uint8 arrays or tensors, 3 channels) packed
+    back to back into one uint8 buffer (``data``), with their byte offsets and (H, W) sizes on the device (``offsets_dev`` int64
+    [n], ``sizes_dev`` int32 [n, 2]) and on the host (``offsets``, ``sizes``).  DIV2K train is about 7 GB this way."""
+
+    def __init__(self, images, device):
+        self.device = torch.device(device)
+        flat, sizes, offsets, off = [], [], [], 0
+        for k, im in enumerate(images):
+            t = torch.as_tensor(im)
+            if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3 or t.shape[0] < 1 or t.shape[1] < 1:
+                raise ValueError(f'image {k}: expected a uint8 [H, W, 3] array, got {t.dtype} {tuple(t.shape)}')
+            flat.append(t.contiguous().reshape(-1))
+            sizes.append([t.shape[0], t.shape[1]])
+            offsets.append(off)
+            off += t.numel()
+        if not flat:
+            raise ValueError('an image store needs at least one image')
+        self.sizes = torch.tensor(sizes, dtype=torch.int32)
+        self.offsets = torch.tensor(offsets, dtype=torch.int64)
+        self.data = torch.empty(off, dtype=torch.uint8, device=self.device)
+        for t, o in zip(flat, offsets):                    # image by image: no second host copy of the whole set
+            self.data[o: o + t.numel()].copy_(t)
+        self.sizes_dev, self.offsets_dev = self.sizes.to(self.device), self.offsets.to(self.device)
+
+    def __len__(self):
+        return self.sizes.shape[0]
+
+    def require_window(self, img_size: int):
+        """Every image must hold the (2 S) x (3 S) window the crop keeps (torchvision's crops raise or pad otherwise)."""
+        small = ((self.sizes[:, 0] < 2 * img_size) | (self.sizes[:, 1] < 3 * img_size)).nonzero().flatten().tolist()
+        if small:
+            k = small[0]
+            raise ValueError(f'{len(small)} image(s) are smaller than the {2 * img_size} x {3 * img_size} crop window, the first is '
+                             f'image {k} with {int(self.sizes[k, 0])} x {int(self.sizes[k, 1])}')
+
+
+def div2k_augment_plan(u: torch.Tensor, image: torch.Tensor, sizes: torch.Tensor, img_size: int, train: bool = True):
+    """The random choices of ``DIV2KPatch.read_image`` and of the crop of ``__getitem__`` (div2k_patch.py:89-111) for a whole batch at
+    once, from uniform numbers ``u`` [B, 13] in [0, 1) (columns: horizontal flip, vertical flip, warp, angle, scale, dx, dy, colour
+    shift, its three channel shifts, crop top, crop left), the image indices ``image`` [B] and ``sizes`` int32 [n, 2] = (H, W):
+      image int32 [B]      the indices
+      flags int32 [B]      bit 0 / 1: RandomHorizontalFlip / RandomVerticalFlip (p = 0.5); bit 2: A.ShiftScaleRotate (p = 0.5);
+                           bit 3: A.RGBShift (p = 0.5)
+      minv  fp64  [B, 6]   inverse of  getRotationMatrix2D((W / 2 - 0.5, H / 2 - 0.5), angle ~ U(-20, 20), scale ~ U(0.85, 1.15))
+                           + (dx W, dy H), dx, dy ~ U(-0.05, 0.05), inverted as cv2.warpAffine does; the identity with the warp off
+      rgb   fp32  [B, 3]   channel shifts ~ U(-15, 15); 0 with the colour shift off
+      crop  int32 [B, 2]   RandomCrop origin floor(u (H - 2 S + 1)), floor(u (W - 3 S + 1))
+    ``train=False``: no augmentation and CenterCrop's origin int(round((H - 2 S) / 2)) (round half to even).  Elementwise torch
+    operations on the device of ``u``: no host copy, no sync; every fp64 product and sum is an operation of its own."""
+    u = u.double()
+    n_rows = u.shape[0]
+    image = image.to(device=u.device, dtype=torch.int64)
+    hw = sizes.to(u.device)[image.clamp(0, sizes.shape[0] - 1)]
+    H, W = hw[:, 0].double(), hw[:, 1].double()
+    room_y, room_x = (H - 2 * img_size).clamp_(min=0), (W - 3 * img_size).clamp_(min=0)
+    zero, one = torch.zeros_like(H), torch.ones_like(H)
+    if not train:
+        flags = torch.zeros(n_rows, dtype=torch.int32, device=u.device)
+        minv = torch.stack([one, zero, zero, zero, one, zero], dim=1)
+        rgb = torch.zeros(n_rows, 3, dtype=torch.float32, device=u.device)
+        crop = torch.stack([torch.round(room_y / 2), torch.round(room_x / 2)], dim=1).to(torch.int32)
+        return image.to(torch.int32), flags, minv.contiguous(), rgb, crop.contiguous()
+    hflip, vflip, warp, colour = u[:, 0] < 0.5, u[:, 1] < 0.5, u[:, 2] < 0.5, u[:, 7] < 0.5
+    flags = (hflip.int() + 2 * vflip.int() + 4 * warp.int() + 8 * colour.int()).to(torch.int32)
+    angle = (u[:, 3] * 40.0 - 20.0) * (torch.pi / 180.0)
+    scale = u[:, 4] * 0.3 + 0.85
+    dx, dy = (u[:, 5] * 0.1 - 0.05) * W, (u[:, 6] * 0.1 - 0.05) * H
+    cx, cy = W / 2 - 0.5, H / 2 - 0.5
+    alpha, beta = torch.cos(angle) * scale, torch.sin(angle) * scale
+    m0, m1, m2 = alpha, beta, (1 - alpha) * cx - beta * cy + dx            # cv2.getRotationMatrix2D, then the translation
+    m3, m4, m5 = -beta, alpha, beta * cx + (1 - alpha) * cy + dy
+    det = m0 * m4 - m1 * m3                                                 # cv2.warpAffine without WARP_INVERSE_MAP
+    d = torch.where(det != 0, 1.0 / det, zero)
+    i0, i1, i3, i4 = m4 * d, m1 * (-d), m3 * (-d), m0 * d
+    i2, i5 = -(i0 * m2) - i1 * m5, -(i3 * m2) - i4 * m5
+    minv = torch.stack([torch.where(warp, a, b) for a, b in zip((i0, i1, i2, i3, i4, i5), (one, zero, zero, zero, one, zero))], dim=1)
+    rgb = ((u[:, 8:11] * 30.0 - 15.0) * colour.unsqueeze(1)).float()
+    crop = torch.stack([torch.minimum(torch.floor(u[:, 11] * (room_y + 1)), room_y),
+                        torch.minimum(torch.floor(u[:, 12] * (room_x + 1)), room_x)], dim=1).to(torch.int32)
+    return image.to(torch.int32), flags, minv.contiguous(), rgb.contiguous(), crop.contiguous()
+
+
+class Div2kDeviceLoader:
+    """The DIV2K pair loader on the device: what ``build_loader`` + ``DIV2KPatch`` + ``DevicePrefetcher`` deliver, from a
+    ``Div2kImageStore``, without a host copy or a sync per batch.  An epoch is a permutation (drawn on the device, the same on
+    every rank) of the image indices repeated ``repeat`` times, of which rank r takes every ``world``-th from r on; the last
+    incomplete batch is dropped.  Each batch: uniforms -> ``div2k_augment_plan`` -> ``ops.div2k_regions_u8`` -> ``div2k_pair_plan``
+    -> ``assemble_pairs``; it yields (pairs uint8 [B, 2, 3, S, S], labels fp32 [B, 4]) for ``TrainStep.step``."""
+
+    def __init__(self, store: Div2kImageStore, batch_size: int, img_size: int, erosion_ratio: float, with_negative: bool = True,
+                 train: bool = True, repeat: int = 5, rank: int = 0, world: int = 1, seed: int = 0):
+        store.require_window(img_size)
+        if not 0 <= rank < world:
+            raise ValueError(f'rank {rank} outside a world of {world}')
+        self.store, self.batch_size, self.img_size, self.erosion_ratio = store, int(batch_size), int(img_size), float(erosion_ratio)
+        self.with_negative, self.train, self.repeat, self.rank, self.world, self.seed = with_negative, train, int(repeat), rank, world, seed
+        self.epoch = 0
+        if len(self) < 1:
+            raise ValueError(f'{len(store)} images x {repeat} over {world} rank(s) do not fill one batch of {batch_size}')
+
+    def set_epoch(self, epoch: int):
+        self.epoch = int(epoch)
+
+    def __len__(self):
+        return len(self.store) * self.repeat // self.world // self.batch_size
+
+    def _generator(self, stream: int):
+        g = torch.Generator(device=self.store.device)
+        g.manual_seed((self.seed * 1000003 + self.epoch) * 4099 + stream)
+        return g
+
+    def epoch_order(self) -> torch.Tensor:
+        """The epoch's permutation of the repeated image indices (int64 on the store's device), before sharding."""
+        n = len(self.store)
+        return torch.randperm(n * self.repeat, generator=self._generator(0), device=self.store.device) % n
+
+    def rank_indices(self) -> torch.Tensor:
+        """[len(self), batch_size]: the image index of every sample this rank sees in the epoch."""
+        per_rank = len(self.store) * self.repeat // self.world
+        mine = self.epoch_order()[self.rank::self.world][:per_rank]
+        return mine[: len(self) * self.batch_size].view(len(self), self.batch_size)
+
+    def plan(self, image: torch.Tensor, generator: torch.Generator):
+        """One batch's draws: (the five tensors of ``div2k_augment_plan``, the three of ``div2k_pair_plan``)."""
+        u = torch.rand(image.numel(), 17, generator=generator, device=self.store.device)
+        return (div2k_augment_plan(u[:, :13], image, self.store.sizes_dev, self.img_size, self.train),
+                div2k_pair_plan(u[:, 13:], self.img_size, self.erosion_ratio, self.with_negative, self.train))
+
+    def __iter__(self):
+        from . import ops
+        g = self._generator(1 + self.rank)
+        for image in self.rank_indices():
+            (idx, flags, minv, rgb, crop), (cells, labels, erode) = self.plan(image, g)
+            regions = ops.div2k_regions_u8(self.store.data, self.store.offsets_dev, self.store.sizes_dev, idx, flags, minv, rgb, crop,
+                                           self.img_size)
+            yield assemble_pairs(regions, cells, erode, self.img_size), labels
+
+
+# ---------------------------------------------------------------------------------------------
 # pair mining for the two-stage HisFrag training step (hisfrag.py:117-159, SURVEY.md section 8(f) rank 3)
 # ---------------------------------------------------------------------------------------------
 def mine_pairs(targets: torch.Tensor, neg_per_pos: float = 2.0, generator=None):

@@ -184,6 +184,31 @@ def crop_pairs_u8(regions: torch.Tensor, cells: torch.Tensor, erode: torch.Tenso
     return out
 
 
+def div2k_regions_u8(store: torch.Tensor, img_off: torch.Tensor, img_hw: torch.Tensor, image: torch.Tensor, flags: torch.Tensor,
+                     minv: torch.Tensor, rgb: torch.Tensor, crop: torch.Tensor, img_size: int,
+                     out: torch.Tensor | None = None) -> torch.Tensor:
+    """Resident images -> uint8 regions [B, 3, 2 S, 3 S] (``vited_div2k_regions_u8``; div2k_patch.py:84-111): per sample the image
+    index, the flag bits (1 hflip, 2 vflip, 4 warp, 8 colour shift), the inverse affine map fp64 [B, 6], the channel shifts
+    fp32 [B, 3] and the crop origin int32 [B, 2] (top, left).  store uint8 [bytes] holds the HWC images at the byte offsets
+    img_off int64 [n] with sizes img_hw int32 [n, 2] (H, W); the caller guarantees that every image lies inside the store and is
+    at least 2 S x 3 S (``engine.Div2kImageStore`` does).  Indices and origins are clamped by the kernel."""
+    _need_gpu(store, img_off, img_hw, image, flags, minv, rgb, crop, out)
+    s = int(img_size)
+    n, b = img_off.numel(), image.numel()
+    assert store.dtype == torch.uint8 and store.dim() == 1 and store.is_contiguous()
+    assert img_off.dtype == torch.int64 and img_off.dim() == 1 and img_off.is_contiguous()
+    assert img_hw.dtype == torch.int32 and img_hw.shape == (n, 2) and img_hw.is_contiguous()
+    for t, dtype, shape in ((image, torch.int32, (b,)), (flags, torch.int32, (b,)), (minv, torch.float64, (b, 6)),
+                            (rgb, torch.float32, (b, 3)), (crop, torch.int32, (b, 2))):
+        assert t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous(), (t.dtype, tuple(t.shape), dtype, shape)
+    if out is None:
+        out = torch.empty((b, 3, 2 * s, 3 * s), dtype=torch.uint8, device=store.device)
+    assert out.dtype == torch.uint8 and tuple(out.shape) == (b, 3, 2 * s, 3 * s) and out.is_contiguous()
+    _lib.call('vited_div2k_regions_u8', _ptr(store), _ptr(img_off), _ptr(img_hw), n, _ptr(image), _ptr(flags), _ptr(minv), _ptr(rgb),
+              _ptr(crop), _ptr(out), b, s, _stream())
+    return out
+
+
 def slice_rows_cast(x: torch.Tensor, row_offset: int, rows: int, dtype: torch.dtype) -> torch.Tensor:
     """fp32 [B, R, D] -> dtype [B * rows, D] taking rows [row_offset, row_offset + rows) of every batch."""
     _need_gpu(x)
