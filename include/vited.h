@@ -123,6 +123,39 @@ int vited_div2k_regions_u8(const uint8_t* store, const int64_t* img_off, const i
                            const int* flags, const double* minv, const float* rgb, const int* crop, uint8_t* out, int64_t batch,
                            int img_size, void* stream);
 
+/* Config H's input pipeline (hisfrag.py:63-81) from images that stay on the device, in three steps; DESIGN.md section 17 defines
+ * every one.  All arrays are DEVICE memory; flags[b] carries one bit per augmentation for all three entry points:
+ *   bit 0 RandomAffine, bit 1 A.ShiftScaleRotate, bit 2 ColorJitter, bit 3 GaussianBlur.
+ * VITED_ERR_BAD_ARG everywhere: a null pointer, batch outside 1..65535, img_size outside 2..4096.
+ *
+ * vited_hisfrag_windows_u8: store / img_off / img_hw / image as for vited_div2k_regions_u8.  out[b] = uint8 [3, S, S], the window of
+ * the augmented image whose top-left corner is origin[b] = (top, left) in unpadded image coordinates; they may be negative or
+ * past the image (RandomCrop's pad_if_needed), everything outside the image is 0.
+ *   afix[b]  6 int64, Pillow's 16.16 coefficients of the RandomAffine output -> input matrix (nearest); read when bit 0 is set
+ *   minv[b]  6 doubles, the inverse ShiftScaleRotate map; read when bit 1 is set.  cv2's linear scheme as in
+ *            vited_div2k_regions_u8, with BORDER_CONSTANT 0: a tap outside the image is 0.
+ * Also VITED_ERR_BAD_ARG: n_images <= 0. */
+int vited_hisfrag_windows_u8(const uint8_t* store, const int64_t* img_off, const int* img_hw, int n_images, const int* image,
+                             const int* flags, const int64_t* afix, const double* minv, const int* origin, uint8_t* out, int64_t batch,
+                             int img_size, void* stream);
+
+/* ColorJitter on uint8 [batch, 3, S, S], Pillow's arithmetic bit for bit (ImageEnhance.Brightness / Contrast / Color, the HSV
+ * round trip for hue).  Samples without bit 2 are copied.
+ *   order[b]    4 ints, the operations in the order they run: 0 brightness, 1 contrast, 2 saturation, 3 hue (others do nothing)
+ *   factors[b]  3 floats: brightness, contrast, saturation
+ *   hue[b]      the uint8 added to H (mod 256)
+ *   sums        workspace of `batch` int64, 8-byte aligned: zeroed here, then the sum of L over each crop as it stands when
+ *               contrast's turn comes (two kernels: the sums, then the pixels)
+ * out may be in itself. */
+int vited_hisfrag_jitter_u8(const uint8_t* in, const int* flags, const int* order, const float* factors, const int* hue, int64_t* sums,
+                            uint8_t* out, int64_t batch, int img_size, void* stream);
+
+/* GaussianBlur((3, 3)) on uint8 [batch, 3, S, S]: weights[b] = (k_edge, k_mid) of the 3-tap kernel, the 2-D weight their fp32
+ * product; nine fp32 products added in row-major order, rounded half to even; the border reflects without repeating the edge.
+ * Samples without bit 3 are copied.  Also VITED_ERR_BAD_ARG: out == in. */
+int vited_hisfrag_blur_u8(const uint8_t* in, const int* flags, const float* weights, uint8_t* out, int64_t batch, int img_size,
+                          void* stream);
+
 /* out[b, r] = (out_dtype) in[b, row_offset + r] for r < rows: drops the cls row of a token-gradient
  * tensor before the patch-embed weight gradient. in is fp32 [batch, in_rows, dim]. */
 int vited_slice_rows_cast(const float* in, void* out, int out_dtype, int64_t batch, int64_t in_rows,

@@ -754,6 +754,178 @@ class Div2kDeviceLoader:
 
 
 # ---------------------------------------------------------------------------------------------
+# config H's input pipeline on the device: RandomAffine, ShiftScaleRotate, RandomCrop, ColorJitter, GaussianBlur (hisfrag.py:63-115;
+# DESIGN.md section 17)
+# ---------------------------------------------------------------------------------------------
+HISFRAG_PLAN_COLUMNS = 21
+
+
+class HisfragPlan(NamedTuple):
+    """One batch's per-sample arguments of ``ops.hisfrag_windows_u8`` / ``hisfrag_jitter_u8`` / ``hisfrag_blur_u8``."""
+    image: torch.Tensor      # int32 [B]     image index
+    flags: torch.Tensor      # int32 [B]     bit 0 RandomAffine, bit 1 ShiftScaleRotate, bit 2 ColorJitter, bit 3 GaussianBlur
+    afix: torch.Tensor       # int64 [B, 6]  Pillow's 16.16 coefficients a0..a5 of the RandomAffine matrix
+    minv: torch.Tensor       # fp64  [B, 6]  inverse ShiftScaleRotate matrix
+    origin: torch.Tensor     # int32 [B, 2]  (top, left) of the window in unpadded image coordinates
+    order: torch.Tensor      # int32 [B, 4]  jitter operations in the order they run (0 brightness, 1 contrast, 2 saturation, 3 hue)
+    factors: torch.Tensor    # fp32  [B, 3]  brightness, contrast, saturation factors
+    hue: torch.Tensor        # int32 [B]     the uint8 added to H
+    blur: torch.Tensor       # fp32  [B, 2]  (k_edge, k_mid) of the 3-tap Gaussian
+
+
+def hisfrag_augment_plan(u: torch.Tensor, image: torch.Tensor, sizes: torch.Tensor, img_size: int, train: bool = True) -> HisfragPlan:
+    """The random choices of ``HisfragTrainer.get_transforms`` (hisfrag.py:66-78) for a whole batch at once, from uniform numbers
+    ``u`` [B, 21] in [0, 1), the image indices ``image`` [B] and ``sizes`` int32 [n, 2] = (H, W).  Columns of ``u``:
+      0-2    RandomAffine(5, translate=(0.1, 0.1)): angle ~ U(-5, 5), tx = round(U(-0.1 W, 0.1 W)), ty likewise (half to even);
+             the matrix is torchvision's _get_inverse_affine_matrix about (0.5 W, 0.5 H), its 16.16 form Pillow's FIX
+      3-7    A.ShiftScaleRotate at p = 0.5: angle ~ U(-10, 10), scale ~ U(0.9, 1.1), dx, dy ~ U(-0.05, 0.05) of W, H; the forward
+             matrix and its inversion as in ``div2k_augment_plan``
+      8-9    RandomCrop(S, pad_if_needed=True): origin floor(u (Hp - S + 1)) - pad, pad = max(S - H, 0), Hp = H + 2 pad
+      10-18  ColorJitter(0.3, 0.3, 0.3, 0.3) at p = 0.5: the order is the argsort of four uniforms, brightness / contrast /
+             saturation ~ U(0.7, 1.3), hue ~ U(-0.3, 0.3) as the uint8 shift trunc(hue 255) mod 256
+      19-20  GaussianBlur((3, 3), (1, 2)) at p = 0.5: sigma ~ U(1, 2), e = exp(-0.5 / sigma^2) rounded to fp32 once, then
+             k_edge = e / (e + 1 + e), k_mid = 1 / (e + 1 + e) in fp32
+    ``train=False``: everything off and CenterCrop's origin (round half to even; torchvision's centre padding for an image smaller
+    than S).  Elementwise torch operations on the device of ``u``: no host copy, no sync; fp64 throughout, every product and sum
+    an operation of its own."""
+    u = u.double()
+    n_rows, dev, S = u.shape[0], u.device, int(img_size)
+    image = image.to(device=dev, dtype=torch.int64)
+    hw = sizes.to(dev)[image.clamp(0, sizes.shape[0] - 1)]
+    H, W = hw[:, 0].double(), hw[:, 1].double()
+    zero, one = torch.zeros_like(H), torch.ones_like(H)
+    ident = torch.stack([one, zero, zero, zero, one, zero], dim=1)
+    ident_fix = torch.tensor([65536, 0, 32768, 0, 65536, 32768], dtype=torch.int64, device=dev).expand(n_rows, 6)
+    natural = torch.arange(4, dtype=torch.int32, device=dev).expand(n_rows, 4)
+    no_blur = torch.tensor([0.0, 1.0], dtype=torch.float32, device=dev).expand(n_rows, 2)
+    if not train:
+        centre = lambda n: torch.where(n >= S, torch.round((n - S) / 2), -torch.floor((S - n) / 2))
+        return HisfragPlan(image.to(torch.int32), torch.zeros(n_rows, dtype=torch.int32, device=dev), ident_fix.contiguous(), ident.contiguous(),
+                           torch.stack([centre(H), centre(W)], dim=1).to(torch.int32).contiguous(), natural.contiguous(),
+                           torch.ones(n_rows, 3, dtype=torch.float32, device=dev), torch.zeros(n_rows, dtype=torch.int32, device=dev),
+                           no_blur.contiguous())
+    warp, jitter, blur_on = u[:, 3] < 0.5, u[:, 10] < 0.5, u[:, 19] < 0.5
+    flags = (1 + 2 * warp.int() + 4 * jitter.int() + 8 * blur_on.int()).to(torch.int32)
+    # RandomAffine
+    rot = (u[:, 0] * 10.0 - 5.0) * (torch.pi / 180.0)
+    tx, ty = torch.round((u[:, 1] * 2.0 - 1.0) * (0.1 * W)), torch.round((u[:, 2] * 2.0 - 1.0) * (0.1 * H))
+    cx, cy = W * 0.5, H * 0.5
+    cos, sin = torch.cos(rot), torch.sin(rot)
+    M0, M1, M3, M4 = cos, sin, -sin, cos
+    M2 = (M0 * (-cx - tx) + M1 * (-cy - ty)) + cx
+    M5 = (M3 * (-cx - tx) + M4 * (-cy - ty)) + cy
+    fix = lambda t: torch.floor(t * 65536.0 + 0.5).to(torch.int64)
+    afix = torch.stack([fix(M0), fix(M1), fix(M2 + M0 * 0.5 + M1 * 0.5), fix(M3), fix(M4), fix(M5 + M3 * 0.5 + M4 * 0.5)], dim=1)
+    # ShiftScaleRotate
+    angle = (u[:, 4] * 20.0 - 10.0) * (torch.pi / 180.0)
+    scale = u[:, 5] * 0.2 + 0.9
+    dx, dy = (u[:, 6] * 0.1 - 0.05) * W, (u[:, 7] * 0.1 - 0.05) * H
+    wx, wy = W / 2 - 0.5, H / 2 - 0.5
+    alpha, beta = torch.cos(angle) * scale, torch.sin(angle) * scale
+    m0, m1, m2 = alpha, beta, (1 - alpha) * wx - beta * wy + dx
+    m3, m4, m5 = -beta, alpha, beta * wx + (1 - alpha) * wy + dy
+    det = m0 * m4 - m1 * m3
+    d = torch.where(det != 0, 1.0 / det, zero)
+    i0, i1, i3, i4 = m4 * d, m1 * (-d), m3 * (-d), m0 * d
+    i2, i5 = -(i0 * m2) - i1 * m5, -(i3 * m2) - i4 * m5
+    minv = torch.where(warp.unsqueeze(1), torch.stack([i0, i1, i2, i3, i4, i5], dim=1), ident)
+    # RandomCrop with pad_if_needed
+    pad_y, pad_x = (S - H).clamp_(min=0), (S - W).clamp_(min=0)
+    room_y, room_x = H + 2 * pad_y - S, W + 2 * pad_x - S
+    origin = torch.stack([torch.minimum(torch.floor(u[:, 8] * (room_y + 1)), room_y) - pad_y,
+                          torch.minimum(torch.floor(u[:, 9] * (room_x + 1)), room_x) - pad_x], dim=1).to(torch.int32)
+    # ColorJitter
+    order = torch.where(jitter.unsqueeze(1), torch.argsort(u[:, 11:15], dim=1, stable=True).to(torch.int32), natural)
+    factors = torch.where(jitter.unsqueeze(1), u[:, 15:18] * 0.6 + 0.7, one.unsqueeze(1)).float()
+    hue = torch.where(jitter, torch.trunc((u[:, 18] * 0.6 - 0.3) * 255.0).to(torch.int64) % 256, 0).to(torch.int32)
+    # GaussianBlur
+    inv_sigma = 1.0 / (u[:, 20] + 1.0)
+    e = torch.exp(-0.5 * (inv_sigma * inv_sigma)).float()
+    den = (e + 1.0) + e
+    blur = torch.where(blur_on.unsqueeze(1), torch.stack([e / den, 1.0 / den], dim=1), no_blur)
+    return HisfragPlan(image.to(torch.int32), flags, afix.contiguous(), minv.contiguous(), origin.contiguous(), order.contiguous(),
+                       factors.contiguous(), hue.contiguous(), blur.contiguous())
+
+
+def hisfrag_feed(store: 'Div2kImageStore', plan: HisfragPlan, img_size: int) -> torch.Tensor:
+    """``plan`` -> uint8 [B, 3, S, S] on the store's device: geometry, colour jitter and blur, three entry points back to back."""
+    from . import ops
+    windows = ops.hisfrag_windows_u8(store.data, store.offsets_dev, store.sizes_dev, plan.image, plan.flags, plan.afix, plan.minv,
+                                     plan.origin, img_size)
+    jittered = ops.hisfrag_jitter_u8(windows, plan.flags, plan.order, plan.factors, plan.hue, out=windows)     # pointwise: in place
+    return ops.hisfrag_blur_u8(jittered, plan.flags, plan.blur)
+
+
+class HisfragDeviceLoader:
+    """Config H's training loader on the device: what ``HisfragTrainer.get_dataloader`` (hisfrag.py:101-115) delivers, from a
+    ``Div2kImageStore`` of the decoded fragments and their writer ids ``labels``, without a host copy or a sync per batch.
+    Sampling is ``MPerClassSampler(labels, m)``'s scheme: passes over a device-drawn permutation of the writers, ``m`` members
+    per writer (a random order without repetition where the writer has at least ``m``, cycling through a random order of its
+    members where it has fewer), passes concatenated and cut into batches.  Every rank draws from its own generator stream (the
+    reference's sampler is not distributed either).  Each batch: uniforms -> ``hisfrag_augment_plan`` -> ``hisfrag_feed``; it yields
+    (images uint8 [B, 3, S, S], targets int64 [B]) for ``hisfrag_prepare_data``.  Images smaller than the window are padded."""
+
+    def __init__(self, store: Div2kImageStore, labels, batch_size: int, img_size: int, m: int = 3, train: bool = True, repeat: int = 1,
+                 rank: int = 0, world: int = 1, seed: int = 0):
+        if not 0 <= rank < world:
+            raise ValueError(f'rank {rank} outside a world of {world}')
+        labels = torch.as_tensor(labels).reshape(-1).to(torch.int64).cpu()
+        if labels.numel() != len(store):
+            raise ValueError(f'{labels.numel()} labels for {len(store)} images')
+        if m < 1 or batch_size % m:
+            raise ValueError(f'batch size {batch_size} is no multiple of m = {m}')
+        self.store, self.batch_size, self.img_size, self.m = store, int(batch_size), int(img_size), int(m)
+        self.train, self.repeat, self.rank, self.world, self.seed = train, int(repeat), rank, world, seed
+        self.epoch = 0
+        writers, member_of = torch.unique(labels, return_inverse=True)
+        counts = torch.bincount(member_of, minlength=writers.numel())
+        table = torch.zeros(writers.numel(), int(counts.max()), dtype=torch.int64)      # the writers' members, padded with 0
+        for w in range(writers.numel()):
+            table[w, : int(counts[w])] = (member_of == w).nonzero().flatten()
+        dev = store.device
+        self.labels_dev, self.members_dev, self.counts_dev = labels.to(dev), table.to(dev), counts.to(dev)
+        if len(self) < 1:
+            raise ValueError(f'{len(store)} images x {repeat} over {world} rank(s) do not fill one batch of {batch_size}')
+
+    def set_epoch(self, epoch: int):
+        self.epoch = int(epoch)
+
+    def __len__(self):
+        return len(self.store) * self.repeat // self.world // self.batch_size
+
+    def _generator(self, stream: int):
+        g = torch.Generator(device=self.store.device)
+        g.manual_seed((self.seed * 1000003 + self.epoch) * 4099 + stream)
+        return g
+
+    def rank_indices(self) -> torch.Tensor:
+        """[len(self), batch_size]: the image index of every sample this rank sees in the epoch (int64 on the store's device)."""
+        dev, m = self.store.device, self.m
+        n_writers, width = self.members_dev.shape
+        need = len(self) * self.batch_size
+        passes = -(-need // (n_writers * m))
+        g = self._generator(2 * self.rank)
+        writer = torch.stack([torch.randperm(n_writers, generator=g, device=dev) for _ in range(passes)])            # [passes, writers]
+        keys = torch.rand(passes, n_writers, width, generator=g, device=dev)
+        count = self.counts_dev[writer]                                                                              # [passes, writers]
+        keys = torch.where(torch.arange(width, device=dev) < count.unsqueeze(2), keys, 2.0)                          # padding sorts last
+        shuffled = torch.argsort(keys, dim=2)                                                # the real members first, in a random order
+        take = torch.arange(m, device=dev).expand(passes, n_writers, m) % count.unsqueeze(2)
+        picked = self.members_dev[writer.unsqueeze(2), shuffled.gather(2, take)]                                     # [passes, writers, m]
+        return picked.reshape(-1)[:need].view(len(self), self.batch_size)
+
+    def plan(self, image: torch.Tensor, generator: torch.Generator) -> HisfragPlan:
+        """One batch's draws."""
+        u = torch.rand(image.numel(), HISFRAG_PLAN_COLUMNS, generator=generator, device=self.store.device)
+        return hisfrag_augment_plan(u, image, self.store.sizes_dev, self.img_size, self.train)
+
+    def __iter__(self):
+        g = self._generator(2 * self.rank + 1)
+        for image in self.rank_indices():
+            yield hisfrag_feed(self.store, self.plan(image, g), self.img_size), self.labels_dev[image]
+
+
+# ---------------------------------------------------------------------------------------------
 # pair mining for the two-stage HisFrag training step (hisfrag.py:117-159, SURVEY.md section 8(f) rank 3)
 # ---------------------------------------------------------------------------------------------
 def mine_pairs(targets: torch.Tensor, neg_per_pos: float = 2.0, generator=None):

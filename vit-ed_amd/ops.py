@@ -209,6 +209,66 @@ def div2k_regions_u8(store: torch.Tensor, img_off: torch.Tensor, img_hw: torch.T
     return out
 
 
+def _batch_args(b: int, *specs):
+    for t, dtype, shape in specs:
+        assert t.dtype == dtype and tuple(t.shape) == (b, *shape) and t.is_contiguous(), (t.dtype, tuple(t.shape), dtype, (b, *shape))
+
+
+def hisfrag_windows_u8(store: torch.Tensor, img_off: torch.Tensor, img_hw: torch.Tensor, image: torch.Tensor, flags: torch.Tensor,
+                       afix: torch.Tensor, minv: torch.Tensor, origin: torch.Tensor, img_size: int,
+                       out: torch.Tensor | None = None) -> torch.Tensor:
+    """Resident images -> uint8 windows [B, 3, S, S] (``vited_hisfrag_windows_u8``; hisfrag.py:67-72): per sample the image index,
+    the flag bits (1 RandomAffine, 2 ShiftScaleRotate; higher bits are ignored), Pillow's 16.16 affine coefficients int64 [B, 6],
+    the inverse warp map fp64 [B, 6] and the window origin int32 [B, 2] (top, left) in unpadded image coordinates, negative in the
+    pad.  store / img_off / img_hw as for ``div2k_regions_u8``.  Everything outside the image is 0; indices are clamped."""
+    _need_gpu(store, img_off, img_hw, image, flags, afix, minv, origin, out)
+    s = int(img_size)
+    n, b = img_off.numel(), image.numel()
+    assert store.dtype == torch.uint8 and store.dim() == 1 and store.is_contiguous()
+    assert img_off.dtype == torch.int64 and img_off.dim() == 1 and img_off.is_contiguous()
+    assert img_hw.dtype == torch.int32 and img_hw.shape == (n, 2) and img_hw.is_contiguous()
+    _batch_args(b, (image, torch.int32, ()), (flags, torch.int32, ()), (afix, torch.int64, (6,)), (minv, torch.float64, (6,)),
+                (origin, torch.int32, (2,)))
+    if out is None:
+        out = torch.empty((b, 3, s, s), dtype=torch.uint8, device=store.device)
+    assert out.dtype == torch.uint8 and tuple(out.shape) == (b, 3, s, s) and out.is_contiguous()
+    _lib.call('vited_hisfrag_windows_u8', _ptr(store), _ptr(img_off), _ptr(img_hw), n, _ptr(image), _ptr(flags), _ptr(afix), _ptr(minv),
+              _ptr(origin), _ptr(out), b, s, _stream())
+    return out
+
+
+def hisfrag_jitter_u8(img: torch.Tensor, flags: torch.Tensor, order: torch.Tensor, factors: torch.Tensor, hue: torch.Tensor,
+                      out: torch.Tensor | None = None) -> torch.Tensor:
+    """ColorJitter on uint8 crops [B, 3, S, S] (``vited_hisfrag_jitter_u8``; hisfrag.py:73-75), Pillow's arithmetic bit for bit: per
+    sample flag bit 4 (jitter on; a sample without it is copied), the four operations in the order they run int32 [B, 4]
+    (0 brightness, 1 contrast, 2 saturation, 3 hue), the brightness / contrast / saturation factors fp32 [B, 3] and the uint8 hue
+    shift int32 [B].  ``out`` may be ``img`` itself."""
+    _need_gpu(img, flags, order, factors, hue, out)
+    assert img.dtype == torch.uint8 and img.dim() == 4 and img.shape[1] == 3 and img.shape[2] == img.shape[3] and img.is_contiguous()
+    b, s = img.shape[0], img.shape[2]
+    _batch_args(b, (flags, torch.int32, ()), (order, torch.int32, (4,)), (factors, torch.float32, (3,)), (hue, torch.int32, ()))
+    if out is None:
+        out = torch.empty_like(img)
+    assert out.dtype == torch.uint8 and out.shape == img.shape and out.is_contiguous()
+    sums = torch.empty(b, dtype=torch.int64, device=img.device)             # the contrast means' L sums; the entry point zeroes them
+    _lib.call('vited_hisfrag_jitter_u8', _ptr(img), _ptr(flags), _ptr(order), _ptr(factors), _ptr(hue), _ptr(sums), _ptr(out), b, s, _stream())
+    return out
+
+
+def hisfrag_blur_u8(img: torch.Tensor, flags: torch.Tensor, weights: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+    """GaussianBlur((3, 3)) on uint8 crops [B, 3, S, S] (``vited_hisfrag_blur_u8``; hisfrag.py:76-78): per sample flag bit 8 (blur on; a
+    sample without it is copied) and the 1-D weights (k_edge, k_mid) fp32 [B, 2].  ``out`` must not overlap ``img``."""
+    _need_gpu(img, flags, weights, out)
+    assert img.dtype == torch.uint8 and img.dim() == 4 and img.shape[1] == 3 and img.shape[2] == img.shape[3] and img.is_contiguous()
+    b, s = img.shape[0], img.shape[2]
+    _batch_args(b, (flags, torch.int32, ()), (weights, torch.float32, (2,)))
+    if out is None:
+        out = torch.empty_like(img)
+    assert out.dtype == torch.uint8 and out.shape == img.shape and out.is_contiguous() and out.data_ptr() != img.data_ptr()
+    _lib.call('vited_hisfrag_blur_u8', _ptr(img), _ptr(flags), _ptr(weights), _ptr(out), b, s, _stream())
+    return out
+
+
 def slice_rows_cast(x: torch.Tensor, row_offset: int, rows: int, dtype: torch.dtype) -> torch.Tensor:
     """fp32 [B, R, D] -> dtype [B * rows, D] taking rows [row_offset, row_offset + rows) of every batch."""
     _need_gpu(x)
