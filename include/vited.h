@@ -156,6 +156,34 @@ int vited_hisfrag_jitter_u8(const uint8_t* in, const int* flags, const int* orde
 int vited_hisfrag_blur_u8(const uint8_t* in, const int* flags, const float* weights, uint8_t* out, int64_t batch, int img_size,
                           void* stream);
 
+/* michigan.py's input pipeline (michigan.py:68-101) from images that stay on the device: vited_michigan_windows_u8, then
+ * vited_hisfrag_jitter_u8 (unchanged: it reads bit 2 only), then vited_michigan_blur_gray_u8; DESIGN.md section 18 defines every
+ * step.  All arrays are DEVICE memory; flags[b] carries one bit per augmentation:
+ *   bit 0 CoarseDropout, bit 1 horizontal flip, bit 2 ColorJitter, bit 3 GaussianBlur, bit 4 vertical flip, bit 5 grayscale.
+ * VITED_ERR_BAD_ARG everywhere: a null pointer, batch outside 1..65535, img_size outside 2..4096.
+ *
+ * vited_michigan_windows_u8: store / img_off / img_hw / image as for vited_div2k_regions_u8.  out[b] = uint8 [3, S, S].  The window
+ * Wd(u, v), 0 <= u, v < S, is the image at (v + top, u + left), origin[b] = (top, left) in unpadded image coordinates (they may be
+ * negative or past the image: RandomCrop's pad_if_needed), and 255 outside the image; a tap outside the window reads 255 too.
+ * The window is resampled with Pillow's two-pass 8-bit bilinear scheme (horizontal, then vertical, a uint8 intermediate) from tap
+ * tables: per output column x the first tap x0[b][x] (window coordinates) and three 22-bit fixed-point weights kx[b][x][0..2]
+ * (unused taps 0), likewise y0 / ky per output row:
+ *   T(x, r) = clip8((2^21 + sum_i kx[x][i] Wd(x0[x] + i, r)) >> 22),  R(x, y) = clip8((2^21 + sum_j ky[y][j] T(x, y0[y] + j)) >> 22).
+ * With bit 0 set, a pixel of R inside any of the first n_holes[b] (clamped to 0..16) rectangles holes[b][h] = (x1, y1, x2, y2),
+ * half-open, becomes 255.  out(x, y) is the holed image at (bit 1 ? S - 1 - x : x, bit 4 ? S - 1 - y : y).
+ * Also VITED_ERR_BAD_ARG: n_images <= 0. */
+int vited_michigan_windows_u8(const uint8_t* store, const int64_t* img_off, const int* img_hw, int n_images, const int* image,
+                              const int* flags, const int* origin, const int* x0, const int* kx, const int* y0, const int* ky,
+                              const int* holes, const int* n_holes, uint8_t* out, int64_t batch, int img_size, void* stream);
+
+/* ImageFilter.GaussianBlur(radius <= 1) and RandomGrayscale on uint8 [batch, 3, S, S].  With bit 3 set: Pillow's box blur of box
+ * radius 0, three passes along x, then three along y, each
+ *   out[x] = (in[x] ww + (in[max(x - 1, 0)] + in[min(x + 1, S - 1)]) fw + 2^23) >> 24     (unsigned 32-bit)
+ * with weights[b] = (ww, fw) and a uint8 intermediate after every pass.  With bit 5 set, afterwards, all three channels become
+ * L = (R 19595 + G 38470 + B 7471 + 32768) >> 16.  With neither the sample is copied.  Also VITED_ERR_BAD_ARG: out == in. */
+int vited_michigan_blur_gray_u8(const uint8_t* in, const int* flags, const int* weights, uint8_t* out, int64_t batch, int img_size,
+                                void* stream);
+
 /* out[b, r] = (out_dtype) in[b, row_offset + r] for r < rows: drops the cls row of a token-gradient
  * tensor before the patch-embed weight gradient. in is fp32 [batch, in_rows, dim]. */
 int vited_slice_rows_cast(const float* in, void* out, int out_dtype, int64_t batch, int64_t in_rows,

@@ -7,7 +7,7 @@
 // The fixed-point coordinates are sums of separately rounded fp64 terms and the colour arithmetic is Pillow's separate fp32
 // multiply and add: nothing in this file may be contracted into an fma (the Makefile builds it with -ffp-contract=off as well).
 #pragma STDC FP_CONTRACT OFF
-#include "common.h"
+#include "u8_items.h"
 
 namespace {
 
@@ -74,10 +74,6 @@ __device__ __forceinline__ int blend(int d, int p, float f) {
     if (f >= 0.0f && f <= 1.0f) return (int)t;
     return !(t > 0.0f) ? 0 : (t >= 255.0f ? 255 : (int)t);
 }
-
-__device__ __forceinline__ int luma(int r, int g, int b) { return (r * 19595 + g * 38470 + b * 7471 + 32768) >> 16; }
-
-__device__ __forceinline__ int clip8(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
 
 // Pillow's rgb2hsv_row, with its mix of fp32 and fp64 steps
 __device__ __forceinline__ void rgb2hsv(int r, int g, int b, int& H, int& S, int& V) {
@@ -179,31 +175,6 @@ __device__ __forceinline__ int reflect_one(int i, int S) { return i < 0 ? -i : (
 // ---------------------------------------------------------------------------------------------------------------------------
 constexpr int HF_THREADS = 256;
 constexpr int HF_BAND_ROWS = 8;       // S = 512: 64 bands of 1,024 four-pixel items per sample
-
-__device__ __forceinline__ void store_item(uint8_t* __restrict__ o, int64_t plane, int S, int y, int x0, const uint32_t pk[3], bool dwords) {
-    uint8_t* row = o + (int64_t)y * S + x0;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        if (dwords) {
-            *reinterpret_cast<uint32_t*>(row + c * plane) = pk[c];            // S % 4 == 0: every item is whole and aligned
-        } else {
-            for (int j = 0; j < 4 && x0 + j < S; ++j) row[c * plane + j] = (uint8_t)(pk[c] >> (8 * j));
-        }
-    }
-}
-
-__device__ __forceinline__ void load_item(const uint8_t* __restrict__ in, int64_t plane, int S, int y, int x0, uint32_t pk[3], bool dwords) {
-    const uint8_t* row = in + (int64_t)y * S + x0;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        if (dwords) {
-            pk[c] = *reinterpret_cast<const uint32_t*>(row + c * plane);
-        } else {
-            pk[c] = 0u;
-            for (int j = 0; j < 4 && x0 + j < S; ++j) pk[c] |= (uint32_t)row[c * plane + j] << (8 * j);
-        }
-    }
-}
 
 __global__ void __launch_bounds__(HF_THREADS)
 hisfrag_windows_u8_kernel(const uint8_t* __restrict__ store, const int64_t* __restrict__ img_off, const int* __restrict__ img_hw,

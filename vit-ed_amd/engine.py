@@ -9,6 +9,7 @@ loading, logging and checkpoint rotation stay in the reference's ``Trainer``.
 """
 from __future__ import annotations
 
+import math
 import os
 from typing import NamedTuple
 
@@ -923,6 +924,177 @@ class HisfragDeviceLoader:
         g = self._generator(2 * self.rank + 1)
         for image in self.rank_indices():
             yield hisfrag_feed(self.store, self.plan(image, g), self.img_size), self.labels_dev[image]
+
+
+# ---------------------------------------------------------------------------------------------
+# michigan.py's input pipeline on the device: RandomCrop, RandomResizedCrop, CoarseDropout, flips, ColorJitter, Pillow's GaussianBlur,
+# RandomGrayscale (michigan.py:68-101)
+# ---------------------------------------------------------------------------------------------
+MICHIGAN_PLAN_COLUMNS = 104
+MICHIGAN_MAX_HOLES = 16
+_RRC_ATTEMPTS = 10
+
+
+class MichiganPlan(NamedTuple):
+    """One batch's per-sample arguments of ``ops.michigan_windows_u8`` / ``hisfrag_jitter_u8`` / ``michigan_blur_gray_u8``."""
+    image: torch.Tensor      # int32 [B]         image index
+    flags: torch.Tensor      # int32 [B]         bit 0 dropout, 1 horizontal flip, 2 ColorJitter, 3 GaussianBlur, 4 vertical flip, 5 grey
+    origin: torch.Tensor     # int32 [B, 2]      (top, left) of the window in unpadded image coordinates
+    box: torch.Tensor        # int32 [B, 4]      RandomResizedCrop's (i, j, h, w) in the window (what the tap tables were made from)
+    x0: torch.Tensor         # int32 [B, S]      first horizontal tap per output column, in window coordinates
+    kx: torch.Tensor         # int32 [B, S, 3]   its 22-bit fixed-point weights
+    y0: torch.Tensor         # int32 [B, S]      first vertical tap per output row
+    ky: torch.Tensor         # int32 [B, S, 3]
+    holes: torch.Tensor      # int32 [B, 16, 4]  (x1, y1, x2, y2), half-open, before the flips
+    n_holes: torch.Tensor    # int32 [B]
+    order: torch.Tensor      # int32 [B, 4]      jitter operations in the order they run (0 brightness, 1 contrast, 2 saturation, 3 hue)
+    factors: torch.Tensor    # fp32  [B, 3]      brightness, contrast, saturation factors
+    hue: torch.Tensor        # int32 [B]         the uint8 added to H
+    blur: torch.Tensor       # int32 [B, 2]      (ww, fw) of Pillow's box blur
+
+
+def _bilinear_taps(in_size: torch.Tensor, out_size: int, first: torch.Tensor, index: torch.Tensor):
+    """Pillow's precompute_coeffs + normalize_coeffs_8bpc for the bilinear filter where it scales up (support 1, three taps): per
+    sample ``in_size`` fp64 [B] source pixels starting at ``first`` fp64 [B] are resized to ``out_size``; for the output indices
+    ``index`` fp64 [n] -> (first tap int32 [B, n], weights int32 [B, n, 3])."""
+    scale = in_size / torch.full_like(in_size, float(out_size))          # a tensor divisor: a true division on every device
+    center = (index.unsqueeze(0) + 0.5) * scale.unsqueeze(1)
+    xmin = torch.trunc(center - 1.0 + 0.5).clamp_(min=0)
+    xmax = torch.minimum(torch.trunc(center + 1.0 + 0.5), in_size.unsqueeze(1)) - xmin
+    w = []
+    for t in range(3):
+        wt = (1.0 - torch.abs((t + xmin) - center + 0.5)).clamp_(min=0)
+        w.append(torch.where(t < xmax, wt, torch.zeros_like(wt)))
+    ww = (w[0] + w[1]) + w[2]
+    k = torch.stack([torch.trunc(0.5 + (wt / ww) * float(1 << 22)) for wt in w], dim=2)
+    return (xmin + first.unsqueeze(1)).to(torch.int32).contiguous(), k.to(torch.int32).contiguous()
+
+
+def _inclusive_draw(t: torch.Tensor, lo, hi):
+    """random.randint(lo, hi) from uniforms ``t``: lo + floor(t (hi - lo + 1)), never above hi; lo / hi numbers or tensors like t."""
+    span = torch.as_tensor(hi - lo, dtype=t.dtype, device=t.device)
+    return torch.minimum(torch.floor(t * (span + 1)), span) + lo
+
+
+def michigan_augment_plan(u: torch.Tensor, image: torch.Tensor, sizes: torch.Tensor, img_size: int, train: bool = True,
+                          holes=(3, 16), hole_size=(16, 64), radius_max: float = 1.0) -> MichiganPlan:
+    """The random choices of michigan.py's ``HisfragTrainer.get_transforms`` (michigan.py:71-85) for a whole batch at once, from
+    uniform numbers ``u`` [B, 104] in [0, 1), the image indices ``image`` [B] and ``sizes`` int32 [n, 2] = (H, W).  Columns of ``u``:
+      0-1      RandomCrop(S, pad_if_needed=True, fill 255): origin floor(u (Hp - S + 1)) - pad, pad = max(S - H, 0), Hp = H + 2 pad
+      2-21     RandomResizedCrop(S, scale=(0.6, 1)) on the window: ten attempts of (area, ratio) uniforms, area = (0.6 + 0.4 u) S^2,
+               ratio = exp(log(3/4) + u (log(4/3) - log(3/4))), w = round(sqrt(area ratio)), h = round(sqrt(area / ratio)) (half to
+               even); the first attempt with 0 < w <= S and 0 < h <= S wins, otherwise the whole window
+      22-23    its position: i = floor(u (S - h + 1)), j = floor(u (S - w + 1)); the tap tables are Pillow's bilinear coefficients for
+               (h, w) -> (S, S), first taps offset by (i, j)
+      24-25    CoarseDropout at p = 0.9; the number of holes, an inclusive integer draw lo + floor(u (hi - lo + 1)) in ``holes``
+      26-89    per hole (height, width, y1, x1): height / width inclusive draws in ``hole_size`` clamped to S, y1 in [0, S - height],
+               x1 in [0, S - width]
+      90-91    horizontal, vertical flip at p = 0.5
+      92-100   ColorJitter(0.2, 0.3, 0.3, 0.1) at p = 0.5: the order is the argsort of four uniforms, brightness ~ U(0.8, 1.2),
+               contrast / saturation ~ U(0.7, 1.3), hue ~ U(-0.1, 0.1) as the uint8 shift trunc(hue 255) mod 256
+      101-102  GaussianBlur at p = 0.5: r = fp32(0.1 + (radius_max - 0.1) u), then in fp32 s = r r / 3, a = (-(3 s)) / (6 (s - 1)),
+               ww = trunc(2^24 / (a 2 + 1)), and fw = (2^24 - ww) // 2 (Pillow's box radius is 0 for every r <= 1)
+      103      RandomGrayscale at p = 0.2
+    ``train=False``: PadCenterCrop((S, S), fill 255) -> Resize(R = int(1.15 S)) -> CenterCrop(S): the origin is round((W - S) / 2) for
+    W >= S and round(d / 2) - d for a deficit d = S - W (the reference pads both sides by d), the tables are those of S -> R at the
+    output indices x + round((R - S) / 2), every flag is 0.  Elementwise torch operations on the device of ``u``: no host copy, no
+    sync; fp64 except where stated, every product and sum an operation of its own."""
+    S = int(img_size)
+    lo_n, hi_n = (int(t) for t in holes)
+    lo_s, hi_s = (int(t) for t in hole_size)
+    if not 0 <= lo_n <= hi_n <= MICHIGAN_MAX_HOLES or not 1 <= lo_s <= hi_s:
+        raise ValueError(f'holes {holes} must lie in 0..{MICHIGAN_MAX_HOLES} and hole_size {hole_size} be positive, both ascending')
+    if not 0.1 <= radius_max <= 1.0:
+        raise ValueError(f'radius_max {radius_max} outside [0.1, 1]: beyond 1 Pillow\'s box radius is no longer 0')
+    u = u.double()
+    n_rows, dev = u.shape[0], u.device
+    image = image.to(device=dev, dtype=torch.int64)
+    hw = sizes.to(dev)[image.clamp(0, sizes.shape[0] - 1)]
+    H, W = hw[:, 0].double(), hw[:, 1].double()
+    zero, one = torch.zeros_like(H), torch.ones_like(H)
+    izero = torch.zeros(n_rows, dtype=torch.int32, device=dev)
+    natural = torch.arange(4, dtype=torch.int32, device=dev).expand(n_rows, 4)
+    no_blur = torch.tensor([1 << 24, 0], dtype=torch.int32, device=dev).expand(n_rows, 2)
+    no_holes = torch.zeros(n_rows, MICHIGAN_MAX_HOLES, 4, dtype=torch.int32, device=dev)
+    index = torch.arange(S, dtype=torch.float64, device=dev)
+    full = one * S
+    if not train:
+        centre = lambda n: torch.where(n >= S, torch.round((n - S) / 2), torch.round((S - n) / 2) - (S - n))
+        R = int(S * 1.15)
+        x0, kx = _bilinear_taps(full, R, zero, index + round((R - S) / 2))
+        box = torch.stack([zero, zero, full, full], dim=1).to(torch.int32)
+        return MichiganPlan(image.to(torch.int32), izero, torch.stack([centre(H), centre(W)], dim=1).to(torch.int32).contiguous(),
+                            box.contiguous(), x0, kx, x0.clone(), kx.clone(), no_holes, izero.clone(), natural.contiguous(),
+                            torch.ones(n_rows, 3, dtype=torch.float32, device=dev), izero.clone(), no_blur.contiguous())
+    draw = _inclusive_draw
+    # RandomCrop with pad_if_needed
+    pad_y, pad_x = (S - H).clamp_(min=0), (S - W).clamp_(min=0)
+    origin = torch.stack([draw(u[:, 0], 0.0, H + 2 * pad_y - S) - pad_y, draw(u[:, 1], 0.0, W + 2 * pad_x - S) - pad_x], dim=1).to(torch.int32)
+    # RandomResizedCrop
+    log_lo, log_hi = math.log(3.0 / 4.0), math.log(4.0 / 3.0)
+    area = (u[:, 2:22:2] * 0.4 + 0.6) * float(S * S)
+    ratio = torch.exp(u[:, 3:22:2] * (log_hi - log_lo) + log_lo)
+    w_try, h_try = torch.round(torch.sqrt(area * ratio)), torch.round(torch.sqrt(area / ratio))
+    valid = (w_try > 0) & (w_try <= S) & (h_try > 0) & (h_try <= S)
+    first = (valid.int().cumsum(1) == 0).sum(1)                            # the attempts in front of the first valid one
+    pick = first.clamp(max=_RRC_ATTEMPTS - 1).unsqueeze(1)
+    found = first < _RRC_ATTEMPTS
+    bw, bh = torch.where(found, w_try.gather(1, pick).squeeze(1), full), torch.where(found, h_try.gather(1, pick).squeeze(1), full)
+    bi, bj = torch.where(found, draw(u[:, 22], 0.0, S - bh), zero), torch.where(found, draw(u[:, 23], 0.0, S - bw), zero)
+    x0, kx = _bilinear_taps(bw, S, bj, index)
+    y0, ky = _bilinear_taps(bh, S, bi, index)
+    # CoarseDropout
+    dropout = u[:, 24] < 0.9
+    count = torch.where(dropout, draw(u[:, 25], float(lo_n), float(hi_n)), zero)
+    hu = u[:, 26:90].reshape(n_rows, MICHIGAN_MAX_HOLES, 4)
+    limit = lambda t: t.clamp(max=float(S))
+    hh = limit(draw(hu[:, :, 0], float(lo_s), float(hi_s)))
+    hwid = limit(draw(hu[:, :, 1], float(lo_s), float(hi_s)))
+    y1, x1 = draw(hu[:, :, 2], 0.0, S - hh), draw(hu[:, :, 3], 0.0, S - hwid)
+    used = torch.arange(MICHIGAN_MAX_HOLES, device=dev).unsqueeze(0) < count.unsqueeze(1)
+    rects = torch.where(used.unsqueeze(2), torch.stack([x1, y1, x1 + hwid, y1 + hh], dim=2), zero.view(-1, 1, 1)).to(torch.int32)
+    # flips, jitter, blur, grey
+    hflip, vflip, jitter, blur_on, grey = u[:, 90] < 0.5, u[:, 91] < 0.5, u[:, 92] < 0.5, u[:, 101] < 0.5, u[:, 103] < 0.2
+    flags = (dropout.int() + 2 * hflip.int() + 4 * jitter.int() + 8 * blur_on.int() + 16 * vflip.int() + 32 * grey.int()).to(torch.int32)
+    order = torch.where(jitter.unsqueeze(1), torch.argsort(u[:, 93:97], dim=1, stable=True).to(torch.int32), natural)
+    drawn = torch.stack([u[:, 97] * 0.4 + 0.8, u[:, 98] * 0.6 + 0.7, u[:, 99] * 0.6 + 0.7], dim=1)
+    factors = torch.where(jitter.unsqueeze(1), drawn, one.unsqueeze(1)).float()
+    hue = torch.where(jitter, torch.trunc((u[:, 100] * 0.2 - 0.1) * 255.0).to(torch.int64) % 256, 0).to(torch.int32)
+    r = (u[:, 102] * (float(radius_max) - 0.1) + 0.1).float()              # Pillow takes the radius as a C float: fp32 from here on
+    s2 = (r * r) / torch.full_like(r, 3.0)                                  # tensor divisors: true divisions on every device
+    a = (-(s2 * 3.0)) / ((s2 - 1.0) * 6.0)
+    ww = torch.trunc(16777216.0 / (a * 2.0 + 1.0)).to(torch.int64)
+    fw = torch.div((1 << 24) - ww, 2, rounding_mode='floor')
+    blur = torch.where(blur_on.unsqueeze(1), torch.stack([ww, fw], dim=1).to(torch.int32), no_blur)
+    box = torch.stack([bi, bj, bh, bw], dim=1).to(torch.int32)
+    return MichiganPlan(image.to(torch.int32), flags, origin.contiguous(), box.contiguous(), x0, kx, y0, ky, rects.contiguous(),
+                        count.to(torch.int32), order.contiguous(), factors.contiguous(), hue.contiguous(), blur.contiguous())
+
+
+def michigan_feed(store: 'Div2kImageStore', plan: MichiganPlan, img_size: int) -> torch.Tensor:
+    """``plan`` -> uint8 [B, 3, S, S] on the store's device: geometry, colour jitter, blur and grey, three entry points back to back."""
+    from . import ops
+    windows = ops.michigan_windows_u8(store.data, store.offsets_dev, store.sizes_dev, plan.image, plan.flags, plan.origin, plan.x0,
+                                      plan.kx, plan.y0, plan.ky, plan.holes, plan.n_holes, img_size)
+    jittered = ops.hisfrag_jitter_u8(windows, plan.flags, plan.order, plan.factors, plan.hue, out=windows)     # pointwise: in place
+    return ops.michigan_blur_gray_u8(jittered, plan.flags, plan.blur)
+
+
+class MichiganDeviceLoader(HisfragDeviceLoader):
+    """michigan.py's training loader on the device: ``HisfragDeviceLoader``'s sampler, epochs, ranks and generator streams, with
+    michigan.py's transforms (michigan.py:68-101).  Each batch: uniforms -> ``michigan_augment_plan`` -> ``michigan_feed``; it yields
+    (images uint8 [B, 3, S, S], targets int64 [B]) for ``hisfrag_prepare_data``.  Images smaller than the window are padded with
+    255.  The reference runs 20 passes over the set per epoch (michigan.py:110-112): that is the caller's ``repeat``."""
+
+    def plan(self, image: torch.Tensor, generator: torch.Generator) -> MichiganPlan:
+        """One batch's draws."""
+        u = torch.rand(image.numel(), MICHIGAN_PLAN_COLUMNS, generator=generator, device=self.store.device)
+        return michigan_augment_plan(u, image, self.store.sizes_dev, self.img_size, self.train)
+
+    def __iter__(self):
+        g = self._generator(2 * self.rank + 1)
+        for image in self.rank_indices():
+            yield michigan_feed(self.store, self.plan(image, g), self.img_size), self.labels_dev[image]
 
 
 # ---------------------------------------------------------------------------------------------

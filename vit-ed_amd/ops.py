@@ -269,6 +269,47 @@ def hisfrag_blur_u8(img: torch.Tensor, flags: torch.Tensor, weights: torch.Tenso
     return out
 
 
+def michigan_windows_u8(store: torch.Tensor, img_off: torch.Tensor, img_hw: torch.Tensor, image: torch.Tensor, flags: torch.Tensor,
+                        origin: torch.Tensor, x0: torch.Tensor, kx: torch.Tensor, y0: torch.Tensor, ky: torch.Tensor, holes: torch.Tensor,
+                        n_holes: torch.Tensor, img_size: int, out: torch.Tensor | None = None) -> torch.Tensor:
+    """Resident images -> uint8 crops [B, 3, S, S] (``vited_michigan_windows_u8``; michigan.py:72-79): per sample the image index, the
+    flag bits (1 dropout, 2 horizontal flip, 16 vertical flip; the others are ignored), the window origin int32 [B, 2] (top, left)
+    in unpadded image coordinates, Pillow's bilinear tap tables per axis (first tap int32 [B, S] in window coordinates, 22-bit
+    weights int32 [B, S, 3]) and the dropout rectangles int32 [B, 16, 4] = (x1, y1, x2, y2), half-open, of which the first
+    n_holes int32 [B] count.  store / img_off / img_hw as for ``div2k_regions_u8``.  Everything outside the image, and a tap outside
+    the window, is 255; indices and the hole count are clamped."""
+    _need_gpu(store, img_off, img_hw, image, flags, origin, x0, kx, y0, ky, holes, n_holes, out)
+    s = int(img_size)
+    n, b = img_off.numel(), image.numel()
+    assert store.dtype == torch.uint8 and store.dim() == 1 and store.is_contiguous()
+    assert img_off.dtype == torch.int64 and img_off.dim() == 1 and img_off.is_contiguous()
+    assert img_hw.dtype == torch.int32 and img_hw.shape == (n, 2) and img_hw.is_contiguous()
+    i32 = torch.int32
+    _batch_args(b, (image, i32, ()), (flags, i32, ()), (origin, i32, (2,)), (x0, i32, (s,)), (kx, i32, (s, 3)), (y0, i32, (s,)),
+                (ky, i32, (s, 3)), (holes, i32, (16, 4)), (n_holes, i32, ()))
+    if out is None:
+        out = torch.empty((b, 3, s, s), dtype=torch.uint8, device=store.device)
+    assert out.dtype == torch.uint8 and tuple(out.shape) == (b, 3, s, s) and out.is_contiguous()
+    _lib.call('vited_michigan_windows_u8', _ptr(store), _ptr(img_off), _ptr(img_hw), n, _ptr(image), _ptr(flags), _ptr(origin), _ptr(x0),
+              _ptr(kx), _ptr(y0), _ptr(ky), _ptr(holes), _ptr(n_holes), _ptr(out), b, s, _stream())
+    return out
+
+
+def michigan_blur_gray_u8(img: torch.Tensor, flags: torch.Tensor, weights: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+    """ImageFilter.GaussianBlur(radius <= 1) and RandomGrayscale on uint8 crops [B, 3, S, S] (``vited_michigan_blur_gray_u8``;
+    michigan.py:83-85): per sample flag bit 8 (blur), bit 32 (grey; a sample with neither is copied) and the box-blur weights
+    (ww, fw) int32 [B, 2].  ``out`` must not overlap ``img``."""
+    _need_gpu(img, flags, weights, out)
+    assert img.dtype == torch.uint8 and img.dim() == 4 and img.shape[1] == 3 and img.shape[2] == img.shape[3] and img.is_contiguous()
+    b, s = img.shape[0], img.shape[2]
+    _batch_args(b, (flags, torch.int32, ()), (weights, torch.int32, (2,)))
+    if out is None:
+        out = torch.empty_like(img)
+    assert out.dtype == torch.uint8 and out.shape == img.shape and out.is_contiguous() and out.data_ptr() != img.data_ptr()
+    _lib.call('vited_michigan_blur_gray_u8', _ptr(img), _ptr(flags), _ptr(weights), _ptr(out), b, s, _stream())
+    return out
+
+
 def slice_rows_cast(x: torch.Tensor, row_offset: int, rows: int, dtype: torch.dtype) -> torch.Tensor:
     """fp32 [B, R, D] -> dtype [B * rows, D] taking rows [row_offset, row_offset + rows) of every batch."""
     _need_gpu(x)
