@@ -405,6 +405,28 @@ int vited_attention_bwd(const void* q, int64_t q_bs, int64_t q_ts, const void* k
                         int64_t dv_ts, int dtype, int64_t batch, int heads, int64_t nq, int64_t nk,
                         int head_dim, float scale, void* stream);
 
+/* Head-averaged relevancy map of one attention (scripts/visualise_attentions.py: avg_heads, generate_raw_attn,
+ * generate_attn_gradcam), folded over the heads inside the kernel: no [B, H, Nq, Nk] tensor, no workspace, no atomics.
+ *   P_h[i, j]  = exp(scale * q[b,i,h,:] . k[b,j,h,:] - lse[b,h,i])      lse: what vited_attention_fwd saved for these q / k
+ *   dP_h[i, j] = d_o[b,i,h,:] . v[b,j,h,:]                              what the reference's attn.register_hook records
+ *   mode VITED_CAM_GRAD: cam[b,i,j] = (1/H) sum_h max(P_h[i,j] * dP_h[i,j], 0)
+ *   mode VITED_CAM_PROB: cam[b,i,j] = sum_h head_weight[b,h] * P_h[i,j]  (head_weight: DEVICE fp32 [B, H], null = 1/H each;
+ *                        v and d_o are not read and may be null)
+ * q / k / v as in vited_attention_fwd (packed projections in place); d_o is [B, Nq, H*hd] with batch stride do_bs and token stride
+ * do_ts.  cam is fp32, element (b, i, j) at cam + b*cam_bs + i*cam_ld + j; every element with i < nq, j < nk is written exactly
+ * once (the output need not be initialised), nothing else is touched, and two calls on the same operands give the same bits.
+ * bf16 operands that meet the MFMA attention kernels' alignment (16-byte aligned pointers, strides multiples of 8 elements,
+ * head_dim 32 or 64) take the MFMA kernel, everything else the portable fp32 kernel (any head_dim); vited_last_attention_path()
+ * tells which.
+ * VITED_ERR_BAD_ARG: unknown mode; q, k, lse or cam null; v or d_o null in VITED_CAM_GRAD; a non-positive size; cam_ld < nk;
+ * cam_bs < 0.  VITED_ERR_UNSUPPORTED: dtype other than VITED_F32 / VITED_BF16; batch or heads above 65535; nq or nk above 2^20. */
+enum { VITED_CAM_GRAD = 0, VITED_CAM_PROB = 1 };   /* mode of vited_attention_cam */
+int vited_attention_cam(const void* q, int64_t q_bs, int64_t q_ts, const void* k, int64_t k_bs, int64_t k_ts,
+                        const void* v, int64_t v_bs, int64_t v_ts, const void* d_o, int64_t do_bs, int64_t do_ts,
+                        const float* lse, const float* head_weight, float* cam, int64_t cam_bs, int64_t cam_ld,
+                        int mode, int dtype, int64_t batch, int heads, int64_t nq, int64_t nk, int head_dim,
+                        float scale, void* stream);
+
 /* ---- evaluation: retrieval metrics of a distance matrix (misc/wi19_evaluate.get_metrics) ------ */
 
 /* Row records and their sums for the rows [r0, r1) of an n x n matrix D (dtype VITED_F32, VITED_BF16 or VITED_F16; row stride

@@ -4,6 +4,7 @@
 
 static thread_local int g_last_attn_path = 0;
 extern "C" int vited_last_attention_path(void) { return g_last_attn_path; }
+void attention_set_last_path(int path) { g_last_attn_path = path; }
 
 static int check_common(const AttnArgs& a, int dtype) {
     if (!a.q || !a.k || !a.v || !a.o || !a.lse) return VITED_ERR_BAD_ARG;

@@ -30,3 +30,6 @@ int attention_bwd_mfma(const AttnArgs& a, hipStream_t s);
 // tiled online-softmax kernels for long sequences (attention_flash.hip)
 int attention_fwd_flash(const AttnArgs& a, hipStream_t s);
 int attention_bwd_flash(const AttnArgs& a, hipStream_t s);
+
+// what vited_last_attention_path() reports, for dispatchers outside attention.hip (attention_cam.hip)
+void attention_set_last_path(int path);

@@ -68,3 +68,70 @@ __device__ __forceinline__ float group_sum4(float v) {
 #define LOG2E 1.4426950408889634f
 #define LN2 0.6931471805599453f
 
+// ---- 64-row tiles of the long-sequence kernels (attention_flash.hip, attention_cam.hip): staging and fragment helpers ----
+#define FL_TILE 64   // keys (or queries) per LDS tile
+#ifndef FL_W
+#define FL_W 2       // 16-row tiles per wave
+#endif
+
+template <int HD> struct FlashCfg {
+    using C = SmallCfg<HD>;
+    static constexpr int TILE_BYTES = FL_TILE * C::ROW_BYTES;
+    static constexpr int CHUNKS_PER_ROW = HD / 8;
+    static constexpr int PASSES = FL_TILE * CHUNKS_PER_ROW / 256;   // 16-byte chunks per thread and tile
+};
+
+// This thread's 16-byte chunks of a 64-row tile: what does not change from tile to tile (the loops below are VALU-bound - PMC:
+// 8 vector instructions per MFMA in the forward - and the staging arithmetic redone per tile was a third of them: row clamp as
+// compare + select, 64-bit row * stride, the swizzle, a select per stored dword).
+template <int HD> struct TileMap {
+    int row[FlashCfg<HD>::PASSES];   // row inside the tile
+    int col2[FlashCfg<HD>::PASSES];  // column, in bytes
+    int loff[FlashCfg<HD>::PASSES];  // byte offset inside the swizzled LDS image
+    __device__ __forceinline__ TileMap(int tid) {
+#pragma unroll
+        for (int c = 0; c < FlashCfg<HD>::PASSES; ++c) {
+            const int idx = tid + 256 * c;
+            const int ch = idx % FlashCfg<HD>::CHUNKS_PER_ROW;
+            row[c] = idx / FlashCfg<HD>::CHUNKS_PER_ROW;
+            col2[c] = ch * 16;
+            loff[c] = SmallCfg<HD>::off(row[c], ch * 16);
+        }
+    }
+};
+// cooperative tile copy, global -> registers.  Rows past n - 1 re-read row n - 1 (finite values; regs_to_tile zeroes them): the
+// clamp is one v_min against a wave-uniform bound and the address is a 64-bit uniform tile base + a 32-bit per-lane byte offset
+// (attention_fwd_flash / attention_bwd_flash refuse token strides of 2^24 elements or more) ...
+template <int HD>
+__device__ __forceinline__ void tile_to_regs(const bf16* base, int64_t ts, int row0, int n, const TileMap<HD>& m, bf16x8 (&r)[FlashCfg<HD>::PASSES]) {
+    const char* tb = (const char*)(base + (int64_t)row0 * ts);   // wave-uniform
+    const int last = n - 1 - row0;                               // >= 0: a tile is only staged when it holds a valid row
+    const unsigned ts2 = (unsigned)ts * 2u;
+#pragma unroll
+    for (int c = 0; c < FlashCfg<HD>::PASSES; ++c) {
+        const unsigned rr = (unsigned)(m.row[c] < last ? m.row[c] : last);
+        r[c] = *(const bf16x8*)(tb + (rr * ts2 + (unsigned)m.col2[c]));
+    }
+}
+// ... and registers -> LDS image (rows >= n zeroed; only the ragged last tile pays for the selects)
+template <int HD>
+__device__ __forceinline__ void regs_to_tile(char* lds, int row0, int n, const TileMap<HD>& m, const bf16x8 (&r)[FlashCfg<HD>::PASSES]) {
+    if (row0 + FL_TILE > n) {   // wave-uniform
+        asm volatile("" ::: "memory");   // keep this a branch: if-converted it costs a select per stored dword on EVERY tile
+#pragma unroll
+        for (int c = 0; c < FlashCfg<HD>::PASSES; ++c) {
+            bf16x8 v = r[c];
+            if (row0 + m.row[c] >= n) v = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
+            *(bf16x8*)(lds + m.loff[c]) = v;
+        }
+    } else {
+#pragma unroll
+        for (int c = 0; c < FlashCfg<HD>::PASSES; ++c) *(bf16x8*)(lds + m.loff[c]) = r[c];
+    }
+}
+// MFMA row fragment (row fr of 16-row tile t, k chunk g + 4c) out of an LDS image
+template <int HD>
+__device__ __forceinline__ void lds_row_frags(const char* lds, int t, int fr, int g, bf16x8 (&f)[HD / 32]) {
+#pragma unroll
+    for (int c = 0; c < HD / 32; ++c) f[c] = *(const bf16x8*)(lds + SmallCfg<HD>::off(16 * t + fr, 16 * (g + 4 * c)));
+}

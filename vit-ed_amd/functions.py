@@ -97,7 +97,9 @@ class Runtime:
         self.direct_grads = False   # accumulate parameter gradients straight into existing p.grad (engine.FlatGradients)
         self.input_mean, self.input_std = (0.5, 0.5, 0.5), (0.5, 0.5, 0.5)   # Normalize() of data/transforms.py:14-18, for uint8 inputs
         self.keep_attn = False      # MODEL.PJS.KEEP_ATTN: also materialise the attention maps (visualisation slow path)
-        self.attn_store = {}        # (kind, block index, 'attn' | 'cross_attn') -> {'attn': ..., 'grad': ...}
+        self.keep_cam = False       # record the head-averaged relevancy map of every attention in the backward (ops.attention_cam): no
+                                    # per-head map is formed, and the backward leaves every parameter gradient alone (see _cam_only)
+        self.attn_store = {}        # (kind, block index, 'attn' | 'cross_attn') -> {'attn': ..., 'grad': ..., 'cam': [B, Nq, Nk]}
         self.cls_tail = os.environ.get('VITED_CLS_TAIL', '1') != '0'   # last decoder block on the cls rows only (exact; see _dec_self_fwd)
         self.fused_mlp = os.environ.get('VITED_FUSED_MLP', '1') != '0'   # vited_mlp_fwd on the no-grad paths
         self.fused_ln = os.environ.get('VITED_FUSED_LN', '1') != '0'     # LayerNorm inside the neighbouring Linear's kernel (gemm_row.hip)
@@ -224,7 +226,10 @@ def _ln_bwd(rt, dy, x, gamma, beta, mean, rstd, **kw):
 
 def _weight_grads(rt, dy, x_saved, w, b):
     """(dW | None, db | None) of y = x W^T + b; None when accumulated straight into w.grad / b.grad.  Inside a _DwBatch (one
-    transformer block's backward) the product is only QUEUED: the block's weight gradients then go out as one launch."""
+    transformer block's backward) the product is only QUEUED: the block's weight gradients then go out as one launch.
+    Under ``rt.keep_cam`` nothing is launched: that backward exists for the relevancy maps and hands no parameter gradient on."""
+    if rt.keep_cam:
+        return None, None
     gw = _gtarget(rt, w)
     gb = _gtarget(rt, b) if b is not None else None
     direct = gw is not None and (b is None or gb is not None)
@@ -397,6 +402,21 @@ def _keep_attention_grad(rt, key, do, v):
     rt.attn_store.setdefault(key, {})['grad'] = doh @ vh.transpose(-2, -1)
 
 
+def _keep_attention_cam(rt, key, q, k, v, do, lse):
+    """keep_cam: what the consumer of the two maps above reduces them to, mean_h max(attn o grad, 0) [B, Nq, Nk] (avg_heads of
+    scripts/visualise_attentions.py), from the operands the attention backward is about to read - one kernel, no per-head map."""
+    ent = rt.attn_store.setdefault(key, {})
+    ent['cam'] = ops.attention_cam(q, k, v, do, lse, rt.heads, rt.scale, mode='grad')
+    if key == ('cross_blocks', rt.c_depth - 1, 'cross_attn'):
+        ent['cam_operands'] = (q, k, v, do, lse)   # the last cross-attention's operands: the 'raw' / 'gradcam' maps of engine.pair_relevancy
+
+
+def _cam_only(rt, grads):
+    """The parameter gradients a Function's backward returns: under ``rt.keep_cam`` none - autograd then adds nothing to any
+    p.grad, and with direct gradients switched off for that backward (model.runtime) no kernel has added to one either."""
+    return [None] * len(grads) if rt.keep_cam else grads
+
+
 def _self_attn_fwd(rt, h, wqkv, bqkv, batch, n, key=None):
     d = rt.dim
     qkv = ops.gemm(h, rt.weight(wqkv), bias=bqkv)                   # [M, 3D], columns [3][h][hd] (:58)
@@ -412,6 +432,8 @@ def _self_attn_bwd(rt, do, qkv, o, lse, batch, n, key=None):
     qkv3 = qkv.view(batch, n, 3 * d)
     if rt.keep_attn and key is not None:
         _keep_attention_grad(rt, key, do.view(batch, n, d), qkv3[:, :, 2 * d:3 * d])
+    if rt.keep_cam and key is not None:
+        _keep_attention_cam(rt, key, qkv3[:, :, 0:d], qkv3[:, :, d:2 * d], qkv3[:, :, 2 * d:3 * d], do.view(batch, n, d), lse)
     dqkv = torch.empty_like(qkv)
     dqkv3 = dqkv.view(batch, n, 3 * d)
     ops.attention_bwd(qkv3[:, :, 0:d], qkv3[:, :, d:2 * d], qkv3[:, :, 2 * d:3 * d], o.view(batch, n, d),
@@ -577,7 +599,7 @@ class EncoderFn(torch.autograd.Function):
                 gblocks[i] = EncBlock(**ga, **gm)
         gshared = EncShared(**_patch_tokens_bwd(rt, dx, ctx.patches, shared, with_cls=False, batch=batch))
         ctx.tape = ctx.patches = None
-        return (None, None, *flatten_params(gshared, gblocks))
+        return (None, None, *_cam_only(rt, flatten_params(gshared, gblocks)))
 
 
 # ---------------------------------------------------------------------------------------------
@@ -677,6 +699,9 @@ def _dec_cross_bwd(rt, dx, dx_lp, xa, P, saved, ctxf, dctx, batch, index, dkv3=N
         kv3, dkv3 = kv.view(batch, rt.n1, 2 * d), dkv.view(batch, rt.n1, 2 * d)
     if rt.keep_attn:
         _keep_attention_grad(rt, ('cross_blocks', index, 'cross_attn'), doc.view(batch, nq, d), kv3[:, :, d:2 * d])
+    if rt.keep_cam:
+        _keep_attention_cam(rt, ('cross_blocks', index, 'cross_attn'), q.view(batch, nq, d), kv3[:, :, 0:d], kv3[:, :, d:2 * d],
+                            doc.view(batch, nq, d), lse_c)
     ops.attention_bwd(q.view(batch, nq, d), kv3[:, :, 0:d], kv3[:, :, d:2 * d], oc.view(batch, nq, d),
                       doc.view(batch, nq, d), lse_c, rt.heads, rt.scale, dq.view(batch, nq, d), dkv3[:, :, 0:d],
                       dkv3[:, :, d:2 * d])
@@ -850,7 +875,7 @@ class DecoderFn(torch.autograd.Function):
         ctxf = feats.detach().contiguous().float().view(batch * rt.n1, rt.dim)
         tape = []
         d = rt.dim
-        cls_tail = rt.cls_tail and rt.c_depth > 0 and not rt.keep_attn    # the visualisation path wants every query row's map
+        cls_tail = rt.cls_tail and rt.c_depth > 0 and not (rt.keep_attn or rt.keep_cam)    # the visualisation paths want every query row's map
         ln1 = None
         fold = rt.fold_context and not rt.exact and rt.c_depth > 1 and rt.c_depth <= ops.MAX_FOLDED_BLOCKS and rt.dim % 32 == 0
         kv_all = kv_saved = fold_bufs = None
@@ -920,4 +945,4 @@ class DecoderFn(torch.autograd.Function):
         gshared = DecShared(**_patch_tokens_bwd(rt, dx, ctx.patches, shared, with_cls=True, batch=batch), gN=dgN, bN=dbN, wh=dwh, bh=dbh)
         dfeats = dctx.view(batch, rt.n1, d) if ctx.feats_needs_grad and dctx is not None else None
         ctx.tape = ctx.patches = ctx.ctxf = ctx.final = None
-        return (None, dfeats, None, None, *flatten_params(gshared, gblocks))
+        return (None, dfeats, None, None, *_cam_only(rt, flatten_params(gshared, gblocks)))

@@ -72,7 +72,8 @@ class _SelfAttn(_Holder):
         ent = (self._store() or {}).get(self._key) if self._store is not None else None
         if ent is None or what not in ent:
             raise RuntimeError('no attention map recorded: build the model with MODEL.PJS.KEEP_ATTN True (keep_attn=True) and '
-                               'run a forward' + (' and a backward' if what == 'grad' else '') + ' first')
+                               'run a forward' + (' and a backward' if what in ('grad', 'cam') else '') + ' first'
+                               + (' (get_attn_cam: set model.keep_cam = True instead)' if what == 'cam' else ''))
         return ent[what]
 
     def get_attn(self):
@@ -82,6 +83,11 @@ class _SelfAttn(_Holder):
     def get_attn_gradients(self):
         """d loss / d attn of the last backward (vision_transformer.py:49-50,169-170)."""
         return self._lookup('grad')
+
+    def get_attn_cam(self):
+        """mean_h max(attn o grad, 0) [B, Nq, Nk] of the last backward under ``model.keep_cam``: avg_heads(get_attn(),
+        get_attn_gradients()) of scripts/visualise_attentions.py for every sample, from one fused kernel (ops.attention_cam)."""
+        return self._lookup('cam')
 
 
 class _CrossAttn(_SelfAttn):
@@ -165,6 +171,8 @@ class VisionTransformerCustom(nn.Module):
         self.num_features = embed_dim
         self.depth, self.c_depth, self.num_heads = depth, c_depth, num_heads
         self.keep_attn = bool(keep_attn)    # visualisation slow path: attention maps are ALSO materialised (PyTorch ops)
+        self.keep_cam = False               # record head-averaged relevancy maps in the backward (fused kernel; engine.pair_relevancy):
+                                            # such a backward leaves every parameter gradient untouched
         self.arch_version = arch_version.lower()
         self.compute_dtype = compute_dtype
         # uint8 inputs are normalised inside the patch-embedding kernel: ToTensor + Normalize(0.5, 0.5) of data/transforms.py:14-18
@@ -217,6 +225,9 @@ class VisionTransformerCustom(nn.Module):
         rt.direct_grads = bool(getattr(self, 'direct_param_grads', False))
         rt.input_mean, rt.input_std = self.input_mean, self.input_std
         rt.keep_attn, rt.attn_store = self.keep_attn, self._attn_store
+        rt.keep_cam = bool(self.keep_cam)
+        if rt.keep_cam:
+            rt.direct_grads = False         # nothing of that backward may reach a p.grad or the flat gradient buffer behind it
         return rt
 
     def _encoder_params(self):

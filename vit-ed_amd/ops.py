@@ -721,6 +721,66 @@ def attention_bwd(q, k, v, o, do, lse, heads: int, scale: float, dq, dk, dv):
     return dq, dk, dv
 
 
+CAM_GRAD, CAM_PROB = 0, 1          # VITED_CAM_GRAD / VITED_CAM_PROB
+_CAM_MODES = {'grad': CAM_GRAD, 'prob': CAM_PROB, CAM_GRAD: CAM_GRAD, CAM_PROB: CAM_PROB}
+
+
+def _cam_operand(name, t, heads, like=None):
+    if t.dim() != 3 or t.stride(2) != 1 or t.shape[2] % heads:
+        raise ValueError(f'attention_cam: {name} must be [B, N, heads*head_dim] with a dense last dim, got shape {tuple(t.shape)} '
+                         f'stride {t.stride()} for {heads} heads')
+    if like is not None and (t.dtype != like.dtype or t.device != like.device or t.shape[0] != like.shape[0] or t.shape[2] != like.shape[2]):
+        raise ValueError(f'attention_cam: {name} {tuple(t.shape)} {t.dtype} does not match q {tuple(like.shape)} {like.dtype}')
+    return t.stride(0), t.stride(1)
+
+
+def attention_cam(q, k, v, do, lse, heads: int, scale: float, *, mode, head_weight=None, out=None):
+    """Head-averaged relevancy map [B, Nq, Nk] fp32 of one attention, never forming a per-head map (vited_attention_cam):
+    ``mode='grad'``: mean_h max(P_h o dP_h, 0) with P_h = softmax(scale q_h k_h^T) rebuilt from ``lse`` (what attention_fwd
+    returned for these q / k) and dP_h = dO_h v_h^T - avg_heads(attn, grad) of scripts/visualise_attentions.py;
+    ``mode='prob'``: sum_h head_weight[b, h] P_h (``head_weight`` fp32 [B, H]; None = 1/H, the head mean of the attention);
+    ``v`` and ``do`` are not read and may be None.  q [B,Nq,D], k / v [B,Nk,D], do [B,Nq,D]: strided views of the packed
+    projections are fine.  ``out``: fp32 [B, Nq, >= Nk] view with a dense last dim; only [:, :, :Nk] is written."""
+    if mode not in _CAM_MODES:
+        raise ValueError(f"attention_cam: mode must be 'grad' or 'prob', got {mode!r}")
+    mode = _CAM_MODES[mode]
+    if mode == CAM_GRAD and (v is None or do is None):
+        raise ValueError("attention_cam: mode='grad' needs v and do")
+    if mode == CAM_GRAD and head_weight is not None:
+        raise ValueError("attention_cam: head_weight belongs to mode='prob'")
+    if mode == CAM_PROB:
+        v = do = None
+    _need_gpu(q, k, v, do, lse, head_weight, out)
+    if heads <= 0:
+        raise ValueError(f'attention_cam: heads must be positive, got {heads}')
+    q_bs, q_ts = _cam_operand('q', q, heads)
+    k_bs, k_ts = _cam_operand('k', k, heads, q)
+    v_bs, v_ts = _cam_operand('v', v, heads, q) if v is not None else (0, 0)
+    do_bs, do_ts = _cam_operand('do', do, heads, q) if do is not None else (0, 0)
+    b, nq, d = q.shape
+    nk = k.shape[1]
+    if v is not None and v.shape[1] != nk:
+        raise ValueError(f'attention_cam: v has {v.shape[1]} tokens, k has {nk}')
+    if do is not None and do.shape[1] != nq:
+        raise ValueError(f'attention_cam: do has {do.shape[1]} tokens, q has {nq}')
+    if b == 0 or nq == 0 or nk == 0:
+        raise ValueError(f'attention_cam: empty operands (B {b}, Nq {nq}, Nk {nk})')
+    if lse.dtype != torch.float32 or tuple(lse.shape) != (b, heads, nq) or not lse.is_contiguous():
+        raise ValueError(f'attention_cam: lse must be contiguous float32 [{b}, {heads}, {nq}], got {tuple(lse.shape)} {lse.dtype}')
+    if head_weight is not None and (head_weight.dtype != torch.float32 or tuple(head_weight.shape) != (b, heads) or not head_weight.is_contiguous()):
+        raise ValueError(f'attention_cam: head_weight must be contiguous float32 [{b}, {heads}], got {tuple(head_weight.shape)} {head_weight.dtype}')
+    if out is None:
+        out = torch.empty((b, nq, nk), dtype=torch.float32, device=q.device)
+    elif (out.dtype != torch.float32 or out.dim() != 3 or out.shape[0] != b or out.shape[1] != nq or out.shape[2] < nk or out.stride(2) != 1
+          or out.stride(1) < nk or out.device != q.device):
+        raise ValueError(f'attention_cam: out must be float32 [{b}, {nq}, >= {nk}] with a dense last dim, got {tuple(out.shape)} '
+                         f'stride {out.stride()} {out.dtype}')
+    _lib.call('vited_attention_cam', _ptr(q), q_bs, q_ts, _ptr(k), k_bs, k_ts, _ptr(v), v_bs, v_ts, _ptr(do), do_bs, do_ts, _ptr(lse),
+              _ptr(head_weight), _ptr(out), out.stride(0), out.stride(1), mode, _code(q.dtype), b, heads, nq, nk, d // heads,
+              float(scale), _stream())
+    return out[:, :, :nk] if out.shape[2] != nk else out
+
+
 def last_paths():
     lib = _lib.load()
     return lib.vited_last_gemm_path(), lib.vited_last_attention_path()
