@@ -217,6 +217,21 @@ int vited_layernorm_bwd(const void* dy, int dy_dtype, int64_t dy_ld, const float
                         int64_t dx_lp_ld, float* dgamma, float* dbeta, int accumulate, int64_t rows, int64_t dim,
                         float* workspace, int64_t workspace_bytes, void* stream);
 
+/* vited_layernorm_bwd whose low-precision copy ALONE is scaled per row: dx_lp[r, :] = T(lp_scale[r] * dx_out[r, :]), dx_out
+ * unscaled.  Under stochastic depth the copy is what the next branch's backward consumes (its d(input) GEMM, weight and bias
+ * gradients), and that branch sees s[b] * dy while the residual path carries dy.  dx_lp is required and may be VITED_BF16 or
+ * VITED_F32 (the exact path, where the copy otherwise is dx_out itself).  lp_scale == null is vited_layernorm_bwd. */
+int vited_layernorm_bwd_scaled(const void* dy, int dy_dtype, int64_t dy_ld, const float* x, int64_t x_ld,
+                               const float* gamma, const float* mean, const float* rstd, const float* dx_in,
+                               int64_t dx_in_ld, float* dx_out, int64_t dx_out_ld, void* dx_lp, int dx_lp_dtype,
+                               int64_t dx_lp_ld, const float* lp_scale, float* dgamma, float* dbeta, int accumulate,
+                               int64_t rows, int64_t dim, float* workspace, int64_t workspace_bytes, void* stream);
+
+/* dst[r, :] = (dst_dtype)(row_scale[r] * src[r, :]), src fp32 [rows, dim]: the scaled copy of the incoming stream gradient at the
+ * head of a backward pass (the last branch of the encoder / decoder consumes it).  dim and the row strides multiples of 4. */
+int vited_scale_rows_cast(const float* src, int64_t src_ld, const float* row_scale, void* dst, int dst_dtype, int64_t dst_ld,
+                          int64_t rows, int64_t dim, void* stream);
+
 /* ---- Linear / GEMM (nn.Linear: qkv :34, proj :38, q :151, kv :152, timm Mlp fc1/fc2, head) ---- */
 
 /* acc[m, n] = sum_k A[m, k] * B(n, k), fp32 accumulation; A is `dtype` [M, K] (row stride lda);
@@ -233,6 +248,15 @@ int vited_gemm(const void* A, int64_t lda, const void* B, int64_t ldb, int b_lay
                int64_t N, int64_t K, int epilogue, const float* bias, const void* aux,
                const float* residual, void* out, void* out2, int64_t ldo, int64_t rows_per_batch,
                int64_t out_rows_per_batch, int64_t row_offset, int residual_bcast, void* stream);
+
+/* VITED_EPI_RESIDUAL under stochastic depth (timm DropPath, scale_by_keep; the residual adds of Block.forward / CrossBlock.forward,
+ * vision_transformer.py:125-126, 269-271):  out[m, n] = residual[m, n] + row_scale[m] * (acc[m, n] + bias[n]),
+ * row_scale fp32 [M] with the sample's 0 or 1 / keep repeated over its rows (read once per row, beside the residual row).
+ * Identity row map; out and residual fp32 with row stride ldo.  row_scale == null is vited_gemm(VITED_EPI_RESIDUAL) itself: the
+ * same kernel instance, so a model without stochastic depth runs the code it ran before. */
+int vited_gemm_scaled(const void* A, int64_t lda, const void* B, int64_t ldb, int b_layout, int dtype, int64_t M, int64_t N,
+                      int64_t K, const float* bias, const float* residual, const float* row_scale, float* out, int64_t ldo,
+                      void* stream);
 
 /* dW[n, k] = sum_m dY[m, n] * X[m, k] (fp32 [N, K]) and, if dbias != null, dbias[n] = sum_m dY[m, n];
  * overwritten, or added onto their current content when `accumulate` != 0.  dY / X are `dtype`.
@@ -273,6 +297,13 @@ int vited_linear_residual_layernorm_fwd(const void* a, int64_t lda, const void* 
                                         const float* beta, float eps, void* h, int64_t ldh, float* mean, float* rstd,
                                         int64_t M, int64_t N, int64_t K, void* stream);
 
+/* The same with y = residual + row_scale[m] * (a . w^T + bias) (stochastic depth, see vited_gemm_scaled); the LayerNorm statistics
+ * are those of the scaled y.  row_scale fp32 [M]; null = vited_linear_residual_layernorm_fwd (the unscaled kernel instance). */
+int vited_linear_residual_layernorm_fwd_scaled(const void* a, int64_t lda, const void* w, int64_t ldw, const float* bias,
+                                               const float* residual, int64_t ldr, const float* row_scale, float* y, int64_t ldy,
+                                               const float* gamma, const float* beta, float eps, void* h, int64_t ldh, float* mean,
+                                               float* rstd, int64_t M, int64_t N, int64_t K, void* stream);
+
 /* dh = dy . wt^T  (wt = the transposed weight shadow, bf16 [N, K]: dX of y = LN(x) W^T), never written anywhere;
  * dx_out = (dx_in ? dx_in : 0) + LN'(dh; x, mean, rstd, gamma)  fp32 (dx_out may alias dx_in), optional bf16 copy dx_lp;
  * dgamma / dbeta: column sums of dh * xhat / dh, overwritten or (accumulate != 0) added.  workspace >= *_workspace_bytes.
@@ -296,6 +327,14 @@ int vited_linear_layernorm_bwd(const void* dy, int64_t lddy, const void* wt, int
                                int64_t dx_in_ld, float* dx_out, int64_t dx_out_ld, void* dx_lp, int64_t dx_lp_ld,
                                float* dgamma, float* dbeta, int accumulate, int64_t M, int64_t N, int64_t K,
                                float* workspace, int64_t workspace_bytes, void* stream);
+
+/* vited_linear_layernorm_bwd with dx_lp[m, :] = bf16(lp_scale[m] * dx_out[m, :]) (see vited_layernorm_bwd_scaled); dx_lp is
+ * required.  lp_scale == null is vited_linear_layernorm_bwd (the unscaled kernel instance). */
+int vited_linear_layernorm_bwd_scaled(const void* dy, int64_t lddy, const void* wt, int64_t ldwt, const float* x, int64_t ldx,
+                                      const float* gamma, const float* mean, const float* rstd, const float* dx_in,
+                                      int64_t dx_in_ld, float* dx_out, int64_t dx_out_ld, void* dx_lp, int64_t dx_lp_ld,
+                                      const float* lp_scale, float* dgamma, float* dbeta, int accumulate, int64_t M, int64_t N,
+                                      int64_t K, float* workspace, int64_t workspace_bytes, void* stream);
 
 /* ---- norm_context + kv projection of all decoder blocks as one GEMM (context_fold.hip) ----
  * Every CrossBlock normalises the SAME encoder features with its own norm_context (vision_transformer.py:245,269-270) before

@@ -7,7 +7,10 @@ part of the ViT-ED hot path and are rejected with a clear message.
 from .model import VisionTransformerCustom
 
 
-def build_model(config, is_pretrain=False):
+def build_model(config, is_pretrain=False, drop_path_rate=None):
+    """``drop_path_rate``: stochastic depth.  The default (None) reads exactly the keys the reference reads, and the reference's
+    factory does not forward ``MODEL.DROP_PATH_RATE`` to the pjs model - the shipped YAMLs set it to 0.1 without effect.  Pass
+    ``drop_path_rate=config.MODEL.DROP_PATH_RATE`` to train the regularised model those configs describe."""
     model_type = config.MODEL.TYPE
     if model_type != 'pjs':
         raise NotImplementedError(
@@ -27,4 +30,5 @@ def build_model(config, is_pretrain=False):
         qkv_bias=pjs.QKV_BIAS,
         keep_attn=pjs.KEEP_ATTN,
         arch_version=pjs.ARCH_VERSION,
+        drop_path_rate=0. if drop_path_rate is None else drop_path_rate,
     )

@@ -40,6 +40,45 @@ extern "C" int vited_cast(const void* src, int src_dtype, void* dst, int dst_dty
     return vited_check_launch();
 }
 
+// dst[r, :] = D(scale[r] * src[r, :]): the head of a Function's backward under stochastic depth.  A 32-lane
+// half-wave owns a row (the LayerNorm kernels' row loop): the scale is read once per row, 16 bytes per lane, no index division.
+template <typename D>
+__global__ void __launch_bounds__(256)
+scale_rows_cast_kernel(const float* __restrict__ src, int64_t src_ld, const float* __restrict__ scale, D* __restrict__ dst, int64_t dst_ld,
+                       int64_t rows, int dim) {
+    const int hl = threadIdx.x & 31;
+    const int64_t half = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 5;
+    const int64_t nhalf = ((int64_t)gridDim.x * blockDim.x) >> 5;
+    for (int64_t r = half; r < rows; r += nhalf) {
+        const float sc = scale[r];
+        for (int c = hl * 4; c < dim; c += 128) {
+            const f32x4 v = *(const f32x4*)(src + r * src_ld + c);
+            if constexpr (sizeof(D) == 2) {
+                *(bf16x4*)((bf16*)dst + r * dst_ld + c) = bf16x4{(bf16)(sc * v[0]), (bf16)(sc * v[1]), (bf16)(sc * v[2]), (bf16)(sc * v[3])};
+            } else {
+                *(f32x4*)((float*)dst + r * dst_ld + c) = f32x4{sc * v[0], sc * v[1], sc * v[2], sc * v[3]};
+            }
+        }
+    }
+}
+
+extern "C" int vited_scale_rows_cast(const float* src, int64_t src_ld, const float* row_scale, void* dst, int dst_dtype, int64_t dst_ld,
+                                     int64_t rows, int64_t dim, void* stream) {
+    if (!src || !row_scale || !dst || rows <= 0 || dim <= 0 || src_ld < dim || dst_ld < dim) return VITED_ERR_BAD_ARG;
+    if (dim % 4 || src_ld % 4 || dst_ld % 4 || dim > (1 << 20)) return VITED_ERR_UNSUPPORTED;
+    if (((uintptr_t)src & 15) || ((uintptr_t)dst & (dst_dtype == VITED_F32 ? 15 : 7))) return VITED_ERR_BAD_ARG;
+    int64_t blocks = ceil_div64(rows, 8);
+    if (blocks > 2048) blocks = 2048;
+    hipStream_t s = (hipStream_t)stream;
+    if (dst_dtype == VITED_BF16)
+        hipLaunchKernelGGL((scale_rows_cast_kernel<bf16>), dim3(blocks), dim3(256), 0, s, src, src_ld, row_scale, (bf16*)dst, dst_ld, rows, (int)dim);
+    else if (dst_dtype == VITED_F32)
+        hipLaunchKernelGGL((scale_rows_cast_kernel<float>), dim3(blocks), dim3(256), 0, s, src, src_ld, row_scale, (float*)dst, dst_ld, rows, (int)dim);
+    else
+        return VITED_ERR_UNSUPPORTED;
+    return vited_check_launch();
+}
+
 // ------------------------------------------------------------------------------------------------
 // cast + transpose through a padded 32x32 LDS tile (both sides coalesced)
 // ------------------------------------------------------------------------------------------------

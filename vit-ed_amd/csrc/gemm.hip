@@ -8,19 +8,26 @@
 static thread_local int g_last_gemm_path = 0;
 extern "C" int vited_last_gemm_path(void) { return g_last_gemm_path; }
 
-extern "C" int vited_gemm(const void* A, int64_t lda, const void* B, int64_t ldb, int b_layout, int dtype, int64_t M,
-                          int64_t N, int64_t K, int epilogue, const float* bias, const void* aux, const float* residual,
-                          void* out, void* out2, int64_t ldo, int64_t rows_per_batch, int64_t out_rows_per_batch,
-                          int64_t row_offset, int residual_bcast, void* stream) {
+static int gemm_impl(const void* A, int64_t lda, const void* B, int64_t ldb, int b_layout, int dtype, int64_t M, int64_t N, int64_t K,
+                     int epilogue, const float* bias, const void* aux, const float* residual, void* out, void* out2, int64_t ldo,
+                     int64_t rows_per_batch, int64_t out_rows_per_batch, int64_t row_offset, int residual_bcast,
+                     const float* row_scale, void* stream) {
     if (!A || !B || !out || M <= 0 || N <= 0 || K <= 0 || lda < K || ldo < N) return VITED_ERR_BAD_ARG;
     if (b_layout != VITED_B_NK && b_layout != VITED_B_KN) return VITED_ERR_BAD_ARG;
     if (ldb < (b_layout == VITED_B_NK ? K : N)) return VITED_ERR_BAD_ARG;
+    // only the public codes arrive here: EPI_RESIDUAL_SCALED is chosen below and nowhere else, so it always has its scale and residual
+    if (epilogue < VITED_EPI_STORE || epilogue > VITED_EPI_GELU_GRAD) return VITED_ERR_BAD_ARG;
     if ((epilogue == VITED_EPI_GELU || epilogue == VITED_EPI_GELU_GRAD) && !out2) return VITED_ERR_BAD_ARG;
     if (epilogue == VITED_EPI_RESIDUAL && !residual) return VITED_ERR_BAD_ARG;
     if ((epilogue == VITED_EPI_MUL_GELU_GRAD || epilogue == VITED_EPI_MUL) && !aux) return VITED_ERR_BAD_ARG;
     if (rows_per_batch < 0 || (rows_per_batch > 0 && (out_rows_per_batch < rows_per_batch + row_offset || row_offset < 0)))
         return VITED_ERR_BAD_ARG;
+    if (row_scale) {     // a live scale selects the scaled instance of the residual epilogue; a null one leaves every kernel as it was
+        if (epilogue != VITED_EPI_RESIDUAL || rows_per_batch != 0) return VITED_ERR_BAD_ARG;
+        epilogue = EPI_RESIDUAL_SCALED;
+    }
     EpiParams ep;
+    ep.row_scale = row_scale;
     ep.bias = bias;
     ep.aux = aux;
     ep.residual = residual;
@@ -38,6 +45,21 @@ extern "C" int vited_gemm(const void* A, int64_t lda, const void* B, int64_t ldb
     }
     g_last_gemm_path = 1;
     return gemm_portable(A, lda, B, ldb, b_layout, dtype, M, N, K, epilogue, ep, s);
+}
+
+extern "C" int vited_gemm(const void* A, int64_t lda, const void* B, int64_t ldb, int b_layout, int dtype, int64_t M,
+                          int64_t N, int64_t K, int epilogue, const float* bias, const void* aux, const float* residual,
+                          void* out, void* out2, int64_t ldo, int64_t rows_per_batch, int64_t out_rows_per_batch,
+                          int64_t row_offset, int residual_bcast, void* stream) {
+    return gemm_impl(A, lda, B, ldb, b_layout, dtype, M, N, K, epilogue, bias, aux, residual, out, out2, ldo, rows_per_batch,
+                     out_rows_per_batch, row_offset, residual_bcast, nullptr, stream);
+}
+
+extern "C" int vited_gemm_scaled(const void* A, int64_t lda, const void* B, int64_t ldb, int b_layout, int dtype, int64_t M,
+                                 int64_t N, int64_t K, const float* bias, const float* residual, const float* row_scale,
+                                 float* out, int64_t ldo, void* stream) {
+    return gemm_impl(A, lda, B, ldb, b_layout, dtype, M, N, K, VITED_EPI_RESIDUAL, bias, nullptr, residual, out, nullptr, ldo, 0, 0, 0, 0,
+                     row_scale, stream);
 }
 
 static inline int64_t tn_portable_splits(int64_t M, int64_t N, int64_t K) {

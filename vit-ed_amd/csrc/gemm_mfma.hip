@@ -211,7 +211,7 @@ bool gemm_nt_mfma_supported(const void* A, int64_t lda, const void* B, int64_t l
     if (ep.bias && !al16(ep.bias)) return false;
     if ((epilogue == VITED_EPI_GELU || epilogue == VITED_EPI_GELU_GRAD) && !al16(ep.out2)) return false;
     if ((epilogue == VITED_EPI_MUL_GELU_GRAD || epilogue == VITED_EPI_MUL) && !al16(ep.aux)) return false;
-    if (epilogue == VITED_EPI_RESIDUAL && !al16(ep.residual)) return false;
+    if ((epilogue == VITED_EPI_RESIDUAL || epilogue == EPI_RESIDUAL_SCALED) && !al16(ep.residual)) return false;
     if (ceil_div64(M, 128) * ceil_div64(N, BN) > (1 << 30)) return false;
     if (M >= ((int64_t)1 << 31) || ep.rows_per_batch >= ((int64_t)1 << 31)) return false;   // the row remap divides in 32 bits
     return true;
@@ -298,6 +298,7 @@ int gemm_nt_mfma(const void* A, int64_t lda, const void* B, int64_t ldb, int64_t
         case VITED_EPI_STORE_F32: rc = dispatch_nt<VITED_EPI_STORE_F32>(a, lda, b, ldb, M, N, K, ep, s); break;
         case VITED_EPI_MUL: rc = dispatch_nt<VITED_EPI_MUL>(a, lda, b, ldb, M, N, K, ep, s); break;
         case VITED_EPI_GELU_GRAD: rc = dispatch_nt<VITED_EPI_GELU_GRAD>(a, lda, b, ldb, M, N, K, ep, s); break;
+        case EPI_RESIDUAL_SCALED: rc = dispatch_nt<EPI_RESIDUAL_SCALED>(a, lda, b, ldb, M, N, K, ep, s); break;
         default: return VITED_ERR_BAD_ARG;
     }
     return rc != VITED_OK ? rc : vited_check_launch();

@@ -23,7 +23,7 @@
 #define SCRATCH_BYTES (16 * SCRATCH_LD * 4)
 
 template <int EPI> struct EpiTraits {
-    static constexpr bool F32_OUT = (EPI == VITED_EPI_RESIDUAL || EPI == VITED_EPI_STORE_F32);
+    static constexpr bool F32_OUT = (epi_is_residual<EPI> || EPI == VITED_EPI_STORE_F32);
     static constexpr int PIECES = F32_OUT ? 4 : 2;      // (row, vector) pieces per lane per 16-row sub-tile
     static constexpr int WIDTH = F32_OUT ? 4 : 8;       // consecutive columns per piece
     static constexpr int ROWS_PER_PIECE = 16 / PIECES;  // rows covered by one store instruction
@@ -34,7 +34,8 @@ template <int EPI> struct EpiTraits {
 };
 
 template <int EPI> struct EpiPrefetch {
-    f32x4 res[EPI == VITED_EPI_RESIDUAL ? 4 : 1][4];          // [sub-tile][piece]
+    f32x4 res[epi_is_residual<EPI> ? 4 : 1][4];               // [sub-tile][piece]
+    float rscale[EPI == EPI_RESIDUAL_SCALED ? 4 : 1][4];      // [sub-tile][piece]: a piece is one row, so one scale - fetched with its residual row
     bf16x8 aux[(EPI == VITED_EPI_MUL_GELU_GRAD || EPI == VITED_EPI_MUL) ? 4 : 1][2];    // [sub-tile][piece]
     f32x4 bias[2];                                            // this lane's 4 or 8 columns
 };
@@ -68,13 +69,14 @@ __device__ __forceinline__ void epilogue_prefetch_subtile(const EpiParams& p, Ep
     using T = EpiTraits<EPI>;
     const int64_t n = ntile + T::col(lane);
     const bool ncol = n < N;
-    if constexpr (EPI == VITED_EPI_RESIDUAL) {
+    if constexpr (epi_is_residual<EPI>) {
 #pragma unroll
         for (int pc = 0; pc < 4; ++pc) {
             const int64_t m = mtile + i * 16 + T::row(lane, pc);
             int64_t orow, rrow;
             remap_rows(p, m, orow, rrow);
             pf.res[i][pc] = (m < M && ncol) ? EPI_LOAD16((const f32x4*)(p.residual + rrow * p.ldo + n)) : f32x4{0.f, 0.f, 0.f, 0.f};
+            if constexpr (EPI == EPI_RESIDUAL_SCALED) pf.rscale[i][pc] = m < M ? p.row_scale[m] : 0.f;
         }
     }
     if constexpr (EPI == VITED_EPI_MUL_GELU_GRAD || EPI == VITED_EPI_MUL) {
@@ -117,6 +119,10 @@ __device__ __forceinline__ void epilogue_subtile(const EpiParams& p, const EpiPr
                 remap_rows(p, m, orow, rrow);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) v[e] += pf.res[i][pc][e];
+            }
+            if constexpr (EPI == EPI_RESIDUAL_SCALED) {     // identity row map
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = pf.res[i][pc][e] + pf.rscale[i][pc] * v[e];
             }
             EPI_STORE16F((f32x4*)((float*)p.out + orow * p.ldo + n), v);
         } else {

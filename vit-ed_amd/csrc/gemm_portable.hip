@@ -64,10 +64,12 @@ gemm_portable_kernel(const T* __restrict__ A, int64_t lda, const T* __restrict__
     for (int i = 0; i < 4; ++i) {
         const int64_t m = m0 + ty * 4 + i;
         if (m >= M) continue;
+        float rs = 1.f;
+        if constexpr (EPI == EPI_RESIDUAL_SCALED) rs = ep.row_scale[m];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int64_t n = n0 + tx * 4 + j;
-            if (n < N) epilogue_store<T, EPI>(ep, m, n, acc[i][j]);
+            if (n < N) epilogue_store<T, EPI>(ep, m, n, acc[i][j], rs);
         }
     }
 }
@@ -93,6 +95,7 @@ static int dispatch_portable(const void* A, int64_t lda, const void* B, int64_t 
         case VITED_EPI_STORE_F32: launch_portable<T, VITED_EPI_STORE_F32>(A, lda, B, ldb, b_layout, M, N, K, ep, s); break;
         case VITED_EPI_MUL: launch_portable<T, VITED_EPI_MUL>(A, lda, B, ldb, b_layout, M, N, K, ep, s); break;
         case VITED_EPI_GELU_GRAD: launch_portable<T, VITED_EPI_GELU_GRAD>(A, lda, B, ldb, b_layout, M, N, K, ep, s); break;
+        case EPI_RESIDUAL_SCALED: launch_portable<T, EPI_RESIDUAL_SCALED>(A, lda, B, ldb, b_layout, M, N, K, ep, s); break;
         default: return VITED_ERR_BAD_ARG;
     }
     return vited_check_launch();

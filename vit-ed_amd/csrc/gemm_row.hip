@@ -54,6 +54,9 @@ struct RowArgs {
     const float* x; int64_t ldx; const float* mean_in; const float* rstd_in;
     const float* dx_in; int64_t ldxi; float* dx; int64_t lddx; bf16* dx_lp; int64_t ldlp;
     float* partial;     // [tiles][2][384]
+    // stochastic depth (SCALED instances only): fp32 [M], one value per row
+    const float* row_scale;     // forward: y = residual + row_scale[m] * (a . w^T + bias)
+    const float* lp_scale;      // backward: dx_lp = bf16(lp_scale[m] * dx) - the fp32 dx stays unscaled
 };
 
 template <int MT> struct RowCfg {
@@ -87,10 +90,11 @@ __device__ __forceinline__ float row_half_sum(float v) { return half_wave_sum(v)
 // ... and its row operands (residual, x, incoming gradient) are read exactly once: streaming loads (step 26.09 -> 25.9 ms)
 #define ROW_LOAD(ptr) __builtin_nontemporal_load(ptr)
 
-struct RowFwdIn { f32x4 res[3]; };
-struct RowBwdIn { f32x4 x[3], din[3]; float mu, rs; };
+// (SC = 1 in the SCALED instances: the row's drop-path scale rides with its other row operands; no member otherwise)
+template <int SC> struct RowFwdIn { f32x4 res[3]; float scale[SC]; };
+template <int SC> struct RowBwdIn { f32x4 x[3], din[3]; float mu, rs; float lps[SC]; };
 
-template <int MODE, int MT>
+template <int MODE, int MT, bool SCALED>
 __global__ void __launch_bounds__(512)
 gemm_row_kernel(const RowArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -301,14 +305,16 @@ gemm_row_kernel(const RowArgs a) {
         dg[j] = f32x4{0.f, 0.f, 0.f, 0.f};
         db[j] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
-    auto load_fwd = [&](RowFwdIn& in, int64_t m) {
+    auto load_fwd = [&](RowFwdIn<SCALED>& in, int64_t m) {
         const bool ok = m < a.M;
+        if constexpr (SCALED) in.scale[0] = ok ? a.row_scale[m] : 0.f;
 #pragma unroll
         for (int j = 0; j < 3; ++j)
             in.res[j] = ok ? ROW_LOAD((const f32x4*)(a.residual + m * a.ldr + (j * 32 + hl) * 4)) : f32x4{0.f, 0.f, 0.f, 0.f};
     };
-    auto load_bwd = [&](RowBwdIn& in, int64_t m) {
+    auto load_bwd = [&](RowBwdIn<SCALED>& in, int64_t m) {
         const bool ok = m < a.M;
+        if constexpr (SCALED) in.lps[0] = ok ? a.lp_scale[m] : 0.f;
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
             const int c = (j * 32 + hl) * 4;
@@ -318,7 +324,7 @@ gemm_row_kernel(const RowArgs a) {
         in.mu = ok ? a.mean_in[m] : 0.f;
         in.rs = ok ? a.rstd_in[m] : 0.f;
     };
-    auto row_fwd = [&](const RowFwdIn& in, int r, int64_t m) {
+    auto row_fwd = [&](const RowFwdIn<SCALED>& in, int r, int64_t m) {
         if (m >= a.M) return;
         f32x4 v[3];
         float s = 0.f;
@@ -329,7 +335,8 @@ gemm_row_kernel(const RowArgs a) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 v[j][e] += bs[j][e];
-                v[j][e] += in.res[j][e];
+                if constexpr (SCALED) v[j][e] = in.res[j][e] + in.scale[0] * v[j][e];      // the LayerNorm below sees the scaled y
+                else v[j][e] += in.res[j][e];
             }
             ROW_STORE((f32x4*)(a.y + m * a.ldy + c), v[j]);
             s += (v[j][0] + v[j][1]) + (v[j][2] + v[j][3]);
@@ -358,7 +365,7 @@ gemm_row_kernel(const RowArgs a) {
             a.rstd[m] = rs;
         }
     };
-    auto row_bwd = [&](const RowBwdIn& in, int r, int64_t m) {
+    auto row_bwd = [&](const RowBwdIn<SCALED>& in, int r, int64_t m) {
         if (m >= a.M) return;
         f32x4 xh[3], gg[3];
         float s1 = 0.f, s2 = 0.f;
@@ -384,6 +391,10 @@ gemm_row_kernel(const RowArgs a) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] = in.rs * (gg[j][e] - c1 - xh[j][e] * c2) + in.din[j][e];
             ROW_STORE((f32x4*)(a.dx + m * a.lddx + c), v);
+            if constexpr (SCALED) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] *= in.lps[0];
+            }
             if (a.dx_lp) ROW_STORE_LP((bf16x4*)(a.dx_lp + m * a.ldlp + c), (bf16x4{(bf16)v[0], (bf16)v[1], (bf16)v[2], (bf16)v[3]}));
         }
     };
@@ -395,8 +406,8 @@ gemm_row_kernel(const RowArgs a) {
         // (a half-wave is one of only 16 per CU: with one row - 1.5 to 3 KB - in flight each the epilogue was 2-3 % slower);
         // the 160-row tile keeps one row ahead
         constexpr int AHEAD = R::EPI_ALL_ROWS ? R::ROWS_PER_HALF : 1;
-        RowFwdIn fin[AHEAD + (R::EPI_ALL_ROWS ? 0 : 1)];
-        RowBwdIn bin[AHEAD + (R::EPI_ALL_ROWS ? 0 : 1)];
+        RowFwdIn<SCALED> fin[AHEAD + (R::EPI_ALL_ROWS ? 0 : 1)];
+        RowBwdIn<SCALED> bin[AHEAD + (R::EPI_ALL_ROWS ? 0 : 1)];
 #pragma unroll
         for (int k = 0; k < AHEAD; ++k) {
             if (MODE == ROW_MODE_FWD) load_fwd(fin[k], mp + hw + 16 * k);
@@ -474,15 +485,22 @@ static bool row_shape_ok(int64_t M, int64_t N, int64_t K) { return N == ROW_N &&
 
 extern "C" int vited_linear_layernorm_supported(int64_t M, int64_t N, int64_t K) { return row_shape_ok(M, N, K) ? 1 : 0; }
 
-template <int MODE, int MT>
-static int row_launch_mt(const RowArgs& a, unsigned tiles, hipStream_t s) {
-    auto kernel = gemm_row_kernel<MODE, MT>;
+template <int MODE, int MT, bool SCALED>
+static int row_launch_scaled(const RowArgs& a, unsigned tiles, hipStream_t s) {
+    auto kernel = gemm_row_kernel<MODE, MT, SCALED>;
     static std::once_flag once;          // dynamic LDS above 64 KB needs the opt-in, once per kernel instance
     static hipError_t status = hipSuccess;
     std::call_once(once, [&] { status = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, RowCfg<MT>::LDS_BYTES); });
     if (status != hipSuccess) return VITED_ERR_LAUNCH;
     hipLaunchKernelGGL(kernel, dim3(tiles), dim3(512), RowCfg<MT>::LDS_BYTES, s, a);
     return vited_check_launch();
+}
+
+// a null scale takes the unscaled instance: the code of a model without stochastic depth
+template <int MODE, int MT>
+static int row_launch_mt(const RowArgs& a, unsigned tiles, hipStream_t s) {
+    if (MODE == ROW_MODE_FWD ? a.row_scale != nullptr : a.lp_scale != nullptr) return row_launch_scaled<MODE, MT, true>(a, tiles, s);
+    return row_launch_scaled<MODE, MT, false>(a, tiles, s);
 }
 
 template <int MODE>
@@ -498,10 +516,10 @@ static int row_launch(const RowArgs& a, hipStream_t s) {
 
 static inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
-extern "C" int vited_linear_residual_layernorm_fwd(const void* a, int64_t lda, const void* w, int64_t ldw, const float* bias,
-                                                   const float* residual, int64_t ldr, float* y, int64_t ldy, const float* gamma,
-                                                   const float* beta, float eps, void* h, int64_t ldh, float* mean, float* rstd,
-                                                   int64_t M, int64_t N, int64_t K, void* stream) {
+static int linear_residual_layernorm_fwd_impl(const void* a, int64_t lda, const void* w, int64_t ldw, const float* bias,
+                                             const float* residual, int64_t ldr, const float* row_scale, float* y, int64_t ldy,
+                                             const float* gamma, const float* beta, float eps, void* h, int64_t ldh, float* mean,
+                                             float* rstd, int64_t M, int64_t N, int64_t K, void* stream) {
     if (!a || !w || !residual || !y || M <= 0 || N <= 0 || K <= 0 || lda < K || ldw < K || ldr < N || ldy < N) return VITED_ERR_BAD_ARG;
     if (h && (!gamma || !beta || !mean || !rstd || ldh < N)) return VITED_ERR_BAD_ARG;
     if (!row_shape_ok(M, N, K)) return VITED_ERR_UNSUPPORTED;
@@ -512,7 +530,25 @@ extern "C" int vited_linear_residual_layernorm_fwd(const void* a, int64_t lda, c
     r.A = (const bf16*)a; r.lda = lda; r.seg_k = (int)K; r.seg_stride = 0; r.W = (const bf16*)w; r.ldw = ldw; r.M = M; r.K = (int)K;
     r.bias = bias; r.residual = residual; r.ldr = ldr; r.y = y; r.ldy = ldy;
     r.gamma = gamma; r.beta = beta; r.eps = eps; r.h = (bf16*)h; r.ldh = ldh; r.mean = mean; r.rstd = rstd;
+    r.row_scale = row_scale;
     return row_launch<ROW_MODE_FWD>(r, (hipStream_t)stream);
+}
+
+extern "C" int vited_linear_residual_layernorm_fwd(const void* a, int64_t lda, const void* w, int64_t ldw, const float* bias,
+                                                   const float* residual, int64_t ldr, float* y, int64_t ldy, const float* gamma,
+                                                   const float* beta, float eps, void* h, int64_t ldh, float* mean, float* rstd,
+                                                   int64_t M, int64_t N, int64_t K, void* stream) {
+    return linear_residual_layernorm_fwd_impl(a, lda, w, ldw, bias, residual, ldr, nullptr, y, ldy, gamma, beta, eps, h, ldh, mean, rstd,
+                                              M, N, K, stream);
+}
+
+extern "C" int vited_linear_residual_layernorm_fwd_scaled(const void* a, int64_t lda, const void* w, int64_t ldw, const float* bias,
+                                                          const float* residual, int64_t ldr, const float* row_scale, float* y,
+                                                          int64_t ldy, const float* gamma, const float* beta, float eps, void* h,
+                                                          int64_t ldh, float* mean, float* rstd, int64_t M, int64_t N, int64_t K,
+                                                          void* stream) {
+    return linear_residual_layernorm_fwd_impl(a, lda, w, ldw, bias, residual, ldr, row_scale, y, ldy, gamma, beta, eps, h, ldh, mean,
+                                              rstd, M, N, K, stream);
 }
 
 // layernorm.hip
@@ -527,8 +563,9 @@ extern "C" int64_t vited_linear_layernorm_bwd_workspace_bytes(int64_t M, int64_t
 static int linear_layernorm_bwd_impl(const void* dy, int64_t lddy, int64_t seg_k, int64_t seg_stride, const void* wt, int64_t ldwt,
                                     const float* x, int64_t ldx, const float* gamma, const float* mean, const float* rstd,
                                     const float* dx_in, int64_t dx_in_ld, float* dx_out, int64_t dx_out_ld, void* dx_lp, int64_t dx_lp_ld,
-                                    float* dgamma, float* dbeta, int accumulate, int64_t M, int64_t N, int64_t K, float* workspace,
-                                    int64_t workspace_bytes, void* stream) {
+                                    const float* lp_scale, float* dgamma, float* dbeta, int accumulate, int64_t M, int64_t N, int64_t K,
+                                    float* workspace, int64_t workspace_bytes, void* stream) {
+    if (lp_scale && !dx_lp) return VITED_ERR_BAD_ARG;
     if (!dy || !wt || !x || !gamma || !mean || !rstd || !dx_out || M <= 0 || N <= 0 || K <= 0) return VITED_ERR_BAD_ARG;
     if ((dgamma == nullptr) != (dbeta == nullptr)) return VITED_ERR_BAD_ARG;
     if (seg_k <= 0 || K % seg_k || lddy < seg_k || ldwt < K || ldx < N || dx_out_ld < N || (dx_in && dx_in_ld < N) || (dx_lp && dx_lp_ld < N))
@@ -542,6 +579,7 @@ static int linear_layernorm_bwd_impl(const void* dy, int64_t lddy, int64_t seg_k
     r.gamma = gamma; r.x = x; r.ldx = ldx; r.mean_in = mean; r.rstd_in = rstd;
     r.dx_in = dx_in; r.ldxi = dx_in_ld; r.dx = dx_out; r.lddx = dx_out_ld; r.dx_lp = (bf16*)dx_lp; r.ldlp = dx_lp_ld;
     r.partial = workspace;
+    r.lp_scale = lp_scale;
     const int rc = row_launch<ROW_MODE_BWD>(r, (hipStream_t)stream);
     if (rc != VITED_OK || !dgamma) return rc;     // dgamma == null: the caller keeps the partials and finishes several LayerNorms at once
     return ln_bwd_finish(workspace, (int)row_tiles(M), ROW_N, dgamma, dbeta, accumulate, (hipStream_t)stream);
@@ -553,7 +591,7 @@ extern "C" int vited_linear_layernorm_bwd(const void* dy, int64_t lddy, const vo
                                           float* dgamma, float* dbeta, int accumulate, int64_t M, int64_t N, int64_t K,
                                           float* workspace, int64_t workspace_bytes, void* stream) {
     return linear_layernorm_bwd_impl(dy, lddy, K, 0, wt, ldwt, x, ldx, gamma, mean, rstd, dx_in, dx_in_ld, dx_out, dx_out_ld, dx_lp, dx_lp_ld,
-                                     dgamma, dbeta, accumulate, M, N, K, workspace, workspace_bytes, stream);
+                                     nullptr, dgamma, dbeta, accumulate, M, N, K, workspace, workspace_bytes, stream);
 }
 
 // dy = `segments` tensors [M, seg_k] (row stride lddy) laid out seg_stride ELEMENTS apart: column block j of the contraction
@@ -566,5 +604,14 @@ extern "C" int vited_linear_layernorm_bwd_segmented(const void* dy, int64_t lddy
                                                     int64_t workspace_bytes, void* stream) {
     if (segments <= 0) return VITED_ERR_BAD_ARG;
     return linear_layernorm_bwd_impl(dy, lddy, seg_k, seg_stride, wt, ldwt, x, ldx, gamma, mean, rstd, dx_in, dx_in_ld, dx_out, dx_out_ld, dx_lp,
-                                     dx_lp_ld, dgamma, dbeta, accumulate, M, N, segments * seg_k, workspace, workspace_bytes, stream);
+                                     dx_lp_ld, nullptr, dgamma, dbeta, accumulate, M, N, segments * seg_k, workspace, workspace_bytes, stream);
+}
+
+extern "C" int vited_linear_layernorm_bwd_scaled(const void* dy, int64_t lddy, const void* wt, int64_t ldwt, const float* x, int64_t ldx,
+                                                 const float* gamma, const float* mean, const float* rstd, const float* dx_in,
+                                                 int64_t dx_in_ld, float* dx_out, int64_t dx_out_ld, void* dx_lp, int64_t dx_lp_ld,
+                                                 const float* lp_scale, float* dgamma, float* dbeta, int accumulate, int64_t M, int64_t N,
+                                                 int64_t K, float* workspace, int64_t workspace_bytes, void* stream) {
+    return linear_layernorm_bwd_impl(dy, lddy, K, 0, wt, ldwt, x, ldx, gamma, mean, rstd, dx_in, dx_in_ld, dx_out, dx_out_ld, dx_lp, dx_lp_ld,
+                                     lp_scale, dgamma, dbeta, accumulate, M, N, K, workspace, workspace_bytes, stream);
 }

@@ -129,12 +129,15 @@ extern "C" int vited_layernorm_fwd(const float* x, int64_t x_ld, const float* ga
 //   dx = rstd * (g - mean_c(g) - xhat * mean_c(g * xhat))  (+ dx_in)
 //   dgamma = sum_rows dy * xhat ; dbeta = sum_rows dy
 // ------------------------------------------------------------------------------------------------
-template <typename T, int VPL>
+// SCALED (stochastic depth): the low-precision copy alone is multiplied by lp_scale[row] - it is what the next
+// branch's backward consumes - and may then be fp32 too (lp_f32: the exact path, where the copy otherwise IS dx_out).
+template <typename T, int VPL, bool SCALED>
 __global__ void __launch_bounds__(256)
 layernorm_bwd_kernel(const T* __restrict__ dy, int64_t dy_ld, const float* __restrict__ x, int64_t x_ld,
                      const float* __restrict__ gamma, const float* __restrict__ mean, const float* __restrict__ rstd,
                      const float* __restrict__ dx_in, int64_t dx_in_ld, float* __restrict__ dx_out, int64_t dx_out_ld,
-                     bf16* __restrict__ dx_lp, int64_t dx_lp_ld, float* __restrict__ partial, int64_t rows, int dim) {
+                     bf16* __restrict__ dx_lp, int64_t dx_lp_ld, float* __restrict__ partial, int64_t rows, int dim,
+                     const float* __restrict__ lp_scale, int lp_f32) {
     extern __shared__ __attribute__((aligned(16))) float lds[];  // [8 half-waves][2][dim]
     const int hl = threadIdx.x & 31;
     const int hid = threadIdx.x >> 5;
@@ -151,6 +154,8 @@ layernorm_bwd_kernel(const T* __restrict__ dy, int64_t dy_ld, const float* __res
     const float inv_d = 1.f / dim;
     for (int64_t r = half; r < rows; r += nhalf) {
         const float mu = mean[r], rs = rstd[r];
+        float lps = 1.f;
+        if constexpr (SCALED) lps = lp_scale[r];
         const T* dyr = dy + r * dy_ld;
         const float* xr = x + r * x_ld;
         f32x4 xh[VPL], gg[VPL], res[VPL];
@@ -189,7 +194,12 @@ layernorm_bwd_kernel(const T* __restrict__ dy, int64_t dy_ld, const float* __res
 #pragma unroll
                 for (int e = 0; e < 4; ++e) v[e] = rs * (gg[j][e] - c1 - xh[j][e] * c2) + res[j][e];
                 *(f32x4*)(dx_out + r * dx_out_ld + c) = v;
-                if (dx_lp) Vec4<bf16>::store(dx_lp + r * dx_lp_ld + c, v);
+                if constexpr (SCALED) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[e] *= lps;
+                    if (lp_f32) Vec4<float>::store((float*)dx_lp + r * dx_lp_ld + c, v);
+                    else Vec4<bf16>::store(dx_lp + r * dx_lp_ld + c, v);
+                } else if (dx_lp) Vec4<bf16>::store(dx_lp + r * dx_lp_ld + c, v);
             }
         }
     }
@@ -319,12 +329,14 @@ extern "C" int64_t vited_layernorm_bwd_workspace_bytes(int64_t rows, int64_t dim
 template <typename T>
 static int ln_bwd_launch(const void* dy, int64_t dy_ld, const float* x, int64_t x_ld, const float* gamma, const float* mean,
                          const float* rstd, const float* dx_in, int64_t dx_in_ld, float* dx_out, int64_t dx_out_ld, void* dx_lp,
-                         int64_t dx_lp_ld, float* dgamma, float* dbeta, int accumulate, int64_t rows, int dim, float* ws, hipStream_t s) {
+                         int64_t dx_lp_ld, float* dgamma, float* dbeta, int accumulate, int64_t rows, int dim, float* ws, hipStream_t s,
+                         const float* lp_scale, int lp_f32) {
     const int64_t blocks = ln_bwd_blocks(rows);
     const size_t lds = (size_t)8 * 2 * dim * sizeof(float);
     const int vpl = (int)ceil_div64(dim, 128);
-#define L(V) hipLaunchKernelGGL((layernorm_bwd_kernel<T, V>), dim3(blocks), dim3(256), lds, s, (const T*)dy, dy_ld, x, x_ld, gamma, mean, \
-                                rstd, dx_in, dx_in_ld, dx_out, dx_out_ld, (bf16*)dx_lp, dx_lp_ld, ws, rows, dim)
+#define L1(V, SC) hipLaunchKernelGGL((layernorm_bwd_kernel<T, V, SC>), dim3(blocks), dim3(256), lds, s, (const T*)dy, dy_ld, x, x_ld, gamma, \
+                                     mean, rstd, dx_in, dx_in_ld, dx_out, dx_out_ld, (bf16*)dx_lp, dx_lp_ld, ws, rows, dim, lp_scale, lp_f32)
+#define L(V) do { if (lp_scale) L1(V, true); else L1(V, false); } while (0)   /* a null scale: the unscaled instance */
     switch (vpl) {
         case 1: L(1); break;
         case 2: L(2); break;
@@ -336,8 +348,33 @@ static int ln_bwd_launch(const void* dy, int64_t dy_ld, const float* x, int64_t 
         default: L(8); break;
     }
 #undef L
+#undef L1
     hipLaunchKernelGGL(ln_bwd_finish_kernel, dim3((2 * dim + 15) / 16), dim3(16 * LNF_GROUPS), 0, s, ws, (int)blocks, 2 * dim, dgamma, dbeta, dim, accumulate);
     return vited_check_launch();
+}
+
+static int layernorm_bwd_impl(const void* dy, int dy_dtype, int64_t dy_ld, const float* x, int64_t x_ld, const float* gamma,
+                              const float* mean, const float* rstd, const float* dx_in, int64_t dx_in_ld, float* dx_out,
+                              int64_t dx_out_ld, void* dx_lp, int dx_lp_dtype, int64_t dx_lp_ld, const float* lp_scale, float* dgamma,
+                              float* dbeta, int accumulate, int64_t rows, int64_t dim, float* workspace, int64_t workspace_bytes,
+                              void* stream) {
+    if (lp_scale && !dx_lp) return VITED_ERR_BAD_ARG;
+    if (!dy || !x || !gamma || !mean || !rstd || !dx_out || !dgamma || !dbeta || rows <= 0 || dim <= 0) return VITED_ERR_BAD_ARG;
+    if (!ln_shape_ok(dim, x_ld, dy_ld, dx_out_ld) || (dx_in && dx_in_ld % 4) || (dx_lp && dx_lp_ld % 4)) return VITED_ERR_UNSUPPORTED;
+    if (((uintptr_t)x | (uintptr_t)gamma | (uintptr_t)dx_out | (uintptr_t)dx_in) & 15) return VITED_ERR_BAD_ARG;
+    if (((uintptr_t)dy | (uintptr_t)dx_lp) & 7) return VITED_ERR_BAD_ARG;
+    if (dy_dtype == VITED_F32 && ((uintptr_t)dy & 15)) return VITED_ERR_BAD_ARG;
+    if (!workspace || workspace_bytes < vited_layernorm_bwd_workspace_bytes(rows, dim)) return VITED_ERR_WORKSPACE;
+    if (dx_lp && dx_lp_dtype != VITED_BF16 && !(lp_scale && dx_lp_dtype == VITED_F32)) return VITED_ERR_UNSUPPORTED;
+    const int lp_f32 = dx_lp && dx_lp_dtype == VITED_F32;
+    if (lp_f32 && ((uintptr_t)dx_lp & 15)) return VITED_ERR_BAD_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    const int d = (int)dim;
+    if (dy_dtype == VITED_BF16)
+        return ln_bwd_launch<bf16>(dy, dy_ld, x, x_ld, gamma, mean, rstd, dx_in, dx_in_ld, dx_out, dx_out_ld, dx_lp, dx_lp_ld, dgamma, dbeta, accumulate, rows, d, workspace, s, lp_scale, lp_f32);
+    if (dy_dtype == VITED_F32)
+        return ln_bwd_launch<float>(dy, dy_ld, x, x_ld, gamma, mean, rstd, dx_in, dx_in_ld, dx_out, dx_out_ld, dx_lp, dx_lp_ld, dgamma, dbeta, accumulate, rows, d, workspace, s, lp_scale, lp_f32);
+    return VITED_ERR_UNSUPPORTED;
 }
 
 extern "C" int vited_layernorm_bwd(const void* dy, int dy_dtype, int64_t dy_ld, const float* x, int64_t x_ld,
@@ -345,18 +382,15 @@ extern "C" int vited_layernorm_bwd(const void* dy, int dy_dtype, int64_t dy_ld, 
                                    int64_t dx_in_ld, float* dx_out, int64_t dx_out_ld, void* dx_lp, int dx_lp_dtype,
                                    int64_t dx_lp_ld, float* dgamma, float* dbeta, int accumulate, int64_t rows, int64_t dim,
                                    float* workspace, int64_t workspace_bytes, void* stream) {
-    if (!dy || !x || !gamma || !mean || !rstd || !dx_out || !dgamma || !dbeta || rows <= 0 || dim <= 0) return VITED_ERR_BAD_ARG;
-    if (!ln_shape_ok(dim, x_ld, dy_ld, dx_out_ld) || (dx_in && dx_in_ld % 4) || (dx_lp && dx_lp_ld % 4)) return VITED_ERR_UNSUPPORTED;
-    if (((uintptr_t)x | (uintptr_t)gamma | (uintptr_t)dx_out | (uintptr_t)dx_in) & 15) return VITED_ERR_BAD_ARG;
-    if (((uintptr_t)dy | (uintptr_t)dx_lp) & 7) return VITED_ERR_BAD_ARG;
-    if (dy_dtype == VITED_F32 && ((uintptr_t)dy & 15)) return VITED_ERR_BAD_ARG;
-    if (!workspace || workspace_bytes < vited_layernorm_bwd_workspace_bytes(rows, dim)) return VITED_ERR_WORKSPACE;
-    if (dx_lp && dx_lp_dtype != VITED_BF16) return VITED_ERR_UNSUPPORTED;
-    hipStream_t s = (hipStream_t)stream;
-    const int d = (int)dim;
-    if (dy_dtype == VITED_BF16)
-        return ln_bwd_launch<bf16>(dy, dy_ld, x, x_ld, gamma, mean, rstd, dx_in, dx_in_ld, dx_out, dx_out_ld, dx_lp, dx_lp_ld, dgamma, dbeta, accumulate, rows, d, workspace, s);
-    if (dy_dtype == VITED_F32)
-        return ln_bwd_launch<float>(dy, dy_ld, x, x_ld, gamma, mean, rstd, dx_in, dx_in_ld, dx_out, dx_out_ld, dx_lp, dx_lp_ld, dgamma, dbeta, accumulate, rows, d, workspace, s);
-    return VITED_ERR_UNSUPPORTED;
+    return layernorm_bwd_impl(dy, dy_dtype, dy_ld, x, x_ld, gamma, mean, rstd, dx_in, dx_in_ld, dx_out, dx_out_ld, dx_lp, dx_lp_dtype,
+                              dx_lp_ld, nullptr, dgamma, dbeta, accumulate, rows, dim, workspace, workspace_bytes, stream);
+}
+
+extern "C" int vited_layernorm_bwd_scaled(const void* dy, int dy_dtype, int64_t dy_ld, const float* x, int64_t x_ld,
+                                          const float* gamma, const float* mean, const float* rstd, const float* dx_in,
+                                          int64_t dx_in_ld, float* dx_out, int64_t dx_out_ld, void* dx_lp, int dx_lp_dtype,
+                                          int64_t dx_lp_ld, const float* lp_scale, float* dgamma, float* dbeta, int accumulate,
+                                          int64_t rows, int64_t dim, float* workspace, int64_t workspace_bytes, void* stream) {
+    return layernorm_bwd_impl(dy, dy_dtype, dy_ld, x, x_ld, gamma, mean, rstd, dx_in, dx_in_ld, dx_out, dx_out_ld, dx_lp, dx_lp_dtype,
+                              dx_lp_ld, lp_scale, dgamma, dbeta, accumulate, rows, dim, workspace, workspace_bytes, stream);
 }

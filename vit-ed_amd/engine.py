@@ -292,7 +292,13 @@ class TrainStep:
     * ``use_graph=True`` replays hipGraphs (forward + decoder backward | encoder backward | update) captured
       after two eager warm-up steps, with the RCCL all-reduces issued between the replays, so the ~900
       launches of a step cost three graph launches on the host.  The learning rate lives in a device scalar,
-      so ``lr_scheduler.step_update`` / ``set_lr`` take effect in the replayed update."""
+      so ``lr_scheduler.step_update`` / ``set_lr`` take effect in the replayed update.
+    * Stochastic depth (a model built with ``drop_path_rate`` > 0, in training mode): every step draws its scales inside the
+      model's forward.  Under ``use_graph`` the draw is part of the captured graph and uses the device's default generator,
+      which torch registers with the graph: every replay draws anew, and ``model.last_drop_path`` is a static buffer that holds
+      the latest replay's scales.  A custom ``model.drop_path_generator`` raises at capture.  ``step.drop_path`` = a
+      ``DropPathScales`` of static tensors forces the scales instead (tests, reproducing a step): a captured graph reads those
+      tensors in place."""
 
     def __init__(self, model, optimizer, *, clip_grad=5.0, amp=True, criterion=None, use_graph=False,
                  compress_bf16=False, forward_fn=None, accumulation_steps=1, lr_scheduler=None, overlap=True, group=None,
@@ -306,7 +312,8 @@ class TrainStep:
                                   early=_decoder_only_parameters(model) if self.split else None)
         if hasattr(model, 'direct_param_grads') or hasattr(model, 'runtime'):
             model.direct_param_grads = True     # HIP model: weight-gradient kernels add straight into the flat buffer
-        self.forward_fn = forward_fn or (lambda m, x: m(x))
+        self.drop_path = None       # forced stochastic-depth scales (a DropPathScales); None: the model draws when it should
+        self.forward_fn = forward_fn or (lambda m, x: m(x) if self.drop_path is None else m(x, drop_path=self.drop_path))
         self.use_graph = use_graph and torch.cuda.is_available()
         self.hip_opt = hasattr(optimizer, 'bind_flat')       # optim.FlatAdamW: clip + AdamW + shadow refresh in one kernel
         if self.hip_opt:
@@ -374,9 +381,10 @@ class TrainStep:
         """Stage 1 of the split backward: encoder forward, decoder + head forward, loss, decoder backward.
         Returns (loss, features, d loss / d features)."""
         with torch.autocast(self.device_type, dtype=torch.bfloat16, enabled=self.amp):
-            feats = self.model(x[:, 0], forward_first_part=True)
+            forced = {} if self.drop_path is None else dict(drop_path=self.drop_path)
+            feats = self.model(x[:, 0], forward_first_part=True, **forced)
             leaf = feats.detach().requires_grad_(True)
-            out = self.model(leaf, x[:, 1])
+            out = self.model(leaf, x[:, 1], **forced)
             loss = self._loss(out, y)
         loss.backward()
         return loss.detach(), feats, leaf.grad

@@ -110,6 +110,8 @@ class Runtime:
         self.fold_context = os.environ.get('VITED_FOLD_CONTEXT', '1') != '0'   # norm_context + kv of all decoder blocks as one GEMM
         self._fold_bufs = None      # (folded W [L 2D, D], its transpose, folded bias): refreshed in place every forward
         self._unit_ln = None        # (ones, zeros) for the affine-free LayerNorm of the features
+        self.drop_path = None       # (encoder scales fp32 [depth, 2, B] | None, decoder scales fp32 [c_depth, 3, B] | None, (live encoder
+                                    # branches, live decoder branches)): set by the model around a call, read by the Functions' forward
         self.tap = None             # test/diagnostic: a dict that receives clones of per-block activations and gradients
         self.block_events = None    # measurement (bench.py): a list that receives (kind, block, 'fwd' | 'bwd', start event, end event)
         self.pinned = False         # a captured hipGraph reads the shadow buffers: never free one, only refresh in place
@@ -199,6 +201,47 @@ class _BlockSpan:
 
 def _lp(rt: Runtime, t_f32: torch.Tensor) -> torch.Tensor:
     return t_f32 if rt.exact else ops.cast(t_f32, rt.act_dtype)
+
+
+def _lp_scaled(rt: Runtime, t_f32: torch.Tensor, row_scale) -> torch.Tensor:
+    """_lp with the copy scaled per row (on the exact path the copy then is a tensor of its own)."""
+    return _lp(rt, t_f32) if row_scale is None else ops.scale_rows_cast(t_f32, row_scale, rt.act_dtype)
+
+
+class _DropRows:
+    """Stochastic-depth scales of one Function call as the kernels read them: one fp32 value per ROW.
+    ``scales`` fp32 [blocks, branches, B] holds 0 or 1 / keep per sample; ``live[i][j]`` says whether branch j of block i drops at
+    all - a branch that does not gets None everywhere and its launches are those of a model without stochastic depth.  The
+    per-sample values are repeated over the ``n`` rows of a sample for every branch of the Function in ONE launch; a block
+    that runs on the cls rows alone (``cls_block``: one row per sample) reads the per-sample vector itself."""
+
+    def __init__(self, scales, live, n, cls_block=None):
+        nblk, nbr, batch = scales.shape
+        self.per_sample, self.live, self.cls_block = scales, live, cls_block
+        self.per_row = scales.unsqueeze(-1).expand(nblk, nbr, batch, n).reshape(nblk, nbr, batch * n)
+
+    def get(self, i, j):
+        """Branch j of block i, one value per row of that block's stream; None where the branch does not drop (or i < 0)."""
+        if i < 0 or not self.live[i][j]:
+            return None
+        return (self.per_sample if i == self.cls_block else self.per_row)[i, j]
+
+    def block(self, i):
+        return tuple(self.get(i, j) for j in range(self.per_sample.shape[1]))
+
+
+def _take_drop_rows(rt, which, nblk, nbr, batch, n, device, cls_block=None):
+    """The _DropRows of this call from ``rt.drop_path`` (None: no stochastic depth in this call)."""
+    dp = rt.drop_path
+    if dp is None or dp[which] is None:
+        return None
+    scales, live = dp[which], dp[2][which]
+    if not any(any(row) for row in live):
+        return None
+    if tuple(scales.shape) != (nblk, nbr, batch) or scales.dtype != torch.float32 or scales.device != device:
+        raise ValueError(f'drop-path scales: expected fp32 {(nblk, nbr, batch)} on {device}, got {scales.dtype} {tuple(scales.shape)} on '
+                         f'{scales.device}')
+    return _DropRows(scales.contiguous(), live, n, cls_block)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -339,22 +382,25 @@ def _row_kernel_ok(rt, m, n, k, dtype, *rowwise):
             and all(t is None or (t.dim() == 2 and t.stride(1) == 1 and t.stride(0) % 4 == 0) for t in rowwise))
 
 
-def _res_linear(rt, a, w, bias, residual, ln=None):
+def _res_linear(rt, a, w, bias, residual, ln=None, scale=None):
     """y = residual + a W^T + bias (fp32) and, with ``ln`` = (gamma, beta) of the LayerNorm that FOLLOWS on the residual stream
     (the next sub-block's norm: vision_transformer.py:124-127, 268-272), also (h, mean, rstd) = LayerNorm(y) - in ONE kernel when
     the row-complete kernel covers the shape, otherwise as vited_gemm(RESIDUAL) + vited_layernorm_fwd.
+    ``scale`` (fp32, one value per row; stochastic depth): y = residual + scale[row] * (a W^T + bias), in the same kernels.
     Returns (y, (h, mean, rstd) | None)."""
     wsh = rt.weight(w)
     if ln is not None and _row_kernel_ok(rt, a.shape[0], wsh.shape[0], a.shape[1], a.dtype, a, residual):
-        y, h, mean, rstd = ops.linear_residual_layernorm_fwd(a, wsh, bias, residual, ln[0], ln[1], LN_EPS)
+        y, h, mean, rstd = ops.linear_residual_layernorm_fwd(a, wsh, bias, residual, ln[0], ln[1], LN_EPS, row_scale=scale)
         return y, (h, mean, rstd)
-    y = ops.gemm(a, wsh, epilogue=EPI_RESIDUAL, bias=bias, residual=residual)
+    y = ops.gemm(a, wsh, epilogue=EPI_RESIDUAL, bias=bias, residual=residual, row_scale=scale)
     return y, (ops.layernorm_fwd(y, ln[0], ln[1], LN_EPS, rt.act_dtype) if ln is not None else None)
 
 
-def _linear_ln_bwd(rt, dy, h_saved, w, bias, x, gamma, beta, mean, rstd, dx_in=None, dx_out=None, want_lp=True):
+def _linear_ln_bwd(rt, dy, h_saved, w, bias, x, gamma, beta, mean, rstd, dx_in=None, dx_out=None, want_lp=True, lp_scale=None):
     """Backward of  y = LayerNorm(x; gamma, beta) W^T + bias  given dy: the input-gradient GEMM and the LayerNorm backward in
     ONE kernel when the row-complete kernel covers the shape (d(LayerNorm output) then never exists in HBM).
+    ``lp_scale`` (fp32, one value per row): the low-precision copy alone is scaled, dx_lp = T(lp_scale[row] * dx) - the stochastic-depth
+    scale of the branch whose backward consumes it; on the exact path the copy then is an fp32 tensor of its own.
     Returns (dx fp32 = dx_in + ..., dx_lp | None (dx itself on the exact path), dgamma, dbeta, dW, dbias) - gradients are None when
     accumulated in place."""
     want_lp = want_lp and not rt.exact
@@ -363,14 +409,16 @@ def _linear_ln_bwd(rt, dy, h_saved, w, bias, x, gamma, beta, mean, rstd, dx_in=N
         gg, gb = _gtarget(rt, gamma), _gtarget(rt, beta)
         direct = gg is not None and gb is not None
         dx, dx_lp, dg, db = ops.linear_layernorm_bwd(dy, wt, x, gamma, mean, rstd, dx_in=dx_in, dx_out=dx_out, want_lp=want_lp,
-                                                     dgamma=gg if direct else None, dbeta=gb if direct else None, defer=rt.ln_queue)
+                                                     dgamma=gg if direct else None, dbeta=gb if direct else None, defer=rt.ln_queue,
+                                                     lp_scale=lp_scale)
         if direct:
             dg = db = None
     else:
         dh = ops.gemm(dy, wt, b_layout=layout)
-        dx, dx_lp, dg, db = _ln_bwd(rt, dh, x, gamma, beta, mean, rstd, dx_in=dx_in, dx_out=dx_out, want_lp=want_lp)
+        dx, dx_lp, dg, db = _ln_bwd(rt, dh, x, gamma, beta, mean, rstd, dx_in=dx_in, dx_out=dx_out, want_lp=want_lp, lp_scale=lp_scale,
+                                    lp_dtype=rt.act_dtype)
     dw, dbias = _weight_grads(rt, dy, h_saved, w, bias)
-    return dx, (dx if rt.exact else dx_lp), dg, db, dw, dbias
+    return dx, (dx if rt.exact and lp_scale is None else dx_lp), dg, db, dw, dbias
 
 
 @contextlib.contextmanager
@@ -470,12 +518,13 @@ def _hand_over_ln(rt, x, P, grad):
     return grad or not _fused_mlp_rows(rt, x, P.w1, grad)
 
 
-def _mlp_fwd(rt, x, P, grad=True, ln=None, next_ln=None):
+def _mlp_fwd(rt, x, P, grad=True, ln=None, next_ln=None, scale=None):
     """x + fc2(gelu(fc1(LayerNorm(x)))) with the block's norm2 / mlp parameters (P: an EncBlock or a DecBlock).  ``ln`` = (h, mean,
     rstd) when the LayerNorm was already produced by the kernel that wrote x; ``next_ln`` = (gamma, beta) of the LayerNorm that
-    follows on the output.  Returns (y, saved | None, next | None)."""
+    follows on the output.  ``scale``: the branch's stochastic-depth scale per row; the one-kernel MLP does not know it and is
+    then not chosen.  Returns (y, saved | None, next | None)."""
     g, b, w1, b1, w2, b2 = P.g2, P.b2, P.w1, P.bb1, P.w2, P.bb2
-    rows = _fused_mlp_rows(rt, x, w1, grad) if ln is None else 0
+    rows = _fused_mlp_rows(rt, x, w1, grad) if ln is None and scale is None else 0
     if rows:
         y = torch.empty_like(x)
         ops.mlp_fwd(x[:rows], g, b, rt.weight(w1), b1, rt.weight(w2), b2, LN_EPS, save=False, out=(y[:rows], None, None, None, None, None))
@@ -489,33 +538,36 @@ def _mlp_fwd(rt, x, P, grad=True, ln=None, next_ln=None):
     h, mean, rstd = ln if ln is not None else ops.layernorm_fwd(x, g, b, LN_EPS, rt.act_dtype)
     # fc1 saves gelu'(z) and gelu(z) (one exponential serves both): the backward of the activation is then one multiply
     gd, u = ops.gemm(h, rt.weight(w1), epilogue=EPI_GELU_GRAD, bias=b1)
-    y, nxt = _res_linear(rt, u, w2, b2, x, next_ln)
+    y, nxt = _res_linear(rt, u, w2, b2, x, next_ln, scale)
     return y, (mean, rstd, h, gd, u), nxt
 
 
-def _mlp_bwd(rt, dy, dy_lp, x, P, saved):
-    """Backward of _mlp_fwd.  Returns (dx, its low-precision copy, the six parameter gradients by field name)."""
+def _mlp_bwd(rt, dy, dy_lp, x, P, saved, lp_scale=None):
+    """Backward of _mlp_fwd.  Under stochastic depth ``dy_lp`` arrives scaled by this branch's scale (so everything inside the branch
+    sees s dy, the residual path dy) and ``lp_scale`` is the scale of the branch whose backward runs next: the returned copy carries it.
+    Returns (dx, its low-precision copy, the six parameter gradients by field name)."""
     mean, rstd, h, gd, u = saved
     dz, dw2, dbb2 = _linear_bwd(rt, dy_lp, u, P.w2, P.bb2, aux=gd)
-    dx, dx_lp, dg2, db2, dw1, dbb1 = _linear_ln_bwd(rt, dz, h, P.w1, P.bb1, x, P.g2, P.b2, mean, rstd, dx_in=dy)
+    dx, dx_lp, dg2, db2, dw1, dbb1 = _linear_ln_bwd(rt, dz, h, P.w1, P.bb1, x, P.g2, P.b2, mean, rstd, dx_in=dy, lp_scale=lp_scale)
     return dx, dx_lp, dict(g2=dg2, b2=db2, w1=dw1, bb1=dbb1, w2=dw2, bb2=dbb2)
 
 
-def _attn_branch_fwd(rt, x, P, batch, n, key=None, ln=None, next_ln=None):
+def _attn_branch_fwd(rt, x, P, batch, n, key=None, ln=None, next_ln=None, scale=None):
     """x + proj(attention(qkv(LayerNorm(x)))) with the block's norm1 / attn parameters; ``ln`` / ``next_ln`` as in _mlp_fwd.
     Returns (y, saved, next | None)."""
     h, mean, rstd = ln if ln is not None else ops.layernorm_fwd(x, P.g1, P.b1, LN_EPS, rt.act_dtype)
     qkv, o, lse = _self_attn_fwd(rt, h, P.wqkv, P.bqkv, batch, n, key)
-    y, nxt = _res_linear(rt, o, P.wproj, P.bproj, x, next_ln)
+    y, nxt = _res_linear(rt, o, P.wproj, P.bproj, x, next_ln, scale)
     return y, (mean, rstd, h, qkv, o, lse), nxt
 
 
-def _attn_branch_bwd(rt, dy, dy_lp, x, P, saved, batch, n, key=None):
-    """Backward of _attn_branch_fwd.  Returns (dx, its low-precision copy, the six parameter gradients by field name)."""
+def _attn_branch_bwd(rt, dy, dy_lp, x, P, saved, batch, n, key=None, lp_scale=None):
+    """Backward of _attn_branch_fwd (``lp_scale`` as in _mlp_bwd).  Returns (dx, its low-precision copy, the six parameter gradients by
+    field name)."""
     mean, rstd, h, qkv, o, lse = saved
     do, dwproj, dbproj = _linear_bwd(rt, dy_lp, o, P.wproj, P.bproj)
     dqkv = _self_attn_bwd(rt, do, qkv, o, lse, batch, n, key)
-    dx, dx_lp, dg1, db1, dwqkv, dbqkv = _linear_ln_bwd(rt, dqkv, h, P.wqkv, P.bqkv, x, P.g1, P.b1, mean, rstd, dx_in=dy)
+    dx, dx_lp, dg1, db1, dwqkv, dbqkv = _linear_ln_bwd(rt, dqkv, h, P.wqkv, P.bqkv, x, P.g1, P.b1, mean, rstd, dx_in=dy, lp_scale=lp_scale)
     return dx, dx_lp, dict(g1=dg1, b1=db1, wqkv=dwqkv, bqkv=dbqkv, wproj=dwproj, bproj=dbproj)
 
 
@@ -564,13 +616,16 @@ class EncoderFn(torch.autograd.Function):
         shared, blocks = split_params(params, EncShared, EncBlock)
         grad = any(ctx.needs_input_grad)  # False under no_grad: nothing is saved for inference
         x, patches, batch, n = _patch_tokens_fwd(rt, img, shared, with_cls=False)
+        drop = _take_drop_rows(rt, 0, len(blocks), 2, batch, n, x.device)      # stochastic depth: per-row scales of (attn, mlp) per block
         tape = []
         ln1 = None          # (h, mean, rstd) of this block's norm1 when the previous block's fc2 kernel already produced it
         for i, P in enumerate(blocks):
-            chain = _hand_over_ln(rt, x, P, grad)
+            s_attn, s_mlp = drop.block(i) if drop is not None else (None, None)
+            chain = _hand_over_ln(rt, x, P, grad or s_mlp is not None)
             with _BlockSpan(rt, 'enc', i, 'fwd'):
-                xa, sa, ln2 = _attn_branch_fwd(rt, x, P, batch, n, key=('blocks', i, 'attn'), ln=ln1, next_ln=(P.g2, P.b2) if chain else None)
-                xb, sm, ln1 = _mlp_fwd(rt, xa, P, grad, ln=ln2, next_ln=_norm1_of(blocks, i + 1) if chain else None)
+                xa, sa, ln2 = _attn_branch_fwd(rt, x, P, batch, n, key=('blocks', i, 'attn'), ln=ln1, next_ln=(P.g2, P.b2) if chain else None,
+                                               scale=s_attn)
+                xb, sm, ln1 = _mlp_fwd(rt, xa, P, grad, ln=ln2, next_ln=_norm1_of(blocks, i + 1) if chain else None, scale=s_mlp)
             if grad:
                 tape.append((x, sa, xa, sm))
             x = xb
@@ -578,6 +633,7 @@ class EncoderFn(torch.autograd.Function):
                 rt.tap[f'enc.x.{len(tape) - 1 if grad else 0}'] = x.clone()
         if grad:
             ctx.rt, ctx.tape, ctx.patches, ctx.batch, ctx.params = rt, tape, patches, batch, (shared, blocks)
+            ctx.drop = drop
         return x.view(batch, n, rt.dim)
 
     @staticmethod
@@ -585,20 +641,23 @@ class EncoderFn(torch.autograd.Function):
         rt, batch, n = ctx.rt, ctx.batch, ctx.rt.n1
         shared, blocks = ctx.params
         dx = dout.contiguous().view(batch * n, rt.dim).float()
-        dx_lp = _lp(rt, dx)
+        drop = ctx.drop
+        scale_of = (lambda i, j: drop.get(i, j)) if drop is not None else (lambda i, j: None)
+        dx_lp = _lp_scaled(rt, dx, scale_of(len(blocks) - 1, 1))      # the last block's MLP branch consumes it
         gblocks = [None] * len(blocks)
         with _ln_sums(rt), _DwBatch(rt, kind='enc') as dwg:      # the encoder's 2 x depth LayerNorm column sums
             for i in reversed(range(len(blocks))):
                 x, sa, xa, sm = ctx.tape[i]
                 ctx.tape[i] = None
                 with _BlockSpan(rt, 'enc', i, 'bwd'), dwg.block():
-                    dx, dx_lp, gm = _mlp_bwd(rt, dx, dx_lp, xa, blocks[i], sm)
-                    dx, dx_lp, ga = _attn_branch_bwd(rt, dx, dx_lp, x, blocks[i], sa, batch, n, key=('blocks', i, 'attn'))
+                    dx, dx_lp, gm = _mlp_bwd(rt, dx, dx_lp, xa, blocks[i], sm, lp_scale=scale_of(i, 0))
+                    dx, dx_lp, ga = _attn_branch_bwd(rt, dx, dx_lp, x, blocks[i], sa, batch, n, key=('blocks', i, 'attn'),
+                                                     lp_scale=scale_of(i - 1, 1))
                 if rt.tap is not None:
                     rt.tap[f'enc.dx.{i}'] = dx.clone()      # gradient w.r.t. the INPUT of encoder block i
                 gblocks[i] = EncBlock(**ga, **gm)
         gshared = EncShared(**_patch_tokens_bwd(rt, dx, ctx.patches, shared, with_cls=False, batch=batch))
-        ctx.tape = ctx.patches = None
+        ctx.tape = ctx.patches = ctx.drop = None
         return (None, None, *_cam_only(rt, flatten_params(gshared, gblocks)))
 
 
@@ -613,17 +672,18 @@ def _dense_rows(t):
     return out
 
 
-def _dec_self_fwd(rt, x, P, batch, n, cls_only, key=None, ln1=None, fuse_ln=True):
+def _dec_self_fwd(rt, x, P, batch, n, cls_only, key=None, ln1=None, fuse_ln=True, scale=None):
     """Self stage: x -> (xa = x + attn(norm1(x)), saved, lnq).  ``cls_only`` (the LAST decoder block): only x[:, 0] of the
     block's output reaches the head (:400, :417 - the final norm and the head are row-wise), and within a CrossBlock the
     token rows only mix in the self-attention, as keys / values.  So after the block's qkv projection everything runs on the
     cls row alone: self-attention for query 0, proj, the whole cross-attention query side and the MLP - 1 row instead of
     N2 = 65 / 1025 per pair - with identical logits and gradients (the dropped rows' outputs are dead, their gradients exactly
     zero); xa is then [batch, D].  ``ln1`` = (h, mean, rstd) of norm1(x) when the previous block's fc2 kernel produced it.
-    ``fuse_ln``: the proj kernel also produces lnq = (h, mean, rstd) of norm_cross(xa); else lnq is None (_cross_q computes it)."""
+    ``fuse_ln``: the proj kernel also produces lnq = (h, mean, rstd) of norm_cross(xa); else lnq is None (_cross_q computes it).
+    ``scale``: the branch's stochastic-depth scale, one value per row of xa (per sample when cls_only)."""
     next_ln = (P.gc, P.bc) if fuse_ln else None
     if not cls_only:
-        return _attn_branch_fwd(rt, x, P, batch, n, key=key, ln=ln1, next_ln=next_ln)
+        return _attn_branch_fwd(rt, x, P, batch, n, key=key, ln=ln1, next_ln=next_ln, scale=scale)
     d = rt.dim
     h1, m1, r1 = ln1 if ln1 is not None else ops.layernorm_fwd(x, P.g1, P.b1, LN_EPS, rt.act_dtype)
     qkv = ops.gemm(h1, rt.weight(P.wqkv), bias=P.bqkv)            # K and V of every row feed query 0
@@ -631,15 +691,16 @@ def _dec_self_fwd(rt, x, P, batch, n, cls_only, key=None, ln1=None, fuse_ln=True
     o0, lse0 = ops.attention_fwd(qkv3[:, 0:1, 0:d], qkv3[:, :, d:2 * d], qkv3[:, :, 2 * d:3 * d], rt.heads, rt.scale)
     o0 = o0.view(batch, d)
     x0 = _dense_rows(x.view(batch, n, d)[:, 0, :])
-    xa, lnq = _res_linear(rt, o0, P.wproj, P.bproj, x0, next_ln)
+    xa, lnq = _res_linear(rt, o0, P.wproj, P.bproj, x0, next_ln, scale)
     return xa, (m1, r1, h1, qkv, o0, lse0), lnq
 
 
-def _dec_self_bwd(rt, dx, dx_lp, x, P, saved, batch, n, cls_only, key=None):
-    """Backward of _dec_self_fwd.  dx / dx_lp: gradient w.r.t. xa (all rows, or the cls rows when cls_only).
+def _dec_self_bwd(rt, dx, dx_lp, x, P, saved, batch, n, cls_only, key=None, lp_scale=None):
+    """Backward of _dec_self_fwd.  dx / dx_lp: gradient w.r.t. xa (all rows, or the cls rows when cls_only); ``lp_scale`` as in _mlp_bwd
+    (one value per row of x: all rows, also when cls_only).
     Returns (d x fp32 [batch n, D], its low-precision copy, the six parameter gradients by field name)."""
     if not cls_only:
-        return _attn_branch_bwd(rt, dx, dx_lp, x, P, saved, batch, n, key=key)
+        return _attn_branch_bwd(rt, dx, dx_lp, x, P, saved, batch, n, key=key, lp_scale=lp_scale)
     d = rt.dim
     m1, r1, h1, qkv, o0, lse0 = saved
     do0, dwproj, dbproj = _linear_bwd(rt, dx_lp, o0, P.wproj, P.bproj)
@@ -650,7 +711,7 @@ def _dec_self_bwd(rt, dx, dx_lp, x, P, saved, batch, n, cls_only, key=None):
                       lse0, rt.heads, rt.scale, dqkv3[:, 0:1, 0:d], dqkv3[:, :, d:2 * d], dqkv3[:, :, 2 * d:3 * d])
     dres = torch.zeros((batch * n, d), dtype=torch.float32, device=dx.device)   # the residual path carries gradient on the cls rows only
     dres.view(batch, n, d)[:, 0, :].copy_(dx)
-    dx, dx_lp, dg1, db1, dwqkv, dbqkv = _linear_ln_bwd(rt, dqkv, h1, P.wqkv, P.bqkv, x, P.g1, P.b1, m1, r1, dx_in=dres)
+    dx, dx_lp, dg1, db1, dwqkv, dbqkv = _linear_ln_bwd(rt, dqkv, h1, P.wqkv, P.bqkv, x, P.g1, P.b1, m1, r1, dx_in=dres, lp_scale=lp_scale)
     return dx, dx_lp, dict(g1=dg1, b1=db1, wqkv=dwqkv, bqkv=dbqkv, wproj=dwproj, bproj=dbproj)
 
 
@@ -661,7 +722,7 @@ def _cross_q(rt, xa, P, lnq=None):
     return ops.gemm(hq, rt.weight(P.wq), bias=P.bq), (hq, mq, rq)
 
 
-def _dec_cross_fwd(rt, xa, P, batch, lnq=None, q=None, kv3=None, ctxf=None, kv_index=None, key=None, fuse_ln=True):
+def _dec_cross_fwd(rt, xa, P, batch, lnq=None, q=None, kv3=None, ctxf=None, kv_index=None, key=None, fuse_ln=True, scale=None):
     """Cross stage (:174-200, :270): xa [batch Nq, D] -> (xb = xa + proj(attention(q, k, v)), saved, ln2) with q from the image-2
     tokens (_cross_q, unless the pair cache hands ``q`` over) and k / v from the image-1 features: ``kv3`` [., N1, 2 D] when they
     were computed ahead for all blocks (_context_kv_folded, context_kv; with ``kv_index`` pair p reads kv3[kv_index[p]]), else
@@ -679,11 +740,11 @@ def _dec_cross_fwd(rt, xa, P, batch, lnq=None, q=None, kv3=None, ctxf=None, kv_i
     if rt.keep_attn and key is not None:
         _keep_attention(rt, key, q.view(batch, nq, d), kv3[:, :, 0:d])
     oc = oc.view(batch * nq, d)
-    xb, ln2 = _res_linear(rt, oc, P.wcp, P.bcp, xa, (P.g2, P.b2) if fuse_ln else None)
+    xb, ln2 = _res_linear(rt, oc, P.wcp, P.bcp, xa, (P.g2, P.b2) if fuse_ln else None, scale)
     return xb, (mq, rq, hq, mc, rc, hc, q, kv, oc, lse_c), ln2
 
 
-def _dec_cross_bwd(rt, dx, dx_lp, xa, P, saved, ctxf, dctx, batch, index, dkv3=None):
+def _dec_cross_bwd(rt, dx, dx_lp, xa, P, saved, ctxf, dctx, batch, index, dkv3=None, lp_scale=None):
     """Backward of _dec_cross_fwd.  Returns (d xa fp32, its low-precision copy, d context (accumulated in place), the ten parameter
     gradients by field name).  When the keys / values came from _context_kv_folded, d(kv) is written into ``dkv3`` (this block's
     view of the all-blocks tensor) and gx, bx, wkv, bkv stay None: _context_kv_folded_bwd fills them in after the last block."""
@@ -710,7 +771,7 @@ def _dec_cross_bwd(rt, dx, dx_lp, xa, P, saved, ctxf, dctx, batch, index, dkv3=N
         rt.tap[f'dec.doc.{i}'], rt.tap[f'dec.dq.{i}'], rt.tap[f'dec.dkv.{i}'] = doc.clone(), dq.clone(), dkv.clone()
         rt.tap[f'dec.q.{i}'], rt.tap[f'dec.kv.{i}'], rt.tap[f'dec.oc.{i}'] = q.clone(), kv.clone(), oc.clone()
     # q = Linear(norm_cross(x')), kv = Linear(norm_context(features)): input-gradient GEMM + LayerNorm backward fused
-    dx, dx_lp, dgc, dbc, dwq, dbq = _linear_ln_bwd(rt, dq, hq, P.wq, P.bq, xa, P.gc, P.bc, mq, rq, dx_in=dx)
+    dx, dx_lp, dgc, dbc, dwq, dbq = _linear_ln_bwd(rt, dq, hq, P.wq, P.bq, xa, P.gc, P.bc, mq, rq, dx_in=dx, lp_scale=lp_scale)
     dgx = dbx = dwkv = dbkv = None
     if not folded:
         # d(context) accumulates over the c_depth blocks in fp32, in place
@@ -718,23 +779,26 @@ def _dec_cross_bwd(rt, dx, dx_lp, xa, P, saved, ctxf, dctx, batch, index, dkv3=N
     return dx, dx_lp, dctx, dict(gc=dgc, bc=dbc, gx=dgx, bx=dbx, wq=dwq, bq=dbq, wkv=dwkv, bkv=dbkv, wcp=dwcp, bcp=dbcp)
 
 
-def _dec_block_fwd(rt, x, ctxf, P, batch, n, grad, cls_only, index=0, ln1=None, next_ln=None, kv3=None):
+def _dec_block_fwd(rt, x, ctxf, P, batch, n, grad, cls_only, index=0, ln1=None, next_ln=None, kv3=None, scales=(None, None, None)):
     """One CrossBlock forward of DecoderFn: self + cross + MLP stage, every following LayerNorm asked of the Linear before it
-    (``next_ln`` = (gamma, beta) of the NEXT block's norm1).  Returns (block output, tape entry | None, next block's ln1 | None)."""
-    xa, sa, lnq = _dec_self_fwd(rt, x, P, batch, n, cls_only, key=('cross_blocks', index, 'attn'), ln1=ln1)
+    (``next_ln`` = (gamma, beta) of the NEXT block's norm1).  ``scales``: the stochastic-depth scales of the (self, cross, mlp) branches,
+    each one value per row of its stage or None.  Returns (block output, tape entry | None, next block's ln1 | None)."""
+    xa, sa, lnq = _dec_self_fwd(rt, x, P, batch, n, cls_only, key=('cross_blocks', index, 'attn'), ln1=ln1, scale=scales[0])
     xb, sc, ln2 = _dec_cross_fwd(rt, xa, P, batch, lnq=lnq, kv3=kv3, ctxf=ctxf, key=('cross_blocks', index, 'cross_attn'),
-                                 fuse_ln=_hand_over_ln(rt, xa, P, grad))
-    xc, sm, nxt = _mlp_fwd(rt, xb, P, grad, ln=ln2, next_ln=next_ln)
+                                 fuse_ln=_hand_over_ln(rt, xa, P, grad or scales[2] is not None), scale=scales[1])
+    xc, sm, nxt = _mlp_fwd(rt, xb, P, grad, ln=ln2, next_ln=next_ln, scale=scales[2])
     return xc, ((x, sa, xa, sc, xb, sm) if grad else None), nxt
 
 
-def _dec_block_bwd(rt, dx, dx_lp, ctxf, dctx, P, entry, batch, n, cls_only, index, dkv3=None):
+def _dec_block_bwd(rt, dx, dx_lp, ctxf, dctx, P, entry, batch, n, cls_only, index, dkv3=None, lp_scales=(None, None, None)):
     """Backward of _dec_block_fwd.  dx / dx_lp: gradient w.r.t. the block's output (all rows, or the cls rows when cls_only).
+    ``lp_scales``: the stochastic-depth scales carried by the low-precision copies that leave the MLP, cross and self stage - those
+    of this block's cross branch, of its self branch and of the PREVIOUS block's MLP branch.
     Returns (d input fp32, its low-precision copy, d context (accumulated in place), the parameter gradients as a DecBlock)."""
     x, sa, xa, sc, xb, sm = entry
-    dx, dx_lp, gm = _mlp_bwd(rt, dx, dx_lp, xb, P, sm)
-    dx, dx_lp, dctx, gc = _dec_cross_bwd(rt, dx, dx_lp, xa, P, sc, ctxf, dctx, batch, index, dkv3)
-    dx, dx_lp, ga = _dec_self_bwd(rt, dx, dx_lp, x, P, sa, batch, n, cls_only, key=('cross_blocks', index, 'attn'))
+    dx, dx_lp, gm = _mlp_bwd(rt, dx, dx_lp, xb, P, sm, lp_scale=lp_scales[0])
+    dx, dx_lp, dctx, gc = _dec_cross_bwd(rt, dx, dx_lp, xa, P, sc, ctxf, dctx, batch, index, dkv3, lp_scale=lp_scales[1])
+    dx, dx_lp, ga = _dec_self_bwd(rt, dx, dx_lp, x, P, sa, batch, n, cls_only, key=('cross_blocks', index, 'attn'), lp_scale=lp_scales[2])
     return dx, dx_lp, dctx, DecBlock(**ga, **gc, **gm)
 
 
@@ -876,6 +940,7 @@ class DecoderFn(torch.autograd.Function):
         tape = []
         d = rt.dim
         cls_tail = rt.cls_tail and rt.c_depth > 0 and not (rt.keep_attn or rt.keep_cam)    # the visualisation paths want every query row's map
+        drop = _take_drop_rows(rt, 1, len(blocks), 3, batch, n, x.device, cls_block=rt.c_depth - 1 if cls_tail else None)
         ln1 = None
         fold = rt.fold_context and not rt.exact and rt.c_depth > 1 and rt.c_depth <= ops.MAX_FOLDED_BLOCKS and rt.dim % 32 == 0
         kv_all = kv_saved = fold_bufs = None
@@ -883,7 +948,8 @@ class DecoderFn(torch.autograd.Function):
             kv_all, kv_saved, fold_bufs = _context_kv_folded(rt, ctxf, blocks)
         for i, P in enumerate(blocks):
             x, entry, ln1 = _dec_block_fwd(rt, x, ctxf, P, batch, n, grad, cls_tail and i == rt.c_depth - 1, index=i, ln1=ln1,
-                                           next_ln=_norm1_of(blocks, i + 1), kv3=kv_all[i].view(batch, rt.n1, 2 * d) if fold else None)
+                                           next_ln=_norm1_of(blocks, i + 1), kv3=kv_all[i].view(batch, rt.n1, 2 * d) if fold else None,
+                                           scales=drop.block(i) if drop is not None else (None, None, None))
             if grad:
                 tape.append(entry)
             if rt.tap is not None:
@@ -897,6 +963,7 @@ class DecoderFn(torch.autograd.Function):
             ctx.ctxf, ctx.final, ctx.cls_tail = ctxf, (xcls, y, mN, rN), cls_tail
             ctx.feats_needs_grad = feats.requires_grad
             ctx.fold = (kv_all, kv_saved, fold_bufs) if fold else None
+            ctx.drop = drop
         return logits
 
     @staticmethod
@@ -909,7 +976,21 @@ class DecoderFn(torch.autograd.Function):
         wh_act = rt.weight(shared.wh)
         dy = ops.gemm(dl, wh_act, b_layout=B_KN)                         # [B, D]
         dwh, dbh = _weight_grads(rt, dl, y, shared.wh, shared.bh)
-        if ctx.cls_tail:
+        drop, last = ctx.drop, len(blocks) - 1
+        scale_of = (lambda i, j: drop.get(i, j)) if drop is not None else (lambda i, j: None)
+        # the low-precision copy that leaves the final norm feeds the last block's MLP branch: it carries that branch's scale, per
+        # sample (the final norm runs on the cls rows)
+        s_head = drop.per_sample[last, 2] if drop is not None and drop.live[last][2] else None
+        if s_head is not None:
+            lp_dtype = rt.act_dtype
+            if ctx.cls_tail:
+                dx, dx_lp, dgN, dbN = _ln_bwd(rt, dy, xcls, shared.gN, shared.bN, mN, rN, lp_scale=s_head, lp_dtype=lp_dtype)
+            else:
+                dx = torch.zeros((batch * n, d), dtype=torch.float32, device=dy.device)
+                dx_lp = torch.zeros((batch * n, d), dtype=lp_dtype, device=dy.device)
+                _, _, dgN, dbN = _ln_bwd(rt, dy, xcls, shared.gN, shared.bN, mN, rN, dx_out=dx.view(batch, n, d)[:, 0, :],
+                                         dx_lp=dx_lp.view(batch, n, d)[:, 0, :], lp_scale=s_head, lp_dtype=lp_dtype)
+        elif ctx.cls_tail:
             # the last block ran on the cls rows only: so does its gradient
             dx, dx_lp, dgN, dbN = _ln_bwd(rt, dy, xcls, shared.gN, shared.bN, mN, rN, want_lp=not rt.exact)
         else:
@@ -920,7 +1001,7 @@ class DecoderFn(torch.autograd.Function):
                 dx_lp = torch.zeros((batch * n, d), dtype=rt.act_dtype, device=dy.device)
                 dx_lp3 = dx_lp.view(batch, n, d)[:, 0, :]
             _, _, dgN, dbN = _ln_bwd(rt, dy, xcls, shared.gN, shared.bN, mN, rN, dx_out=dx.view(batch, n, d)[:, 0, :], dx_lp=dx_lp3)
-        if rt.exact:
+        if rt.exact and s_head is None:
             dx_lp = dx
         dctx = None
         gblocks = [None] * len(blocks)
@@ -933,7 +1014,8 @@ class DecoderFn(torch.autograd.Function):
                     with dwg.block():
                         dx, dx_lp, dctx, gblocks[i] = _dec_block_bwd(rt, dx, dx_lp, ctx.ctxf, dctx, blocks[i], entry, batch, n,
                                                                      ctx.cls_tail and i == rt.c_depth - 1, i,
-                                                                     dkv3=dkv_all[i].view(batch, rt.n1, 2 * d) if dkv_all is not None else None)
+                                                                     dkv3=dkv_all[i].view(batch, rt.n1, 2 * d) if dkv_all is not None else None,
+                                                                     lp_scales=(scale_of(i, 1), scale_of(i, 0), scale_of(i - 1, 2)))
                     if rt.tap is not None:
                         rt.tap[f'dec.dx.{i}'] = dx.clone()      # gradient w.r.t. the INPUT of decoder block i
                         if dctx is not None:
@@ -944,5 +1026,5 @@ class DecoderFn(torch.autograd.Function):
                 ctx.fold = None
         gshared = DecShared(**_patch_tokens_bwd(rt, dx, ctx.patches, shared, with_cls=True, batch=batch), gN=dgN, bN=dbN, wh=dwh, bh=dbh)
         dfeats = dctx.view(batch, rt.n1, d) if ctx.feats_needs_grad and dctx is not None else None
-        ctx.tape = ctx.patches = ctx.ctxf = ctx.final = None
+        ctx.tape = ctx.patches = ctx.ctxf = ctx.final = ctx.drop = None
         return (None, dfeats, None, None, *_cam_only(rt, flatten_params(gshared, gblocks)))

@@ -9,6 +9,8 @@ Drop-in surface kept:
     ``misc/optimizer.py:36-46`` puts ``ndim == 1`` / ``*.bias`` in the no-decay group; ``.head`` is
     re-initialised by ``misc/utils.py:110-119``);
   * raw fp32 logits out.
+  * ``drop_path_rate``: stochastic depth on every residual branch in training mode, applied inside the residual epilogues of
+    the kernels (``draw_drop_path`` / ``forward(..., drop_path=...)`` / ``last_drop_path``).
 
 Precision follows the caller exactly like the reference follows ``torch.cuda.amp.autocast``
 (misc/engine.py:208): inside an autocast region the bf16 MFMA kernels run, outside it the fp32
@@ -19,6 +21,8 @@ There is no PyTorch fallback: calling the model with CPU tensors or without the 
 """
 from __future__ import annotations
 
+from collections import namedtuple
+
 import torch
 import torch.nn as nn
 
@@ -26,6 +30,11 @@ from . import functions as F_
 from .functions import DEC_BLOCK_KEYS, DEC_SHARED_KEYS, ENC_BLOCK_KEYS, ENC_SHARED_KEYS, Runtime
 
 LN_EPS = F_.LN_EPS
+
+# Stochastic-depth scales of one forward: enc fp32 [depth, 2, B] for the (attn, mlp) branches of every encoder block, dec fp32
+# [c_depth, 3, B] for the (self, cross, mlp) branches of every decoder block; each value 0 (the sample skips the branch) or
+# 1 / keep.  Either field may be None for a call that runs only the other half.
+DropPathScales = namedtuple('DropPathScales', 'enc dec')
 
 
 class _Holder(nn.Module):
@@ -150,8 +159,11 @@ def _get(module, dotted):
 class VisionTransformerCustom(nn.Module):
     def __init__(self, img_size=224, patch_size=16, in_chans=3, num_classes=1000, embed_dim=768, depth=12, c_depth=12,
                  num_heads=12, mlp_ratio=4., qkv_bias=True, keep_attn=False, arch_version='v1', compute_dtype=None,
-                 **unsupported):
+                 drop_path_rate=0., **unsupported):
         super().__init__()
+        drop_path_rate = float(drop_path_rate or 0.)
+        if not 0. <= drop_path_rate < 1.:
+            raise ValueError(f'drop_path_rate={drop_path_rate}: stochastic depth takes a rate in [0, 1)')
         live = {k: v for k, v in unsupported.items() if v not in (None, False, 0, 0., '', 'token')}
         if live:
             raise NotImplementedError(f'options outside the shipped pjs configs are not on the HIP hot path: {sorted(live)}')
@@ -175,6 +187,14 @@ class VisionTransformerCustom(nn.Module):
                                             # such a backward leaves every parameter gradient untouched
         self.arch_version = arch_version.lower()
         self.compute_dtype = compute_dtype
+        # stochastic depth (timm DropPath, scale_by_keep): the reference's two decay rules, fp32 linspace as it computes them
+        # (vision_transformer.py:351 for the decoder, timm's VisionTransformer for the encoder); DropPath has no parameters
+        self.drop_path_rate = drop_path_rate
+        self._drop_probs = ([torch.linspace(0, drop_path_rate, depth)[i].item() for i in range(depth)],
+                            [torch.linspace(0, drop_path_rate, c_depth)[i].item() for i in range(c_depth)])
+        self.drop_path_generator = None     # torch.Generator of the draws in training mode (None: the device's default generator)
+        self.last_drop_path = None          # DropPathScales of the latest forward (None: it ran without stochastic depth)
+        self._keep_cache = {}
         # uint8 inputs are normalised inside the patch-embedding kernel: ToTensor + Normalize(0.5, 0.5) of data/transforms.py:14-18
         self.input_mean, self.input_std = (0.5,) * in_chans, (0.5,) * in_chans
         hidden = int(embed_dim * mlp_ratio)
@@ -249,20 +269,110 @@ class VisionTransformerCustom(nn.Module):
         if not img.is_cuda:
             raise RuntimeError('the HIP ViT-ED runs on MI355X only: got a CPU tensor (no CPU fallback exists)')
 
+    # -- stochastic depth ---------------------------------------------------------------------
+    @property
+    def drop_path_probs(self):
+        """(drop probability of every encoder block, of every decoder block): both branches of encoder block i drop with
+        linspace(0, rate, depth)[i], the three branches of decoder block i with linspace(0, rate, c_depth)[i]."""
+        return list(self._drop_probs[0]), list(self._drop_probs[1])
+
+    def _keep(self, which, device):
+        """(keep probability, fp32(1) / fp32(keep)) of every block of the encoder (0) / decoder (1) as fp32 [blocks, 1, 1].  Built
+        on the host and uploaded once per device; ``_apply`` does that when the model moves, so a capture finds them in place."""
+        key = (which, str(device))
+        ent = self._keep_cache.get(key)
+        if ent is None:
+            if device.type == 'cuda' and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError(f'the keep probabilities are not on {device} yet and a graph capture cannot upload them: draw once '
+                                   'eagerly on that device before capturing')
+            keep = torch.tensor([1.0 - p for p in self._drop_probs[which]], dtype=torch.float32).view(-1, 1, 1)
+            ent = self._keep_cache[key] = (keep.to(device), (torch.ones((), dtype=torch.float32) / keep).to(device))
+        return ent
+
+    def _apply(self, fn, *args, **kwargs):
+        out = super()._apply(fn, *args, **kwargs)
+        self._keep_cache.clear()
+        device = self.pos_embed.device
+        if self.drop_path_rate > 0. and device.type == 'cuda':
+            self._keep(0, device), self._keep(1, device)
+        return out
+
+    def draw_drop_path(self, batch_enc, batch_dec, generator=None, device=None):
+        """Draw the scales of one forward: DropPathScales(enc fp32 [depth, 2, batch_enc], dec fp32 [c_depth, 3, batch_dec]), every
+        branch and sample independently 1 / keep with probability keep, else 0 (timm drop_path, scale_by_keep=True).  A batch of
+        None leaves that field None.  One Bernoulli launch and one multiply per half, whatever the depth; plain torch, so it
+        also runs on the CPU."""
+        device = torch.device(device) if device is not None else self.pos_embed.device
+        if generator is not None and device.type == 'cuda' and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('drop-path draws inside a graph capture use the device\'s default generator (torch registers it with '
+                               'the graph, so every replay draws anew); a custom generator would freeze one mask into the graph')
+        out = []
+        for which, (batch, branches) in enumerate(((batch_enc, 2), (batch_dec, 3))):
+            if batch is None or not self._drop_probs[which]:
+                out.append(None)
+                continue
+            keep, inv_keep = self._keep(which, device)
+            kept = torch.bernoulli(keep.expand(-1, branches, int(batch)), generator=generator)
+            out.append(kept * inv_keep)
+        return DropPathScales(*out)
+
+    def _resolve_drop_path(self, drop_path, batch_enc, batch_dec, device):
+        """What a forward passes on to the Functions: (enc, dec, (live enc, live dec)) or None.  Explicit scales hold in any mode and
+        make every branch live; otherwise training mode with a live rate draws, and only the branches with p > 0 are live."""
+        if drop_path is not None:
+            enc, dec = drop_path
+            live = ([[True, True]] * self.depth, [[True, True, True]] * self.c_depth)
+            used = DropPathScales(enc if batch_enc is not None else None, dec if batch_dec is not None else None)
+        elif self.training and self.drop_path_rate > 0. and not self.keep_cam:      # (a relevancy-map backward never drops)
+            used = self.draw_drop_path(batch_enc, batch_dec, generator=self.drop_path_generator, device=device)
+            live = ([[p > 0.] * 2 for p in self._drop_probs[0]], [[p > 0.] * 3 for p in self._drop_probs[1]])
+        else:
+            self.last_drop_path = None
+            return None
+        for name, t, b in (('enc', used.enc, batch_enc), ('dec', used.dec, batch_dec)):
+            if b is not None and t is None and (self.depth if name == 'enc' else self.c_depth):
+                raise ValueError(f'drop_path.{name} is missing for a call that runs that half of the model')
+        # a two-stage step is two calls: each records its half and leaves the other call's half in place
+        prev = self.last_drop_path or DropPathScales(None, None)
+        self.last_drop_path = DropPathScales(used.enc if batch_enc is not None else prev.enc, used.dec if batch_dec is not None else prev.dec)
+        return used.enc, used.dec, live
+
+    def _run_fn(self, fn, drop, *args):
+        rt = self.runtime()
+        rt.drop_path = drop
+        try:
+            return fn.apply(rt, *args)
+        finally:
+            rt.drop_path = None
+
     # -- the reference's forward surface -----------------------------------------------------
-    def forward_first_part(self, x1):
+    def forward_first_part(self, x1, drop_path=None):
         self._check_images(x1)
-        return F_.EncoderFn.apply(self.runtime(), x1, *self._encoder_params())
+        return self._encode(x1, self._resolve_drop_path(drop_path, x1.shape[0], None, x1.device))
+
+    def _encode(self, x1, drop):
+        """The encoder with what ``_resolve_drop_path`` returned."""
+        return self._run_fn(F_.EncoderFn, drop, x1, *self._encoder_params())
 
     supports_x2_index = True   # engine.pairwise_similarity gathers image-2 rows inside the patch-embed kernel
 
-    def forward_second_part_head(self, x1_feats, x2, x2_index=None):
+    def _check_x2(self, x2, x2_index):
+        """The checked index and the number of pairs of a decoder call."""
         self._check_images(x2)
-        if x2_index is not None:
-            if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-                raise NotImplementedError('x2_index (gather-in-kernel) is an inference path: call it under torch.no_grad()')
-            x2_index = x2_index.to(device=x2.device, dtype=torch.int64).contiguous()
-        return F_.DecoderFn.apply(self.runtime(), x1_feats, x2, x2_index, *self._decoder_params())
+        if x2_index is None:
+            return None, x2.shape[0]
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            raise NotImplementedError('x2_index (gather-in-kernel) is an inference path: call it under torch.no_grad()')
+        x2_index = x2_index.to(device=x2.device, dtype=torch.int64).contiguous()
+        return x2_index, x2_index.numel()
+
+    def forward_second_part_head(self, x1_feats, x2, x2_index=None, drop_path=None):
+        x2_index, pairs = self._check_x2(x2, x2_index)
+        return self._decode_head(x1_feats, x2, x2_index, self._resolve_drop_path(drop_path, None, pairs, x2.device))
+
+    def _decode_head(self, x1_feats, x2, x2_index, drop):
+        """The decoder and head with what ``_resolve_drop_path`` returned."""
+        return self._run_fn(F_.DecoderFn, drop, x1_feats, x2, x2_index, *self._decoder_params())
 
     # -- pair-cached inference (engine.pairwise_similarity; SURVEY.md section 8(f) rank 2) ---------------------------------
     supports_pair_cache = True
@@ -287,15 +397,22 @@ class VisionTransformerCustom(nn.Module):
         i_idx = i_idx.to(device=dev, dtype=torch.int64).contiguous()
         return F_.decoder_cached(self.runtime(), tokens2, j_idx, kvs, i_idx, self._decoder_params(), q0)
 
-    def forward(self, x, x2=None, forward_first_part=False, x2_index=None):
+    def forward(self, x, x2=None, forward_first_part=False, x2_index=None, drop_path=None):
+        """``drop_path``: explicit DropPathScales for this call (any mode; tests, reproducing a step).  None: training mode with a
+        live ``drop_path_rate`` draws them for the batch of the call - the images of ``forward_first_part``, the pairs of
+        ``(feats, x2)``, the B pairs of a one-shot call for both halves - and ``eval()`` or rate 0 runs without.  The scales used
+        are kept in ``last_drop_path``."""
         if forward_first_part:
-            return self.forward_first_part(x)
+            return self.forward_first_part(x, drop_path)
         if x2 is not None:
-            return self.forward_second_part_head(x, x2, x2_index)
+            return self.forward_second_part_head(x, x2, x2_index, drop_path)
         if x.dim() != 5 or x.shape[1] != 2:
             raise AssertionError(f'expected stacked pairs [B, 2, C, S, S], got {tuple(x.shape)}')
-        feats = self.forward_first_part(x[:, 0])      # strided views: the kernels take a batch stride
-        return self.forward_second_part_head(feats, x[:, 1])
+        drop = self._resolve_drop_path(drop_path, x.shape[0], x.shape[0], x.device)
+        x1, x2 = x[:, 0], x[:, 1]                                           # strided views: the kernels take a batch stride
+        self._check_images(x1)
+        self._check_images(x2)
+        return self._decode_head(self._encode(x1, drop), x2, None, drop)
 
     def flops_parts(self):
         """Algorithmic forward FLOPs (2MNK per contraction) of (the encoder on ONE image incl. its

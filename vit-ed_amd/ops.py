@@ -102,6 +102,23 @@ def cast(src: torch.Tensor, dtype: torch.dtype, out: torch.Tensor | None = None)
     return out
 
 
+def scale_rows_cast(src: torch.Tensor, row_scale: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+    """dst[r, :] = dtype(row_scale[r] * src[r, :]) for fp32 ``src`` [rows, dim] (``vited_scale_rows_cast``)."""
+    _need_gpu(src, row_scale)
+    rows, dim = src.shape
+    _check_row_scale(row_scale, rows)
+    assert src.dtype == torch.float32
+    out = torch.empty((rows, dim), dtype=dtype, device=src.device)
+    _lib.call('vited_scale_rows_cast', _ptr(src), _rows2d(src), _ptr(row_scale), _ptr(out), _code(dtype), dim, rows, dim, _stream())
+    return out
+
+
+def _check_row_scale(row_scale, rows):
+    """A drop-path scale vector: fp32, one value per row, contiguous."""
+    if row_scale.dtype != torch.float32 or row_scale.dim() != 1 or row_scale.numel() != rows or not row_scale.is_contiguous():
+        raise ValueError(f'row scale: expected a contiguous fp32 vector of {rows} rows, got {row_scale.dtype} {tuple(row_scale.shape)}')
+
+
 def cast_transpose(w: torch.Tensor, dtype: torch.dtype, out: torch.Tensor | None = None) -> torch.Tensor:
     """fp32 [R, C] -> dtype [C, R] (transposed weight shadow)."""
     _need_gpu(w, out)
@@ -360,20 +377,27 @@ def layernorm_fwd(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps:
 
 
 def layernorm_bwd(dy, x, gamma, mean, rstd, dx_in=None, dx_out=None, want_lp: bool = False, dx_lp=None, dgamma=None,
-                  dbeta=None):
+                  dbeta=None, lp_scale=None, lp_dtype=torch.bfloat16):
     """Returns (dx fp32, dx_lp bf16 | None, dgamma, dbeta).  When ``dgamma`` / ``dbeta`` are given (fp32,
     contiguous - e.g. views of the flat gradient buffer) the column sums are ADDED onto them.
 
     dx = (dx_in or 0) + LN'(dy).  ``dx_out`` / ``dx_lp`` may be given as pre-made (row-strided)
-    destinations - e.g. the cls rows of a zero-filled token-gradient tensor."""
-    _need_gpu(dy, x, gamma, mean, rstd, dx_in, dx_out, dx_lp)
+    destinations - e.g. the cls rows of a zero-filled token-gradient tensor.
+    ``lp_scale`` (fp32 [rows]): dx_lp = lp_dtype(lp_scale[r] * dx[r]) (``vited_layernorm_bwd_scaled``; fp32 allowed then)."""
+    _need_gpu(dy, x, gamma, mean, rstd, dx_in, dx_out, dx_lp, lp_scale)
     dy_ld, x_ld = _rows2d(dy), _rows2d(x)
     rows, dim = x.shape
     assert dy.shape == x.shape and x.dtype == torch.float32
     if dx_out is None:
         dx_out = torch.empty((rows, dim), dtype=torch.float32, device=x.device)
+    if lp_scale is not None:
+        _check_row_scale(lp_scale, rows)
+        want_lp = True
+    else:
+        lp_dtype = torch.bfloat16
     if want_lp and dx_lp is None:
-        dx_lp = torch.empty((rows, dim), dtype=torch.bfloat16, device=x.device)
+        dx_lp = torch.empty((rows, dim), dtype=lp_dtype, device=x.device)
+    assert dx_lp is None or dx_lp.dtype == lp_dtype
     if dx_in is not None:
         assert dx_in.dtype == torch.float32 and dx_in.shape == x.shape
     accumulate = dgamma is not None
@@ -383,19 +407,23 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, dx_in=None, dx_out=None, want_lp: bo
         dgamma = torch.empty(dim, dtype=torch.float32, device=x.device)
         dbeta = torch.empty(dim, dtype=torch.float32, device=x.device)
     ws = _scratch(_lib.load().vited_layernorm_bwd_workspace_bytes(rows, dim), x.device)
-    _lib.call('vited_layernorm_bwd',
-              _ptr(dy), _code(dy.dtype), dy_ld, _ptr(x), x_ld, _ptr(gamma), _ptr(mean), _ptr(rstd),
-              _ptr(dx_in), _rows2d(dx_in) if dx_in is not None else 0, _ptr(dx_out), _rows2d(dx_out),
-              _ptr(dx_lp), BF16, _rows2d(dx_lp) if dx_lp is not None else 0, _ptr(dgamma), _ptr(dbeta), int(accumulate), rows, dim,
-              *ws, _stream())
+    head = (_ptr(dy), _code(dy.dtype), dy_ld, _ptr(x), x_ld, _ptr(gamma), _ptr(mean), _ptr(rstd),
+            _ptr(dx_in), _rows2d(dx_in) if dx_in is not None else 0, _ptr(dx_out), _rows2d(dx_out),
+            _ptr(dx_lp), _code(lp_dtype), _rows2d(dx_lp) if dx_lp is not None else 0)
+    tail = (_ptr(dgamma), _ptr(dbeta), int(accumulate), rows, dim, *ws, _stream())
+    if lp_scale is not None:
+        _lib.call('vited_layernorm_bwd_scaled', *head, _ptr(lp_scale), *tail)
+    else:
+        _lib.call('vited_layernorm_bwd', *head, *tail)
     return dx_out, dx_lp, dgamma, dbeta
 
 
 # ---------------------------------------------------------------------------------------------
 def gemm(a: torch.Tensor, b: torch.Tensor, *, b_layout: int = B_NK, epilogue: int = EPI_STORE, bias=None, aux=None,
          residual=None, out=None, out2=None, rows_per_batch: int = 0, out_rows_per_batch: int = 0, row_offset: int = 0,
-         residual_bcast: bool = False, out_rows: int | None = None):
-    """acc = a[M,K] . (b[N,K]^T | b[K,N]); see VITED_EPI_* in include/vited.h.
+         residual_bcast: bool = False, out_rows: int | None = None, row_scale=None):
+    """acc = a[M,K] . (b[N,K]^T | b[K,N]); see VITED_EPI_* in include/vited.h.  ``row_scale`` (fp32 [M], EPI_RESIDUAL with the
+    identity row map only): out = residual + row_scale[m] * (acc + bias) (``vited_gemm_scaled``).
 
     Returns ``out`` (and ``out2`` for EPI_GELU)."""
     _need_gpu(a, b, bias, aux, residual, out)
@@ -424,6 +452,15 @@ def gemm(a: torch.Tensor, b: torch.Tensor, *, b_layout: int = B_NK, epilogue: in
         assert residual.stride(-2) == ldo if residual.dim() >= 2 else True
     if bias is not None:
         assert bias.dtype == torch.float32 and bias.numel() == n
+    if row_scale is not None:
+        _need_gpu(row_scale)
+        _check_row_scale(row_scale, m)
+        if epilogue != EPI_RESIDUAL or rows_per_batch:
+            raise ValueError('row_scale goes with EPI_RESIDUAL and the identity row map')
+        assert out.shape[0] == m
+        _lib.call('vited_gemm_scaled', _ptr(a), lda, _ptr(b), ldb, b_layout, _code(a.dtype), m, n, k, _ptr(bias), _ptr(residual),
+                  _ptr(row_scale), _ptr(out), ldo, _stream())
+        return out
     _lib.call('vited_gemm', _ptr(a), lda, _ptr(b), ldb, b_layout, _code(a.dtype), m, n, k, epilogue, _ptr(bias), _ptr(aux), _ptr(residual),
               _ptr(out), _ptr(out2), ldo, rows_per_batch, out_rows_per_batch, row_offset, int(bool(residual_bcast)), _stream())
     return (out, out2) if epilogue in (EPI_GELU, EPI_GELU_GRAD) else out
@@ -490,10 +527,11 @@ def linear_layernorm_supported(m: int, n: int, k: int, dtype: torch.dtype) -> bo
     return dtype == torch.bfloat16 and bool(_lib.load().vited_linear_layernorm_supported(int(m), int(n), int(k)))
 
 
-def linear_residual_layernorm_fwd(a, w, bias, residual, gamma=None, beta=None, eps: float = 1e-6, out=None):
+def linear_residual_layernorm_fwd(a, w, bias, residual, gamma=None, beta=None, eps: float = 1e-6, out=None, row_scale=None):
     """y = residual + a w^T + bias (fp32) and, with gamma / beta, h = LayerNorm(y) (bf16), mean, rstd - one kernel
-    (``vited_linear_residual_layernorm_fwd``).  Returns (y, h | None, mean | None, rstd | None)."""
-    _need_gpu(a, w, bias, residual, gamma, beta, out)
+    (``vited_linear_residual_layernorm_fwd``).  Returns (y, h | None, mean | None, rstd | None).
+    ``row_scale`` (fp32 [M]): y = residual + row_scale[m] * (a w^T + bias) (``vited_linear_residual_layernorm_fwd_scaled``)."""
+    _need_gpu(a, w, bias, residual, gamma, beta, out, row_scale)
     assert a.dtype == w.dtype == torch.bfloat16 and residual.dtype == torch.float32
     lda, ldw, ldr = _rows2d(a), _rows2d(w), _rows2d(residual)
     m, k = a.shape
@@ -506,19 +544,25 @@ def linear_residual_layernorm_fwd(a, w, bias, residual, gamma=None, beta=None, e
         h = torch.empty((m, n), dtype=torch.bfloat16, device=a.device)
         mean = torch.empty(m, dtype=torch.float32, device=a.device)
         rstd = torch.empty(m, dtype=torch.float32, device=a.device)
-    _lib.call('vited_linear_residual_layernorm_fwd', _ptr(a), lda, _ptr(w), ldw, _ptr(bias), _ptr(residual), ldr, _ptr(y), _rows2d(y),
-              _ptr(gamma), _ptr(beta), float(eps), _ptr(h), n, _ptr(mean), _ptr(rstd), m, n, k, _stream())
+    tail = (_ptr(y), _rows2d(y), _ptr(gamma), _ptr(beta), float(eps), _ptr(h), n, _ptr(mean), _ptr(rstd), m, n, k, _stream())
+    if row_scale is not None:
+        _check_row_scale(row_scale, m)
+        _lib.call('vited_linear_residual_layernorm_fwd_scaled', _ptr(a), lda, _ptr(w), ldw, _ptr(bias), _ptr(residual), ldr, _ptr(row_scale),
+                  *tail)
+    else:
+        _lib.call('vited_linear_residual_layernorm_fwd', _ptr(a), lda, _ptr(w), ldw, _ptr(bias), _ptr(residual), ldr, *tail)
     return y, h, mean, rstd
 
 
 def linear_layernorm_bwd(dy, wt, x, gamma, mean, rstd, dx_in=None, dx_out=None, want_lp: bool = False, dgamma=None, dbeta=None,
-                         defer=None):
+                         defer=None, lp_scale=None):
     """dx = (dx_in or 0) + LN'(dy wt^T; x, mean, rstd, gamma) in one kernel (``vited_linear_layernorm_bwd``): the input
     gradient of ``y = LayerNorm(x) W^T`` without materialising d(LayerNorm output).  ``wt`` = the transposed weight shadow
     [N, K].  Returns (dx fp32, dx_lp bf16 | None, dgamma, dbeta); given ``dgamma`` / ``dbeta`` are ADDED onto.
     ``defer`` (a list): the column sums are NOT finished here - (partials, rows, dgamma, dbeta, accumulate) is appended and
-    ``layernorm_bwd_finish(defer)`` later finishes many LayerNorms with one launch."""
-    _need_gpu(dy, wt, x, gamma, mean, rstd, dx_in, dx_out)
+    ``layernorm_bwd_finish(defer)`` later finishes many LayerNorms with one launch.
+    ``lp_scale`` (fp32 [M]): dx_lp = bf16(lp_scale[m] * dx[m]) (``vited_linear_layernorm_bwd_scaled``)."""
+    _need_gpu(dy, wt, x, gamma, mean, rstd, dx_in, dx_out, lp_scale)
     assert dy.dtype == wt.dtype == torch.bfloat16 and x.dtype == torch.float32
     segments = 1
     if dy.dim() == 3:
@@ -535,6 +579,10 @@ def linear_layernorm_bwd(dy, wt, x, gamma, mean, rstd, dx_in=None, dx_out=None, 
     lib = _lib.load()
     if dx_out is None:
         dx_out = torch.empty((m, n), dtype=torch.float32, device=x.device)
+    if lp_scale is not None:
+        _check_row_scale(lp_scale, m)
+        assert segments == 1
+        want_lp = True
     dx_lp = torch.empty((m, n), dtype=torch.bfloat16, device=x.device) if want_lp else None
     accumulate = dgamma is not None
     if accumulate:
@@ -549,9 +597,14 @@ def linear_layernorm_bwd(dy, wt, x, gamma, mean, rstd, dx_in=None, dx_out=None, 
         ws = (part.data_ptr(), part.numel() * 4)
     else:
         ws = _scratch(lib.vited_linear_layernorm_bwd_workspace_bytes(m, n), x.device)
-    tail = (_ptr(x), ldx, _ptr(gamma), _ptr(mean), _ptr(rstd), _ptr(dx_in), _rows2d(dx_in) if dx_in is not None else 0, _ptr(dx_out),
-            _rows2d(dx_out), _ptr(dx_lp), n, 0 if defer is not None else _ptr(dgamma), 0 if defer is not None else _ptr(dbeta), int(accumulate))
-    if segments > 1:
+    dx_args = (_ptr(x), ldx, _ptr(gamma), _ptr(mean), _ptr(rstd), _ptr(dx_in), _rows2d(dx_in) if dx_in is not None else 0, _ptr(dx_out),
+               _rows2d(dx_out), _ptr(dx_lp), n)
+    sum_args = (0 if defer is not None else _ptr(dgamma), 0 if defer is not None else _ptr(dbeta), int(accumulate))
+    tail = dx_args + sum_args
+    if lp_scale is not None:          # the scaled prototype takes the scale right after the low-precision copy it applies to
+        _lib.call('vited_linear_layernorm_bwd_scaled', _ptr(dy), lddy, _ptr(wt), ldwt, *dx_args, _ptr(lp_scale), *sum_args, m, n, k, *ws,
+                  _stream())
+    elif segments > 1:
         _lib.call('vited_linear_layernorm_bwd_segmented', _ptr(dy), lddy, seg_k, seg_stride, segments, _ptr(wt), ldwt, *tail, m, n, *ws,
                   _stream())
     else:
