@@ -430,7 +430,8 @@ int vited_attention_fwd(const void* q, int64_t q_bs, int64_t q_ts, const void* k
  * (kv_index: DEVICE int64 [batch], values in [0, number of k/v batch items); null = identity).  Serves the pairwise
  * similarity-matrix inference (hisfrag.py:218-231): the cross-attention keys/values of an image-1 row block are projected
  * ONCE and every (i, j) pair of a pair batch reads row i's - no materialised features[i] gather (hisfrag.py:227), no
- * per-pair norm_context + kv projection (vision_transformer.py:174-179 re-runs them for every pair).  Forward only. */
+ * per-pair norm_context + kv projection (vision_transformer.py:174-179 re-runs them for every pair).  Its backward is
+ * vited_attention_bwd_indexed. */
 int vited_attention_fwd_indexed(const void* q, int64_t q_bs, int64_t q_ts, const void* k, int64_t k_bs, int64_t k_ts,
                                 const void* v, int64_t v_bs, int64_t v_ts, const int64_t* kv_index, void* o, int64_t o_bs,
                                 int64_t o_ts, float* lse, int dtype, int64_t batch, int heads, int64_t nq, int64_t nk,
@@ -443,6 +444,30 @@ int vited_attention_bwd(const void* q, int64_t q_bs, int64_t q_ts, const void* k
                         int64_t dq_ts, void* dk, int64_t dk_bs, int64_t dk_ts, void* dv, int64_t dv_bs,
                         int64_t dv_ts, int dtype, int64_t batch, int heads, int64_t nq, int64_t nk,
                         int head_dim, float scale, void* stream);
+
+/* vited_attention_bwd with the indirection of vited_attention_fwd_indexed: batch item b (a pair) reads k / v of item kv_index[b],
+ * dq stays per pair, and dk / dv have kv_items batch items:  dk[g] = sum over the pairs b with kv_index[b] == g of pair b's dk
+ * term, added in ascending b (the same for dv).  The training counterpart of the pair cache (hisfrag.py:117-159: the decoder
+ * runs on mined pairs of a batch's images, and its cross-attention keys / values depend on image 1 only).
+ *   kv_index     DEVICE int64 [batch], values in [0, kv_items)
+ *   seg_order    DEVICE int64 [batch]: the stable argsort of kv_index (pair numbers grouped by item, ascending in a group)
+ *   seg_offsets  DEVICE int64 [kv_items + 1]: group g is seg_order[seg_offsets[g] .. seg_offsets[g + 1])
+ *   workspace    >= vited_attention_bwd_indexed_workspace_bytes(), 16-byte aligned
+ * Two steps: the kernels of vited_attention_bwd (portable fp32, short-sequence MFMA or flash - vited_last_attention_path() tells
+ * which) write every pair's dk / dv term into the workspace IN THE OPERAND DTYPE, then a segmented sum adds each item's terms in
+ * fp32 and rounds once to the operand dtype.  No atomics: every element of every dk / dv item is written exactly once (an item
+ * that no pair reads as zeros; the outputs need not be initialised) and two calls on the same operands give the same bits.
+ * VITED_ERR_BAD_ARG: a null pointer, a non-positive size, a misaligned workspace.  VITED_ERR_UNSUPPORTED: dtype other than
+ * VITED_F32 / VITED_BF16; batch, heads or kv_items above 65535.  VITED_ERR_WORKSPACE: workspace too small.  The index tables are
+ * the caller's to validate (ops.pair_segments does): the kernels follow kv_index as given. */
+int64_t vited_attention_bwd_indexed_workspace_bytes(int dtype, int64_t batch, int heads, int64_t nk, int head_dim);
+int vited_attention_bwd_indexed(const void* q, int64_t q_bs, int64_t q_ts, const void* k, int64_t k_bs, int64_t k_ts,
+                                const void* v, int64_t v_bs, int64_t v_ts, const int64_t* kv_index, const int64_t* seg_order,
+                                const int64_t* seg_offsets, int64_t kv_items, const void* o, const void* d_o, int64_t o_bs,
+                                int64_t o_ts, const float* lse, float* delta, void* dq, int64_t dq_bs, int64_t dq_ts, void* dk,
+                                int64_t dk_bs, int64_t dk_ts, void* dv, int64_t dv_bs, int64_t dv_ts, int dtype, int64_t batch,
+                                int heads, int64_t nq, int64_t nk, int head_dim, float scale, void* workspace,
+                                int64_t workspace_bytes, void* stream);
 
 /* Head-averaged relevancy map of one attention (scripts/visualise_attentions.py: avg_heads, generate_raw_attn,
  * generate_attn_gradcam), folded over the heads inside the kernel: no [B, H, Nq, Nk] tensor, no workspace, no atomics.

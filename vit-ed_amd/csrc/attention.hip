@@ -1,6 +1,7 @@
 // C-ABI attention entry points: validation + dispatch (bf16 MFMA kernels when the shape is
 // covered, portable fp32-VALU kernels otherwise).
 #include "attention_kernels.h"
+#include "pair_segsum.h"
 
 static thread_local int g_last_attn_path = 0;
 extern "C" int vited_last_attention_path(void) { return g_last_attn_path; }
@@ -44,6 +45,15 @@ extern "C" int vited_attention_fwd_indexed(const void* q, int64_t q_bs, int64_t 
     return attention_fwd_portable(a, dtype, s);
 }
 
+static int bwd_dispatch(const AttnArgs& a, int dtype, hipStream_t s) {
+    if (dtype == VITED_BF16 && attention_mfma_supported(a, true)) {
+        g_last_attn_path = 2;
+        return attention_bwd_mfma(a, s);
+    }
+    g_last_attn_path = 1;
+    return attention_bwd_portable(a, dtype, s);
+}
+
 extern "C" int vited_attention_bwd(const void* q, int64_t q_bs, int64_t q_ts, const void* k, int64_t k_bs, int64_t k_ts,
                                    const void* v, int64_t v_bs, int64_t v_ts, const void* o, const void* d_o, int64_t o_bs,
                                    int64_t o_ts, const float* lse, float* delta, void* dq, int64_t dq_bs, int64_t dq_ts,
@@ -60,11 +70,53 @@ extern "C" int vited_attention_bwd(const void* q, int64_t q_bs, int64_t q_ts, co
     int rc = check_common(a, dtype);
     if (rc != VITED_OK) return rc;
     if (!d_o || !delta || !dq || !dk || !dv) return VITED_ERR_BAD_ARG;
+    return bwd_dispatch(a, dtype, (hipStream_t)stream);
+}
+
+static int64_t elem_bytes(int dtype) { return dtype == VITED_BF16 ? 2 : 4; }
+
+extern "C" int64_t vited_attention_bwd_indexed_workspace_bytes(int dtype, int64_t batch, int heads, int64_t nk, int head_dim) {
+    if ((dtype != VITED_F32 && dtype != VITED_BF16) || batch <= 0 || heads <= 0 || nk <= 0 || head_dim <= 0) return -1;
+    return batch * nk * 2 * (int64_t)heads * head_dim * elem_bytes(dtype);
+}
+
+extern "C" int vited_attention_bwd_indexed(const void* q, int64_t q_bs, int64_t q_ts, const void* k, int64_t k_bs, int64_t k_ts,
+                                           const void* v, int64_t v_bs, int64_t v_ts, const int64_t* kv_index,
+                                           const int64_t* seg_order, const int64_t* seg_offsets, int64_t kv_items, const void* o,
+                                           const void* d_o, int64_t o_bs, int64_t o_ts, const float* lse, float* delta, void* dq,
+                                           int64_t dq_bs, int64_t dq_ts, void* dk, int64_t dk_bs, int64_t dk_ts, void* dv,
+                                           int64_t dv_bs, int64_t dv_ts, int dtype, int64_t batch, int heads, int64_t nq, int64_t nk,
+                                           int head_dim, float scale, void* workspace, int64_t workspace_bytes, void* stream) {
+    AttnArgs a = {};
+    a.q = q; a.k = k; a.v = v;
+    a.kv_index = kv_index;
+    a.q_bs = q_bs; a.q_ts = q_ts; a.k_bs = k_bs; a.k_ts = k_ts; a.v_bs = v_bs; a.v_ts = v_ts;
+    a.o = o; a.d_o = d_o; a.o_bs = o_bs; a.o_ts = o_ts;
+    a.lse = (float*)lse; a.delta = delta;
+    a.dq = dq; a.dq_bs = dq_bs; a.dq_ts = dq_ts;
+    a.batch = batch; a.heads = heads; a.nq = nq; a.nk = nk; a.head_dim = head_dim; a.scale = scale;
+    int rc = check_common(a, dtype);
+    if (rc != VITED_OK) return rc;
+    if (!d_o || !delta || !dq || !dk || !dv || !kv_index || !seg_order || !seg_offsets || !workspace) return VITED_ERR_BAD_ARG;
+    if (kv_items <= 0 || ((uintptr_t)workspace % 16) != 0) return VITED_ERR_BAD_ARG;
+    if (kv_items > 65535) return VITED_ERR_UNSUPPORTED;
+    if (workspace_bytes < vited_attention_bwd_indexed_workspace_bytes(dtype, batch, heads, nk, head_dim)) return VITED_ERR_WORKSPACE;
+    // the kernels of vited_attention_bwd write pair b's dK / dV term into the workspace, packed [batch][nk][dK | dV] like a kv
+    // projection, while they read k / v of item kv_index[b] ...
+    const int64_t width = (int64_t)heads * head_dim;
+    a.dk = workspace;
+    a.dv = (char*)workspace + width * elem_bytes(dtype);
+    a.dk_ts = a.dv_ts = 2 * width;
+    a.dk_bs = a.dv_bs = nk * 2 * width;
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == VITED_BF16 && attention_mfma_supported(a, true)) {
-        g_last_attn_path = 2;
-        return attention_bwd_mfma(a, s);
-    }
-    g_last_attn_path = 1;
-    return attention_bwd_portable(a, dtype, s);
+    rc = bwd_dispatch(a, dtype, s);
+    if (rc != VITED_OK) return rc;
+    // ... and the segmented sum adds the terms of every item's pairs in ascending pair order
+    SegSumArgs g = {};
+    g.ws = workspace;
+    g.out[0] = dk; g.out_bs[0] = dk_bs; g.out_ts[0] = dk_ts;
+    g.out[1] = dv; g.out_bs[1] = dv_bs; g.out_ts[1] = dv_ts;
+    g.order = seg_order; g.offsets = seg_offsets;
+    g.batch = batch; g.items = kv_items; g.nk = nk; g.width = (int)width;
+    return attention_segsum(g, dtype, s);
 }

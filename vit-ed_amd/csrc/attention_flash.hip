@@ -194,8 +194,9 @@ attn_bwd_dq_flash_kernel(AttnArgs a) {
     const int q0 = blockIdx.x * (64 * FL_W) + wave * (16 * FL_W);
     const int64_t hoff = (int64_t)h * HD;
     const bf16* qb = (const bf16*)a.q + b * a.q_bs + hoff;
-    const bf16* kb = (const bf16*)a.k + b * a.k_bs + hoff;
-    const bf16* vb = (const bf16*)a.v + b * a.v_bs + hoff;
+    const int64_t bkv = a.kv_index ? a.kv_index[b] : b;
+    const bf16* kb = (const bf16*)a.k + bkv * a.k_bs + hoff;
+    const bf16* vb = (const bf16*)a.v + bkv * a.v_bs + hoff;
     const bf16* ob = (const bf16*)a.o + b * a.o_bs + hoff;
     const bf16* dob = (const bf16*)a.d_o + b * a.o_bs + hoff;
     const float sc = a.scale * LOG2E;
@@ -335,8 +336,9 @@ attn_bwd_dkv_flash_kernel(AttnArgs a) {
     const int k0 = blockIdx.x * (64 * FL_W) + wave * (16 * FL_W);
     const int64_t hoff = (int64_t)h * HD;
     const bf16* qb = (const bf16*)a.q + b * a.q_bs + hoff;
-    const bf16* kb = (const bf16*)a.k + b * a.k_bs + hoff;
-    const bf16* vb = (const bf16*)a.v + b * a.v_bs + hoff;
+    const int64_t bkv = a.kv_index ? a.kv_index[b] : b;
+    const bf16* kb = (const bf16*)a.k + bkv * a.k_bs + hoff;
+    const bf16* vb = (const bf16*)a.v + bkv * a.v_bs + hoff;
     const bf16* dob = (const bf16*)a.d_o + b * a.o_bs + hoff;
     const float* lse_g = a.lse + (b * a.heads + h) * a.nq;
     const float* del_g = a.delta + (b * a.heads + h) * a.nq;

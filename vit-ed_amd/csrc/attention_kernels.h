@@ -4,7 +4,7 @@
 
 struct AttnArgs {
     const void *q, *k, *v;
-    const int64_t* kv_index;   // forward only, nullable: batch item b reads k / v of batch item kv_index[b]
+    const int64_t* kv_index;   // nullable: batch item b reads k / v of batch item kv_index[b] (dk / dv stay per batch item b)
     int64_t q_bs, q_ts, k_bs, k_ts, v_bs, v_ts;
     const void* o;    // forward: output (written); backward: saved output
     const void* d_o;  // backward only
@@ -30,6 +30,10 @@ int attention_bwd_mfma(const AttnArgs& a, hipStream_t s);
 // tiled online-softmax kernels for long sequences (attention_flash.hip)
 int attention_fwd_flash(const AttnArgs& a, hipStream_t s);
 int attention_bwd_flash(const AttnArgs& a, hipStream_t s);
+
+// per-pair dK / dV terms -> per-item sums, the reduction of vited_attention_bwd_indexed (attention_segsum.hip)
+struct SegSumArgs;
+int attention_segsum(const SegSumArgs& a, int dtype, hipStream_t s);
 
 // what vited_last_attention_path() reports, for dispatchers outside attention.hip (attention_cam.hip)
 void attention_set_last_path(int path);

@@ -171,8 +171,9 @@ attn_bwd_small_kernel(AttnArgs a) {
     const int nq = (int)a.nq, nk = (int)a.nk;
     const int64_t hoff = (int64_t)h * HD;
     const bf16* qb = (const bf16*)a.q + b * a.q_bs + hoff;
-    const bf16* kb = (const bf16*)a.k + b * a.k_bs + hoff;
-    const bf16* vb = (const bf16*)a.v + b * a.v_bs + hoff;
+    const int64_t bkv = a.kv_index ? a.kv_index[b] : b;
+    const bf16* kb = (const bf16*)a.k + bkv * a.k_bs + hoff;
+    const bf16* vb = (const bf16*)a.v + bkv * a.v_bs + hoff;
     const bf16* dob = (const bf16*)a.d_o + b * a.o_bs + hoff;
     // wave-private LDS: image slot 0 holds K during phase T and Q during phase N, slot 1 holds dO.  Two slots
     // instead of three is what lets a third workgroup fit on a CU; everything is written and read by the same

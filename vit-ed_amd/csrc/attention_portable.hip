@@ -96,8 +96,9 @@ attn_bwd_dq_portable_kernel(AttnArgs a) {
     const int h = blockIdx.y;
     const int64_t i = (int64_t)blockIdx.x * AP_THREADS + threadIdx.x;
     const bool live = i < a.nq;
-    const T* kb = (const T*)a.k + b * a.k_bs + (int64_t)h * HD;
-    const T* vb = (const T*)a.v + b * a.v_bs + (int64_t)h * HD;
+    const int64_t bkv = a.kv_index ? a.kv_index[b] : b;
+    const T* kb = (const T*)a.k + bkv * a.k_bs + (int64_t)h * HD;
+    const T* vb = (const T*)a.v + bkv * a.v_bs + (int64_t)h * HD;
     float qr[HD], dor[HD], dq[HD];
     float delta = 0.f, lse = 0.f;
 #pragma unroll
@@ -157,8 +158,9 @@ attn_bwd_dkv_portable_kernel(AttnArgs a) {
 #pragma unroll
     for (int d = 0; d < HD; ++d) { dk[d] = 0.f; dv[d] = 0.f; }
     if (live) {
-        load_row<T, HD>((const T*)a.k + b * a.k_bs + j * a.k_ts + (int64_t)h * HD, kr, a.scale);
-        load_row<T, HD>((const T*)a.v + b * a.v_bs + j * a.v_ts + (int64_t)h * HD, vr, 1.f);
+        const int64_t bkv = a.kv_index ? a.kv_index[b] : b;
+        load_row<T, HD>((const T*)a.k + bkv * a.k_bs + j * a.k_ts + (int64_t)h * HD, kr, a.scale);
+        load_row<T, HD>((const T*)a.v + bkv * a.v_bs + j * a.v_ts + (int64_t)h * HD, vr, 1.f);
     } else {
 #pragma unroll
         for (int d = 0; d < HD; ++d) { kr[d] = 0.f; vr[d] = 0.f; }

@@ -1108,18 +1108,24 @@ class MichiganDeviceLoader(HisfragDeviceLoader):
 # ---------------------------------------------------------------------------------------------
 # pair mining for the two-stage HisFrag training step (hisfrag.py:117-159)
 # ---------------------------------------------------------------------------------------------
-def mine_pairs(targets: torch.Tensor, neg_per_pos: float = 2.0, generator=None):
+def mine_pairs(targets: torch.Tensor, neg_per_pos: float = 2.0, generator=None, ordered_negatives: bool = False):
     """(groups int64 [P, 2], labels fp32 [P, 1]): every same-label pair (i, j), j > i, in row-major order, then a
     random subset of the different-label pairs of size min(#neg, int(neg_per_pos * #pos)) - what
     ``HisfragTrainer.prepare_data`` (hisfrag.py:117-145) builds with a Python loop over the batch and 2n
     ``nonzero`` host syncs.  Here: one ``triu_indices`` + two boolean selects on the device (the pair count is
-    data-dependent, so one host sync per step remains)."""
+    data-dependent, so one host sync per step remains).
+    ``ordered_negatives``: the negative candidates are ALL ordered pairs (i, j), i != j, with different labels, row-major
+    (michigan.py:142-148 scans the whole row, not its upper half); with ``neg_per_pos=1.0`` that is michigan's rule
+    (michigan.py:150).  The positives are the upper-triangle pairs either way."""
     t = targets.reshape(-1)
     n = t.numel()
     i, j = torch.triu_indices(n, n, offset=1, device=t.device)
     same = t[i] == t[j]
     pos = torch.stack([i[same], j[same]], dim=1)
-    neg = torch.stack([i[~same], j[~same]], dim=1)
+    if ordered_negatives:
+        neg = torch.nonzero(t.view(-1, 1) != t.view(1, -1))            # row-major: i outer, j ascending
+    else:
+        neg = torch.stack([i[~same], j[~same]], dim=1)
     keep = min(neg.shape[0], int(neg_per_pos * pos.shape[0]))
     perm = torch.randperm(neg.shape[0], generator=generator, device=neg.device if generator is None else generator.device)[:keep]
     neg = neg[perm.to(neg.device)]
@@ -1136,6 +1142,22 @@ def hisfrag_prepare_data(model, samples: torch.Tensor, targets: torch.Tensor, am
     with torch.autocast(samples.device.type, dtype=torch.bfloat16, enabled=amp):
         feats = model(samples, forward_first_part=True)
     return (samples[groups[:, 0]], feats[groups[:, 1]]), labels
+
+
+def hisfrag_prepare_indexed(model, samples: torch.Tensor, targets: torch.Tensor, amp: bool = True, generator=None, neg_per_pos: float = 2.0,
+                            ordered_negatives: bool = False):
+    """``hisfrag_prepare_data`` without its two gathers: returns ((samples, feats, x2_index, x1_index), labels) with
+    x2_index = groups[:, 0] (int64 [P]) and x1_index = ops.pair_segments(groups[:, 1], n) - what hisfrag.py:153-154 gathers - for
+    ``model(feats, samples, x2_index=x2_index, x1_index=x1_index)``.  The decoder then embeds image 2 through the index, projects
+    the cross-attention keys / values once per IMAGE and sums every image's key / value gradient over its pairs in a fixed order:
+    the step is bitwise reproducible, which the gathered form (an atomic scatter-add in ``feats[index]``'s backward) is not.
+    ``neg_per_pos`` / ``ordered_negatives``: ``mine_pairs``' rule (1.0 / True: michigan.py:150)."""
+    from . import ops
+    groups, labels = mine_pairs(targets, neg_per_pos=neg_per_pos, generator=generator, ordered_negatives=ordered_negatives)
+    with torch.autocast(samples.device.type, dtype=torch.bfloat16, enabled=amp):
+        feats = model(samples, forward_first_part=True)
+    x2_index = groups[:, 0].contiguous()
+    return (samples, feats, x2_index, ops.pair_segments(groups[:, 1], samples.shape[0])), labels
 
 
 # ---------------------------------------------------------------------------------------------

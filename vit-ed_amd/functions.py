@@ -722,11 +722,12 @@ def _cross_q(rt, xa, P, lnq=None):
     return ops.gemm(hq, rt.weight(P.wq), bias=P.bq), (hq, mq, rq)
 
 
-def _dec_cross_fwd(rt, xa, P, batch, lnq=None, q=None, kv3=None, ctxf=None, kv_index=None, key=None, fuse_ln=True, scale=None):
+def _dec_cross_fwd(rt, xa, P, batch, lnq=None, q=None, kv3=None, ctxf=None, kv_index=None, key=None, fuse_ln=True, scale=None, items=None):
     """Cross stage (:174-200, :270): xa [batch Nq, D] -> (xb = xa + proj(attention(q, k, v)), saved, ln2) with q from the image-2
     tokens (_cross_q, unless the pair cache hands ``q`` over) and k / v from the image-1 features: ``kv3`` [., N1, 2 D] when they
     were computed ahead for all blocks (_context_kv_folded, context_kv; with ``kv_index`` pair p reads kv3[kv_index[p]]), else
-    Linear_kv(norm_context(ctxf)) here.  ``fuse_ln``: the cross-proj kernel also produces ln2 = (h, mean, rstd) of norm2(xb)."""
+    Linear_kv(norm_context(ctxf)) here - on ``items`` feature maps (default: one per pair).  ``fuse_ln``: the cross-proj kernel also
+    produces ln2 = (h, mean, rstd) of norm2(xb)."""
     d, nq = rt.dim, xa.shape[0] // batch
     hq = mq = rq = hc = mc = rc = None
     if q is None:
@@ -735,7 +736,7 @@ def _dec_cross_fwd(rt, xa, P, batch, lnq=None, q=None, kv3=None, ctxf=None, kv_i
     if kv3 is None:
         hc, mc, rc = ops.layernorm_fwd(ctxf, P.gx, P.bx, LN_EPS, rt.act_dtype)
         kv = ops.gemm(hc, rt.weight(P.wkv), bias=P.bkv)              # [Mc, 2D], columns [2][h][hd] (:178)
-        kv3 = kv.view(batch, rt.n1, 2 * d)
+        kv3 = kv.view(batch if items is None else items, rt.n1, 2 * d)
     oc, lse_c = ops.attention_fwd(q.view(batch, nq, d), kv3[:, :, 0:d], kv3[:, :, d:2 * d], rt.heads, rt.scale, kv_index=kv_index)
     if rt.keep_attn and key is not None:
         _keep_attention(rt, key, q.view(batch, nq, d), kv3[:, :, 0:d])
@@ -744,11 +745,14 @@ def _dec_cross_fwd(rt, xa, P, batch, lnq=None, q=None, kv3=None, ctxf=None, kv_i
     return xb, (mq, rq, hq, mc, rc, hc, q, kv, oc, lse_c), ln2
 
 
-def _dec_cross_bwd(rt, dx, dx_lp, xa, P, saved, ctxf, dctx, batch, index, dkv3=None, lp_scale=None):
+def _dec_cross_bwd(rt, dx, dx_lp, xa, P, saved, ctxf, dctx, batch, index, dkv3=None, lp_scale=None, seg=None):
     """Backward of _dec_cross_fwd.  Returns (d xa fp32, its low-precision copy, d context (accumulated in place), the ten parameter
     gradients by field name).  When the keys / values came from _context_kv_folded, d(kv) is written into ``dkv3`` (this block's
-    view of the all-blocks tensor) and gx, bx, wkv, bkv stay None: _context_kv_folded_bwd fills them in after the last block."""
+    view of the all-blocks tensor) and gx, bx, wkv, bkv stay None: _context_kv_folded_bwd fills them in after the last block.
+    ``seg`` (ops.PairSegments): the keys / values are per IMAGE and pair p read item seg.index[p]; d(kv) is then per image too, each
+    item the sum of its pairs' terms (ops.attention_bwd(segments=...)), and so is everything that follows it."""
     d, nq = rt.dim, xa.shape[0] // batch
+    items = batch if seg is None else seg.items
     mq, rq, hq, mc, rc, hc, q, kv, oc, lse_c = saved
     doc, dwcp, dbcp = _linear_bwd(rt, dx_lp, oc, P.wcp, P.bcp)
     dq = torch.empty_like(q)
@@ -757,7 +761,7 @@ def _dec_cross_bwd(rt, dx, dx_lp, xa, P, saved, ctxf, dctx, batch, index, dkv3=N
         kv3, dkv = kv, dkv3                 # views of the all-blocks kv / d(kv) tensors
     else:
         dkv = torch.empty_like(kv)
-        kv3, dkv3 = kv.view(batch, rt.n1, 2 * d), dkv.view(batch, rt.n1, 2 * d)
+        kv3, dkv3 = kv.view(items, rt.n1, 2 * d), dkv.view(items, rt.n1, 2 * d)
     if rt.keep_attn:
         _keep_attention_grad(rt, ('cross_blocks', index, 'cross_attn'), doc.view(batch, nq, d), kv3[:, :, d:2 * d])
     if rt.keep_cam:
@@ -765,7 +769,7 @@ def _dec_cross_bwd(rt, dx, dx_lp, xa, P, saved, ctxf, dctx, batch, index, dkv3=N
                             doc.view(batch, nq, d), lse_c)
     ops.attention_bwd(q.view(batch, nq, d), kv3[:, :, 0:d], kv3[:, :, d:2 * d], oc.view(batch, nq, d),
                       doc.view(batch, nq, d), lse_c, rt.heads, rt.scale, dq.view(batch, nq, d), dkv3[:, :, 0:d],
-                      dkv3[:, :, d:2 * d])
+                      dkv3[:, :, d:2 * d], segments=seg)
     if rt.tap is not None:
         i = index
         rt.tap[f'dec.doc.{i}'], rt.tap[f'dec.dq.{i}'], rt.tap[f'dec.dkv.{i}'] = doc.clone(), dq.clone(), dkv.clone()
@@ -779,25 +783,28 @@ def _dec_cross_bwd(rt, dx, dx_lp, xa, P, saved, ctxf, dctx, batch, index, dkv3=N
     return dx, dx_lp, dctx, dict(gc=dgc, bc=dbc, gx=dgx, bx=dbx, wq=dwq, bq=dbq, wkv=dwkv, bkv=dbkv, wcp=dwcp, bcp=dbcp)
 
 
-def _dec_block_fwd(rt, x, ctxf, P, batch, n, grad, cls_only, index=0, ln1=None, next_ln=None, kv3=None, scales=(None, None, None)):
+def _dec_block_fwd(rt, x, ctxf, P, batch, n, grad, cls_only, index=0, ln1=None, next_ln=None, kv3=None, scales=(None, None, None),
+                   seg=None):
     """One CrossBlock forward of DecoderFn: self + cross + MLP stage, every following LayerNorm asked of the Linear before it
     (``next_ln`` = (gamma, beta) of the NEXT block's norm1).  ``scales``: the stochastic-depth scales of the (self, cross, mlp) branches,
-    each one value per row of its stage or None.  Returns (block output, tape entry | None, next block's ln1 | None)."""
+    each one value per row of its stage or None.  ``seg``: the context is per image, pair p attends over item seg.index[p].
+    Returns (block output, tape entry | None, next block's ln1 | None)."""
     xa, sa, lnq = _dec_self_fwd(rt, x, P, batch, n, cls_only, key=('cross_blocks', index, 'attn'), ln1=ln1, scale=scales[0])
     xb, sc, ln2 = _dec_cross_fwd(rt, xa, P, batch, lnq=lnq, kv3=kv3, ctxf=ctxf, key=('cross_blocks', index, 'cross_attn'),
-                                 fuse_ln=_hand_over_ln(rt, xa, P, grad or scales[2] is not None), scale=scales[1])
+                                 fuse_ln=_hand_over_ln(rt, xa, P, grad or scales[2] is not None), scale=scales[1],
+                                 kv_index=seg.index if seg is not None else None, items=seg.items if seg is not None else None)
     xc, sm, nxt = _mlp_fwd(rt, xb, P, grad, ln=ln2, next_ln=next_ln, scale=scales[2])
     return xc, ((x, sa, xa, sc, xb, sm) if grad else None), nxt
 
 
-def _dec_block_bwd(rt, dx, dx_lp, ctxf, dctx, P, entry, batch, n, cls_only, index, dkv3=None, lp_scales=(None, None, None)):
+def _dec_block_bwd(rt, dx, dx_lp, ctxf, dctx, P, entry, batch, n, cls_only, index, dkv3=None, lp_scales=(None, None, None), seg=None):
     """Backward of _dec_block_fwd.  dx / dx_lp: gradient w.r.t. the block's output (all rows, or the cls rows when cls_only).
     ``lp_scales``: the stochastic-depth scales carried by the low-precision copies that leave the MLP, cross and self stage - those
     of this block's cross branch, of its self branch and of the PREVIOUS block's MLP branch.
     Returns (d input fp32, its low-precision copy, d context (accumulated in place), the parameter gradients as a DecBlock)."""
     x, sa, xa, sc, xb, sm = entry
     dx, dx_lp, gm = _mlp_bwd(rt, dx, dx_lp, xb, P, sm, lp_scale=lp_scales[0])
-    dx, dx_lp, dctx, gc = _dec_cross_bwd(rt, dx, dx_lp, xa, P, sc, ctxf, dctx, batch, index, dkv3, lp_scale=lp_scales[1])
+    dx, dx_lp, dctx, gc = _dec_cross_bwd(rt, dx, dx_lp, xa, P, sc, ctxf, dctx, batch, index, dkv3, lp_scale=lp_scales[1], seg=seg)
     dx, dx_lp, ga = _dec_self_bwd(rt, dx, dx_lp, x, P, sa, batch, n, cls_only, key=('cross_blocks', index, 'attn'), lp_scale=lp_scales[2])
     return dx, dx_lp, dctx, DecBlock(**ga, **gc, **gm)
 
@@ -931,12 +938,22 @@ def _context_kv_folded_bwd(rt, dkv_all, ctxf, saved, bufs, blocks):
 
 class DecoderFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, rt: Runtime, feats, img2, img2_index, *params):
+    def forward(ctx, rt: Runtime, feats, img2, img2_index, img1_index, *params):
+        """``img2_index`` (int64 [P] | None): pair p embeds img2[img2_index[p]] (gathered inside the patch-embedding kernel).
+        ``img1_index`` (ops.PairSegments | None): ``feats`` holds one item per IMAGE and pair p attends over feats[index[p]]: norm_context
+        and the kv projections run once per image, the cross-attention reads them through the index, and the backward sums every
+        image's d(kv) over its pairs before the per-image kv / norm_context backward (hisfrag.py:117-159 without its two gathers)."""
         shared, blocks = split_params(params, DecShared, DecBlock)
         grad = any(ctx.needs_input_grad)
         x, patches, batch, n = _patch_tokens_fwd(rt, img2, shared, with_cls=True, batch_index=img2_index)
-        assert feats.shape == (batch, rt.n1, rt.dim), f'features {tuple(feats.shape)} do not match {batch} image-2 samples'
-        ctxf = feats.detach().contiguous().float().view(batch * rt.n1, rt.dim)
+        seg = img1_index
+        b1 = batch if seg is None else seg.items
+        if seg is not None:
+            if rt.keep_attn or rt.keep_cam:
+                raise NotImplementedError('the attention-map paths (keep_attn / keep_cam) take gathered features, not an image-1 index')
+            assert seg.index.numel() == batch, f'{seg.index.numel()} image-1 indices for {batch} image-2 samples'
+        assert feats.shape == (b1, rt.n1, rt.dim), f'features {tuple(feats.shape)} do not match {b1} context items'
+        ctxf = feats.detach().contiguous().float().view(b1 * rt.n1, rt.dim)
         tape = []
         d = rt.dim
         cls_tail = rt.cls_tail and rt.c_depth > 0 and not (rt.keep_attn or rt.keep_cam)    # the visualisation paths want every query row's map
@@ -948,8 +965,8 @@ class DecoderFn(torch.autograd.Function):
             kv_all, kv_saved, fold_bufs = _context_kv_folded(rt, ctxf, blocks)
         for i, P in enumerate(blocks):
             x, entry, ln1 = _dec_block_fwd(rt, x, ctxf, P, batch, n, grad, cls_tail and i == rt.c_depth - 1, index=i, ln1=ln1,
-                                           next_ln=_norm1_of(blocks, i + 1), kv3=kv_all[i].view(batch, rt.n1, 2 * d) if fold else None,
-                                           scales=drop.block(i) if drop is not None else (None, None, None))
+                                           next_ln=_norm1_of(blocks, i + 1), kv3=kv_all[i].view(b1, rt.n1, 2 * d) if fold else None,
+                                           scales=drop.block(i) if drop is not None else (None, None, None), seg=seg)
             if grad:
                 tape.append(entry)
             if rt.tap is not None:
@@ -964,6 +981,7 @@ class DecoderFn(torch.autograd.Function):
             ctx.feats_needs_grad = feats.requires_grad
             ctx.fold = (kv_all, kv_saved, fold_bufs) if fold else None
             ctx.drop = drop
+            ctx.seg = seg
         return logits
 
     @staticmethod
@@ -977,6 +995,8 @@ class DecoderFn(torch.autograd.Function):
         dy = ops.gemm(dl, wh_act, b_layout=B_KN)                         # [B, D]
         dwh, dbh = _weight_grads(rt, dl, y, shared.wh, shared.bh)
         drop, last = ctx.drop, len(blocks) - 1
+        seg = ctx.seg
+        b1 = batch if seg is None else seg.items
         scale_of = (lambda i, j: drop.get(i, j)) if drop is not None else (lambda i, j: None)
         # the low-precision copy that leaves the final norm feeds the last block's MLP branch: it carries that branch's scale, per
         # sample (the final norm runs on the cls rows)
@@ -1014,8 +1034,8 @@ class DecoderFn(torch.autograd.Function):
                     with dwg.block():
                         dx, dx_lp, dctx, gblocks[i] = _dec_block_bwd(rt, dx, dx_lp, ctx.ctxf, dctx, blocks[i], entry, batch, n,
                                                                      ctx.cls_tail and i == rt.c_depth - 1, i,
-                                                                     dkv3=dkv_all[i].view(batch, rt.n1, 2 * d) if dkv_all is not None else None,
-                                                                     lp_scales=(scale_of(i, 1), scale_of(i, 0), scale_of(i - 1, 2)))
+                                                                     dkv3=dkv_all[i].view(b1, rt.n1, 2 * d) if dkv_all is not None else None,
+                                                                     lp_scales=(scale_of(i, 1), scale_of(i, 0), scale_of(i - 1, 2)), seg=seg)
                     if rt.tap is not None:
                         rt.tap[f'dec.dx.{i}'] = dx.clone()      # gradient w.r.t. the INPUT of decoder block i
                         if dctx is not None:
@@ -1025,6 +1045,6 @@ class DecoderFn(torch.autograd.Function):
                 gblocks = [g._replace(**kv) for g, kv in zip(gblocks, kv_grads)]
                 ctx.fold = None
         gshared = DecShared(**_patch_tokens_bwd(rt, dx, ctx.patches, shared, with_cls=True, batch=batch), gN=dgN, bN=dbN, wh=dwh, bh=dbh)
-        dfeats = dctx.view(batch, rt.n1, d) if ctx.feats_needs_grad and dctx is not None else None
-        ctx.tape = ctx.patches = ctx.ctxf = ctx.final = ctx.drop = None
-        return (None, dfeats, None, None, *_cam_only(rt, flatten_params(gshared, gblocks)))
+        dfeats = dctx.view(b1, rt.n1, d) if ctx.feats_needs_grad and dctx is not None else None
+        ctx.tape = ctx.patches = ctx.ctxf = ctx.final = ctx.drop = ctx.seg = None
+        return (None, dfeats, None, None, None, *_cam_only(rt, flatten_params(gshared, gblocks)))

@@ -27,6 +27,7 @@ import torch
 import torch.nn as nn
 
 from . import functions as F_
+from . import ops
 from .functions import DEC_BLOCK_KEYS, DEC_SHARED_KEYS, ENC_BLOCK_KEYS, ENC_SHARED_KEYS, Runtime
 
 LN_EPS = F_.LN_EPS
@@ -356,23 +357,49 @@ class VisionTransformerCustom(nn.Module):
 
     supports_x2_index = True   # engine.pairwise_similarity gathers image-2 rows inside the patch-embed kernel
 
-    def _check_x2(self, x2, x2_index):
+    def _check_x2(self, x2, x2_index, indexed_features=False):
         """The checked index and the number of pairs of a decoder call."""
         self._check_images(x2)
         if x2_index is None:
             return None, x2.shape[0]
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            raise NotImplementedError('x2_index (gather-in-kernel) is an inference path: call it under torch.no_grad()')
+        if not indexed_features and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            raise NotImplementedError('x2_index (gather-in-kernel) without x1_index is an inference path: call it under torch.no_grad(), '
+                                      'or train on the pair-indexed form model(feats, x2, x2_index=j, x1_index=i)')
         x2_index = x2_index.to(device=x2.device, dtype=torch.int64).contiguous()
         return x2_index, x2_index.numel()
 
-    def forward_second_part_head(self, x1_feats, x2, x2_index=None, drop_path=None):
-        x2_index, pairs = self._check_x2(x2, x2_index)
-        return self._decode_head(x1_feats, x2, x2_index, self._resolve_drop_path(drop_path, None, pairs, x2.device))
+    supports_x1_index = True   # the pair-indexed two-stage step: engine.hisfrag_prepare_indexed
 
-    def _decode_head(self, x1_feats, x2, x2_index, drop):
+    def _check_x1(self, x1_feats, x1_index, pairs):
+        """The image-1 index of a decoder call as ``ops.PairSegments`` on the features' device (None stays None)."""
+        if x1_index is None:
+            return None
+        if self.keep_attn or self.keep_cam:
+            raise NotImplementedError('x1_index is a training / scoring path: the attention-map paths (keep_attn / keep_cam) take '
+                                      'gathered features, model(feats[i], x2[j])')
+        if x1_feats.dim() != 3:
+            raise ValueError(f'x1_index goes with per-image features [images, N1, D], got {tuple(x1_feats.shape)}')
+        if isinstance(x1_index, ops.PairSegments):
+            seg = x1_index.to(x1_feats.device)
+            if seg.items != x1_feats.shape[0]:
+                raise ValueError(f'x1_index groups {seg.items} items, the features hold {x1_feats.shape[0]}')
+        else:
+            seg = ops.pair_segments(x1_index.to(device=x1_feats.device), x1_feats.shape[0])
+        if seg.index.numel() != pairs:
+            raise ValueError(f'x1_index names {seg.index.numel()} pairs, the image-2 side {pairs}')
+        return seg
+
+    def forward_second_part_head(self, x1_feats, x2, x2_index=None, drop_path=None, x1_index=None):
+        """``x1_index`` (int64 [P] or ``ops.PairSegments``): ``x1_feats`` holds one item per IMAGE and pair p reads
+        x1_feats[x1_index[p]] - == self(x1_feats[x1_index], x2[x2_index]) (hisfrag.py:153-159) without the two gathers and with
+        norm_context + the kv projections once per image; under autograd and under no_grad.  Returns [P, C] logits."""
+        x2_index, pairs = self._check_x2(x2, x2_index, indexed_features=x1_index is not None)
+        x1_index = self._check_x1(x1_feats, x1_index, pairs)
+        return self._decode_head(x1_feats, x2, x2_index, self._resolve_drop_path(drop_path, None, pairs, x2.device), x1_index)
+
+    def _decode_head(self, x1_feats, x2, x2_index, drop, x1_index=None):
         """The decoder and head with what ``_resolve_drop_path`` returned."""
-        return self._run_fn(F_.DecoderFn, drop, x1_feats, x2, x2_index, *self._decoder_params())
+        return self._run_fn(F_.DecoderFn, drop, x1_feats, x2, x2_index, x1_index, *self._decoder_params())
 
     # -- pair-cached inference (engine.pairwise_similarity; SURVEY.md section 8(f) rank 2) ---------------------------------
     supports_pair_cache = True
@@ -397,7 +424,7 @@ class VisionTransformerCustom(nn.Module):
         i_idx = i_idx.to(device=dev, dtype=torch.int64).contiguous()
         return F_.decoder_cached(self.runtime(), tokens2, j_idx, kvs, i_idx, self._decoder_params(), q0)
 
-    def forward(self, x, x2=None, forward_first_part=False, x2_index=None, drop_path=None):
+    def forward(self, x, x2=None, forward_first_part=False, x2_index=None, drop_path=None, x1_index=None):
         """``drop_path``: explicit DropPathScales for this call (any mode; tests, reproducing a step).  None: training mode with a
         live ``drop_path_rate`` draws them for the batch of the call - the images of ``forward_first_part``, the pairs of
         ``(feats, x2)``, the B pairs of a one-shot call for both halves - and ``eval()`` or rate 0 runs without.  The scales used
@@ -405,7 +432,9 @@ class VisionTransformerCustom(nn.Module):
         if forward_first_part:
             return self.forward_first_part(x, drop_path)
         if x2 is not None:
-            return self.forward_second_part_head(x, x2, x2_index, drop_path)
+            return self.forward_second_part_head(x, x2, x2_index, drop_path, x1_index)
+        if x1_index is not None:
+            raise ValueError('x1_index belongs to the two-stage form model(feats, x2, x1_index=...)')
         if x.dim() != 5 or x.shape[1] != 2:
             raise AssertionError(f'expected stacked pairs [B, 2, C, S, S], got {tuple(x.shape)}')
         drop = self._resolve_drop_path(drop_path, x.shape[0], x.shape[0], x.device)

@@ -9,6 +9,7 @@ is hipGraph-capturable.
 from __future__ import annotations
 
 import ctypes as C
+from typing import NamedTuple
 
 import torch
 
@@ -753,13 +754,54 @@ def attention_fwd(q, k, v, heads: int, scale: float, kv_index=None):
     return o, lse
 
 
-def attention_bwd(q, k, v, o, do, lse, heads: int, scale: float, dq, dk, dv):
-    """Writes dq/dk/dv (pre-allocated, same strided conventions as q/k/v)."""
+class PairSegments(NamedTuple):
+    """The pairs of a pair batch grouped by the key/value item they read (``pair_segments``)."""
+    index: torch.Tensor      # int64 [P]: pair p reads item index[p]
+    order: torch.Tensor      # int64 [P]: the stable argsort of index - pair numbers grouped by item, ascending inside a group
+    offsets: torch.Tensor    # int64 [items + 1]: group g is order[offsets[g]:offsets[g + 1]]
+
+    @property
+    def items(self) -> int:
+        return self.offsets.numel() - 1
+
+    def to(self, device):
+        return self if self.index.device == torch.device(device) else PairSegments(*(t.to(device) for t in self))
+
+
+def pair_segments(index: torch.Tensor, items: int) -> PairSegments:
+    """Group the pairs of ``index`` (integers [P], pair p reads item index[p] of ``items``) for ``attention_bwd(segments=...)``.
+    Plain torch (stable argsort, counts, cumsum), on the index's device - CPU tensors too.  Raises ValueError for an index outside
+    [0, items): that check reads one flag back (one synchronisation on a GPU tensor), so that no bad index ever reaches a kernel."""
+    items = int(items)
+    if index.dim() != 1 or index.dtype.is_floating_point or index.dtype == torch.bool:
+        raise ValueError(f'pair_segments: expected a 1-D integer index, got {index.dtype} {tuple(index.shape)}')
+    if items < 0 or (items == 0 and index.numel()):
+        raise ValueError(f'pair_segments: {index.numel()} pairs over {items} items')
+    index = index.to(torch.int64).contiguous()
+    if index.numel() and bool(((index < 0) | (index >= items)).any()):
+        raise ValueError(f'pair_segments: index outside [0, {items}): min {int(index.min())}, max {int(index.max())}')
+    order = torch.argsort(index, stable=True)
+    offsets = torch.zeros(items + 1, dtype=torch.int64, device=index.device)
+    if items:
+        offsets[1:] = torch.cumsum(torch.bincount(index, minlength=items), 0)
+    return PairSegments(index, order, offsets)
+
+
+def attention_bwd(q, k, v, o, do, lse, heads: int, scale: float, dq, dk, dv, kv_index=None, segments=None):
+    """Writes dq/dk/dv (pre-allocated, same strided conventions as q/k/v).
+    With ``segments`` (a ``PairSegments``; or ``kv_index``, an integer [B] tensor it is then built from) batch item b read
+    k[index[b]] / v[index[b]] in the forward: k / v / dk / dv hold ``segments.items`` items, dq stays per pair and
+    dk[g] / dv[g] are the sums over the pairs of item g in ascending pair order - zeros for an item without pairs
+    (``vited_attention_bwd_indexed``: per-pair terms in the workspace, then a segmented sum; no atomics)."""
     _need_gpu(q, k, v, o, do, lse, dq, dk, dv)
     b, nq, d = q.shape
     nk = k.shape[1]
     hd = d // heads
     assert o.is_contiguous() and do.is_contiguous() and o.dtype == do.dtype == q.dtype
+    if segments is None and kv_index is not None:
+        segments = pair_segments(kv_index, k.shape[0])
+    if segments is not None:
+        return _attention_bwd_indexed(q, k, v, o, do, lse, heads, scale, dq, dk, dv, kv_index, segments)
     q_bs, q_ts = _head_view(q, heads, hd)
     k_bs, k_ts = _head_view(k, heads, hd)
     v_bs, v_ts = _head_view(v, heads, hd)
@@ -771,6 +813,39 @@ def attention_bwd(q, k, v, o, do, lse, heads: int, scale: float, dq, dk, dv):
               _ptr(q), q_bs, q_ts, _ptr(k), k_bs, k_ts, _ptr(v), v_bs, v_ts, _ptr(o), _ptr(do), nq * d, d, _ptr(lse), _ptr(delta),
               _ptr(dq), dq_bs, dq_ts, _ptr(dk), dk_bs, dk_ts, _ptr(dv), dv_bs, dv_ts, _code(q.dtype), b, heads, nq, nk, hd,
               float(scale), _stream())
+    return dq, dk, dv
+
+
+def _attention_bwd_indexed(q, k, v, o, do, lse, heads, scale, dq, dk, dv, kv_index, seg):
+    if not isinstance(seg, PairSegments):
+        raise TypeError(f'attention_bwd: segments must be a PairSegments (ops.pair_segments), got {type(seg).__name__}')
+    b, nq, d = q.shape
+    items, nk = k.shape[0], k.shape[1]
+    hd = d // heads
+    if kv_index is not None and kv_index is not seg.index and not torch.equal(kv_index.to(seg.index.device), seg.index):
+        raise ValueError('attention_bwd: kv_index and segments.index differ')
+    for name, t, size in (('index', seg.index, b), ('order', seg.order, b), ('offsets', seg.offsets, items + 1)):
+        if t.dtype != torch.int64 or t.dim() != 1 or t.numel() != size or not t.is_contiguous() or t.device != q.device:
+            raise ValueError(f'attention_bwd: segments.{name} must be a contiguous int64 [{size}] tensor on {q.device}, got {t.dtype} '
+                             f'{tuple(t.shape)} on {t.device} ({b} pairs over {items} key/value items)')
+    assert q.dtype == k.dtype == v.dtype == dq.dtype == dk.dtype == dv.dtype
+    assert k.shape == v.shape == dk.shape == dv.shape and k.shape[2] == d and dq.shape == q.shape
+    q_bs, q_ts = _head_view(q, heads, hd)
+    k_bs, k_ts = _head_view(k, heads, hd)
+    v_bs, v_ts = _head_view(v, heads, hd)
+    dq_bs, dq_ts = _head_view(dq, heads, hd)
+    dk_bs, dk_ts = _head_view(dk, heads, hd)
+    dv_bs, dv_ts = _head_view(dv, heads, hd)
+    delta = torch.empty((b, heads, nq), dtype=torch.float32, device=q.device)
+    nbytes = _lib.load().vited_attention_bwd_indexed_workspace_bytes(_code(q.dtype), b, heads, nk, hd)
+    if nbytes < 0:
+        raise ValueError(f'attention_bwd: empty operands (B {b}, heads {heads}, Nk {nk}, head_dim {hd})')
+    ws, ws_bytes = _scratch(nbytes + 16, q.device)
+    base = (ws + 15) // 16 * 16
+    _lib.call('vited_attention_bwd_indexed',
+              _ptr(q), q_bs, q_ts, _ptr(k), k_bs, k_ts, _ptr(v), v_bs, v_ts, _ptr(seg.index), _ptr(seg.order), _ptr(seg.offsets), items,
+              _ptr(o), _ptr(do), nq * d, d, _ptr(lse), _ptr(delta), _ptr(dq), dq_bs, dq_ts, _ptr(dk), dk_bs, dk_ts, _ptr(dv), dv_bs, dv_ts,
+              _code(q.dtype), b, heads, nq, nk, hd, float(scale), base, ws_bytes - (base - ws), _stream())
     return dq, dk, dv
 
 
