@@ -601,6 +601,30 @@ int vited_puzzle_best_slot(const float* mutual, int64_t n, const int* placed, co
 int vited_cls_metrics_update(const float* logits, int64_t ld_logits, const float* targets, int64_t ld_targets, int64_t batch,
                              int64_t classes, double* meters, double* last, int* bad, void* stream);
 
+/* ---- training: pair mining of the two-stage step on the device (hisfrag.py:117-145, michigan.py:120-150) ----------------------
+ * One launch of one workgroup, no host read, a fixed-shape result.  targets int64 [n] (any values); keys fp32 [n * n] in [0, 1),
+ * one per ordered cell c = i * n + j (i.i.d. uniform keys give the distribution of the reference's randperm subset).
+ *   positives   the cells with i < j and targets[i] == targets[j], in ascending cell order
+ *   candidates  the cells with different targets and i < j (ordered_negatives == 0, hisfrag.py:135) or i != j (!= 0,
+ *               michigan.py:142-148)
+ *   keep        min(#candidates, (int)(neg_per_pos * #positives)), the product formed in double and truncated; the kept negatives
+ *               are the `keep` candidates with the smallest (key, cell) - the key compared as a float, equal keys to the lower
+ *               cell - in that ascending order
+ * Rows: positives, kept negatives, padding up to `capacity`.  groups int64 [capacity, 2] = (i, j); labels fp32 [capacity] 1 / 0;
+ * weights fp32 [capacity] 1 for a pair, 0 for a padding row, which is pair (0, 0) with label 0.  When the pairs exceed capacity,
+ * negatives are dropped from the end first, then positives.  seg_index [capacity] = groups[:, 1]; seg_order [capacity] its stable
+ * grouping by item (ascending row number inside an item) and seg_offsets [n + 1] the group boundaries: the tables
+ * vited_attention_bwd_indexed takes, padding rows at the end of item 0's group.
+ * counts int32 [5]: positives found, candidates found, negatives emitted, pairs emitted, pairs dropped for lack of capacity.
+ * Every output element is written on every call (the outputs need not be initialised), by plain stores: no atomics on global
+ * memory, the same bits on every call.  All arrays are DEVICE memory.
+ * VITED_ERR_BAD_ARG: a null pointer, n <= 0, capacity <= 0.  VITED_ERR_UNSUPPORTED: n > vited_mine_pairs_max_images() (128), or
+ * capacity > 24576 (3 n (n - 1) / 2 + 1 at n = 128, rounded up to a multiple of 1024: the kernel keeps one byte of LDS per row). */
+int vited_mine_pairs_max_images(void);
+int vited_mine_pairs(const int64_t* targets, int n, const float* keys, double neg_per_pos, int ordered_negatives, int64_t capacity,
+                     int64_t* groups, float* labels, float* weights, int64_t* seg_index, int64_t* seg_order, int64_t* seg_offsets,
+                     int32_t* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

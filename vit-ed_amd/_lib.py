@@ -36,29 +36,31 @@ _C_SCALARS = {'int': C.c_int, 'int64_t': C.c_int64, 'float': C.c_float}
 _PROTOTYPE = re.compile(r'(\w[\w\s*]*?)\s*\b(vited_\w+)\s*\(([^)]*)\)\s*;')
 
 
-def _ctype(decl: str, where: str):
+def _ctype(decl: str, where: str, scalars: dict):
     """ctypes type of a C type of the header: every pointer is a c_void_p, the scalars map one to one."""
     if '*' in decl:
         return C.c_void_p
     try:
-        return _C_SCALARS[' '.join(decl.split())]
+        return scalars[' '.join(decl.split())]
     except KeyError:
         raise VitedLibraryError(f'include/vited.h: {where} has the C type {decl.strip()!r}, which the binding cannot express') from None
 
 
-def parse_signatures(text: str) -> dict:
-    """name -> (restype, argtypes) of every ``vited_*`` prototype in ``text`` (the source of include/vited.h)."""
+def parse_signatures(text: str, scalars: dict | None = None) -> dict:
+    """name -> (restype, argtypes) of every ``vited_*`` prototype in ``text`` (the source of include/vited.h).  ``scalars``: the
+    by-value C types accepted (default: ``int``, ``int64_t``, ``float``)."""
+    scalars = _C_SCALARS if scalars is None else scalars
     text = re.sub(r'/\*.*?\*/|//[^\n]*', ' ', text, flags=re.S)
     text = re.sub(r'^\s*#.*$', '', text, flags=re.M)
     sigs = {}
     for ret, name, params in _PROTOTYPE.findall(text):
         ret = ' '.join(ret.replace('*', ' *').split())
-        restype = C.c_char_p if ret == 'const char *' else _ctype(ret, f'the return of {name}')
+        restype = C.c_char_p if ret == 'const char *' else _ctype(ret, f'the return of {name}', scalars)
         argtypes = []
         if params.strip() != 'void':
             for i, param in enumerate(params.split(',')):
                 decl = re.sub(r'\b\w+\s*$', '', param)          # drop the parameter's name
-                argtypes.append(_ctype(decl, f'parameter {i} ({" ".join(param.split())}) of {name}'))
+                argtypes.append(_ctype(decl, f'parameter {i} ({" ".join(param.split())}) of {name}', scalars))
         sigs[name] = (restype, argtypes)
     missed = set(re.findall(r'\b(vited_\w+)\s*\(', text)) - set(sigs)
     if missed:
@@ -67,7 +69,8 @@ def parse_signatures(text: str) -> dict:
 
 
 # name -> (restype, argtypes), derived from include/vited.h: the header is the only statement of each signature
-SIGNATURES = parse_signatures(open(HEADER_PATH).read())
+# the header itself also passes one double by value (vited_mine_pairs' neg_per_pos: Python's float, undiminished)
+SIGNATURES = parse_signatures(open(HEADER_PATH).read(), {**_C_SCALARS, 'double': C.c_double})
 
 
 def load():

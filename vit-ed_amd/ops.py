@@ -787,6 +787,78 @@ def pair_segments(index: torch.Tensor, items: int) -> PairSegments:
     return PairSegments(index, order, offsets)
 
 
+MINE_MAX_CAPACITY = 24576      # vited_mine_pairs keeps one byte of LDS per output row (include/vited.h)
+
+
+def mine_pairs_max_images() -> int:
+    """The largest batch ``mine_pairs`` takes (128: its sort of the n * n cells lives in one workgroup's LDS)."""
+    return int(_lib.load().vited_mine_pairs_max_images())
+
+
+def _mine_pairs_args(targets, keys, neg_per_pos, capacity):
+    """The argument checks of ``mine_pairs`` (before any launch, also without a GPU).  Returns (n, neg_per_pos, capacity)."""
+    for name, t, dtype in (('targets', targets, torch.int64), ('keys', keys, torch.float32)):
+        if not torch.is_tensor(t) or t.dtype != dtype or t.dim() != 1:
+            raise ValueError(f'mine_pairs: {name} must be a 1-D {dtype} tensor, got '
+                             f'{(t.dtype, tuple(t.shape)) if torch.is_tensor(t) else type(t).__name__}')
+        if not t.is_contiguous():
+            raise ValueError(f'mine_pairs: {name} must be contiguous, got strides {t.stride()}')
+    n = targets.numel()
+    if n < 1:
+        raise ValueError('mine_pairs: no images')
+    if keys.numel() != n * n:
+        raise ValueError(f'mine_pairs: {keys.numel()} keys for {n} images, expected one per ordered cell: {n * n}')
+    if keys.device != targets.device:
+        raise ValueError(f'mine_pairs: keys on {keys.device}, targets on {targets.device}')
+    neg_per_pos, capacity = float(neg_per_pos), int(capacity)
+    if not 0.0 <= neg_per_pos < float('inf'):
+        raise ValueError(f'mine_pairs: neg_per_pos must be a finite number >= 0, got {neg_per_pos}')
+    if capacity < 1:
+        raise ValueError(f'mine_pairs: capacity must be at least 1, got {capacity}')
+    if not targets.is_cuda:
+        raise ValueError('mine_pairs: the kernel takes device tensors (engine.mine_pairs_device restates the rule for CPU tensors)')
+    if n > mine_pairs_max_images():
+        raise ValueError(f'mine_pairs: {n} images, the kernel takes at most {mine_pairs_max_images()}')
+    if capacity > MINE_MAX_CAPACITY:
+        raise ValueError(f'mine_pairs: capacity {capacity} above the {MINE_MAX_CAPACITY} rows the kernel supports')
+    return n, neg_per_pos, capacity
+
+
+def mine_pairs_out(targets, keys, neg_per_pos, ordered_negatives, groups, labels, weights, seg_index, seg_order, seg_offsets, counts):
+    """``mine_pairs`` into the caller's buffers (every element of every one is written): groups int64 [capacity, 2], labels /
+    weights fp32 [capacity, 1], seg_index / seg_order int64 [capacity], seg_offsets int64 [n + 1], counts int32 [5]."""
+    n, neg_per_pos, capacity = _mine_pairs_args(targets, keys, neg_per_pos, groups.shape[0] if torch.is_tensor(groups) and groups.dim() else 0)
+    for name, t, dtype, shape in (('groups', groups, torch.int64, (capacity, 2)), ('labels', labels, torch.float32, (capacity, 1)),
+                                  ('weights', weights, torch.float32, (capacity, 1)), ('seg_index', seg_index, torch.int64, (capacity,)),
+                                  ('seg_order', seg_order, torch.int64, (capacity,)), ('seg_offsets', seg_offsets, torch.int64, (n + 1,)),
+                                  ('counts', counts, torch.int32, (5,))):
+        if not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != targets.device:
+            raise ValueError(f'mine_pairs: {name} must be a contiguous {dtype} tensor of shape {shape} on {targets.device}')
+    _lib.call('vited_mine_pairs', _ptr(targets), n, _ptr(keys), neg_per_pos, int(bool(ordered_negatives)), capacity, _ptr(groups),
+              _ptr(labels), _ptr(weights), _ptr(seg_index), _ptr(seg_order), _ptr(seg_offsets), _ptr(counts), _stream())
+
+
+def mine_pairs(targets: torch.Tensor, keys: torch.Tensor, neg_per_pos: float, ordered_negatives: bool, capacity: int):
+    """Pair mining of the two-stage training step in one launch, without a host read (include/vited.h states the rule).
+
+    ``targets`` int64 [n] (n <= 128), ``keys`` fp32 [n * n] in [0, 1): one per ordered cell i * n + j.  Rows: every cell with i < j and
+    equal targets in ascending cell order, then the min(#candidates, int(neg_per_pos * #positives)) different-target candidates
+    (i < j, or i != j with ``ordered_negatives``) with the smallest (key, cell), then padding rows (0, 0) up to ``capacity``.
+    Returns (groups int64 [capacity, 2], labels fp32 [capacity, 1], weights fp32 [capacity, 1] - 1 for a pair, 0 for padding -,
+    ``PairSegments`` of groups[:, 1] over n items, counts int32 [5]: positives, candidates, negatives emitted, pairs emitted,
+    pairs dropped for lack of capacity).  Raises ValueError for a bad argument before anything is launched."""
+    n, neg_per_pos, capacity = _mine_pairs_args(targets, keys, neg_per_pos, capacity)
+    dev = targets.device
+    groups = torch.empty((capacity, 2), dtype=torch.int64, device=dev)
+    labels = torch.empty((capacity, 1), dtype=torch.float32, device=dev)
+    weights = torch.empty((capacity, 1), dtype=torch.float32, device=dev)
+    seg_index, seg_order = (torch.empty(capacity, dtype=torch.int64, device=dev) for _ in range(2))
+    seg_offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    counts = torch.empty(5, dtype=torch.int32, device=dev)
+    mine_pairs_out(targets, keys, neg_per_pos, ordered_negatives, groups, labels, weights, seg_index, seg_order, seg_offsets, counts)
+    return groups, labels, weights, PairSegments(seg_index, seg_order, seg_offsets), counts
+
+
 def attention_bwd(q, k, v, o, do, lse, heads: int, scale: float, dq, dk, dv, kv_index=None, segments=None):
     """Writes dq/dk/dv (pre-allocated, same strided conventions as q/k/v).
     With ``segments`` (a ``PairSegments``; or ``kv_index``, an integer [B] tensor it is then built from) batch item b read
