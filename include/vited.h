@@ -395,25 +395,41 @@ int vited_cross_block_fwd(const float* x, const float* context, float* y, int64_
 
 /* ---- optimizer step on the flat gradient buffer ----------------- */
 
-/* Gradient clip + AdamW + bf16 weight-shadow refresh + gradient zeroing in two launches; replaces
- * clip_grad_norm_ + optimizer.step() + zero_grad() of misc/utils.py:215-223 / misc/engine.py:231 and the
- * torch.optim.AdamW that misc/optimizer.py:25-27 builds (same update rule; parity in tests/test_gpu_optim.py).
+/* Gradient clip + AdamW + bf16 weight-shadow refresh + gradient zeroing in three launches (sum of squares, a one-workgroup
+ * decision, the update); replaces clip_grad_norm_ + optimizer.step() + zero_grad() of misc/utils.py:215-223 /
+ * misc/engine.py:231 and the torch.optim.AdamW that misc/optimizer.py:25-27 builds (same update rule; parity in
+ * tests/test_gpu_engine.py).
  *   desc        DEVICE array of count x 10 int64, one row per parameter:
  *               {p fp32 [rows, cols], g fp32 (its slice of grad_flat), exp_avg, exp_avg_sq, shadow bf16 [rows, cols] or 0,
  *                shadow_t bf16 [cols, rows] or 0, rows, cols, first_tile, group}
  *               first_tile = running sum of ceil(rows/64) * ceil(cols/64); total_tiles the sum over all rows.
  *   grad_flat   the contiguous fp32 gradient buffer every g points into (the L2 norm is taken over all of it)
- *   hyper       DEVICE fp32 array: [0] = number of updates done so far (the call increments it: bias correction uses
- *               the incremented value), [1..7] unused, then 8 floats per parameter group
- *               {lr, beta1, beta2, eps, weight_decay, 0, 0, 0} - device-resident so that a replayed hipGraph follows
- *               lr_scheduler.step_update (misc/engine.py:228)
+ *   hyper       DEVICE fp32 array: [0] = number of updates applied so far (an applied update increments it: bias correction
+ *               uses the incremented value), [1] = skip flag, [2] = number of updates skipped, [3..7] unused, then 8 floats
+ *               per parameter group {lr, beta1, beta2, eps, weight_decay, 0, 0, 0} - device-resident so that a replayed
+ *               hipGraph follows lr_scheduler.step_update (misc/engine.py:228)
  *   max_norm    clip_grad_norm_ threshold (<= 0: no clipping); norm_out (nullable) receives the pre-clip norm
  *   zero_grad   != 0: every g is zeroed after it was read
- *   workspace   >= vited_adamw_workspace_bytes() */
+ *   workspace   >= vited_adamw_workspace_bytes()
+ * Skipping (what GradScaler.step does for the reference, misc/utils.py:206-226): with hyper[1] != 0 and a pre-clip norm
+ * that is inf or NaN, p, the moments and the shadows keep their bits, g is still zeroed when zero_grad is set, hyper[0]
+ * stays, hyper[2] goes up by one and norm_out receives the non-finite norm.  With hyper[1] == 0 nothing is ever skipped (a
+ * non-finite gradient then reaches its parameter).  The norm is that of grad_flat as passed in, i.e. of the ALL-REDUCED buffer in a
+ * data-parallel run, so every rank takes the same decision.  On finite gradients the flag changes no bit of any output. */
 int64_t vited_adamw_workspace_bytes(void);
 int vited_adamw_step(const int64_t* desc, int count, int64_t total_tiles, const float* grad_flat, int64_t grad_numel,
                      float* hyper, float max_norm, int zero_grad, float* norm_out, float* workspace,
                      int64_t workspace_bytes, void* stream);
+
+/* torch.optim.SGD (dampening 0; misc/optimizer.py:22-24 builds it with nesterov=True) in place of AdamW: same arguments, same
+ * launches, same hyper header (skipping included), same workspace (vited_adamw_workspace_bytes).
+ *   desc row    {p, g, momentum_buffer (may be 0 when the group's momentum is 0), 0, shadow, shadow_t, rows, cols, first_tile, group}
+ *   group words {lr, momentum, nesterov (0 / 1), 0, weight_decay, 0, 0, 0}
+ *   per element g' = g * clip + weight_decay * p;  buf = momentum * buf + g';  p -= lr * (nesterov ? g' + momentum * buf : buf)
+ * A zero momentum buffer makes the first update torch's (buf = g'); with momentum == 0 buf is neither read nor written. */
+int vited_sgd_step(const int64_t* desc, int count, int64_t total_tiles, const float* grad_flat, int64_t grad_numel,
+                   float* hyper, float max_norm, int zero_grad, float* norm_out, float* workspace,
+                   int64_t workspace_bytes, void* stream);
 
 /* ---- attention core (F.scaled_dot_product_attention, vision_transformer.py:63-66,183-186) ----- */
 

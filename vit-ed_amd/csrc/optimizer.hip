@@ -1,26 +1,39 @@
-// Fused gradient clip + AdamW + bf16 weight-shadow refresh + gradient zeroing on the flat gradient buffer
-// (replaces clip_grad_norm_ + torch.optim.AdamW.step + vited_cast_weights + zero_grad:
-// misc/utils.py:215-223, misc/optimizer.py:25-46, misc/engine.py:231).
+// Fused gradient clip + optimizer update + bf16 weight-shadow refresh + gradient zeroing on the flat gradient buffer, for AdamW
+// (vited_adamw_step) and Nesterov / momentum SGD (vited_sgd_step)
+// (replaces clip_grad_norm_ + torch.optim.AdamW.step / SGD.step + vited_cast_weights + zero_grad:
+// misc/utils.py:215-223, misc/optimizer.py:22-46, misc/engine.py:231).
 //
-//   launch 1  adamw_sumsq_kernel : partial[b] = sum of squares of a slice of the flat gradient (fixed slices and a
-//                                  fixed reduction order: deterministic); block 0 also advances the step counter.
-//   launch 2  adamw_update_kernel: one workgroup per 64 x 64 tile of one parameter (device descriptor table, as
-//                                  vited_cast_weights).  Every workgroup re-reduces the partials in the same order, so
-//                                  all of them see the same norm and clip coefficient; then per element
+//   launch 1  optim_sumsq_kernel : partial[b] = sum of squares of a slice of the flat gradient (fixed slices and a
+//                                  fixed reduction order: deterministic).
+//   launch 2  optim_decide_kernel: ONE workgroup reduces the partials (thread x adds partials x, x + 256, x + 512, x + 768, then
+//                                  the block sum), takes the norm and the clip coefficient, decides whether the update is
+//                                  applied (hyper[1] set and a non-finite norm: skipped), advances hyper[0] or hyper[2] and leaves
+//                                  {norm, clip, applied, step count} behind the partials.  Both counters are written here and
+//                                  read by the NEXT launch only, never by another workgroup of the same one.
+//   launch 3  optim_update_kernel: one workgroup per 64 x 64 tile of one parameter (device descriptor table, as
+//                                  vited_cast_weights).  Per element (optim_update.h)
 //                                      g' = g * min(1, max_norm / (norm + 1e-6))
+//                                    AdamW
 //                                      p  = p * (1 - lr * wd);  m = lerp(m, g', 1 - b1);  v = b2 * v + (1 - b2) * g'^2
 //                                      p -= (lr / (1 - b1^t)) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
-//                                  (torch.optim.AdamW's update), the new p is also written to its bf16 [rows, cols] shadow
-//                                  and, through an LDS tile, to the transposed bf16 [cols, rows] shadow, and g is zeroed.
-// HBM traffic per element: 16 B read (g, p, m, v) + 16 B written (g, p, m, v) + 4 B of shadows = the floor for this update.
+//                                    SGD
+//                                      g' += wd * p;  buf = momentum * buf + g';  p -= lr * (nesterov ? g' + momentum * buf : buf)
+//                                  (torch.optim.AdamW's / SGD's update), the new p is also written to its bf16 [rows, cols] shadow
+//                                  and, through an LDS tile, to the transposed bf16 [cols, rows] shadow, and g is zeroed.  A skipped
+//                                  update zeroes g and touches nothing else.
+// HBM traffic per element: AdamW 16 B read (g, p, m, v) + 16 B written + 4 B of shadows, SGD 12 B read (g, p, buf) + 12 B written
+// + 4 B of shadows (8 + 8 + 4 without momentum) = the floor for these updates.
 // All hyper-parameters that change between steps (learning rate per group, step count) live in a device array, so a
-// hipGraph replay of the two launches follows the scheduler.
+// hipGraph replay of the launches follows the scheduler.
 #include "common.h"
+#include "optim_update.h"
 
 #define AD_DESC_WORDS 10   // {p, g, m, v, shadow, shadow_t, rows, cols, first_tile, group}
-#define AD_HYPER_HEADER 8  // hyper[0] = step count (float), [1..7] reserved; then 8 floats per group
-#define AD_GROUP_WORDS 8   // {lr, beta1, beta2, eps, weight_decay, -, -, -}
+#define AD_HYPER_HEADER 8  // hyper[0] = updates applied (float), [1] = skip-non-finite flag, [2] = updates skipped, [3..7] reserved; then 8 floats per group
+#define AD_GROUP_WORDS 8   // AdamW {lr, beta1, beta2, eps, weight_decay, -, -, -}; SGD {lr, momentum, nesterov, -, weight_decay, -, -, -}
 #define AD_PARTIALS 1024
+#define AD_RESULT_WORDS 4  // behind the partials: {norm, clip, applied, step count}
+enum { OPT_ADAMW = 0, OPT_SGD = 1 };
 
 __device__ __forceinline__ float block_sum_256(float v, float* red) {
     v = wave_sum(v);
@@ -33,7 +46,7 @@ __device__ __forceinline__ float block_sum_256(float v, float* red) {
 }
 
 __global__ void __launch_bounds__(256)
-adamw_sumsq_kernel(const float* __restrict__ g, int64_t n, float* __restrict__ partials, float* __restrict__ hyper) {
+optim_sumsq_kernel(const float* __restrict__ g, int64_t n, float* __restrict__ partials) {
     __shared__ float red[4];
     // fixed contiguous slice per block, so the sum does not depend on the launch
     const int64_t per = ((n + AD_PARTIALS - 1) / AD_PARTIALS + 3) & ~(int64_t)3;
@@ -55,28 +68,30 @@ adamw_sumsq_kernel(const float* __restrict__ g, int64_t n, float* __restrict__ p
         for (int64_t i = lo + threadIdx.x; i < hi; i += 256) s += g[i] * g[i];
     }
     s = block_sum_256(s, red);
-    if (threadIdx.x == 0) {
-        partials[blockIdx.x] = s;
-        if (blockIdx.x == 0) hyper[0] += 1.0f;   // step count t of this update (read by launch 2, which runs after this kernel)
-    }
+    if (threadIdx.x == 0) partials[blockIdx.x] = s;
 }
 
 __global__ void __launch_bounds__(256)
-adamw_update_kernel(const int64_t* __restrict__ desc, int count, const float* __restrict__ partials,
-                    const float* __restrict__ hyper, float max_norm, int zero_grad, float* __restrict__ norm_out) {
-    __shared__ bf16 tile[64][66];
+optim_decide_kernel(float* __restrict__ ws, float* __restrict__ hyper, float max_norm, float* __restrict__ norm_out) {
     __shared__ float red[4];
-    // ---- the same norm in every workgroup (same partials, same order)
     float s = 0.f;
 #pragma unroll
-    for (int i = 0; i < AD_PARTIALS / 256; ++i) s += partials[threadIdx.x + 256 * i];
+    for (int i = 0; i < AD_PARTIALS / 256; ++i) s += ws[threadIdx.x + 256 * i];
     const float norm = sqrtf(block_sum_256(s, red));
-    float clip = 1.0f;
-    if (max_norm > 0.f) {
-        clip = max_norm / (norm + 1e-6f);
-        clip = clip < 1.0f ? clip : 1.0f;
+    if (threadIdx.x == 0) {
+        optim_decide(norm, max_norm, hyper, ws + AD_PARTIALS);
+        if (norm_out) *norm_out = norm;
     }
-    if (blockIdx.x == 0 && threadIdx.x == 0 && norm_out) *norm_out = norm;
+}
+
+template <int OPT>
+__global__ void __launch_bounds__(256)
+optim_update_kernel(const int64_t* __restrict__ desc, int count, const float* __restrict__ res,
+                    const float* __restrict__ hyper, int zero_grad) {
+    __shared__ bf16 tile[64][66];
+    const float clip = res[1], step = res[3];
+    const bool applied = res[2] != 0.f;         // the same word in every workgroup
+    if (!applied && !zero_grad) return;
 
     const int64_t blk = blockIdx.x;
     int lo = 0, hi = count - 1;     // last descriptor whose first_tile <= blk
@@ -85,62 +100,46 @@ adamw_update_kernel(const int64_t* __restrict__ desc, int count, const float* __
         if (desc[(int64_t)mid * AD_DESC_WORDS + 8] <= blk) lo = mid; else hi = mid - 1;
     }
     const int64_t* d = desc + (int64_t)lo * AD_DESC_WORDS;
-    float* __restrict__ p = (float*)d[0];
-    float* __restrict__ g = (float*)d[1];
-    float* __restrict__ m = (float*)d[2];
-    float* __restrict__ v = (float*)d[3];
+    float* p = (float*)d[0];
+    float* g = (float*)d[1];
+    float* m = (float*)d[2];                    // SGD: the momentum buffer
+    float* v = (float*)d[3];                    // SGD: unused (0)
     bf16* __restrict__ dst = (bf16*)d[4];
     bf16* __restrict__ dst_t = (bf16*)d[5];
     const int64_t rows = d[6], cols = d[7];
     const float* hg = hyper + AD_HYPER_HEADER + d[9] * AD_GROUP_WORDS;
-    const float step = hyper[0];
-    const float lr = hg[0], b1 = hg[1], b2 = hg[2], eps = hg[3], wd = hg[4];
-    const float bc1 = 1.0f - powf(b1, step), bc2 = 1.0f - powf(b2, step);
-    const float step_size = lr / bc1, inv_sqrt_bc2 = 1.0f / sqrtf(bc2), decay = 1.0f - lr * wd;
+    AdamWCoef ka = {};
+    SgdCoef ks = {};
+    if constexpr (OPT == OPT_ADAMW) ka = adamw_coef(hg, step);
+    else ks = sgd_coef(hg);
 
     const int64_t t = blk - d[8], tiles_c = (cols + 63) >> 6;
     const int64_t r0 = (t / tiles_c) << 6, c0 = (t % tiles_c) << 6;
     const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;   // 16 x 16: 4 columns x 4 rows per thread
-    const bool vec = (cols & 3) == 0 && (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0;
+    uintptr_t ptrs = (uintptr_t)p | (uintptr_t)g;
+    if constexpr (OPT == OPT_ADAMW) ptrs |= (uintptr_t)m | (uintptr_t)v;
+    else if (ks.momentum != 0.f) ptrs |= (uintptr_t)m;
+    const bool vec = (cols & 3) == 0 && (ptrs & 15) == 0;
+    if (!applied) {                             // skipped update: zero the gradient tile, leave p, the state and the shadows alone
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int64_t r = r0 + ty + 16 * j, c = c0 + tx * 4;
+            if (r < rows && c < cols) {
+                const int n = cols - c < 4 ? (int)(cols - c) : 4;
+                skipped_piece(g, r * cols + c, n, vec && n == 4, zero_grad);
+            }
+        }
+        return;
+    }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int lr_ = ty + 16 * j;
         const int64_t r = r0 + lr_, c = c0 + tx * 4;
         float pn[4] = {0.f, 0.f, 0.f, 0.f};
         if (r < rows && c < cols) {
-            const int64_t o = r * cols + c;
-            const bool full = vec && c + 3 < cols;
-            float gv[4], pv[4], mv[4], vv[4];
-            if (full) {
-                const f32x4 qg = *(const f32x4*)(g + o), qp = *(const f32x4*)(p + o), qm = *(const f32x4*)(m + o), qv = *(const f32x4*)(v + o);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { gv[e] = qg[e]; pv[e] = qp[e]; mv[e] = qm[e]; vv[e] = qv[e]; }
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const bool in = c + e < cols;
-                    gv[e] = in ? g[o + e] : 0.f; pv[e] = in ? p[o + e] : 0.f; mv[e] = in ? m[o + e] : 0.f; vv[e] = in ? v[o + e] : 0.f;
-                }
-            }
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float ge = gv[e] * clip;
-                const float pe = pv[e] * decay;
-                mv[e] = mv[e] + (ge - mv[e]) * (1.0f - b1);
-                vv[e] = vv[e] * b2 + (1.0f - b2) * ge * ge;
-                const float denom = sqrtf(vv[e]) * inv_sqrt_bc2 + eps;
-                pn[e] = pe - step_size * (mv[e] / denom);
-            }
-            if (full) {
-                *(f32x4*)(p + o) = f32x4{pn[0], pn[1], pn[2], pn[3]};
-                *(f32x4*)(m + o) = f32x4{mv[0], mv[1], mv[2], mv[3]};
-                *(f32x4*)(v + o) = f32x4{vv[0], vv[1], vv[2], vv[3]};
-                if (zero_grad) *(f32x4*)(g + o) = f32x4{0.f, 0.f, 0.f, 0.f};
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    if (c + e < cols) { p[o + e] = pn[e]; m[o + e] = mv[e]; v[o + e] = vv[e]; if (zero_grad) g[o + e] = 0.f; }
-            }
+            const int n = cols - c < 4 ? (int)(cols - c) : 4;
+            if constexpr (OPT == OPT_ADAMW) adamw_piece(p, g, m, v, r * cols + c, n, vec && n == 4, ka, clip, zero_grad, pn);
+            else sgd_piece(p, g, m, r * cols + c, n, vec && n == 4, ks, clip, zero_grad, pn);
         }
         if (!dst && !dst_t) continue;
         bf16 b[4];
@@ -173,17 +172,32 @@ adamw_update_kernel(const int64_t* __restrict__ desc, int count, const float* __
     }
 }
 
-extern "C" int64_t vited_adamw_workspace_bytes(void) { return (int64_t)AD_PARTIALS * sizeof(float); }
+extern "C" int64_t vited_adamw_workspace_bytes(void) { return (int64_t)(AD_PARTIALS + AD_RESULT_WORDS) * sizeof(float); }
 
-extern "C" int vited_adamw_step(const int64_t* desc, int count, int64_t total_tiles, const float* grad_flat, int64_t grad_numel,
-                                float* hyper, float max_norm, int zero_grad, float* norm_out, float* workspace,
-                                int64_t workspace_bytes, void* stream) {
+template <int OPT>
+static int optim_step(const int64_t* desc, int count, int64_t total_tiles, const float* grad_flat, int64_t grad_numel, float* hyper,
+                      float max_norm, int zero_grad, float* norm_out, float* workspace, int64_t workspace_bytes, void* stream) {
     if (!desc || !grad_flat || !hyper || !workspace || count <= 0 || grad_numel <= 0 || total_tiles <= 0 || total_tiles > 0x7fffffff)
         return VITED_ERR_BAD_ARG;
     if (workspace_bytes < vited_adamw_workspace_bytes()) return VITED_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(adamw_sumsq_kernel, dim3(AD_PARTIALS), dim3(256), 0, s, grad_flat, grad_numel, workspace, hyper);
-    hipLaunchKernelGGL(adamw_update_kernel, dim3((unsigned)total_tiles), dim3(256), 0, s, desc, count, workspace, hyper, max_norm,
-                       zero_grad, norm_out);
+    hipLaunchKernelGGL(optim_sumsq_kernel, dim3(AD_PARTIALS), dim3(256), 0, s, grad_flat, grad_numel, workspace);
+    hipLaunchKernelGGL(optim_decide_kernel, dim3(1), dim3(256), 0, s, workspace, hyper, max_norm, norm_out);
+    hipLaunchKernelGGL(optim_update_kernel<OPT>, dim3((unsigned)total_tiles), dim3(256), 0, s, desc, count, workspace + AD_PARTIALS,
+                       hyper, zero_grad);
     return vited_check_launch();
+}
+
+extern "C" int vited_adamw_step(const int64_t* desc, int count, int64_t total_tiles, const float* grad_flat, int64_t grad_numel,
+                                float* hyper, float max_norm, int zero_grad, float* norm_out, float* workspace,
+                                int64_t workspace_bytes, void* stream) {
+    return optim_step<OPT_ADAMW>(desc, count, total_tiles, grad_flat, grad_numel, hyper, max_norm, zero_grad, norm_out, workspace,
+                                 workspace_bytes, stream);
+}
+
+extern "C" int vited_sgd_step(const int64_t* desc, int count, int64_t total_tiles, const float* grad_flat, int64_t grad_numel,
+                              float* hyper, float max_norm, int zero_grad, float* norm_out, float* workspace,
+                              int64_t workspace_bytes, void* stream) {
+    return optim_step<OPT_SGD>(desc, count, total_tiles, grad_flat, grad_numel, hyper, max_norm, zero_grad, norm_out, workspace,
+                               workspace_bytes, stream);
 }

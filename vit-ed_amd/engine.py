@@ -194,29 +194,39 @@ def param_groups_no_decay_1d(model):
     return [{'params': decay}, {'params': no_decay, 'weight_decay': 0.}]
 
 
-def build_optimizer(config, model, capturable: bool = False, fused_hip: bool | None = None):
-    """misc/optimizer.py:10-46: AdamW / SGD with the no-decay group for 1-D parameters and ``*.bias``.
+def build_optimizer(config, model, capturable: bool = False, fused_hip: bool | None = None, skip_nonfinite: bool = False):
+    """misc/optimizer.py:10-46: AdamW / Nesterov SGD with the no-decay group for 1-D parameters and ``*.bias``.
 
-    On a GPU model AdamW is ``optim.FlatAdamW`` (the HIP multi-tensor kernel: clip + AdamW + bf16 weight-shadow
-    refresh in one pass, hipGraph-replayable with a per-iteration learning rate); ``fused_hip=False`` gives
-    ``torch.optim.AdamW(fused=True)`` instead, with ``capturable`` forwarded (a torch optimizer captured into a
-    hipGraph must be built with capturable=True, and TrainStep keeps its learning rate in a device tensor)."""
+    On a GPU model they are ``optim.FlatAdamW`` / ``optim.FlatSGD`` (the HIP multi-tensor kernels: clip + update + bf16
+    weight-shadow refresh in one pass, hipGraph-replayable with a per-iteration learning rate); ``fused_hip=False`` gives
+    ``torch.optim.AdamW(fused=True)`` / ``torch.optim.SGD`` instead, with ``capturable`` forwarded to AdamW (a torch optimizer
+    captured into a hipGraph must be built with capturable=True, and TrainStep keeps its learning rate in a device tensor).
+    ``skip_nonfinite=True`` (HIP optimizers only) leaves out an update whose gradient norm is inf or NaN, which is what
+    ``GradScaler.step`` does in the reference's loop (misc/utils.py:206-226)."""
     name = config.TRAIN.OPTIMIZER.NAME.lower()
     groups = param_groups_no_decay_1d(model)
     on_gpu = all(p.is_cuda for g in groups for p in g['params'])
+    hip = on_gpu and (fused_hip is None or fused_hip)
+    if name not in ('adamw', 'sgd'):
+        raise ValueError(f'unknown optimizer {name}')
+    if skip_nonfinite and not hip:
+        raise ValueError('skip_nonfinite=True needs the HIP optimizers (a GPU model and fused_hip in (None, True)): the torch '
+                         'optimizers have no such check')
     if name == 'adamw':
         kw = dict(eps=config.TRAIN.OPTIMIZER.EPS, betas=tuple(config.TRAIN.OPTIMIZER.BETAS), lr=config.TRAIN.BASE_LR,
                   weight_decay=config.TRAIN.WEIGHT_DECAY)
-        if on_gpu and (fused_hip is None or fused_hip):
+        if hip:
             from .optim import FlatAdamW
-            return FlatAdamW(groups, model=model, **kw)     # the model's bf16 weight shadows are refreshed by the update kernel
+            # the model's bf16 weight shadows are refreshed by the update kernel
+            return FlatAdamW(groups, model=model, skip_nonfinite=skip_nonfinite, **kw)
         if on_gpu:
             return torch.optim.AdamW(groups, fused=True, capturable=capturable, **kw)
         return torch.optim.AdamW(groups, **kw)
-    if name == 'sgd':
-        return torch.optim.SGD(groups, momentum=config.TRAIN.OPTIMIZER.MOMENTUM, nesterov=True, lr=config.TRAIN.BASE_LR,
-                               weight_decay=config.TRAIN.WEIGHT_DECAY)
-    raise ValueError(f'unknown optimizer {name}')
+    kw = dict(momentum=config.TRAIN.OPTIMIZER.MOMENTUM, nesterov=True, lr=config.TRAIN.BASE_LR, weight_decay=config.TRAIN.WEIGHT_DECAY)
+    if hip:
+        from .optim import FlatSGD
+        return FlatSGD(groups, model=model, skip_nonfinite=skip_nonfinite, **kw)
+    return torch.optim.SGD(groups, **kw)
 
 
 class NativeScalerWithGradNormCount:
@@ -279,6 +289,62 @@ def _decoder_only_parameters(model):
 _CAPTURE_MODE = 'thread_local'
 
 
+class TrainMeters:
+    """The meters of the reference's training loop (misc/engine.py:195-196, 221-222, 235, 256-257) in fp64 accumulators on the
+    device, so that keeping them costs no host read per iteration:
+      loss       ``loss_meter.update(loss * accumulation_steps, n)`` per micro-step (``loss`` is the divided loss TrainStep returns)
+      grad_norm  ``norm_meter.update(grad_norm)`` per update
+      nonfinite  how many of those norms were inf or NaN (each of them also makes ``grad_norm.avg`` non-finite, as it does in the
+                 reference's log line)
+    The arithmetic is AverageMeter's, operation for operation, in fp64.  Elementwise torch operations on ``device``: they run
+    eagerly or inside a captured graph alike."""
+
+    def __init__(self, device='cuda', accumulation_steps: int = 1):
+        self.accum = max(int(accumulation_steps), 1)
+        # loss: val, sum, count; grad_norm: val, sum, count; non-finite norms
+        self.state = torch.zeros(7, dtype=torch.float64, device=torch.device(device))
+
+    def reset(self):
+        """Start an epoch."""
+        self.state.zero_()
+
+    @torch.no_grad()
+    def update_loss(self, loss: torch.Tensor, n):
+        """``n``: the number of target rows, a Python number or a device scalar (``MinedPairs.counts[3]``)."""
+        v = loss.detach().to(torch.float64)
+        if self.accum > 1:
+            v = v * self.accum
+        n = n.to(torch.float64) if torch.is_tensor(n) else float(n)
+        self.state[0].copy_(v)
+        self.state[1].add_(v * n)
+        self.state[2].add_(n)
+
+    @torch.no_grad()
+    def update_norm(self, norm: torch.Tensor):
+        v = norm.detach().to(torch.float64)
+        self.state[3].copy_(v)
+        self.state[4].add_(v)
+        self.state[5].add_(1.0)
+        self.state[6].add_((~torch.isfinite(v)).to(torch.float64))
+
+    def values(self) -> dict:
+        """{'loss': MeterValue(val, avg), 'grad_norm': MeterValue(val, avg), 'nonfinite': int} of this rank: one host copy."""
+        h = self.state.tolist()
+        return {'loss': MeterValue(h[0], h[1] / h[2] if h[2] else 0.0), 'grad_norm': MeterValue(h[3], h[4] / h[5] if h[5] else 0.0),
+                'nonfinite': int(h[6])}
+
+    def all_reduce(self, group=None) -> float:
+        """``AverageMeter.all_reduce`` of the loss meter (misc/utils.py:293-303): an fp32 [sum, count] SUM all-reduce (the rounding
+        to fp32 happens at world size 1 too, as it does there); returns the average ``train_one_epoch`` returns."""
+        total = self.state[1:3].to(torch.float32)
+        if dist.is_available() and dist.is_initialized():
+            dist.all_reduce(total, op=dist.ReduceOp.SUM, group=group)
+        s, count = total.tolist()
+        if not count:
+            raise ValueError('no training step was metered before all_reduce')
+        return s / count
+
+
 class TrainStep:
     """forward (autocast) -> BCE-with-logits / accumulation_steps -> backward -> flat all-reduce -> clip 5.0 ->
     optimizer step -> lr_scheduler.step_update -> zero   (misc/engine.py:202-231).
@@ -290,6 +356,11 @@ class TrainStep:
       backward still runs (``overlap=True``; needs a model with the reference's 3-way forward), the rest
       after it.  The backward is driven in two stages for that: decoder + head first, then the encoder from
       the gradient of the features.
+    * ``num_updates`` (the index handed to ``lr_scheduler.step_update``) counts iterations, whether or not an optimizer built
+      with ``skip_nonfinite=True`` left an update out - the reference's index does the same; ``optimizer.num_updates`` counts
+      the updates that were applied.
+    * ``meters=True`` keeps the loop's loss and gradient-norm meters (``TrainMeters``) on the device, eagerly and in replay,
+      without a host read; what ``step`` returns does not change.
     * ``use_graph=True`` replays hipGraphs (forward + decoder backward | encoder backward | update) captured
       after two eager warm-up steps, with the RCCL all-reduces issued between the replays, so the ~900
       launches of a step cost three graph launches on the host.  The learning rate lives in a device scalar,
@@ -303,7 +374,7 @@ class TrainStep:
 
     def __init__(self, model, optimizer, *, clip_grad=5.0, amp=True, criterion=None, use_graph=False,
                  compress_bf16=False, forward_fn=None, accumulation_steps=1, lr_scheduler=None, overlap=True, group=None,
-                 start_update=0):
+                 start_update=0, meters=False):
         self.model, self.optimizer, self.clip_grad, self.amp = model, optimizer, clip_grad, amp
         self.criterion = criterion or torch.nn.BCEWithLogitsLoss()
         self.accum = max(int(accumulation_steps), 1)
@@ -316,14 +387,14 @@ class TrainStep:
         self.drop_path = None       # forced stochastic-depth scales (a DropPathScales); None: the model draws when it should
         self.forward_fn = forward_fn or (lambda m, x: m(x) if self.drop_path is None else m(x, drop_path=self.drop_path))
         self.use_graph = use_graph and torch.cuda.is_available()
-        self.hip_opt = hasattr(optimizer, 'bind_flat')       # optim.FlatAdamW: clip + AdamW + shadow refresh in one kernel
+        self.hip_opt = hasattr(optimizer, 'bind_flat')       # optim.FlatAdamW / FlatSGD: clip + update + shadow refresh in one kernel
         if self.hip_opt:
             optimizer.bind_flat(self.flat, model)
         elif self.use_graph:
             bad = [g for g in optimizer.param_groups if not g.get('capturable', False)]
             if bad:
                 raise ValueError('TrainStep(use_graph=True) captures optimizer.step() into a hipGraph: build the torch optimizer with '
-                                 'capturable=True (engine.build_optimizer(config, model, capturable=True)) or use optim.FlatAdamW')
+                                 'capturable=True (engine.build_optimizer(config, model, capturable=True)) or use optim.FlatAdamW / optim.FlatSGD')
         self._g1 = self._g2 = self._g_opt = None
         self._opt_signature = None
         self.recaptures = 0
@@ -340,6 +411,8 @@ class TrainStep:
         self._tensor_lr = (not self.hip_opt) and all(g.get('capturable', False) for g in optimizer.param_groups) \
             and next(model.parameters()).is_cuda
         self.device_type = 'cuda' if next(model.parameters()).is_cuda else 'cpu'
+        # meters=True: the loop's loss / grad-norm meters on the device (read them with ``meters.values()`` when a log line is due)
+        self.meters = TrainMeters(next(model.parameters()).device, self.accum) if meters else None
 
     # -- learning rate -----------------------------------------------------------------------
     def set_lr(self, lr: float, group_index: int | None = None):
@@ -394,9 +467,13 @@ class TrainStep:
     def _enc_bwd(feats, dfeats):
         feats.backward(dfeats)
 
+    def _meter_loss(self, loss, y):
+        if self.meters is not None:
+            self.meters.update_loss(loss, y.counts[3] if hasattr(y, 'counts') else y.shape[0])    # MinedPairs: the real pairs
+
     def _update(self):
         if self.hip_opt:
-            norm = self.optimizer.step_flat(self.clip_grad)      # clip + AdamW + shadow refresh + zero: one pass
+            norm = self.optimizer.step_flat(self.clip_grad)      # clip + update + shadow refresh + zero: one pass
         else:
             norm = self.flat.clip_(self.clip_grad) if self.clip_grad is not None else torch.linalg.vector_norm(self.flat.flat)
             self.optimizer.step()
@@ -474,10 +551,13 @@ class TrainStep:
             loss = self._fwd_bwd(x, y)
             if last:
                 self.flat.start_all_reduce(0, self.flat.flat.numel(), group=self.group)
+        self._meter_loss(loss, y)
         if last:
             self.flat.finish_all_reduce()
             self._sync_lr()
             self.last_norm = self._update()
+            if self.meters is not None:
+                self.meters.update_norm(self.last_norm)
             self._after_update()
         return loss
 
@@ -498,6 +578,7 @@ class TrainStep:
                 self._static_loss, self._feats, self._dfeats = self._fwd_dec_bwd(self._static_x, self._static_y)
             else:
                 self._static_loss = self._fwd_bwd(self._static_x, self._static_y)
+            self._meter_loss(self._static_loss, self._static_y)      # part of the replayed graph
         if split:
             self._g2 = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self._g2, pool=self._g1.pool(), capture_error_mode=_CAPTURE_MODE):
@@ -514,6 +595,8 @@ class TrainStep:
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g, pool=self._g1.pool(), capture_error_mode=_CAPTURE_MODE):
             norm = self._update()
+            if self.meters is not None:
+                self.meters.update_norm(norm)
         if self._static_norm is None:
             self._static_norm = norm
         elif norm.data_ptr() != self._static_norm.data_ptr():

@@ -1,9 +1,15 @@
-"""``FlatAdamW``: torch.optim.AdamW's update (misc/optimizer.py:25-27) as ONE HIP multi-tensor pass over the flat
-gradient buffer - gradient-norm clip (misc/utils.py:215-217), AdamW, refresh of the bf16 weight shadows the MFMA
-kernels read, and ``zero_grad`` (misc/engine.py:231) - ``vited_adamw_step`` of include/vited.h.
+"""``FlatAdamW`` and ``FlatSGD``: torch.optim.AdamW's and torch.optim.SGD's updates (misc/optimizer.py:22-27) as ONE HIP
+multi-tensor pass over the flat gradient buffer - gradient-norm clip (misc/utils.py:215-217), the update, refresh of the
+bf16 weight shadows the MFMA kernels read, and ``zero_grad`` (misc/engine.py:231) - ``vited_adamw_step`` /
+``vited_sgd_step`` of include/vited.h.
 
-It is a ``torch.optim.Optimizer`` (param_groups / state_dict / lr schedulers work as usual); ``engine.TrainStep``
-drives it through ``step_flat``.  There is no CPU path: parameters must live on the GPU.
+They are ``torch.optim.Optimizer``s (param_groups / state_dict / lr schedulers work as usual); ``engine.TrainStep``
+drives them through ``step_flat``.  There is no CPU path: parameters must live on the GPU.
+
+``skip_nonfinite=True`` leaves out an update whose gradient norm is inf or NaN, as ``GradScaler.step`` does for the reference
+(misc/utils.py:206-226): parameters, optimizer state and shadows keep their bits, the gradients are zeroed, the step count
+stays and ``skipped_updates`` goes up.  The norm is that of the all-reduced flat buffer, so every data-parallel rank decides
+alike.
 """
 from __future__ import annotations
 
@@ -12,19 +18,24 @@ import torch
 from . import _lib
 
 HYPER_HEADER, GROUP_WORDS, DESC_WORDS = 8, 8, 10
+HYPER_STEP, HYPER_SKIP_FLAG, HYPER_SKIPPED = 0, 1, 2
 
 
-class FlatAdamW(torch.optim.Optimizer):
+class _FlatOptimizer(torch.optim.Optimizer):
+    """What the fused optimizers share: the binding to a ``FlatGradients``, one flat buffer per state tensor, the descriptor
+    table, the device hyper-parameter array, the weight-shadow bookkeeping and the launch.  A subclass names its entry point
+    (``_entry``), its state tensors (``_state_names``: descriptor words 2 and 3) and its 8 words per parameter group."""
     manages_weight_shadows = True      # functions._install_optimizer_step_hook: this optimizer publishes its updates itself
+    _entry = None
+    _state_names = ()
+    _state_at_bind = True              # install state[p] views when bound (AdamW) or after the first update (SGD, as torch does)
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, model=None):
-        """``model`` (the HIP ViT-ED whose parameters these are) lets the kernel refresh the model's bf16 weight shadows in the
-        same pass; without it the parameters' version counters are bumped after every update instead, so the model recasts its
-        shadows on the next forward (correct, one extra launch per weight)."""
-        super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay))
+    def __init__(self, params, defaults, model=None, skip_nonfinite=False):
+        super().__init__(params, defaults)
         self.flat = None
         self._model = model
-        self._loaded_step = None       # step count of a state_dict loaded before bind_flat (the reference's resume order)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self._bufs = None              # {state name: flat fp32 buffer laid out like the gradient buffer}
         self._desc = self._desc_key = None
         self._hyper = self._hyper_seen = None
         self._norm = self._ws = None
@@ -33,52 +44,71 @@ class FlatAdamW(torch.optim.Optimizer):
     def bind_flat(self, flat, model=None):
         """Use ``flat`` (engine.FlatGradients over the same parameters) as the gradient buffer; ``model`` (optional)
         supplies the bf16 weight shadows to refresh (its ``_runtimes``)."""
+        name = type(self).__name__
         mine = {id(p) for g in self.param_groups for p in g['params'] if p.requires_grad}
         if {id(p) for p in flat.params} != mine:
-            raise ValueError('FlatAdamW.bind_flat: the flat gradient buffer does not cover exactly the optimizer\'s trainable parameters')
+            raise ValueError(f'{name}.bind_flat: the flat gradient buffer does not cover exactly the optimizer\'s trainable parameters')
         dev = flat.flat.device
         if dev.type != 'cuda':
-            raise RuntimeError('FlatAdamW runs on the MI355X HIP kernel only (no CPU path); use torch.optim.AdamW for CPU parameters')
-        rebind = self.flat is flat and getattr(self, 'exp_avg', None) is not None and self.exp_avg.numel() == flat.flat.numel()
+            raise RuntimeError(f'{name} runs on the MI355X HIP kernel only (no CPU path); use torch.optim for CPU parameters')
+        rebind = self.flat is flat and self._bufs is not None and all(b.numel() == flat.flat.numel() for b in self._bufs.values())
         self.flat = flat
         if model is not None:
             self._model = model
         if not rebind:
-            # first binding: the moment buffers, the hyper-parameter array and the workspace are allocated ONCE - a captured
-            # update graph bakes their addresses in, so a later load_state_dict copies INTO them (below) instead of replacing them
-            self.exp_avg = torch.zeros_like(flat.flat)
-            self.exp_avg_sq = torch.zeros_like(flat.flat)
-            self._hyper = torch.zeros(HYPER_HEADER + GROUP_WORDS * len(self.param_groups), dtype=torch.float32, device=dev)
+            # first binding to this buffer: the state buffers, the hyper-parameter array and the workspace are allocated ONCE - a
+            # captured update graph bakes their addresses in, so a later load_state_dict copies INTO them (below) instead of
+            # replacing them
+            self._bufs = {n: torch.zeros_like(flat.flat) for n in self._state_names}
+            hyper = torch.zeros(HYPER_HEADER + GROUP_WORDS * len(self.param_groups), dtype=torch.float32, device=dev)
+            if self._hyper is not None:
+                # bound before (a second TrainStep on the same optimizer): the counts of applied and skipped updates go along with
+                # the state, on the device
+                hyper[:HYPER_HEADER].copy_(self._hyper[:HYPER_HEADER])
+            self._hyper = hyper
             self._norm = torch.zeros(1, dtype=torch.float32, device=dev)
             self._ws = torch.empty(_lib.load().vited_adamw_workspace_bytes() // 4, dtype=torch.float32, device=dev)
             self._desc = self._desc_key = None
+        self._hyper[HYPER_SKIP_FLAG: HYPER_SKIP_FLAG + 1].fill_(1.0 if self.skip_nonfinite else 0.0)
         self._hyper_seen = None
         for p, off in zip(flat.params, flat.offsets):
-            st = self.state[p]
-            old_m, old_v = st.get('exp_avg'), st.get('exp_avg_sq')
-            new_m = self.exp_avg[off: off + p.numel()].view_as(p)
-            new_v = self.exp_avg_sq[off: off + p.numel()].view_as(p)
-            if old_m is not None and old_m.data_ptr() != new_m.data_ptr():
-                new_m.copy_(old_m)
-                new_v.copy_(old_v)
-            st['exp_avg'], st['exp_avg_sq'] = new_m, new_v
-        if self._loaded_step is not None:
-            # torch.optim.AdamW keeps one step count per parameter; they advance together, so one counter serves (bias correction)
-            self._hyper[0] = float(self._loaded_step)
-            self._loaded_step = None
+            st = self.state[p] if (self._state_at_bind or p in self.state) else {}
+            for n in self._state_names:
+                old = st.get(n)
+                if old is None and not self._state_at_bind:
+                    continue                                 # no state yet (or a loaded None): the zero the buffer holds
+                new = self._bufs[n][off: off + p.numel()].view_as(p)
+                if old is not None and old.data_ptr() != new.data_ptr():
+                    new.copy_(old)
+                st[n] = new
+        self._after_bind()
+
+    def _after_bind(self):
+        pass
+
+    def _state_view(self, name, p):
+        off = self.flat.offsets[next(i for i, q in enumerate(self.flat.params) if q is p)]
+        return self._bufs[name][off: off + p.numel()].view_as(p)
 
     @property
     def num_updates(self) -> int:
-        if self._hyper is not None:
-            return int(self._hyper[0].item())
-        return int(self._loaded_step or 0)
+        """Updates applied (one host read once bound); a skipped update does not count."""
+        return int(self._hyper[HYPER_STEP].item()) if self._hyper is not None else 0
+
+    @property
+    def skipped_updates(self) -> int:
+        """Updates left out because the gradient norm was not finite (one host read)."""
+        return int(self._hyper[HYPER_SKIPPED].item()) if self._hyper is not None else 0
+
+    def _group_words(self, group):
+        raise NotImplementedError
 
     def sync_hyperparameters(self):
-        """Fold ``param_groups`` (what schedulers write) into the device hyper-parameter array when they changed.  The step
-        counter (word 0) is owned by the kernel and never overwritten here."""
+        """Fold ``param_groups`` (what schedulers write) into the device hyper-parameter array when they changed.  The header
+        (step count, skip flag, skipped count) is owned by the kernel and ``bind_flat`` and never overwritten here."""
         vals = []
         for g in self.param_groups:
-            vals += [float(g['lr']), float(g['betas'][0]), float(g['betas'][1]), float(g['eps']), float(g['weight_decay']), 0., 0., 0.]
+            vals += self._group_words(g)
         if vals != self._hyper_seen:
             # a fresh host tensor per change and an ordinary (host-synchronous) copy of ~16 floats: a reused pinned buffer
             # with a non-blocking copy could be rewritten with the NEXT iteration's rate before this copy executed (the host
@@ -96,34 +126,35 @@ class FlatAdamW(torch.optim.Optimizer):
     def _descriptors(self):
         shadows = self._shadows()
         group_of = {id(p): gi for gi, g in enumerate(self.param_groups) for p in g['params']}
+        state = [self._bufs[n].data_ptr() for n in self._state_names] + [None] * (2 - len(self._state_names))
         rows_, tile = [], 0
         for p, v, off in zip(self.flat.params, self.flat.views, self.flat.offsets):
-            assert p.is_contiguous() and p.dtype == torch.float32, 'FlatAdamW: parameters must be contiguous fp32'
+            assert p.is_contiguous() and p.dtype == torch.float32, f'{type(self).__name__}: parameters must be contiguous fp32'
             r = p.shape[0] if p.dim() >= 2 else 1
             c = p.numel() // r
             sh = shadows.get(id(p), {})
             n, t = sh.get('n'), sh.get('t')
-            rows_.append([p.data_ptr(), v.data_ptr(), self.exp_avg.data_ptr() + 4 * off, self.exp_avg_sq.data_ptr() + 4 * off,
-                          0 if n is None else n.data_ptr(), 0 if t is None else t.data_ptr(), r, c, tile, group_of[id(p)]])
+            rows_.append([p.data_ptr(), v.data_ptr()] + [0 if s is None else s + 4 * off for s in state]
+                         + [0 if n is None else n.data_ptr(), 0 if t is None else t.data_ptr(), r, c, tile, group_of[id(p)]])
             tile += ((r + 63) // 64) * ((c + 63) // 64)
         key = tuple(tuple(r[:6]) for r in rows_)
         if key != self._desc_key:
             if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError('FlatAdamW: the set of weight shadows changed during graph capture (run one eager step first)')
+                raise RuntimeError(f'{type(self).__name__}: the set of weight shadows changed during graph capture (run one eager step first)')
             self._desc = torch.tensor(rows_, dtype=torch.int64).to(self.flat.flat.device)
             self._desc_key, self._tiles = key, tile
         return self._desc
 
     # -- the update ----------------------------------------------------------------------------
     def step_flat(self, max_norm=None, zero_grad: bool = True):
-        """clip(max_norm) + AdamW + shadow refresh (+ zero the gradients).  Returns the pre-clip gradient norm (device scalar)."""
+        """clip(max_norm) + update + shadow refresh (+ zero the gradients).  Returns the pre-clip gradient norm (device scalar)."""
         if self.flat is None:
-            raise RuntimeError('FlatAdamW.step_flat: call bind_flat(FlatGradients) first (engine.TrainStep does)')
+            raise RuntimeError(f'{type(self).__name__}.step_flat: call bind_flat(FlatGradients) first (engine.TrainStep does)')
         capturing = torch.cuda.is_current_stream_capturing()
         if not capturing:
             self.sync_hyperparameters()
         desc = self._descriptors()
-        _lib.call('vited_adamw_step', desc.data_ptr(), desc.shape[0], self._tiles, self.flat.flat.data_ptr(), self.flat.flat.numel(),
+        _lib.call(self._entry, desc.data_ptr(), desc.shape[0], self._tiles, self.flat.flat.data_ptr(), self.flat.flat.numel(),
                   self._hyper.data_ptr(), float(max_norm) if max_norm else 0.0, int(zero_grad), self._norm.data_ptr(), self._ws.data_ptr(),
                   self._ws.numel() * 4, torch.cuda.current_stream().cuda_stream)
         if not capturing:
@@ -176,6 +207,36 @@ class FlatAdamW(torch.optim.Optimizer):
         else:
             super().zero_grad(set_to_none=set_to_none)
 
+
+class FlatAdamW(_FlatOptimizer):
+    _entry = 'vited_adamw_step'
+    _state_names = ('exp_avg', 'exp_avg_sq')
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, model=None, skip_nonfinite=False):
+        """``model`` (the HIP ViT-ED whose parameters these are) lets the kernel refresh the model's bf16 weight shadows in the
+        same pass; without it the parameters' version counters are bumped after every update instead, so the model recasts its
+        shadows on the next forward (correct, one extra launch per weight)."""
+        super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay), model, skip_nonfinite)
+        self._loaded_step = None       # step count of a state_dict loaded before bind_flat (the reference's resume order)
+
+    exp_avg = property(lambda self: self._bufs['exp_avg'] if self._bufs else None)
+    exp_avg_sq = property(lambda self: self._bufs['exp_avg_sq'] if self._bufs else None)
+
+    def _after_bind(self):
+        if self._loaded_step is not None:
+            # torch.optim.AdamW keeps one step count per parameter; they advance together, so one counter serves (bias correction)
+            self._hyper[HYPER_STEP] = float(self._loaded_step)
+            self._loaded_step = None
+
+    @property
+    def num_updates(self) -> int:
+        if self._hyper is not None:
+            return int(self._hyper[HYPER_STEP].item())
+        return int(self._loaded_step or 0)
+
+    def _group_words(self, g):
+        return [float(g['lr']), float(g['betas'][0]), float(g['betas'][1]), float(g['eps']), float(g['weight_decay']), 0., 0., 0.]
+
     # -- checkpoint compatibility with torch.optim.AdamW (misc/utils.py:130-142 saves optimizer.state_dict()) ----
     def state_dict(self):
         sd = super().state_dict()
@@ -194,3 +255,78 @@ class FlatAdamW(torch.optim.Optimizer):
         self._loaded_step = max(steps) if steps else None
         if flat is not None:
             self.bind_flat(flat)                 # copies the loaded moments into the flat buffers and applies the step count
+
+
+class FlatSGD(_FlatOptimizer):
+    """torch.optim.SGD with momentum / Nesterov momentum (misc/optimizer.py:22-24 builds ``nesterov=True``); dampening is not
+    supported.  ``state[p]['momentum_buffer']`` is a view into one flat buffer; like torch's, the state is empty before the first
+    update and stays empty for a group whose momentum is 0."""
+    _entry = 'vited_sgd_step'
+    _state_names = ('momentum_buffer',)
+    _state_at_bind = False
+
+    def __init__(self, params, lr=1e-3, momentum=0., dampening=0, weight_decay=0., nesterov=False, model=None, skip_nonfinite=False):
+        if lr < 0.0:
+            raise ValueError(f'Invalid learning rate: {lr}')
+        if momentum < 0.0:
+            raise ValueError(f'Invalid momentum value: {momentum}')
+        if dampening != 0:
+            raise ValueError('FlatSGD does not support dampening (torch.optim.SGD does)')
+        if nesterov and momentum <= 0:
+            raise ValueError('Nesterov momentum requires a momentum and zero dampening')
+        # torch.optim.SGD's group keys, so that a state_dict moves between the two in both directions
+        defaults = dict(lr=lr, momentum=momentum, dampening=0, weight_decay=weight_decay, nesterov=bool(nesterov), maximize=False,
+                        foreach=None, differentiable=False, fused=None)
+        super().__init__(params, defaults, model, skip_nonfinite)
+        for g in self.param_groups:
+            self._check_group(g)
+        self._state_installed = False
+
+    @staticmethod
+    def _check_group(g):
+        if g['dampening'] != 0:
+            raise ValueError('FlatSGD does not support dampening (torch.optim.SGD does)')
+        if g['nesterov'] and g['momentum'] <= 0:
+            raise ValueError('Nesterov momentum requires a momentum and zero dampening')
+        if g.get('maximize'):
+            raise ValueError('FlatSGD does not support maximize=True')
+
+    def _group_words(self, g):
+        self._check_group(g)
+        return [float(g['lr']), float(g['momentum']), 1.0 if g['nesterov'] else 0.0, 0., float(g['weight_decay']), 0., 0., 0.]
+
+    def _install_state(self):
+        """After the first update torch.optim.SGD holds a momentum buffer for every parameter of a group with momentum."""
+        for g in self.param_groups:
+            if g['momentum'] != 0:
+                for p in g['params']:
+                    if p.requires_grad and self.state[p].get('momentum_buffer') is None:
+                        self.state[p]['momentum_buffer'] = self._state_view('momentum_buffer', p)
+        self._state_installed = True
+
+    def _after_bind(self):
+        self._state_installed = False
+
+    def _publish_update(self):
+        super()._publish_update()
+        if not self._state_installed:
+            self._install_state()
+
+    def state_dict(self):
+        if self.flat is not None and not self._state_installed and self.num_updates > 0:
+            self._install_state()                # every update so far was a graph replay
+        return super().state_dict()
+
+    def load_state_dict(self, state_dict):
+        """Accepts a ``torch.optim.SGD`` state, before or after ``bind_flat``; a ``None`` or absent momentum buffer loads as zeros.
+        Once bound the loaded buffers are copied INTO the existing flat buffer, so a captured update graph stays valid."""
+        flat = self.flat
+        super().load_state_dict(state_dict)
+        for g in self.param_groups:
+            self._check_group(g)
+        if flat is not None:
+            for st in self.state.values():       # a loaded buffer may be a view of the flat buffer itself (our own state_dict)
+                if st.get('momentum_buffer') is not None:
+                    st['momentum_buffer'] = st['momentum_buffer'].clone()
+            self._bufs['momentum_buffer'].zero_()
+            self.bind_flat(flat)
