@@ -1,0 +1,280 @@
+"""Puzzle evaluation (evaluation.py:100-133, solver_driver.py, paikin_tal_solver/) for type-1 puzzles of one image, fixed size:
+the piece distances from the model's logits, the Paikin-Tal solver with its compatibilities on the device, and the reference's
+accuracies."""
+from __future__ import annotations
+
+import heapq
+from typing import NamedTuple
+
+import torch
+
+from .. import ops
+from .similarity import _ImageSource
+
+
+PUZZLE_SIDES = ('top', 'right', 'bottom', 'left')          # PuzzlePieceSide values 0..3; side s touches side (s + 2) % 4
+_SIDE_STEP = ((-1, 0), (0, 1), (1, 0), (0, -1))
+_DQ_UNSET = 2 ** 31 - 1                                     # the reference's fill of its distance arrays (the diagonal)
+
+
+def _ordered_block_pairs(a0, a1, n, dev):
+    """Pairs (i, j), i in [a0, a1), j in [0, n), j != i, row-major."""
+    ii = torch.arange(a0, a1, device=dev).view(-1, 1).expand(a1 - a0, n)
+    jj = torch.arange(0, n, device=dev).view(1, -1).expand(a1 - a0, n)
+    keep = jj != ii
+    return ii[keep], jj[keep]
+
+
+@torch.no_grad()
+def puzzle_distances(model, pieces, *, pair_batch: int = 1024, amp: bool = True, block: int = 128, return_logits: bool = False):
+    """The reference's integer piece distances ``Dq`` int32 [4, n, n] on the device (evaluation.py:100-133 feeding
+    inter_piece_distance.py:206-223): Dq[s, i, j] is the distance of side s of piece i (top 0, right 1, bottom 2, left 3) to the
+    complementary side of piece j, from the model's logits of the ordered pair (i, j) (bin (s + 3) % 4), quantised as
+    uint32(trunc(fp32(fp32(1 - sigmoid(logit)) * 1000))).  The diagonal holds 2^31 - 1 (never read).
+
+    ``pieces``: the n pieces of one puzzle at model size, uint8 [n, 3, S, S] (normalised in the patch-embedding kernel) or
+    normalised float, on the host or the device.  The encoder and the image-2 token cache run once per piece; the decoder runs on
+    all n (n - 1) ordered pairs, ``pair_batch`` at a time, row block by row block of ``block`` pieces, and every batch's logits
+    are quantised and scattered into Dq on the device.  ``return_logits`` also returns the fp32 logits [n, n, 4] (diagonal 0)."""
+    if not getattr(model, 'supports_pair_cache', False):
+        raise TypeError('puzzle_distances needs the HIP model (VisionTransformerCustom): it runs on the pair caches')
+    if getattr(model, 'num_classes', 4) != 4:
+        raise ValueError(f'puzzle_distances needs the 4-bin puzzle head, the model has {model.num_classes} outputs')
+    dev = next(model.parameters()).device
+    src = _ImageSource(pieces, None, dev)
+    n = src.n
+    if n < 2:
+        raise ValueError('a puzzle needs at least two pieces')
+    dq = torch.full((4, n, n), _DQ_UNSET, dtype=torch.int32, device=dev)
+    bad = torch.zeros(1, dtype=torch.int32, device=dev)
+    logits = torch.zeros((n, n, 4), dtype=torch.float32, device=dev) if return_logits else None
+    dtype_ctx = lambda: torch.autocast(dev.type, dtype=torch.bfloat16, enabled=amp)
+    was_training = model.training
+    model.eval()
+    try:
+        with dtype_ctx():
+            tokens2, q0 = model.cache_image2_tokens(src.block(0, n))        # once per piece
+        for a0 in range(0, n, block):
+            a1 = min(a0 + block, n)
+            with dtype_ctx():
+                feats = model(src.block(a0, a1), forward_first_part=True)   # encoder once per piece
+                kvs = model.cache_context_kv(feats)
+            del feats
+            ii, jj = _ordered_block_pairs(a0, a1, n, dev)
+            for p0 in range(0, ii.numel(), pair_batch):
+                i_sub, j_sub = ii[p0:p0 + pair_batch], jj[p0:p0 + pair_batch]
+                with dtype_ctx():
+                    out = model.forward_pairs_cached(tokens2, j_sub, kvs, i_sub - a0, q0)
+                out = out.float().reshape(-1, 4).contiguous()
+                ops.puzzle_distances_from_logits(out, i_sub.contiguous(), j_sub.contiguous(), dq, bad)
+                if logits is not None:
+                    logits[i_sub, j_sub] = out
+            del kvs
+    finally:
+        model.train(was_training)
+    if int(bad.item()):
+        raise RuntimeError('puzzle_distances: a pair index fell outside the puzzle (internal error)')
+    return (dq, logits) if return_logits else dq
+
+
+class PuzzleCompatibility:
+    """The Paikin-Tal compatibility state of one puzzle on the device (InterPieceDistance, type 1): built from Dq int32 [4, n, n]
+    by ``vited_puzzle_compat_init``; ``recalc`` and ``best_slot`` are the solver's two pool-empty steps.  Tensors: min_d,
+    second_d int64 [n, 4], candidate, best_buddy int32 [n, 4], compat, mutual float32 [4, n, n], start_count int32 [n],
+    start_total float32 [n], start_order int32 [n]."""
+
+    def __init__(self, dq: torch.Tensor):
+        self.dq = dq.to(torch.int32).contiguous()
+        self.n = self.dq.shape[1]
+        self.state = ops.puzzle_compat_init(self.dq)
+        dev = self.dq.device
+        self._placed = torch.empty(self.n, dtype=torch.int32, device=dev)
+        self.changed = torch.zeros(self.n, dtype=torch.int32, device=dev)
+        self._word = torch.empty(1, dtype=torch.int64, device=dev)
+
+    def __getattr__(self, name):
+        state = self.__dict__.get('state')
+        if state is not None and name in state:
+            return state[name]
+        raise AttributeError(name)
+
+    def recalc(self, placed) -> torch.Tensor:
+        """recalculate_remaining_piece_compatibilities for the boolean mask ``placed`` [n]; returns the changed flags (device)."""
+        self._placed.copy_(torch.as_tensor(placed, dtype=torch.int32))
+        ops.puzzle_compat_recalc(self.dq, self._placed, self.state, self.changed)
+        return self.changed
+
+    def best_slot(self, placed, slot_piece, slot_side):
+        """(piece, slot index, value) of the first maximum of mutual[(slot_side[k] + 2) % 4, p, slot_piece[k]] over unplaced p
+        ascending x slots k in list order."""
+        dev = self.dq.device
+        self._placed.copy_(torch.as_tensor(placed, dtype=torch.int32))
+        sp = torch.as_tensor(slot_piece, dtype=torch.int32).to(dev)
+        ss = torch.as_tensor(slot_side, dtype=torch.int32).to(dev)
+        ops.puzzle_best_slot(self.mutual, self._placed, sp, ss, out=self._word)
+        hit = ops.puzzle_unpack_slot(int(self._word.item()), sp.numel())
+        if hit is None:
+            raise RuntimeError('best_slot: no unplaced piece')
+        p, k = hit
+        return p, k, float(self.mutual[(int(slot_side[k]) + 2) % 4, p, int(slot_piece[k])])
+
+
+class PuzzleSolution(NamedTuple):
+    locations: 'object'         # int64 [n, 2]: (row, col) of every piece, the placed block's top-left corner at (0, 0)
+    board_locations: 'object'   # int64 [n, 2]: where the solver put each piece on its n x n board (seed at (n // 2, n // 2))
+    order: 'object'             # int64 [n]: placement order, the seed first
+    recalcs: int                # times the best-buddy pool ran empty and the compatibilities were recalculated
+    grid: 'object'              # int64 [rows, cols]: the piece at each cell, -1 for none
+
+
+class _BuddyHeapEntry:
+    """A best-buddy / open-slot pairing of the solver's heap (solver.py:32-64): heapq pops the largest mutual compatibility, ties
+    falling out of the heap's own structure, so the push order and this one comparison must be the reference's."""
+    __slots__ = ('compat', 'piece', 'piece_side', 'neighbor', 'neighbor_side', 'location')
+
+    def __init__(self, compat, piece, piece_side, neighbor, neighbor_side, location):
+        self.compat, self.piece, self.piece_side = compat, piece, piece_side
+        self.neighbor, self.neighbor_side, self.location = neighbor, neighbor_side, location
+
+    def __lt__(self, other):
+        return self.compat > other.compat
+
+
+def solve_puzzle(distances: torch.Tensor, grid_size) -> PuzzleSolution:
+    """Paikin-Tal placement (PaikinTalSolver, solver.py) of one type-1 puzzle of ``grid_size`` = (rows, cols) pieces from the
+    distances Dq int32 [4, n, n] of ``puzzle_distances``, making the reference's decisions in the reference's order: the seed from
+    the start ordering at the board centre, best buddies pooled as pieces are placed, the best-buddy heap popped until it yields a
+    placeable entry, and - whenever the pool is empty - a device recalculation of the compatibilities followed by a device scan
+    of every unplaced piece against every open slot.  The host keeps a mirror of the mutual compatibility, refreshed by one copy
+    per recalculation, for the heap's lookups."""
+    import numpy as np
+    rows, cols = int(grid_size[0]), int(grid_size[1])
+    n = distances.shape[1]
+    if rows * cols != n or tuple(distances.shape) != (4, n, n):
+        raise ValueError(f'distances {tuple(distances.shape)} do not describe a {rows} x {cols} puzzle')
+    comp = PuzzleCompatibility(distances)
+    mutual = comp.mutual.cpu().numpy()
+    best_buddy = comp.best_buddy.cpu().numpy()
+    seed = int(comp.start_order[0].item())
+
+    placed = np.zeros(n, dtype=bool)
+    occupied = np.zeros((n, n), dtype=bool)                # the reference's board: n x n, indexed as numpy indexes it
+    board_loc = np.full((n, 2), -1, dtype=np.int64)
+    top_left, bottom_right = [n // 2, n // 2], [n // 2, n // 2]
+    open_slots = []                                         # (location, piece, side of that piece facing the slot), list order
+    pool = {}                                               # best buddies waiting, insertion ordered
+    heap = []
+    order = []
+    recalcs = 0
+
+    def fits(loc):
+        for d, size in ((0, rows), (1, cols)):
+            if loc[d] - top_left[d] + 1 > size or bottom_right[d] - loc[d] + 1 > size:
+                return False
+        return True
+
+    def slot_open(loc):
+        return not occupied[loc] and fits(loc)
+
+    def put(piece, loc):
+        board_loc[piece] = loc
+        occupied[loc] = True
+        placed[piece] = True
+        order.append(piece)
+
+    def add_best_buddies(piece):
+        for s in range(4):
+            bb = int(best_buddy[piece, s])
+            if bb < 0 or placed[bb] or bb in pool:
+                continue
+            pool[bb] = None
+            for loc, q, side in open_slots:
+                heapq.heappush(heap, _BuddyHeapEntry(float(mutual[(side + 2) % 4, bb, q]), bb, (side + 2) % 4, q, side, loc))
+
+    def open_slots_around(piece):
+        r, c = board_loc[piece]
+        for s, (dr, dc) in enumerate(_SIDE_STEP):
+            loc = (int(r + dr), int(c + dc))
+            if slot_open(loc):
+                open_slots.append((loc, piece, s))
+                for bb in list(pool):
+                    heapq.heappush(heap, _BuddyHeapEntry(float(mutual[s, piece, bb]), bb, (s + 2) % 4, piece, s, loc))
+
+    put(seed, (n // 2, n // 2))
+    add_best_buddies(seed)
+    open_slots_around(seed)
+    while not placed.all():
+        if pool:
+            while True:
+                e = heapq.heappop(heap)
+                if not placed[e.piece] and slot_open(e.location):
+                    break
+            piece, loc, from_pool = e.piece, e.location, True
+        else:
+            recalcs += 1
+            comp.recalc(placed)
+            mutual = comp.mutual.cpu().numpy()
+            valid = [k for k, (loc, _, _) in enumerate(open_slots) if slot_open(loc)]
+            piece, k, _ = comp.best_slot(placed, [open_slots[v][1] for v in valid], [open_slots[v][2] for v in valid])
+            loc, from_pool = open_slots[valid[k]][0], False
+        for d in range(2):
+            if top_left[d] > loc[d]:
+                top_left[d] = loc[d]
+            elif bottom_right[d] < loc[d]:
+                bottom_right[d] = loc[d]
+        put(piece, loc)
+        open_slots = [slot for slot in open_slots if slot[0] != loc]
+        if from_pool:
+            del pool[piece]
+        add_best_buddies(piece)
+        open_slots_around(piece)
+
+    locations = board_loc - board_loc.min(axis=0)
+    shape = locations.max(axis=0) + 1
+    grid = np.full((int(shape[0]), int(shape[1])), -1, dtype=np.int64)
+    grid[locations[:, 0], locations[:, 1]] = np.arange(n)
+    return PuzzleSolution(locations, board_loc, np.array(order, dtype=np.int64), recalcs, grid)
+
+
+def puzzle_accuracy(solution: PuzzleSolution, true_locations) -> dict:
+    """The accuracies PuzzleResultsCollection.collect_results reports for one solved puzzle (puzzle_importer.py:779-844, the rules
+    of :985-1150 and :1386-1520), every piece from the one original puzzle and unrotated: ``Direct_Standard`` (pieces at their true
+    cell / n), ``Direct_Modified`` (the same, best over the origins the reference's search from the top-left corner offers),
+    ``neighbor`` (sides whose neighbour - or board edge - is the true one / 4n) and ``perfect``.  ``true_locations`` int [n, 2]:
+    where piece i belongs in the original rows x cols grid."""
+    import numpy as np
+    true = np.asarray(true_locations, dtype=np.int64)
+    loc = np.asarray(solution.locations, dtype=np.int64)
+    n = true.shape[0]
+    t_rows, t_cols = int(true[:, 0].max()) + 1, int(true[:, 1].max()) + 1
+    orig_id = true[:, 0] * t_cols + true[:, 1]
+    g_rows, g_cols = int(loc[:, 0].max()) + 1, int(loc[:, 1].max()) + 1
+    placed_id = np.full((g_rows, g_cols), -1, dtype=np.int64)
+    placed_id[loc[:, 0], loc[:, 1]] = orig_id
+
+    def correct_at(origin):
+        return int(np.all(loc == true + np.asarray(origin), axis=1).sum())
+
+    standard = correct_at((0, 0))
+    # the reference's breadth-first search for the candidate origins (puzzle_importer.py:1081-1138)
+    frontier, explored, found = [(0, 0)], [], None
+    while found is None or (frontier and frontier[0][0] + frontier[0][1] <= found):
+        cur = frontier.pop(0)
+        explored.append(cur)
+        if found is None and placed_id[cur] != -1:
+            found = cur[0] + cur[1]
+        else:
+            for nxt in ((cur[0] + 1, cur[1]), (cur[0], cur[1] + 1)):
+                if nxt[0] < g_rows and nxt[1] < g_cols and nxt not in explored and nxt not in frontier:
+                    frontier.append(nxt)
+    modified = max(correct_at(origin) for origin in explored)
+
+    neighbors = 0
+    for p in range(n):
+        for s, (dr, dc) in enumerate(_SIDE_STEP):
+            tr, tc = true[p, 0] + dr, true[p, 1] + dc
+            want = int(tr * t_cols + tc) if 0 <= tr < t_rows and 0 <= tc < t_cols else None
+            r, c = loc[p, 0] + dr, loc[p, 1] + dc
+            got = int(placed_id[r, c]) if 0 <= r < g_rows and 0 <= c < g_cols else -1
+            neighbors += (None if got < 0 else got) == want
+    return {'Direct_Standard': standard / n, 'Direct_Modified': modified / n, 'neighbor': neighbors / (4 * n), 'perfect': standard == n}

@@ -1,0 +1,425 @@
+"""The training step (misc/engine.py:183-257, misc/utils.py:206-232, misc/optimizer.py:10-46): optimizer factory, the reference's
+scaler call shape, ``TrainStep`` (eager or replayed as hipGraphs) and its meters on the device."""
+from __future__ import annotations
+
+import torch
+import torch.distributed as dist
+
+from .. import ops
+from .distributed import FlatGradients
+from .metrics import MeterValue
+
+
+def param_groups_no_decay_1d(model):
+    decay, no_decay = [], []
+    for name, p in model.named_parameters():
+        if not p.requires_grad:
+            continue
+        (no_decay if (p.ndim == 1 or name.endswith('.bias')) else decay).append(p)
+    return [{'params': decay}, {'params': no_decay, 'weight_decay': 0.}]
+
+
+def build_optimizer(config, model, capturable: bool = False, fused_hip: bool | None = None, skip_nonfinite: bool = False):
+    """misc/optimizer.py:10-46: AdamW / Nesterov SGD with the no-decay group for 1-D parameters and ``*.bias``.
+
+    On a GPU model they are ``optim.FlatAdamW`` / ``optim.FlatSGD`` (the HIP multi-tensor kernels: clip + update + bf16
+    weight-shadow refresh in one pass, hipGraph-replayable with a per-iteration learning rate); ``fused_hip=False`` gives
+    ``torch.optim.AdamW(fused=True)`` / ``torch.optim.SGD`` instead, with ``capturable`` forwarded to AdamW (a torch optimizer
+    captured into a hipGraph must be built with capturable=True, and TrainStep keeps its learning rate in a device tensor).
+    ``skip_nonfinite=True`` (HIP optimizers only) leaves out an update whose gradient norm is inf or NaN, which is what
+    ``GradScaler.step`` does in the reference's loop (misc/utils.py:206-226)."""
+    name = config.TRAIN.OPTIMIZER.NAME.lower()
+    groups = param_groups_no_decay_1d(model)
+    on_gpu = all(p.is_cuda for g in groups for p in g['params'])
+    hip = on_gpu and (fused_hip is None or fused_hip)
+    if name not in ('adamw', 'sgd'):
+        raise ValueError(f'unknown optimizer {name}')
+    if skip_nonfinite and not hip:
+        raise ValueError('skip_nonfinite=True needs the HIP optimizers (a GPU model and fused_hip in (None, True)): the torch '
+                         'optimizers have no such check')
+    if name == 'adamw':
+        kw = dict(eps=config.TRAIN.OPTIMIZER.EPS, betas=tuple(config.TRAIN.OPTIMIZER.BETAS), lr=config.TRAIN.BASE_LR,
+                  weight_decay=config.TRAIN.WEIGHT_DECAY)
+        if hip:
+            from ..optim import FlatAdamW     # here, not at the top: optim imports this package (FlatGradients)
+            # the model's bf16 weight shadows are refreshed by the update kernel
+            return FlatAdamW(groups, model=model, skip_nonfinite=skip_nonfinite, **kw)
+        if on_gpu:
+            return torch.optim.AdamW(groups, fused=True, capturable=capturable, **kw)
+        return torch.optim.AdamW(groups, **kw)
+    kw = dict(momentum=config.TRAIN.OPTIMIZER.MOMENTUM, nesterov=True, lr=config.TRAIN.BASE_LR, weight_decay=config.TRAIN.WEIGHT_DECAY)
+    if hip:
+        from ..optim import FlatSGD
+        return FlatSGD(groups, model=model, skip_nonfinite=skip_nonfinite, **kw)
+    return torch.optim.SGD(groups, **kw)
+
+
+class NativeScalerWithGradNormCount:
+    """Call-compatible with misc/utils.py:206-232.  bf16 needs no loss scaling, so ``scale`` is 1;
+    the call still does backward -> (all-reduce) -> clip -> step and returns the gradient norm.
+
+    With ``flat`` (a FlatGradients) the gradients live in one buffer that is all-reduced and clipped as a
+    whole.  The reference's loop calls ``optimizer.zero_grad()`` after every update (misc/engine.py:231),
+    which DETACHES ``p.grad`` from the buffer (set_to_none), so the views are re-attached (and zeroed)
+    before every backward - otherwise the exchange and the clip would act on a stale buffer while the
+    optimizer consumed un-reduced gradients."""
+    state_dict_key = 'amp_scaler'
+
+    def __init__(self, flat: FlatGradients | None = None):
+        self.flat = flat
+
+    def __call__(self, loss, optimizer, clip_grad=None, parameters=None, create_graph=False, update_grad=True):
+        if self.flat is not None:
+            self.flat.attach()
+        loss.backward(create_graph=create_graph)
+        if not update_grad:
+            return None
+        if self.flat is not None:
+            self.flat.attach()     # a backward that found grad=None would have allocated fresh tensors: fold them in
+            self.flat.all_reduce_mean()
+            norm = self.flat.clip_(clip_grad) if clip_grad is not None else torch.linalg.vector_norm(self.flat.flat)
+        else:
+            parameters = list(parameters)
+            if clip_grad is not None:
+                norm = torch.nn.utils.clip_grad_norm_(parameters, clip_grad)
+            else:
+                norm = torch.linalg.vector_norm(torch.stack([torch.linalg.vector_norm(p.grad) for p in parameters]))
+        optimizer.step()
+        return norm
+
+    def state_dict(self):
+        return {'scale': 1.0}
+
+    def load_state_dict(self, state_dict):
+        pass
+
+
+def _decoder_only_parameters(model):
+    """Parameters whose gradient is complete once the decoder + head backward has run: everything except the
+    encoder blocks and the tensors both image paths share (patch_embed.*, pos_embed get gradient from the
+    encoder too, vision_transformer.py:379,391-392)."""
+    out = []
+    for name, p in model.named_parameters():
+        if name.startswith(('cross_blocks.', 'norm.', 'head.')) or name == 'cls_token':
+            out.append(p)
+    return out
+
+
+# Graph capture must not make OTHER threads' HIP calls illegal: RCCL's watchdog thread polls the events of finished collectives
+# (hipEventQuery) whenever it likes, and under the default "global" capture mode such a query during a capture kills the process
+# group ("operation not permitted when stream is capturing").  Only this thread's own calls are restricted.
+_CAPTURE_MODE = 'thread_local'
+
+
+class TrainMeters:
+    """The meters of the reference's training loop (misc/engine.py:195-196, 221-222, 235, 256-257) in fp64 accumulators on the
+    device, so that keeping them costs no host read per iteration:
+      loss       ``loss_meter.update(loss * accumulation_steps, n)`` per micro-step (``loss`` is the divided loss TrainStep returns)
+      grad_norm  ``norm_meter.update(grad_norm)`` per update
+      nonfinite  how many of those norms were inf or NaN (each of them also makes ``grad_norm.avg`` non-finite, as it does in the
+                 reference's log line)
+    The arithmetic is AverageMeter's, operation for operation, in fp64.  Elementwise torch operations on ``device``: they run
+    eagerly or inside a captured graph alike."""
+
+    def __init__(self, device='cuda', accumulation_steps: int = 1):
+        self.accum = max(int(accumulation_steps), 1)
+        # loss: val, sum, count; grad_norm: val, sum, count; non-finite norms
+        self.state = torch.zeros(7, dtype=torch.float64, device=torch.device(device))
+
+    def reset(self):
+        """Start an epoch."""
+        self.state.zero_()
+
+    @torch.no_grad()
+    def update_loss(self, loss: torch.Tensor, n):
+        """``n``: the number of target rows, a Python number or a device scalar (``MinedPairs.counts[3]``)."""
+        v = loss.detach().to(torch.float64)
+        if self.accum > 1:
+            v = v * self.accum
+        n = n.to(torch.float64) if torch.is_tensor(n) else float(n)
+        self.state[0].copy_(v)
+        self.state[1].add_(v * n)
+        self.state[2].add_(n)
+
+    @torch.no_grad()
+    def update_norm(self, norm: torch.Tensor):
+        v = norm.detach().to(torch.float64)
+        self.state[3].copy_(v)
+        self.state[4].add_(v)
+        self.state[5].add_(1.0)
+        self.state[6].add_((~torch.isfinite(v)).to(torch.float64))
+
+    def values(self) -> dict:
+        """{'loss': MeterValue(val, avg), 'grad_norm': MeterValue(val, avg), 'nonfinite': int} of this rank: one host copy."""
+        h = self.state.tolist()
+        return {'loss': MeterValue(h[0], h[1] / h[2] if h[2] else 0.0), 'grad_norm': MeterValue(h[3], h[4] / h[5] if h[5] else 0.0),
+                'nonfinite': int(h[6])}
+
+    def all_reduce(self, group=None) -> float:
+        """``AverageMeter.all_reduce`` of the loss meter (misc/utils.py:293-303): an fp32 [sum, count] SUM all-reduce (the rounding
+        to fp32 happens at world size 1 too, as it does there); returns the average ``train_one_epoch`` returns."""
+        total = self.state[1:3].to(torch.float32)
+        if dist.is_available() and dist.is_initialized():
+            dist.all_reduce(total, op=dist.ReduceOp.SUM, group=group)
+        s, count = total.tolist()
+        if not count:
+            raise ValueError('no training step was metered before all_reduce')
+        return s / count
+
+
+class TrainStep:
+    """forward (autocast) -> BCE-with-logits / accumulation_steps -> backward -> flat all-reduce -> clip 5.0 ->
+    optimizer step -> lr_scheduler.step_update -> zero   (misc/engine.py:202-231).
+
+    * ``accumulation_steps`` > 1: gradients accumulate in the flat buffer over that many calls and the
+      exchange / clip / update happen on the last one (the reference all-reduces on every micro-step because
+      it never uses ``no_sync()``; the mean of sums is the same number).
+    * The exchange is split in two buckets: the decoder-only gradients are all-reduced while the encoder's
+      backward still runs (``overlap=True``; needs a model with the reference's 3-way forward), the rest
+      after it.  The backward is driven in two stages for that: decoder + head first, then the encoder from
+      the gradient of the features.
+    * ``num_updates`` (the index handed to ``lr_scheduler.step_update``) counts iterations, whether or not an optimizer built
+      with ``skip_nonfinite=True`` left an update out - the reference's index does the same; ``optimizer.num_updates`` counts
+      the updates that were applied.
+    * ``meters=True`` keeps the loop's loss and gradient-norm meters (``TrainMeters``) on the device, eagerly and in replay,
+      without a host read; what ``step`` returns does not change.
+    * ``use_graph=True`` replays hipGraphs (forward + decoder backward | encoder backward | update) captured
+      after two eager warm-up steps, with the RCCL all-reduces issued between the replays, so the ~900
+      launches of a step cost three graph launches on the host.  The learning rate lives in a device scalar,
+      so ``lr_scheduler.step_update`` / ``set_lr`` take effect in the replayed update.
+    * Stochastic depth (a model built with ``drop_path_rate`` > 0, in training mode): every step draws its scales inside the
+      model's forward.  Under ``use_graph`` the draw is part of the captured graph and uses the device's default generator,
+      which torch registers with the graph: every replay draws anew, and ``model.last_drop_path`` is a static buffer that holds
+      the latest replay's scales.  A custom ``model.drop_path_generator`` raises at capture.  ``step.drop_path`` = a
+      ``DropPathScales`` of static tensors forces the scales instead (tests, reproducing a step): a captured graph reads those
+      tensors in place."""
+
+    def __init__(self, model, optimizer, *, clip_grad=5.0, amp=True, criterion=None, use_graph=False,
+                 compress_bf16=False, forward_fn=None, accumulation_steps=1, lr_scheduler=None, overlap=True, group=None,
+                 start_update=0, meters=False):
+        self.model, self.optimizer, self.clip_grad, self.amp = model, optimizer, clip_grad, amp
+        self.criterion = criterion or torch.nn.BCEWithLogitsLoss()
+        self.accum = max(int(accumulation_steps), 1)
+        self.lr_scheduler, self.group = lr_scheduler, group
+        self.split = bool(overlap) and forward_fn is None and hasattr(model, 'cross_blocks')
+        self.flat = FlatGradients(model.parameters(), compress_bf16=compress_bf16,
+                                  early=_decoder_only_parameters(model) if self.split else None)
+        if hasattr(model, 'direct_param_grads') or hasattr(model, 'runtime'):
+            model.direct_param_grads = True     # HIP model: weight-gradient kernels add straight into the flat buffer
+        self.drop_path = None       # forced stochastic-depth scales (a DropPathScales); None: the model draws when it should
+        self.forward_fn = forward_fn or (lambda m, x: m(x) if self.drop_path is None else m(x, drop_path=self.drop_path))
+        self.use_graph = use_graph and torch.cuda.is_available()
+        self.hip_opt = hasattr(optimizer, 'bind_flat')       # optim.FlatAdamW / FlatSGD: clip + update + shadow refresh in one kernel
+        if self.hip_opt:
+            optimizer.bind_flat(self.flat, model)
+        elif self.use_graph:
+            bad = [g for g in optimizer.param_groups if not g.get('capturable', False)]
+            if bad:
+                raise ValueError('TrainStep(use_graph=True) captures optimizer.step() into a hipGraph: build the torch optimizer with '
+                                 'capturable=True (engine.build_optimizer(config, model, capturable=True)) or use optim.FlatAdamW / optim.FlatSGD')
+        self._g1 = self._g2 = self._g_opt = None
+        self._opt_signature = None
+        self.recaptures = 0
+        self._static_x = self._static_y = self._static_loss = self._static_norm = None
+        self._eager_steps = 0
+        self._micro = 0
+        # updates done before this TrainStep existed: a resumed run passes epoch * num_steps // accumulation_steps so that the
+        # per-iteration schedule continues where it stopped (misc/engine.py:228 counts from the start of training)
+        self.num_updates = int(start_update)
+        self.last_norm = None
+        self._lr_tensors = None
+        # a torch optimizer built with capturable=True reads its learning rate from a device scalar: keep it there in eager
+        # mode too, so eager and replayed updates see the same (fp32) value
+        self._tensor_lr = (not self.hip_opt) and all(g.get('capturable', False) for g in optimizer.param_groups) \
+            and next(model.parameters()).is_cuda
+        self.device_type = 'cuda' if next(model.parameters()).is_cuda else 'cpu'
+        # meters=True: the loop's loss / grad-norm meters on the device (read them with ``meters.values()`` when a log line is due)
+        self.meters = TrainMeters(next(model.parameters()).device, self.accum) if meters else None
+
+    # -- learning rate -----------------------------------------------------------------------
+    def set_lr(self, lr: float, group_index: int | None = None):
+        """Per-iteration LR (misc/engine.py:228 ``lr_scheduler.step_update``): takes effect in eager and replayed updates."""
+        for i, g in enumerate(self.optimizer.param_groups):
+            if group_index is None or i == group_index:
+                g['lr'] = float(lr) * g.get('lr_scale', 1.0)
+        self._sync_lr()
+
+    def _sync_lr(self):
+        """Schedulers write Python floats into ``param_groups[i]['lr']``; a captured update reads a device scalar.
+        Fold the floats into the per-group device tensors (torch optimizers: the tensors ARE ``group['lr']``)."""
+        if self.hip_opt:
+            self.optimizer.sync_hyperparameters()
+            return
+        if not self._tensor_lr:
+            return
+        if self._lr_tensors is None:
+            dev = next(self.model.parameters()).device
+            self._lr_tensors = [torch.tensor(float(g['lr']), dtype=torch.float32, device=dev) for g in self.optimizer.param_groups]
+        for g, t in zip(self.optimizer.param_groups, self._lr_tensors):
+            if g['lr'] is not t:
+                t.fill_(float(g['lr']))
+                g['lr'] = t
+
+    # -- pieces ------------------------------------------------------------------------------
+    def _loss(self, out, y):
+        loss = self.criterion(out.float(), y)
+        return loss / self.accum if self.accum > 1 else loss
+
+    def _fwd_bwd(self, x, y):
+        """One-stage form (any model / forward_fn)."""
+        with torch.autocast(self.device_type, dtype=torch.bfloat16, enabled=self.amp):
+            out = self.forward_fn(self.model, x)
+            loss = self._loss(out, y)
+        loss.backward()
+        return loss.detach()
+
+    def _fwd_dec_bwd(self, x, y):
+        """Stage 1 of the split backward: encoder forward, decoder + head forward, loss, decoder backward.
+        Returns (loss, features, d loss / d features)."""
+        with torch.autocast(self.device_type, dtype=torch.bfloat16, enabled=self.amp):
+            forced = {} if self.drop_path is None else dict(drop_path=self.drop_path)
+            feats = self.model(x[:, 0], forward_first_part=True, **forced)
+            leaf = feats.detach().requires_grad_(True)
+            out = self.model(leaf, x[:, 1], **forced)
+            loss = self._loss(out, y)
+        loss.backward()
+        return loss.detach(), feats, leaf.grad
+
+    @staticmethod
+    def _enc_bwd(feats, dfeats):
+        feats.backward(dfeats)
+
+    def _meter_loss(self, loss, y):
+        if self.meters is not None:
+            self.meters.update_loss(loss, y.counts[3] if hasattr(y, 'counts') else y.shape[0])    # MinedPairs: the real pairs
+
+    def _update(self):
+        if self.hip_opt:
+            norm = self.optimizer.step_flat(self.clip_grad)      # clip + update + shadow refresh + zero: one pass
+        else:
+            norm = self.flat.clip_(self.clip_grad) if self.clip_grad is not None else torch.linalg.vector_norm(self.flat.flat)
+            self.optimizer.step()
+            self._refresh_shadows()       # the bf16 weight shadows follow the update (eval right after training sees them)
+            self.flat.zero()
+        return norm
+
+    def _refresh_shadows(self):
+        rts = getattr(self.model, '_runtimes', None)
+        if rts:
+            params = list(self.model.parameters())
+            for rt in rts.values():
+                rt.refresh_shadows(params)
+
+    def _after_update(self):
+        # misc/engine.py:228: lr_scheduler.step_update((epoch * num_steps + idx) // ACCUMULATION_STEPS) runs AFTER the update of
+        # iteration idx with the count of updates done BEFORE it: 0, 1, 2, ...
+        if self.lr_scheduler is not None:
+            self.lr_scheduler.step_update(self.num_updates)
+        self.num_updates += 1
+
+    # -- public ------------------------------------------------------------------------------
+    def step(self, x, y):
+        """One call of the loop body.  Returns the (micro-batch) loss; ``last_norm`` holds the gradient norm of the
+        last update."""
+        last = (self._micro + 1) % self.accum == 0
+        self._micro += 1
+        if (self._g1 is not None and self.hip_opt and (self._micro - 1) % self.accum == 0
+                and self.optimizer.shadow_signature() != self._opt_signature):
+            # a bf16 weight shadow was re-created (or added) after capture: the captured forward / backward graphs read the old
+            # buffers and the captured update refreshes the old set.  Drop every graph; this cycle runs eagerly, the next re-captures.
+            torch.cuda.synchronize()
+            self._g1 = self._g2 = self._g_opt = None
+            self._eager_steps = 2 * self.accum - self.accum
+            self.recaptures += 1
+        if self.use_graph and self._g1 is None and self._eager_steps >= 2 * self.accum and (self._micro - 1) % self.accum == 0:
+            self._capture(x, y)     # at the start of an accumulation cycle, after two eager updates: the flat buffer is zero
+        if self._g1 is None:
+            if self.use_graph:             # warm up allocator, workspaces and weight shadows eagerly
+                self._eager_steps += 1
+            return self._eager(x, y, last)
+        self._static_x.copy_(x, non_blocking=True)
+        self._static_y.copy_(y, non_blocking=True)
+        buckets = self.flat.buckets()
+        self._g1.replay()
+        if self._g2 is not None:
+            if last and len(buckets) == 2:
+                self.flat.start_all_reduce(*buckets[0], group=self.group)   # runs under the encoder's backward
+            self._g2.replay()
+        if last:
+            if self._g2 is not None and len(buckets) == 2:
+                self.flat.start_all_reduce(*buckets[1], group=self.group)
+            else:
+                self.flat.start_all_reduce(0, self.flat.flat.numel(), group=self.group)
+            self.flat.finish_all_reduce()
+            self._sync_lr()
+            self._g_opt.replay()
+            self.last_norm = self._static_norm
+            self._after_update()
+        return self._static_loss
+
+    def _eager(self, x, y, last):
+        buckets = self.flat.buckets()
+        if self.split and torch.is_tensor(x) and x.dim() == 5:
+            loss, feats, dfeats = self._fwd_dec_bwd(x, y)
+            if last and len(buckets) == 2:
+                self.flat.start_all_reduce(*buckets[0], group=self.group)
+            self._enc_bwd(feats, dfeats)
+            if last:
+                if len(buckets) == 2:
+                    self.flat.start_all_reduce(*buckets[1], group=self.group)
+                else:
+                    self.flat.start_all_reduce(0, self.flat.flat.numel(), group=self.group)
+        else:
+            loss = self._fwd_bwd(x, y)
+            if last:
+                self.flat.start_all_reduce(0, self.flat.flat.numel(), group=self.group)
+        self._meter_loss(loss, y)
+        if last:
+            self.flat.finish_all_reduce()
+            self._sync_lr()
+            self.last_norm = self._update()
+            if self.meters is not None:
+                self.meters.update_norm(self.last_norm)
+            self._after_update()
+        return loss
+
+    def _capture(self, x, y):
+        if not torch.is_tensor(x):
+            raise TypeError('TrainStep(use_graph=True) replays on a static input tensor: pass use_graph=False for structured batches')
+        self._static_x, self._static_y = x.clone(), y.clone()
+        self._sync_lr()
+        torch.cuda.synchronize()
+        ops.pin_workspace()               # captured kernels bake buffer addresses in: later growth must not free them
+        for rt in getattr(self.model, '_runtimes', {}).values():
+            rt.pinned = True
+        split = self.split and torch.is_tensor(x) and x.dim() == 5
+        self._g1 = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self._g1, capture_error_mode=_CAPTURE_MODE):
+            if split:
+                self._static_loss, self._feats, self._dfeats = self._fwd_dec_bwd(self._static_x, self._static_y)
+            else:
+                self._static_loss = self._fwd_bwd(self._static_x, self._static_y)
+            self._meter_loss(self._static_loss, self._static_y)      # part of the replayed graph
+        if split:
+            self._g2 = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self._g2, pool=self._g1.pool(), capture_error_mode=_CAPTURE_MODE):
+                self._enc_bwd(self._feats, self._dfeats)
+        self._capture_update()
+
+    def _capture_update(self):
+        """(Re-)capture the update graph.  Its kernels bake in the optimizer's descriptor table, i.e. the set of weight-shadow
+        buffers to refresh; ``step`` compares that set before every replay."""
+        torch.cuda.synchronize()
+        if self.hip_opt:
+            self.optimizer._descriptors()          # build the table outside the capture
+            self._opt_signature = self.optimizer.shadow_signature()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, pool=self._g1.pool(), capture_error_mode=_CAPTURE_MODE):
+            norm = self._update()
+            if self.meters is not None:
+                self.meters.update_norm(norm)
+        if self._static_norm is None:
+            self._static_norm = norm
+        elif norm.data_ptr() != self._static_norm.data_ptr():
+            self._static_norm = norm
+        self._g_opt = g

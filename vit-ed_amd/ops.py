@@ -202,6 +202,28 @@ def crop_pairs_u8(regions: torch.Tensor, cells: torch.Tensor, erode: torch.Tenso
     return out
 
 
+def _store_args(store: torch.Tensor, img_off: torch.Tensor, img_hw: torch.Tensor) -> int:
+    """The resident image store of the feed entry points (``engine.Div2kImageStore``); returns its image count."""
+    assert store.dtype == torch.uint8 and store.dim() == 1 and store.is_contiguous()
+    assert img_off.dtype == torch.int64 and img_off.dim() == 1 and img_off.is_contiguous()
+    assert img_hw.dtype == torch.int32 and img_hw.shape == (img_off.numel(), 2) and img_hw.is_contiguous()
+    return img_off.numel()
+
+
+def _batch_args(b: int, *specs):
+    for t, dtype, shape in specs:
+        assert t.dtype == dtype and tuple(t.shape) == (b, *shape) and t.is_contiguous(), (t.dtype, tuple(t.shape), dtype, (b, *shape))
+
+
+def _crop_args(img: torch.Tensor, out: torch.Tensor | None, in_place: bool):
+    """(B, S, out) of uint8 crops [B, 3, S, S] and an ``out`` like them (made here when None); it may be ``img`` only with ``in_place``."""
+    assert img.dtype == torch.uint8 and img.dim() == 4 and img.shape[1] == 3 and img.shape[2] == img.shape[3] and img.is_contiguous()
+    if out is None:
+        out = torch.empty_like(img)
+    assert out.dtype == torch.uint8 and out.shape == img.shape and out.is_contiguous() and (in_place or out.data_ptr() != img.data_ptr())
+    return img.shape[0], img.shape[2], out
+
+
 def div2k_regions_u8(store: torch.Tensor, img_off: torch.Tensor, img_hw: torch.Tensor, image: torch.Tensor, flags: torch.Tensor,
                      minv: torch.Tensor, rgb: torch.Tensor, crop: torch.Tensor, img_size: int,
                      out: torch.Tensor | None = None) -> torch.Tensor:
@@ -211,25 +233,15 @@ def div2k_regions_u8(store: torch.Tensor, img_off: torch.Tensor, img_hw: torch.T
     img_off int64 [n] with sizes img_hw int32 [n, 2] (H, W); the caller guarantees that every image lies inside the store and is
     at least 2 S x 3 S (``engine.Div2kImageStore`` does).  Indices and origins are clamped by the kernel."""
     _need_gpu(store, img_off, img_hw, image, flags, minv, rgb, crop, out)
-    s = int(img_size)
-    n, b = img_off.numel(), image.numel()
-    assert store.dtype == torch.uint8 and store.dim() == 1 and store.is_contiguous()
-    assert img_off.dtype == torch.int64 and img_off.dim() == 1 and img_off.is_contiguous()
-    assert img_hw.dtype == torch.int32 and img_hw.shape == (n, 2) and img_hw.is_contiguous()
-    for t, dtype, shape in ((image, torch.int32, (b,)), (flags, torch.int32, (b,)), (minv, torch.float64, (b, 6)),
-                            (rgb, torch.float32, (b, 3)), (crop, torch.int32, (b, 2))):
-        assert t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous(), (t.dtype, tuple(t.shape), dtype, shape)
+    s, n, b = int(img_size), _store_args(store, img_off, img_hw), image.numel()
+    _batch_args(b, (image, torch.int32, ()), (flags, torch.int32, ()), (minv, torch.float64, (6,)), (rgb, torch.float32, (3,)),
+                (crop, torch.int32, (2,)))
     if out is None:
         out = torch.empty((b, 3, 2 * s, 3 * s), dtype=torch.uint8, device=store.device)
     assert out.dtype == torch.uint8 and tuple(out.shape) == (b, 3, 2 * s, 3 * s) and out.is_contiguous()
     _lib.call('vited_div2k_regions_u8', _ptr(store), _ptr(img_off), _ptr(img_hw), n, _ptr(image), _ptr(flags), _ptr(minv), _ptr(rgb),
               _ptr(crop), _ptr(out), b, s, _stream())
     return out
-
-
-def _batch_args(b: int, *specs):
-    for t, dtype, shape in specs:
-        assert t.dtype == dtype and tuple(t.shape) == (b, *shape) and t.is_contiguous(), (t.dtype, tuple(t.shape), dtype, (b, *shape))
 
 
 def hisfrag_windows_u8(store: torch.Tensor, img_off: torch.Tensor, img_hw: torch.Tensor, image: torch.Tensor, flags: torch.Tensor,
@@ -240,11 +252,7 @@ def hisfrag_windows_u8(store: torch.Tensor, img_off: torch.Tensor, img_hw: torch
     the inverse warp map fp64 [B, 6] and the window origin int32 [B, 2] (top, left) in unpadded image coordinates, negative in the
     pad.  store / img_off / img_hw as for ``div2k_regions_u8``.  Everything outside the image is 0; indices are clamped."""
     _need_gpu(store, img_off, img_hw, image, flags, afix, minv, origin, out)
-    s = int(img_size)
-    n, b = img_off.numel(), image.numel()
-    assert store.dtype == torch.uint8 and store.dim() == 1 and store.is_contiguous()
-    assert img_off.dtype == torch.int64 and img_off.dim() == 1 and img_off.is_contiguous()
-    assert img_hw.dtype == torch.int32 and img_hw.shape == (n, 2) and img_hw.is_contiguous()
+    s, n, b = int(img_size), _store_args(store, img_off, img_hw), image.numel()
     _batch_args(b, (image, torch.int32, ()), (flags, torch.int32, ()), (afix, torch.int64, (6,)), (minv, torch.float64, (6,)),
                 (origin, torch.int32, (2,)))
     if out is None:
@@ -262,12 +270,8 @@ def hisfrag_jitter_u8(img: torch.Tensor, flags: torch.Tensor, order: torch.Tenso
     (0 brightness, 1 contrast, 2 saturation, 3 hue), the brightness / contrast / saturation factors fp32 [B, 3] and the uint8 hue
     shift int32 [B].  ``out`` may be ``img`` itself."""
     _need_gpu(img, flags, order, factors, hue, out)
-    assert img.dtype == torch.uint8 and img.dim() == 4 and img.shape[1] == 3 and img.shape[2] == img.shape[3] and img.is_contiguous()
-    b, s = img.shape[0], img.shape[2]
+    b, s, out = _crop_args(img, out, in_place=True)
     _batch_args(b, (flags, torch.int32, ()), (order, torch.int32, (4,)), (factors, torch.float32, (3,)), (hue, torch.int32, ()))
-    if out is None:
-        out = torch.empty_like(img)
-    assert out.dtype == torch.uint8 and out.shape == img.shape and out.is_contiguous()
     sums = torch.empty(b, dtype=torch.int64, device=img.device)             # the contrast means' L sums; the entry point zeroes them
     _lib.call('vited_hisfrag_jitter_u8', _ptr(img), _ptr(flags), _ptr(order), _ptr(factors), _ptr(hue), _ptr(sums), _ptr(out), b, s, _stream())
     return out
@@ -277,12 +281,8 @@ def hisfrag_blur_u8(img: torch.Tensor, flags: torch.Tensor, weights: torch.Tenso
     """GaussianBlur((3, 3)) on uint8 crops [B, 3, S, S] (``vited_hisfrag_blur_u8``; hisfrag.py:76-78): per sample flag bit 8 (blur on; a
     sample without it is copied) and the 1-D weights (k_edge, k_mid) fp32 [B, 2].  ``out`` must not overlap ``img``."""
     _need_gpu(img, flags, weights, out)
-    assert img.dtype == torch.uint8 and img.dim() == 4 and img.shape[1] == 3 and img.shape[2] == img.shape[3] and img.is_contiguous()
-    b, s = img.shape[0], img.shape[2]
+    b, s, out = _crop_args(img, out, in_place=False)
     _batch_args(b, (flags, torch.int32, ()), (weights, torch.float32, (2,)))
-    if out is None:
-        out = torch.empty_like(img)
-    assert out.dtype == torch.uint8 and out.shape == img.shape and out.is_contiguous() and out.data_ptr() != img.data_ptr()
     _lib.call('vited_hisfrag_blur_u8', _ptr(img), _ptr(flags), _ptr(weights), _ptr(out), b, s, _stream())
     return out
 
@@ -297,11 +297,7 @@ def michigan_windows_u8(store: torch.Tensor, img_off: torch.Tensor, img_hw: torc
     n_holes int32 [B] count.  store / img_off / img_hw as for ``div2k_regions_u8``.  Everything outside the image, and a tap outside
     the window, is 255; indices and the hole count are clamped."""
     _need_gpu(store, img_off, img_hw, image, flags, origin, x0, kx, y0, ky, holes, n_holes, out)
-    s = int(img_size)
-    n, b = img_off.numel(), image.numel()
-    assert store.dtype == torch.uint8 and store.dim() == 1 and store.is_contiguous()
-    assert img_off.dtype == torch.int64 and img_off.dim() == 1 and img_off.is_contiguous()
-    assert img_hw.dtype == torch.int32 and img_hw.shape == (n, 2) and img_hw.is_contiguous()
+    s, n, b = int(img_size), _store_args(store, img_off, img_hw), image.numel()
     i32 = torch.int32
     _batch_args(b, (image, i32, ()), (flags, i32, ()), (origin, i32, (2,)), (x0, i32, (s,)), (kx, i32, (s, 3)), (y0, i32, (s,)),
                 (ky, i32, (s, 3)), (holes, i32, (16, 4)), (n_holes, i32, ()))
@@ -318,12 +314,8 @@ def michigan_blur_gray_u8(img: torch.Tensor, flags: torch.Tensor, weights: torch
     michigan.py:83-85): per sample flag bit 8 (blur), bit 32 (grey; a sample with neither is copied) and the box-blur weights
     (ww, fw) int32 [B, 2].  ``out`` must not overlap ``img``."""
     _need_gpu(img, flags, weights, out)
-    assert img.dtype == torch.uint8 and img.dim() == 4 and img.shape[1] == 3 and img.shape[2] == img.shape[3] and img.is_contiguous()
-    b, s = img.shape[0], img.shape[2]
+    b, s, out = _crop_args(img, out, in_place=False)
     _batch_args(b, (flags, torch.int32, ()), (weights, torch.int32, (2,)))
-    if out is None:
-        out = torch.empty_like(img)
-    assert out.dtype == torch.uint8 and out.shape == img.shape and out.is_contiguous() and out.data_ptr() != img.data_ptr()
     _lib.call('vited_michigan_blur_gray_u8', _ptr(img), _ptr(flags), _ptr(weights), _ptr(out), b, s, _stream())
     return out
 
