@@ -232,6 +232,33 @@ int vited_layernorm_bwd_scaled(const void* dy, int dy_dtype, int64_t dy_ld, cons
 int vited_scale_rows_cast(const float* src, int64_t src_ld, const float* row_scale, void* dst, int dst_dtype, int64_t dst_ld,
                           int64_t rows, int64_t dim, void* stream);
 
+/* ---- q/k-norm (qk_norm=True: q_norm / k_norm = LayerNorm(head_dim, eps=1e-6), vision_transformer.py:35-36,60,153-154,180) ---- */
+
+/* For every token row and head: out[r, h, :] = (x[r, h, :] - mean) * rstd * gamma + beta over the head_dim elements, biased
+ * variance of the centred values, statistics in fp32.  q and k are the two operands of ONE launch; either may be null (then its
+ * other arguments are ignored), not both.  Each is `dtype` (VITED_F32 / VITED_BF16) [rows, heads * head_dim] with its own row
+ * stride and a dense last dim - a column slice of the packed [M, 3D] / [M, 2D] projection or a dense [M, D] - and its own row
+ * count; the output has the same shape and its own row stride (it may be the input itself: in place).  gamma / beta fp32
+ * [head_dim], shared by all heads; mean / rstd fp32 [rows, heads] dense, saved for the backward.  head_dim 32 or 64 (else
+ * VITED_ERR_UNSUPPORTED); a null pointer of a present operand, a row stride below heads * head_dim (rows would overlap) or a
+ * pointer / stride that is no multiple of a lane's vector (head_dim / 8 elements, 16 bytes at most) is VITED_ERR_BAD_ARG. */
+int vited_qk_norm_fwd(const void* q, int64_t q_ld, int64_t q_rows, const void* k, int64_t k_ld, int64_t k_rows,
+                      const float* gamma_q, const float* beta_q, const float* gamma_k, const float* beta_k, void* q_out,
+                      int64_t q_out_ld, void* k_out, int64_t k_out_ld, float* q_mean, float* q_rstd, float* k_mean,
+                      float* k_rstd, int dtype, int64_t heads, int64_t head_dim, float eps, void* stream);
+
+/* Backward of vited_qk_norm_fwd.  dq / dk hold d(out) on entry (where the attention backward wrote it, inside the d(qkv) / d(q) /
+ * d(kv) buffers) and d(x) on return: dx = rstd * (g - mean_d(g) - xhat * mean_d(g * xhat)), g = dy * gamma, xhat recomputed from
+ * the saved pre-norm q / k and mean / rstd.  dgamma += / = sum dy * xhat, dbeta += / = sum dy over all rows and heads (fp32
+ * [head_dim]; `accumulate` != 0 adds onto their content), from per-workgroup partial rows in `workspace` summed in a fixed order:
+ * no atomics, two runs give the same bits.  Either operand may be null.  workspace >= *_workspace_bytes. */
+int64_t vited_qk_norm_bwd_workspace_bytes(int64_t q_rows, int64_t k_rows, int64_t heads, int64_t head_dim);
+int vited_qk_norm_bwd(void* dq, int64_t dq_ld, const void* q, int64_t q_ld, const float* q_mean, const float* q_rstd,
+                      const float* gamma_q, float* dgamma_q, float* dbeta_q, int64_t q_rows, void* dk, int64_t dk_ld,
+                      const void* k, int64_t k_ld, const float* k_mean, const float* k_rstd, const float* gamma_k,
+                      float* dgamma_k, float* dbeta_k, int64_t k_rows, int dtype, int accumulate, int64_t heads,
+                      int64_t head_dim, float* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- Linear / GEMM (nn.Linear: qkv :34, proj :38, q :151, kv :152, timm Mlp fc1/fc2, head) ---- */
 
 /* acc[m, n] = sum_k A[m, k] * B(n, k), fp32 accumulation; A is `dtype` [M, K] (row stride lda);
@@ -367,6 +394,7 @@ int vited_mlp_fwd(const float* x, int64_t ldx, const float* gamma, const float* 
 /* One encoder Block forward (Block.forward, vision_transformer.py:124-127) behind one call: the launch sequence
  * LayerNorm -> qkv GEMM -> attention -> proj + residual -> fused MLP branch on `stream` (5 launches; 7 when the MLP shape is
  * outside vited_mlp_fwd's cover).  bf16 activations, fp32 residual stream, inference form (nothing saved for backward).
+ * The whole-block entries (this one and vited_cross_block_fwd) have no q/k-norm.
  *   x, y       fp32 [batch * tokens, dim] dense; y may not alias x
  *   wqkv [3 dim, dim], wproj [dim, dim], w1 [hidden, dim], w2 [dim, hidden]   bf16 dense; biases and LayerNorm parameters fp32
  *   workspace  >= vited_block_workspace_bytes(), 256-byte aligned */

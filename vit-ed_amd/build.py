@@ -7,10 +7,12 @@ part of the ViT-ED hot path and are rejected with a clear message.
 from .model import VisionTransformerCustom
 
 
-def build_model(config, is_pretrain=False, drop_path_rate=None):
+def build_model(config, is_pretrain=False, drop_path_rate=None, qk_norm=None):
     """``drop_path_rate``: stochastic depth.  The default (None) reads exactly the keys the reference reads, and the reference's
     factory does not forward ``MODEL.DROP_PATH_RATE`` to the pjs model - the shipped YAMLs set it to 0.1 without effect.  Pass
-    ``drop_path_rate=config.MODEL.DROP_PATH_RATE`` to train the regularised model those configs describe."""
+    ``drop_path_rate=config.MODEL.DROP_PATH_RATE`` to train the regularised model those configs describe.
+    ``qk_norm``: q/k-norm in every attention.  The reference's factory has no config key for it, so the default (None) leaves it off;
+    ``qk_norm=True`` builds the model with ``q_norm`` / ``k_norm`` (a checkpoint of the reference class trained with it loads)."""
     model_type = config.MODEL.TYPE
     if model_type != 'pjs':
         raise NotImplementedError(
@@ -31,4 +33,5 @@ def build_model(config, is_pretrain=False, drop_path_rate=None):
         keep_attn=pjs.KEEP_ATTN,
         arch_version=pjs.ARCH_VERSION,
         drop_path_rate=0. if drop_path_rate is None else drop_path_rate,
+        qk_norm=bool(qk_norm),
     )

@@ -9,6 +9,7 @@ These are the op-level building blocks of the reference's layers, usable from or
   operator                     reference code it replaces                             C entry points
   ===========================  =====================================================  ==============================
   ``vited::layernorm``         ``nn.LayerNorm(eps=1e-6)`` vision_transformer.py:108   vited_layernorm_fwd / _bwd
+  ``vited::qk_norm``           ``q, k = self.q_norm(q), self.k_norm(k)`` (:60, :180)  vited_qk_norm_fwd / _bwd
   ``vited::linear``            ``nn.Linear`` (:33,36,151,152,154 and timm Mlp.fc2)     vited_gemm, vited_linear_bwd_weight
   ``vited::mlp``               timm ``Mlp`` fc1 -> GELU(erf) -> fc2 (:115,259)        vited_gemm (GELU / GELU' epilogues)
   ``vited::attention``         ``F.scaled_dot_product_attention`` (:60-65,181-186)    vited_attention_fwd / _bwd
@@ -105,6 +106,86 @@ def _ln_backward(ctx, dy, _dmean, _drstd):
 
 
 register_autograd('vited::layernorm', _ln_backward, setup_context=_ln_setup)
+
+
+# ---------------------------------------------------------------------------------------------
+# q/k-norm: LayerNorm(head_dim) of every head's query and key row, both in one launch
+# ---------------------------------------------------------------------------------------------
+def _qk_operand(t: Tensor, dtype=None) -> Tensor:
+    t2 = _rows(t)
+    if dtype is not None:
+        t2 = t2.to(dtype)
+    elif t2.dtype not in (torch.float32, _LOWP):
+        t2 = t2.to(_LOWP)
+    return t2 if t2.stride(-1) == 1 else t2.contiguous()
+
+
+def _qk_param(p: Tensor) -> Tensor:
+    return p.detach().float().contiguous()
+
+
+@custom_op('vited::qk_norm', mutates_args=(), device_types='cuda')
+def qk_norm(q: Tensor, k: Tensor, q_weight: Tensor, q_bias: Tensor, k_weight: Tensor, k_bias: Tensor, heads: int,
+            eps: float) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """q_norm(q), k_norm(k) of the reference's attention with ``qk_norm=True``: LayerNorm over the head_dim elements of every head.
+    q [..., heads * head_dim], k likewise (token-major, the layout of the packed projections; last-dim slices are read in place; the
+    two may differ in rows), fp32 or bf16; the weights / biases are [head_dim].  Returns (q_out, k_out, q_mean, q_rstd, k_mean,
+    k_rstd) with the statistics fp32 [rows, heads]."""
+    q2 = _qk_operand(q)
+    k2 = _qk_operand(k, q2.dtype)
+    qo, ko, (qm, qs), (km, ks) = ops.qk_norm_fwd(q2, k2, _qk_param(q_weight), _qk_param(q_bias), _qk_param(k_weight), _qk_param(k_bias), heads,
+                                                 eps)
+    return qo.view(q.shape), ko.view(k.shape), qm, qs, km, ks
+
+
+@qk_norm.register_fake
+def _(q, k, q_weight, q_bias, k_weight, k_bias, heads, eps):
+    dt = q.dtype if q.dtype in (torch.float32, _LOWP) else _LOWP
+    f = torch.float32
+    qr, kr = q.numel() // q.shape[-1], k.numel() // k.shape[-1]
+    return (q.new_empty(q.shape, dtype=dt), k.new_empty(k.shape, dtype=dt), q.new_empty((qr, heads), dtype=f), q.new_empty((qr, heads), dtype=f),
+            k.new_empty((kr, heads), dtype=f), k.new_empty((kr, heads), dtype=f))
+
+
+@custom_op('vited::qk_norm_backward', mutates_args=(), device_types='cuda')
+def qk_norm_backward(dq: Tensor, dk: Tensor, q: Tensor, k: Tensor, q_weight: Tensor, k_weight: Tensor, q_mean: Tensor, q_rstd: Tensor,
+                     k_mean: Tensor, k_rstd: Tensor, heads: int) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """(d q, d k, d q_weight, d q_bias, d k_weight, d k_bias) of vited::qk_norm.  The kernel works in place on copies of dq / dk."""
+    q2 = _qk_operand(q)
+    k2 = _qk_operand(k, q2.dtype)
+    dq2 = _rows(dq).to(q2.dtype).clone(memory_format=torch.contiguous_format)
+    dk2 = _rows(dk).to(q2.dtype).clone(memory_format=torch.contiguous_format)
+    dgq, dbq, dgk, dbk = ops.qk_norm_bwd(dq2, q2, (q_mean, q_rstd), _qk_param(q_weight), dk2, k2, (k_mean, k_rstd), _qk_param(k_weight), heads)
+    return dq2.view(q.shape), dk2.view(k.shape), dgq, dbq, dgk, dbk
+
+
+@qk_norm_backward.register_fake
+def _(dq, dk, q, k, q_weight, k_weight, q_mean, q_rstd, k_mean, k_rstd, heads):
+    dt = q.dtype if q.dtype in (torch.float32, _LOWP) else _LOWP
+    f = torch.float32
+    return (q.new_empty(q.shape, dtype=dt), k.new_empty(k.shape, dtype=dt), q_weight.new_empty(q_weight.shape, dtype=f),
+            q_weight.new_empty(q_weight.shape, dtype=f), k_weight.new_empty(k_weight.shape, dtype=f), k_weight.new_empty(k_weight.shape, dtype=f))
+
+
+def _qkn_setup(ctx, inputs, output):
+    q, k, q_weight, q_bias, k_weight, k_bias, heads, _eps = inputs
+    _qo, _ko, qm, qs, km, ks = output
+    ctx.save_for_backward(q, k, q_weight, k_weight, qm, qs, km, ks)
+    ctx.heads, ctx.bias_dtypes = heads, (q_bias.dtype, k_bias.dtype)
+
+
+def _qkn_backward(ctx, dq, dk, *_dstats):
+    q, k, q_weight, k_weight, qm, qs, km, ks = ctx.saved_tensors
+    if dq is None:
+        dq = torch.zeros_like(q)
+    if dk is None:
+        dk = torch.zeros_like(k)
+    dqi, dki, dgq, dbq, dgk, dbk = torch.ops.vited.qk_norm_backward(dq, dk, q, k, q_weight, k_weight, qm, qs, km, ks, ctx.heads)
+    return (dqi.to(q.dtype), dki.to(k.dtype), dgq.to(q_weight.dtype), dbq.to(ctx.bias_dtypes[0]), dgk.to(k_weight.dtype),
+            dbk.to(ctx.bias_dtypes[1]), None, None)
+
+
+register_autograd('vited::qk_norm', _qkn_backward, setup_context=_qkn_setup)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -371,5 +452,5 @@ def _(img, patch, lowp):
 for _name in ('vited::linear', 'vited::mlp', 'vited::attention'):
     torch.library.register_autocast(_name, 'cuda', _LOWP)
 
-OPERATORS = ('layernorm', 'layernorm_backward', 'linear', 'linear_backward', 'mlp', 'mlp_backward', 'attention',
+OPERATORS = ('layernorm', 'layernorm_backward', 'qk_norm', 'qk_norm_backward', 'linear', 'linear_backward', 'mlp', 'mlp_backward', 'attention',
              'attention_backward', 'patchify', 'linear_residual_layernorm', 'linear_layernorm_backward')

@@ -38,8 +38,14 @@ _CROSS = ('gc=norm_cross.weight bc=norm_cross.bias gx=norm_context.weight bx=nor
           'bq=cross_attn.q.bias wkv=cross_attn.kv.weight bkv=cross_attn.kv.bias wcp=cross_attn.proj.weight bcp=cross_attn.proj.bias ')
 _MLP = 'g2=norm2.weight b2=norm2.bias w1=mlp.fc1.weight bb1=mlp.fc1.bias w2=mlp.fc2.weight bb2=mlp.fc2.bias'
 _PATCH = 'pw=patch_embed.proj.weight pb=patch_embed.proj.bias pos=pos_embed '
+# q/k-norm (qk_norm=True): LayerNorm(head_dim) of the self-attention's and of the cross-attention's queries and keys
+_QKN = 'gqn=attn.q_norm.weight bqn=attn.q_norm.bias gkn=attn.k_norm.weight bkn=attn.k_norm.bias '
+_CQKN = ('gcqn=cross_attn.q_norm.weight bcqn=cross_attn.q_norm.bias gckn=cross_attn.k_norm.weight '
+         'bckn=cross_attn.k_norm.bias ')
 EncBlock, ENC_BLOCK_KEYS = _bundle('EncBlock', _ATTN + _MLP)
 DecBlock, DEC_BLOCK_KEYS = _bundle('DecBlock', _ATTN + _CROSS + _MLP)
+EncBlockQK, ENC_BLOCK_QK_KEYS = _bundle('EncBlockQK', _ATTN + _QKN + _MLP)            # the blocks of a qk_norm=True model
+DecBlockQK, DEC_BLOCK_QK_KEYS = _bundle('DecBlockQK', _ATTN + _QKN + _CROSS + _CQKN + _MLP)
 EncShared, ENC_SHARED_KEYS = _bundle('EncShared', _PATCH)
 DecShared, DEC_SHARED_KEYS = _bundle('DecShared', _PATCH + 'cls=cls_token gN=norm.weight bN=norm.bias wh=head.weight bh=head.bias')
 
@@ -86,7 +92,9 @@ class Runtime:
     """Per-model launch context: static shape, activation dtype and the low-precision weight shadows."""
 
     def __init__(self, *, img_size, patch_size, in_chans, num_classes, embed_dim, depth, c_depth, num_heads,
-                 act_dtype=torch.bfloat16):
+                 act_dtype=torch.bfloat16, qk_norm=False):
+        self.qk_norm = bool(qk_norm)   # q_norm / k_norm in every attention (ops.qk_norm_fwd / _bwd; DESIGN.md section 24)
+        self.enc_block, self.dec_block = (EncBlockQK, DecBlockQK) if self.qk_norm else (EncBlock, DecBlock)   # the blocks' bundles
         self.img_size, self.patch_size, self.in_chans = img_size, patch_size, in_chans
         self.num_classes, self.dim, self.depth, self.c_depth, self.heads = num_classes, embed_dim, depth, c_depth, num_heads
         self.n1 = (img_size // patch_size) ** 2
@@ -465,29 +473,73 @@ def _cam_only(rt, grads):
     return [None] * len(grads) if rt.keep_cam else grads
 
 
-def _self_attn_fwd(rt, h, wqkv, bqkv, batch, n, key=None):
+_QKN_FIELDS = ('gqn', 'bqn', 'gkn', 'bkn')
+
+
+def _qk_norm_self(rt, qkv, P, batch, n, cls_only=False):
+    """q_norm / k_norm of a self-attention on the packed projection qkv [batch n, 3D] (vision_transformer.py:60): the pre-norm q / k
+    stay where the GEMM wrote them (the backward recomputes xhat from them), the normalised ones go to a buffer of their own that
+    the attention kernels read.  ``cls_only``: the query is row 0 of every sample alone.
+    Returns (q view [batch, nq, D], k view [batch, n, D], saved = (normalised buffers, q statistics, k statistics))."""
     d = rt.dim
-    qkv = ops.gemm(h, rt.weight(wqkv), bias=bqkv)                   # [M, 3D], columns [3][h][hd] (:58)
+    if cls_only:
+        qn = torch.empty((batch, d), dtype=qkv.dtype, device=qkv.device)
+        kn = torch.empty((batch * n, d), dtype=qkv.dtype, device=qkv.device)
+        _, _, sq, sk = ops.qk_norm_fwd(qkv.view(batch, n * 3 * d)[:, 0:d], qkv[:, d:2 * d], P.gqn, P.bqn, P.gkn, P.bkn, rt.heads, LN_EPS,
+                                       out=(qn, kn))
+        return qn.view(batch, 1, d), kn.view(batch, n, d), ((qn, kn), sq, sk)
+    qk = torch.empty((batch * n, 2 * d), dtype=qkv.dtype, device=qkv.device)
+    _, _, sq, sk = ops.qk_norm_fwd(qkv[:, 0:d], qkv[:, d:2 * d], P.gqn, P.bqn, P.gkn, P.bkn, rt.heads, LN_EPS,
+                                   out=(qk[:, 0:d], qk[:, d:2 * d]))
+    qk3 = qk.view(batch, n, 2 * d)
+    return qk3[:, :, 0:d], qk3[:, :, d:2 * d], (qk, sq, sk)
+
+
+def _qk_norm_self_bwd(rt, dqkv, qkv, P, qkn, batch, n, cls_only=False):
+    """Backward of _qk_norm_self, in place on the q and k columns of dqkv (they then are the gradient of the qkv projection's output).
+    Returns the four norm-parameter gradients by field name - None when accumulated in place."""
+    d = rt.dim
+    _, sq, sk = qkn
+    rows = (lambda t: t.view(batch, n * 3 * d)[:, 0:d]) if cls_only else (lambda t: t[:, 0:d])
+    targets = [_gtarget(rt, p) for p in (P.gqn, P.bqn, P.gkn, P.bkn)]
+    direct = all(t is not None for t in targets)
+    got = ops.qk_norm_bwd(rows(dqkv), rows(qkv), sq, P.gqn, dqkv[:, d:2 * d], qkv[:, d:2 * d], sk, P.gkn, rt.heads,
+                          *(targets if direct else ()))
+    return dict.fromkeys(_QKN_FIELDS) if direct else dict(zip(_QKN_FIELDS, got))
+
+
+def _self_attn_fwd(rt, h, P, batch, n, key=None):
+    """Returns (qkv, o, lse, qkn): ``qkn`` is what the q/k-norm saved (_qk_norm_self), None on a model without it."""
+    d = rt.dim
+    qkv = ops.gemm(h, rt.weight(P.wqkv), bias=P.bqkv)               # [M, 3D], columns [3][h][hd] (:58)
     qkv3 = qkv.view(batch, n, 3 * d)
-    o, lse = ops.attention_fwd(qkv3[:, :, 0:d], qkv3[:, :, d:2 * d], qkv3[:, :, 2 * d:3 * d], rt.heads, rt.scale)
+    q3, k3, qkn = qkv3[:, :, 0:d], qkv3[:, :, d:2 * d], None
+    if rt.qk_norm:
+        q3, k3, qkn = _qk_norm_self(rt, qkv, P, batch, n)
+    o, lse = ops.attention_fwd(q3, k3, qkv3[:, :, 2 * d:3 * d], rt.heads, rt.scale)
     if rt.keep_attn and key is not None:
-        _keep_attention(rt, key, qkv3[:, :, 0:d], qkv3[:, :, d:2 * d])
-    return qkv, o.view(batch * n, d), lse
+        _keep_attention(rt, key, q3, k3)
+    return qkv, o.view(batch * n, d), lse, qkn
 
 
-def _self_attn_bwd(rt, do, qkv, o, lse, batch, n, key=None):
+def _self_attn_bwd(rt, do, qkv, o, lse, batch, n, key=None, P=None, qkn=None):
+    """Returns (dqkv, the q/k-norm parameter gradients by field name: empty without the norm)."""
     d = rt.dim
     qkv3 = qkv.view(batch, n, 3 * d)
+    q3, k3 = qkv3[:, :, 0:d], qkv3[:, :, d:2 * d]
+    if qkn is not None:                                 # the attention saw the normalised q / k
+        qk3 = qkn[0].view(batch, n, 2 * d)
+        q3, k3 = qk3[:, :, 0:d], qk3[:, :, d:2 * d]
     if rt.keep_attn and key is not None:
         _keep_attention_grad(rt, key, do.view(batch, n, d), qkv3[:, :, 2 * d:3 * d])
     if rt.keep_cam and key is not None:
-        _keep_attention_cam(rt, key, qkv3[:, :, 0:d], qkv3[:, :, d:2 * d], qkv3[:, :, 2 * d:3 * d], do.view(batch, n, d), lse)
+        _keep_attention_cam(rt, key, q3, k3, qkv3[:, :, 2 * d:3 * d], do.view(batch, n, d), lse)
     dqkv = torch.empty_like(qkv)
     dqkv3 = dqkv.view(batch, n, 3 * d)
-    ops.attention_bwd(qkv3[:, :, 0:d], qkv3[:, :, d:2 * d], qkv3[:, :, 2 * d:3 * d], o.view(batch, n, d),
+    ops.attention_bwd(q3, k3, qkv3[:, :, 2 * d:3 * d], o.view(batch, n, d),
                       do.view(batch, n, d), lse, rt.heads, rt.scale, dqkv3[:, :, 0:d], dqkv3[:, :, d:2 * d],
                       dqkv3[:, :, 2 * d:3 * d])
-    return dqkv
+    return dqkv, (_qk_norm_self_bwd(rt, dqkv, qkv, P, qkn, batch, n) if qkn is not None else {})
 
 
 FUSED_MLP_TILE = 128        # token rows per workgroup of vited_mlp_fwd (one workgroup per CU)
@@ -556,19 +608,19 @@ def _attn_branch_fwd(rt, x, P, batch, n, key=None, ln=None, next_ln=None, scale=
     """x + proj(attention(qkv(LayerNorm(x)))) with the block's norm1 / attn parameters; ``ln`` / ``next_ln`` as in _mlp_fwd.
     Returns (y, saved, next | None)."""
     h, mean, rstd = ln if ln is not None else ops.layernorm_fwd(x, P.g1, P.b1, LN_EPS, rt.act_dtype)
-    qkv, o, lse = _self_attn_fwd(rt, h, P.wqkv, P.bqkv, batch, n, key)
+    qkv, o, lse, qkn = _self_attn_fwd(rt, h, P, batch, n, key)
     y, nxt = _res_linear(rt, o, P.wproj, P.bproj, x, next_ln, scale)
-    return y, (mean, rstd, h, qkv, o, lse), nxt
+    return y, (mean, rstd, h, qkv, o, lse, qkn), nxt
 
 
 def _attn_branch_bwd(rt, dy, dy_lp, x, P, saved, batch, n, key=None, lp_scale=None):
     """Backward of _attn_branch_fwd (``lp_scale`` as in _mlp_bwd).  Returns (dx, its low-precision copy, the six parameter gradients by
     field name)."""
-    mean, rstd, h, qkv, o, lse = saved
+    mean, rstd, h, qkv, o, lse, qkn = saved
     do, dwproj, dbproj = _linear_bwd(rt, dy_lp, o, P.wproj, P.bproj)
-    dqkv = _self_attn_bwd(rt, do, qkv, o, lse, batch, n, key)
+    dqkv, gn = _self_attn_bwd(rt, do, qkv, o, lse, batch, n, key, P, qkn)
     dx, dx_lp, dg1, db1, dwqkv, dbqkv = _linear_ln_bwd(rt, dqkv, h, P.wqkv, P.bqkv, x, P.g1, P.b1, mean, rstd, dx_in=dy, lp_scale=lp_scale)
-    return dx, dx_lp, dict(g1=dg1, b1=db1, wqkv=dwqkv, bqkv=dbqkv, wproj=dwproj, bproj=dbproj)
+    return dx, dx_lp, dict(g1=dg1, b1=db1, wqkv=dwqkv, bqkv=dbqkv, wproj=dwproj, bproj=dbproj, **gn)
 
 
 def _patch_tokens_fwd(rt, img, S, with_cls, batch_index=None):
@@ -613,7 +665,7 @@ def _norm1_of(blocks, i):
 class EncoderFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, rt: Runtime, img, *params):
-        shared, blocks = split_params(params, EncShared, EncBlock)
+        shared, blocks = split_params(params, EncShared, rt.enc_block)
         grad = any(ctx.needs_input_grad)  # False under no_grad: nothing is saved for inference
         x, patches, batch, n = _patch_tokens_fwd(rt, img, shared, with_cls=False)
         drop = _take_drop_rows(rt, 0, len(blocks), 2, batch, n, x.device)      # stochastic depth: per-row scales of (attn, mlp) per block
@@ -655,7 +707,7 @@ class EncoderFn(torch.autograd.Function):
                                                      lp_scale=scale_of(i - 1, 1))
                 if rt.tap is not None:
                     rt.tap[f'enc.dx.{i}'] = dx.clone()      # gradient w.r.t. the INPUT of encoder block i
-                gblocks[i] = EncBlock(**ga, **gm)
+                gblocks[i] = rt.enc_block(**ga, **gm)
         gshared = EncShared(**_patch_tokens_bwd(rt, dx, ctx.patches, shared, with_cls=False, batch=batch))
         ctx.tape = ctx.patches = ctx.drop = None
         return (None, None, *_cam_only(rt, flatten_params(gshared, gblocks)))
@@ -688,11 +740,14 @@ def _dec_self_fwd(rt, x, P, batch, n, cls_only, key=None, ln1=None, fuse_ln=True
     h1, m1, r1 = ln1 if ln1 is not None else ops.layernorm_fwd(x, P.g1, P.b1, LN_EPS, rt.act_dtype)
     qkv = ops.gemm(h1, rt.weight(P.wqkv), bias=P.bqkv)            # K and V of every row feed query 0
     qkv3 = qkv.view(batch, n, 3 * d)
-    o0, lse0 = ops.attention_fwd(qkv3[:, 0:1, 0:d], qkv3[:, :, d:2 * d], qkv3[:, :, 2 * d:3 * d], rt.heads, rt.scale)
+    q0, k3, qkn = qkv3[:, 0:1, 0:d], qkv3[:, :, d:2 * d], None
+    if rt.qk_norm:                                                  # the norm is per row: query 0's alone, every key's
+        q0, k3, qkn = _qk_norm_self(rt, qkv, P, batch, n, cls_only=True)
+    o0, lse0 = ops.attention_fwd(q0, k3, qkv3[:, :, 2 * d:3 * d], rt.heads, rt.scale)
     o0 = o0.view(batch, d)
     x0 = _dense_rows(x.view(batch, n, d)[:, 0, :])
     xa, lnq = _res_linear(rt, o0, P.wproj, P.bproj, x0, next_ln, scale)
-    return xa, (m1, r1, h1, qkv, o0, lse0), lnq
+    return xa, (m1, r1, h1, qkv, o0, lse0, qkn), lnq
 
 
 def _dec_self_bwd(rt, dx, dx_lp, x, P, saved, batch, n, cls_only, key=None, lp_scale=None):
@@ -702,47 +757,70 @@ def _dec_self_bwd(rt, dx, dx_lp, x, P, saved, batch, n, cls_only, key=None, lp_s
     if not cls_only:
         return _attn_branch_bwd(rt, dx, dx_lp, x, P, saved, batch, n, key=key, lp_scale=lp_scale)
     d = rt.dim
-    m1, r1, h1, qkv, o0, lse0 = saved
+    m1, r1, h1, qkv, o0, lse0, qkn = saved
     do0, dwproj, dbproj = _linear_bwd(rt, dx_lp, o0, P.wproj, P.bproj)
     qkv3 = qkv.view(batch, n, 3 * d)
+    q0, k3 = qkv3[:, 0:1, 0:d], qkv3[:, :, d:2 * d]
+    if qkn is not None:
+        q0, k3 = qkn[0][0].view(batch, 1, d), qkn[0][1].view(batch, n, d)
     dqkv = torch.zeros_like(qkv)                 # d(q) of the rows that never queried is zero
     dqkv3 = dqkv.view(batch, n, 3 * d)
-    ops.attention_bwd(qkv3[:, 0:1, 0:d], qkv3[:, :, d:2 * d], qkv3[:, :, 2 * d:3 * d], o0.view(batch, 1, d), do0.view(batch, 1, d),
+    ops.attention_bwd(q0, k3, qkv3[:, :, 2 * d:3 * d], o0.view(batch, 1, d), do0.view(batch, 1, d),
                       lse0, rt.heads, rt.scale, dqkv3[:, 0:1, 0:d], dqkv3[:, :, d:2 * d], dqkv3[:, :, 2 * d:3 * d])
+    gn = _qk_norm_self_bwd(rt, dqkv, qkv, P, qkn, batch, n, cls_only=True) if qkn is not None else {}
     dres = torch.zeros((batch * n, d), dtype=torch.float32, device=dx.device)   # the residual path carries gradient on the cls rows only
     dres.view(batch, n, d)[:, 0, :].copy_(dx)
     dx, dx_lp, dg1, db1, dwqkv, dbqkv = _linear_ln_bwd(rt, dqkv, h1, P.wqkv, P.bqkv, x, P.g1, P.b1, m1, r1, dx_in=dres, lp_scale=lp_scale)
-    return dx, dx_lp, dict(g1=dg1, b1=db1, wqkv=dwqkv, bqkv=dbqkv, wproj=dwproj, bproj=dbproj)
+    return dx, dx_lp, dict(g1=dg1, b1=db1, wqkv=dwqkv, bqkv=dbqkv, wproj=dwproj, bproj=dbproj, **gn)
 
 
 def _cross_q(rt, xa, P, lnq=None):
     """q = Linear_q(norm_cross(xa)) of the cross-attention (:176); ``lnq`` = (h, mean, rstd) of norm_cross(xa) when the self
-    stage's proj kernel produced it.  Returns (q in the activation dtype, (h, mean, rstd))."""
+    stage's proj kernel produced it.  Returns (q in the activation dtype as the attention reads it, (h, mean, rstd), qraw): with the
+    q/k-norm q is q_norm(Linear_q(...)) (:180) and ``qraw`` = (the pre-norm q, its statistics) for the backward, else qraw is None."""
     hq, mq, rq = lnq if lnq is not None else ops.layernorm_fwd(xa, P.gc, P.bc, LN_EPS, rt.act_dtype)
-    return ops.gemm(hq, rt.weight(P.wq), bias=P.bq), (hq, mq, rq)
+    q = ops.gemm(hq, rt.weight(P.wq), bias=P.bq)
+    if not rt.qk_norm:
+        return q, (hq, mq, rq), None
+    qn, _, sq, _ = ops.qk_norm_fwd(q, None, P.gcqn, P.bcqn, None, None, rt.heads, LN_EPS)
+    return qn, (hq, mq, rq), (q, sq)
 
 
-def _dec_cross_fwd(rt, xa, P, batch, lnq=None, q=None, kv3=None, ctxf=None, kv_index=None, key=None, fuse_ln=True, scale=None, items=None):
+def _k_norm_cross(rt, kv, P, in_place=False):
+    """k_norm of a cross-attention on the K half of kv [Mc, 2D] (:180).  Returns (normalised keys [Mc, D], their statistics); ``in_place``
+    (the inference caches: nothing is saved for a backward) writes them over the K half itself."""
+    k = kv[:, 0:rt.dim]
+    _, kn, _, sk = ops.qk_norm_fwd(None, k, None, None, P.gckn, P.bckn, rt.heads, LN_EPS, out=(None, k) if in_place else None)
+    return kn, sk
+
+
+def _dec_cross_fwd(rt, xa, P, batch, lnq=None, q=None, kv3=None, ctxf=None, kv_index=None, key=None, fuse_ln=True, scale=None, items=None,
+                   kn=None):
     """Cross stage (:174-200, :270): xa [batch Nq, D] -> (xb = xa + proj(attention(q, k, v)), saved, ln2) with q from the image-2
     tokens (_cross_q, unless the pair cache hands ``q`` over) and k / v from the image-1 features: ``kv3`` [., N1, 2 D] when they
     were computed ahead for all blocks (_context_kv_folded, context_kv; with ``kv_index`` pair p reads kv3[kv_index[p]]), else
     Linear_kv(norm_context(ctxf)) here - on ``items`` feature maps (default: one per pair).  ``fuse_ln``: the cross-proj kernel also
-    produces ln2 = (h, mean, rstd) of norm2(xb)."""
+    produces ln2 = (h, mean, rstd) of norm2(xb).
+    With the q/k-norm a ``q`` handed over is the normalised one, and keys computed ahead are either normalised in place inside ``kv3``
+    (the inference cache) or come as ``kn`` = (normalised keys [items N1, D], their statistics) beside the pre-norm ones in kv3."""
     d, nq = rt.dim, xa.shape[0] // batch
-    hq = mq = rq = hc = mc = rc = None
+    hq = mq = rq = hc = mc = rc = qraw = None
     if q is None:
-        q, (hq, mq, rq) = _cross_q(rt, xa, P, lnq)
+        q, (hq, mq, rq), qraw = _cross_q(rt, xa, P, lnq)
     kv = kv3                    # computed ahead: a view, nothing of norm_context is saved here
     if kv3 is None:
         hc, mc, rc = ops.layernorm_fwd(ctxf, P.gx, P.bx, LN_EPS, rt.act_dtype)
         kv = ops.gemm(hc, rt.weight(P.wkv), bias=P.bkv)              # [Mc, 2D], columns [2][h][hd] (:178)
         kv3 = kv.view(batch if items is None else items, rt.n1, 2 * d)
-    oc, lse_c = ops.attention_fwd(q.view(batch, nq, d), kv3[:, :, 0:d], kv3[:, :, d:2 * d], rt.heads, rt.scale, kv_index=kv_index)
+        if rt.qk_norm:
+            kn = _k_norm_cross(rt, kv, P)
+    k3 = kv3[:, :, 0:d] if kn is None else kn[0].view(kv3.shape[0], rt.n1, d)
+    oc, lse_c = ops.attention_fwd(q.view(batch, nq, d), k3, kv3[:, :, d:2 * d], rt.heads, rt.scale, kv_index=kv_index)
     if rt.keep_attn and key is not None:
-        _keep_attention(rt, key, q.view(batch, nq, d), kv3[:, :, 0:d])
+        _keep_attention(rt, key, q.view(batch, nq, d), k3)
     oc = oc.view(batch * nq, d)
     xb, ln2 = _res_linear(rt, oc, P.wcp, P.bcp, xa, (P.g2, P.b2) if fuse_ln else None, scale)
-    return xb, (mq, rq, hq, mc, rc, hc, q, kv, oc, lse_c), ln2
+    return xb, (mq, rq, hq, mc, rc, hc, q, kv, oc, lse_c, qraw, kn), ln2
 
 
 def _dec_cross_bwd(rt, dx, dx_lp, xa, P, saved, ctxf, dctx, batch, index, dkv3=None, lp_scale=None, seg=None):
@@ -753,7 +831,7 @@ def _dec_cross_bwd(rt, dx, dx_lp, xa, P, saved, ctxf, dctx, batch, index, dkv3=N
     item the sum of its pairs' terms (ops.attention_bwd(segments=...)), and so is everything that follows it."""
     d, nq = rt.dim, xa.shape[0] // batch
     items = batch if seg is None else seg.items
-    mq, rq, hq, mc, rc, hc, q, kv, oc, lse_c = saved
+    mq, rq, hq, mc, rc, hc, q, kv, oc, lse_c, qraw, kn = saved
     doc, dwcp, dbcp = _linear_bwd(rt, dx_lp, oc, P.wcp, P.bcp)
     dq = torch.empty_like(q)
     folded = hc is None
@@ -762,29 +840,40 @@ def _dec_cross_bwd(rt, dx, dx_lp, xa, P, saved, ctxf, dctx, batch, index, dkv3=N
     else:
         dkv = torch.empty_like(kv)
         kv3, dkv3 = kv.view(items, rt.n1, 2 * d), dkv.view(items, rt.n1, 2 * d)
+    k3 = kv3[:, :, 0:d] if kn is None else kn[0].view(items, rt.n1, d)       # what the attention read: the normalised keys
     if rt.keep_attn:
         _keep_attention_grad(rt, ('cross_blocks', index, 'cross_attn'), doc.view(batch, nq, d), kv3[:, :, d:2 * d])
     if rt.keep_cam:
-        _keep_attention_cam(rt, ('cross_blocks', index, 'cross_attn'), q.view(batch, nq, d), kv3[:, :, 0:d], kv3[:, :, d:2 * d],
+        _keep_attention_cam(rt, ('cross_blocks', index, 'cross_attn'), q.view(batch, nq, d), k3, kv3[:, :, d:2 * d],
                             doc.view(batch, nq, d), lse_c)
-    ops.attention_bwd(q.view(batch, nq, d), kv3[:, :, 0:d], kv3[:, :, d:2 * d], oc.view(batch, nq, d),
+    ops.attention_bwd(q.view(batch, nq, d), k3, kv3[:, :, d:2 * d], oc.view(batch, nq, d),
                       doc.view(batch, nq, d), lse_c, rt.heads, rt.scale, dq.view(batch, nq, d), dkv3[:, :, 0:d],
                       dkv3[:, :, d:2 * d], segments=seg)
     if rt.tap is not None:
         i = index
         rt.tap[f'dec.doc.{i}'], rt.tap[f'dec.dq.{i}'], rt.tap[f'dec.dkv.{i}'] = doc.clone(), dq.clone(), dkv.clone()
         rt.tap[f'dec.q.{i}'], rt.tap[f'dec.kv.{i}'], rt.tap[f'dec.oc.{i}'] = q.clone(), kv.clone(), oc.clone()
+    gn = {}
+    if rt.qk_norm:
+        # q_norm and k_norm backward in one launch, in place: dq and the K half of d(kv) become the projections' output gradients.  With
+        # per-image keys (seg) d(kv) already is the sum over each image's pairs, so the norm's backward runs once per image
+        fields = ('gcqn', 'bcqn', 'gckn', 'bckn')
+        targets = [_gtarget(rt, getattr(P, f)) for f in fields]
+        direct = all(t is not None for t in targets)
+        got = ops.qk_norm_bwd(dq, qraw[0], qraw[1], P.gcqn, dkv3.reshape(-1, 2 * d)[:, 0:d], kv3.reshape(-1, 2 * d)[:, 0:d], kn[1], P.gckn,
+                              rt.heads, *(targets if direct else ()))
+        gn = dict.fromkeys(fields) if direct else dict(zip(fields, got))
     # q = Linear(norm_cross(x')), kv = Linear(norm_context(features)): input-gradient GEMM + LayerNorm backward fused
     dx, dx_lp, dgc, dbc, dwq, dbq = _linear_ln_bwd(rt, dq, hq, P.wq, P.bq, xa, P.gc, P.bc, mq, rq, dx_in=dx, lp_scale=lp_scale)
     dgx = dbx = dwkv = dbkv = None
     if not folded:
         # d(context) accumulates over the c_depth blocks in fp32, in place
         dctx, _, dgx, dbx, dwkv, dbkv = _linear_ln_bwd(rt, dkv, hc, P.wkv, P.bkv, ctxf, P.gx, P.bx, mc, rc, dx_in=dctx, dx_out=dctx, want_lp=False)
-    return dx, dx_lp, dctx, dict(gc=dgc, bc=dbc, gx=dgx, bx=dbx, wq=dwq, bq=dbq, wkv=dwkv, bkv=dbkv, wcp=dwcp, bcp=dbcp)
+    return dx, dx_lp, dctx, dict(gc=dgc, bc=dbc, gx=dgx, bx=dbx, wq=dwq, bq=dbq, wkv=dwkv, bkv=dbkv, wcp=dwcp, bcp=dbcp, **gn)
 
 
 def _dec_block_fwd(rt, x, ctxf, P, batch, n, grad, cls_only, index=0, ln1=None, next_ln=None, kv3=None, scales=(None, None, None),
-                   seg=None):
+                   seg=None, kn=None):
     """One CrossBlock forward of DecoderFn: self + cross + MLP stage, every following LayerNorm asked of the Linear before it
     (``next_ln`` = (gamma, beta) of the NEXT block's norm1).  ``scales``: the stochastic-depth scales of the (self, cross, mlp) branches,
     each one value per row of its stage or None.  ``seg``: the context is per image, pair p attends over item seg.index[p].
@@ -792,7 +881,7 @@ def _dec_block_fwd(rt, x, ctxf, P, batch, n, grad, cls_only, index=0, ln1=None, 
     xa, sa, lnq = _dec_self_fwd(rt, x, P, batch, n, cls_only, key=('cross_blocks', index, 'attn'), ln1=ln1, scale=scales[0])
     xb, sc, ln2 = _dec_cross_fwd(rt, xa, P, batch, lnq=lnq, kv3=kv3, ctxf=ctxf, key=('cross_blocks', index, 'cross_attn'),
                                  fuse_ln=_hand_over_ln(rt, xa, P, grad or scales[2] is not None), scale=scales[1],
-                                 kv_index=seg.index if seg is not None else None, items=seg.items if seg is not None else None)
+                                 kv_index=seg.index if seg is not None else None, items=seg.items if seg is not None else None, kn=kn)
     xc, sm, nxt = _mlp_fwd(rt, xb, P, grad, ln=ln2, next_ln=next_ln, scale=scales[2])
     return xc, ((x, sa, xa, sc, xb, sm) if grad else None), nxt
 
@@ -806,7 +895,7 @@ def _dec_block_bwd(rt, dx, dx_lp, ctxf, dctx, P, entry, batch, n, cls_only, inde
     dx, dx_lp, gm = _mlp_bwd(rt, dx, dx_lp, xb, P, sm, lp_scale=lp_scales[0])
     dx, dx_lp, dctx, gc = _dec_cross_bwd(rt, dx, dx_lp, xa, P, sc, ctxf, dctx, batch, index, dkv3, lp_scale=lp_scales[1], seg=seg)
     dx, dx_lp, ga = _dec_self_bwd(rt, dx, dx_lp, x, P, sa, batch, n, cls_only, key=('cross_blocks', index, 'attn'), lp_scale=lp_scales[2])
-    return dx, dx_lp, dctx, DecBlock(**ga, **gc, **gm)
+    return dx, dx_lp, dctx, rt.dec_block(**ga, **gc, **gm)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -826,25 +915,29 @@ def image2_tokens(rt: Runtime, img, params):
              cross-attention that follows, vision_transformer.py:269-270) - unless that block is also the last one (cls-only);
       * q  = Linear_q(norm_cross(x')) of that block's cross-attention (:176), activation dtype.
     Returns (x' or x as [n, N2, D] fp32, q [n, N2, D] or None)."""
-    shared, blocks = split_params(params, DecShared, DecBlock)
+    shared, blocks = split_params(params, DecShared, rt.dec_block)
     x, _, batch, _ = _patch_tokens_fwd(rt, img, shared, with_cls=True)
     if not blocks or (rt.cls_tail and rt.c_depth == 1):
         return x.view(batch, rt.n2, rt.dim), None
     xa, _, lnq = _dec_self_fwd(rt, x, blocks[0], batch, rt.n2, cls_only=False)
-    q, _ = _cross_q(rt, xa, blocks[0], lnq)
+    q, _, _ = _cross_q(rt, xa, blocks[0], lnq)          # (with the q/k-norm: the normalised queries)
     return xa.view(batch, rt.n2, rt.dim), q.view(batch, rt.n2, rt.dim)
 
 
 @torch.no_grad()
 def context_kv(rt: Runtime, feats, params):
-    """Per decoder block: kv = Linear_kv(norm_context(features)) as [b1, N1, 2 D] in the activation dtype (columns [2][h][hd])."""
-    _, blocks = split_params(params, DecShared, DecBlock)
+    """Per decoder block: kv = Linear_kv(norm_context(features)) as [b1, N1, 2 D] in the activation dtype (columns [2][h][hd]); with the
+    q/k-norm the K half is k_norm of it, which is what decoder_cached's attention reads."""
+    _, blocks = split_params(params, DecShared, rt.dec_block)
     b1 = feats.shape[0]
     ctxf = feats.detach().contiguous().float().view(b1 * rt.n1, rt.dim)
     out = []
     for P in blocks:
         hc, _, _ = ops.layernorm_fwd(ctxf, P.gx, P.bx, LN_EPS, rt.act_dtype)
-        out.append(ops.gemm(hc, rt.weight(P.wkv), bias=P.bkv).view(b1, rt.n1, 2 * rt.dim))
+        kv = ops.gemm(hc, rt.weight(P.wkv), bias=P.bkv)
+        if rt.qk_norm:
+            _k_norm_cross(rt, kv, P, in_place=True)          # the cache holds the NORMALISED keys
+        out.append(kv.view(b1, rt.n1, 2 * rt.dim))
     return out
 
 
@@ -853,7 +946,7 @@ def decoder_cached(rt: Runtime, tokens2, j_idx, kvs, i_idx, params, q0=None):
     """Logits [P, C] of the pairs (image-1 row i_idx[p] of the cached block, image j_idx[p]): forward_second_part + forward_head
     (vision_transformer.py:397-405,417) on cached image-2 tokens and cached cross-attention keys / values.  With ``q0`` the cache
     already holds block 0's self-attention branch and cross-attention queries (image2_tokens)."""
-    shared, blocks = split_params(params, DecShared, DecBlock)
+    shared, blocks = split_params(params, DecShared, rt.dec_block)
     d, n = rt.dim, rt.n2
     batch = j_idx.numel()
     x = tokens2.index_select(0, j_idx).view(batch * n, d)
@@ -943,7 +1036,7 @@ class DecoderFn(torch.autograd.Function):
         ``img1_index`` (ops.PairSegments | None): ``feats`` holds one item per IMAGE and pair p attends over feats[index[p]]: norm_context
         and the kv projections run once per image, the cross-attention reads them through the index, and the backward sums every
         image's d(kv) over its pairs before the per-image kv / norm_context backward (hisfrag.py:117-159 without its two gathers)."""
-        shared, blocks = split_params(params, DecShared, DecBlock)
+        shared, blocks = split_params(params, DecShared, rt.dec_block)
         grad = any(ctx.needs_input_grad)
         x, patches, batch, n = _patch_tokens_fwd(rt, img2, shared, with_cls=True, batch_index=img2_index)
         seg = img1_index
@@ -960,13 +1053,16 @@ class DecoderFn(torch.autograd.Function):
         drop = _take_drop_rows(rt, 1, len(blocks), 3, batch, n, x.device, cls_block=rt.c_depth - 1 if cls_tail else None)
         ln1 = None
         fold = rt.fold_context and not rt.exact and rt.c_depth > 1 and rt.c_depth <= ops.MAX_FOLDED_BLOCKS and rt.dim % 32 == 0
-        kv_all = kv_saved = fold_bufs = None
+        kv_all = kv_saved = fold_bufs = kn_all = None
         if fold:
             kv_all, kv_saved, fold_bufs = _context_kv_folded(rt, ctxf, blocks)
+            if rt.qk_norm:          # k_norm per block on its keys, once per context item (per image under an image-1 index)
+                kn_all = [_k_norm_cross(rt, kv_all[l], P) for l, P in enumerate(blocks)]
         for i, P in enumerate(blocks):
             x, entry, ln1 = _dec_block_fwd(rt, x, ctxf, P, batch, n, grad, cls_tail and i == rt.c_depth - 1, index=i, ln1=ln1,
                                            next_ln=_norm1_of(blocks, i + 1), kv3=kv_all[i].view(b1, rt.n1, 2 * d) if fold else None,
-                                           scales=drop.block(i) if drop is not None else (None, None, None), seg=seg)
+                                           scales=drop.block(i) if drop is not None else (None, None, None), seg=seg,
+                                           kn=kn_all[i] if kn_all is not None else None)
             if grad:
                 tape.append(entry)
             if rt.tap is not None:

@@ -11,6 +11,9 @@ Drop-in surface kept:
   * raw fp32 logits out.
   * ``drop_path_rate``: stochastic depth on every residual branch in training mode, applied inside the residual epilogues of
     the kernels (``draw_drop_path`` / ``forward(..., drop_path=...)`` / ``last_drop_path``).
+  * ``qk_norm``: ``q_norm`` / ``k_norm`` = LayerNorm(head_dim, eps=1e-6) on every head's queries and keys of every self- and
+    cross-attention, with the reference's ``state_dict`` keys (``*.attn.q_norm.weight`` ...); a HIP kernel of its own between the
+    projection and the attention kernels.  Off by default: no such module, key or launch exists then.
 
 Precision follows the caller exactly like the reference follows ``torch.cuda.amp.autocast``
 (misc/engine.py:208): inside an autocast region the bf16 MFMA kernels run, outside it the fp32
@@ -28,7 +31,8 @@ import torch.nn as nn
 
 from . import functions as F_
 from . import ops
-from .functions import DEC_BLOCK_KEYS, DEC_SHARED_KEYS, ENC_BLOCK_KEYS, ENC_SHARED_KEYS, Runtime
+from .functions import (DEC_BLOCK_KEYS, DEC_BLOCK_QK_KEYS, DEC_SHARED_KEYS, ENC_BLOCK_KEYS, ENC_BLOCK_QK_KEYS, ENC_SHARED_KEYS,
+                        Runtime)
 
 LN_EPS = F_.LN_EPS
 
@@ -69,12 +73,20 @@ class _Norm(_Holder):
 
 
 class _SelfAttn(_Holder):
-    def __init__(self, d, heads, qkv_bias):
+    def __init__(self, d, heads, qkv_bias, qk_norm=False):
         super().__init__()
         self.num_heads, self.head_dim, self.scale = heads, d // heads, (d // heads) ** -0.5
         self.qkv = _Linear(d, 3 * d, qkv_bias)
+        self._add_qk_norm(qk_norm)
         self.proj = _Linear(d, d)
         self.keep_attn = False
+
+    def _add_qk_norm(self, qk_norm):
+        """q_norm / k_norm holders (vision_transformer.py:35-36, 153-154): weight 1, bias 0; absent without the option, where the
+        reference has parameter-free Identity modules."""
+        if qk_norm:
+            self.q_norm = _Norm(self.head_dim)
+            self.k_norm = _Norm(self.head_dim)
 
     _store, _key = None, None     # set by VisionTransformerCustom: the runtime's attention store and this module's key
 
@@ -101,11 +113,12 @@ class _SelfAttn(_Holder):
 
 
 class _CrossAttn(_SelfAttn):
-    def __init__(self, d, heads, qkv_bias):
+    def __init__(self, d, heads, qkv_bias, qk_norm=False):
         _Holder.__init__(self)
         self.num_heads, self.head_dim, self.scale = heads, d // heads, (d // heads) ** -0.5
         self.q = _Linear(d, d, qkv_bias)
         self.kv = _Linear(d, 2 * d, qkv_bias)
+        self._add_qk_norm(qk_norm)
         self.proj = _Linear(d, d)
         self.keep_attn = False
 
@@ -120,10 +133,10 @@ class _Mlp(_Holder):
 class Block(_Holder):
     """Encoder block parameters (vision_transformer.py:83-127)."""
 
-    def __init__(self, d, heads, hidden, qkv_bias):
+    def __init__(self, d, heads, hidden, qkv_bias, qk_norm=False):
         super().__init__()
         self.norm1 = _Norm(d)
-        self.attn = _SelfAttn(d, heads, qkv_bias)
+        self.attn = _SelfAttn(d, heads, qkv_bias, qk_norm)
         self.norm2 = _Norm(d)
         self.mlp = _Mlp(d, hidden)
 
@@ -131,13 +144,13 @@ class Block(_Holder):
 class CrossBlock(_Holder):
     """Decoder block parameters (vision_transformer.py:213-272)."""
 
-    def __init__(self, d, heads, hidden, qkv_bias):
+    def __init__(self, d, heads, hidden, qkv_bias, qk_norm=False):
         super().__init__()
         self.norm1 = _Norm(d)
-        self.attn = _SelfAttn(d, heads, qkv_bias)
+        self.attn = _SelfAttn(d, heads, qkv_bias, qk_norm)
         self.norm_cross = _Norm(d)
         self.norm_context = _Norm(d)
-        self.cross_attn = _CrossAttn(d, heads, qkv_bias)
+        self.cross_attn = _CrossAttn(d, heads, qkv_bias, qk_norm)
         self.norm2 = _Norm(d)
         self.mlp = _Mlp(d, hidden)
 
@@ -160,7 +173,7 @@ def _get(module, dotted):
 class VisionTransformerCustom(nn.Module):
     def __init__(self, img_size=224, patch_size=16, in_chans=3, num_classes=1000, embed_dim=768, depth=12, c_depth=12,
                  num_heads=12, mlp_ratio=4., qkv_bias=True, keep_attn=False, arch_version='v1', compute_dtype=None,
-                 drop_path_rate=0., **unsupported):
+                 drop_path_rate=0., qk_norm=False, **unsupported):
         super().__init__()
         drop_path_rate = float(drop_path_rate or 0.)
         if not 0. <= drop_path_rate < 1.:
@@ -187,6 +200,7 @@ class VisionTransformerCustom(nn.Module):
         self.keep_cam = False               # record head-averaged relevancy maps in the backward (fused kernel; engine.pair_relevancy):
                                             # such a backward leaves every parameter gradient untouched
         self.arch_version = arch_version.lower()
+        self.qk_norm = bool(qk_norm)        # q_norm / k_norm = LayerNorm(head_dim) in every attention
         self.compute_dtype = compute_dtype
         # stochastic depth (timm DropPath, scale_by_keep): the reference's two decay rules, fp32 linspace as it computes them
         # (vision_transformer.py:351 for the decoder, timm's VisionTransformer for the encoder); DropPath has no parameters
@@ -203,11 +217,11 @@ class VisionTransformerCustom(nn.Module):
         n1 = self.patch_embed.num_patches
         self.cls_token = nn.Parameter(torch.zeros(1, 1, embed_dim))
         self.pos_embed = nn.Parameter(torch.zeros(1, n1 + 1, embed_dim))
-        self.blocks = nn.Sequential(*[Block(embed_dim, num_heads, hidden, qkv_bias) for _ in range(depth)])
+        self.blocks = nn.Sequential(*[Block(embed_dim, num_heads, hidden, qkv_bias, self.qk_norm) for _ in range(depth)])
         self.norm = _Norm(embed_dim)
         self.head = _Linear(embed_dim, num_classes)
         self._init_like_timm()  # runs before the decoder exists, exactly as in the reference ctor (:344-347)
-        self.cross_blocks = nn.ModuleList([CrossBlock(embed_dim, num_heads, hidden, qkv_bias) for _ in range(c_depth)])
+        self.cross_blocks = nn.ModuleList([CrossBlock(embed_dim, num_heads, hidden, qkv_bias, self.qk_norm) for _ in range(c_depth)])
         self._runtimes = {}
         import weakref
         me = weakref.ref(self)
@@ -241,7 +255,7 @@ class VisionTransformerCustom(nn.Module):
         if rt is None:
             rt = Runtime(img_size=self.img_size, patch_size=self.patch_size, in_chans=self.in_chans,
                          num_classes=self.num_classes, embed_dim=self.embed_dim, depth=self.depth, c_depth=self.c_depth,
-                         num_heads=self.num_heads, act_dtype=dt)
+                         num_heads=self.num_heads, act_dtype=dt, qk_norm=self.qk_norm)
             self._runtimes[dt] = rt
         rt.direct_grads = bool(getattr(self, 'direct_param_grads', False))
         rt.input_mean, rt.input_std = self.input_mean, self.input_std
@@ -254,13 +268,13 @@ class VisionTransformerCustom(nn.Module):
     def _encoder_params(self):
         ps = [_get(self, k) for k in ENC_SHARED_KEYS]
         for blk in self.blocks:
-            ps += [_get(blk, k) for k in ENC_BLOCK_KEYS]
+            ps += [_get(blk, k) for k in (ENC_BLOCK_QK_KEYS if self.qk_norm else ENC_BLOCK_KEYS)]
         return ps
 
     def _decoder_params(self):
         ps = [_get(self, k) for k in DEC_SHARED_KEYS]
         for blk in self.cross_blocks:
-            ps += [_get(blk, k) for k in DEC_BLOCK_KEYS]
+            ps += [_get(blk, k) for k in (DEC_BLOCK_QK_KEYS if self.qk_norm else DEC_BLOCK_KEYS)]
         return ps
 
     def _check_images(self, img):

@@ -412,6 +412,104 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, dx_in=None, dx_out=None, want_lp: bo
 
 
 # ---------------------------------------------------------------------------------------------
+def _qkn_operand(name, t, heads, like=None):
+    """(rows, row stride, head_dim) of a q / k operand of the q/k-norm: [rows, heads * head_dim], dense last dim, any row stride."""
+    ld = _rows2d(t)
+    if t.shape[1] % heads:
+        raise ValueError(f'{name}: {t.shape[1]} columns are not {heads} heads')
+    if like is not None and (t.shape != like.shape or t.dtype != like.dtype):
+        raise ValueError(f'{name}: {t.dtype} {tuple(t.shape)} does not match {like.dtype} {tuple(like.shape)}')
+    return t.shape[0], ld, t.shape[1] // heads
+
+
+def _qkn_params(hd, *params):
+    for p in params:
+        assert p.dtype == torch.float32 and p.is_contiguous() and p.numel() == hd, 'q/k-norm parameters are fp32 [head_dim]'
+
+
+def qk_norm_fwd(q, k, gq, bq, gk, bk, heads: int, eps: float, out=None):
+    """q_norm / k_norm of the reference's attention (``qk_norm=True``): LayerNorm over the head_dim elements of every head of every
+    row, for q and k in ONE launch (``vited_qk_norm_fwd``).  q, k: [rows, heads * head_dim] fp32 or bf16 with a dense last dim and
+    any row stride - column slices of the packed projections - each with its own row count; either may be None (and its
+    parameters with it).  gq, bq, gk, bk: fp32 [head_dim].  ``out`` = (q_out | None, k_out | None) pre-made (a slice of a larger
+    buffer, or the input itself: in place).
+    Returns (q_out, k_out, (q_mean, q_rstd), (k_mean, k_rstd)) - None for an absent operand; the statistics are fp32 [rows, heads]."""
+    if q is None and k is None:
+        raise ValueError('qk_norm_fwd: neither q nor k given')
+    _need_gpu(q, k, gq, bq, gk, bk)
+    ref = q if q is not None else k
+    dtype, dev = ref.dtype, ref.device
+    outs, stats, args, hd = [], [], [], None
+    for name, t, g, b, o in (('q', q, gq, bq, out[0] if out else None), ('k', k, gk, bk, out[1] if out else None)):
+        if t is None:
+            outs.append(None)
+            stats.append(None)
+            args.append((0, 0, 0, 0, 0, 0, 0, 0, 0))
+            continue
+        rows, ld, hd_t = _qkn_operand(name, t, heads)
+        assert t.dtype == dtype and (hd is None or hd == hd_t), 'q and k share the dtype and the head width'
+        hd = hd_t
+        _qkn_params(hd, g, b)
+        if o is None:
+            o = torch.empty((rows, heads * hd), dtype=dtype, device=dev)
+        else:
+            _need_gpu(o)
+            _qkn_operand(name + '_out', o, heads, like=t)
+        mean = torch.empty((rows, heads), dtype=torch.float32, device=dev)
+        rstd = torch.empty((rows, heads), dtype=torch.float32, device=dev)
+        outs.append(o)
+        stats.append((mean, rstd))
+        args.append((_ptr(t), ld, rows, _ptr(g), _ptr(b), _ptr(o), _rows2d(o), _ptr(mean), _ptr(rstd)))
+    (qp, qld, qr, gqp, bqp, qop, qold, qm, qs), (kp, kld, kr, gkp, bkp, kop, kold, km, ks) = args
+    _lib.call('vited_qk_norm_fwd', qp, qld, qr, kp, kld, kr, gqp, bqp, gkp, bkp, qop, qold, kop, kold, qm, qs, km, ks, _code(dtype), heads, hd,
+              float(eps), _stream())
+    return outs[0], outs[1], stats[0], stats[1]
+
+
+def qk_norm_bwd(dq, q, q_stats, gq, dk, k, k_stats, gk, heads: int, dgq=None, dbq=None, dgk=None, dbk=None):
+    """Backward of ``qk_norm_fwd`` (``vited_qk_norm_bwd``), one launch for both operands.  dq / dk hold the gradient of the NORMALISED
+    q / k (where the attention backward wrote it) and are overwritten IN PLACE by the gradient of the pre-norm q / k; q, k are the
+    saved pre-norm operands, q_stats / k_stats their (mean, rstd).  Either operand may be None.  The parameter gradients are
+    deterministic sums over all rows and heads; given ``dgq`` ... ``dbk`` (fp32 [head_dim], contiguous - e.g. views of the flat
+    gradient buffer; all of the present operands' or none) they are ADDED onto them.
+    Returns (dgq, dbq, dgk, dbk), None for an absent operand."""
+    if dq is None and dk is None:
+        raise ValueError('qk_norm_bwd: neither dq nor dk given')
+    _need_gpu(dq, q, gq, dk, k, gk, dgq, dbq, dgk, dbk)
+    ref = dq if dq is not None else dk
+    dtype, dev = ref.dtype, ref.device
+    given = [t is not None for d, pair in ((dq, (dgq, dbq)), (dk, (dgk, dbk))) if d is not None for t in pair]
+    accumulate = all(given)
+    if any(given) and not accumulate:
+        raise ValueError('qk_norm_bwd: give every gradient destination of the present operands, or none')
+    args, grads, hd, rows_of = [], [], None, []
+    for name, d, x, st, g, dg, db in (('q', dq, q, q_stats, gq, dgq, dbq), ('k', dk, k, k_stats, gk, dgk, dbk)):
+        if d is None:
+            args.append((0,) * 10)
+            grads += [None, None]
+            rows_of.append(0)
+            continue
+        rows, ld, hd_t = _qkn_operand('d' + name, d, heads)
+        _qkn_operand(name, x, heads, like=d)
+        assert d.dtype == dtype and (hd is None or hd == hd_t), 'q and k share the dtype and the head width'
+        hd = hd_t
+        mean, rstd = st
+        assert mean.shape == rstd.shape == (rows, heads) and mean.dtype == rstd.dtype == torch.float32 and mean.is_contiguous() and rstd.is_contiguous()
+        _qkn_params(hd, g)
+        if accumulate:
+            _qkn_params(hd, dg, db)
+        else:
+            dg = torch.empty(hd, dtype=torch.float32, device=dev)
+            db = torch.empty(hd, dtype=torch.float32, device=dev)
+        grads += [dg, db]
+        rows_of.append(rows)
+        args.append((_ptr(d), ld, _ptr(x), _rows2d(x), _ptr(mean), _ptr(rstd), _ptr(g), _ptr(dg), _ptr(db), rows))
+    ws = _scratch(_lib.load().vited_qk_norm_bwd_workspace_bytes(rows_of[0], rows_of[1], heads, hd), dev)
+    _lib.call('vited_qk_norm_bwd', *args[0], *args[1], _code(dtype), int(accumulate), heads, hd, *ws, _stream())
+    return tuple(grads)
+
+
+# ---------------------------------------------------------------------------------------------
 def gemm(a: torch.Tensor, b: torch.Tensor, *, b_layout: int = B_NK, epilogue: int = EPI_STORE, bias=None, aux=None,
          residual=None, out=None, out2=None, rows_per_batch: int = 0, out_rows_per_batch: int = 0, row_offset: int = 0,
          residual_bcast: bool = False, out_rows: int | None = None, row_scale=None):
@@ -680,7 +778,8 @@ def mlp_fwd(x, gamma, beta, w1, b1, w2, b2, eps: float, save: bool = True, out=N
 
 
 def block_fwd(x, heads: int, ln1_g, ln1_b, wqkv, bqkv, wproj, bproj, ln2_g, ln2_b, w1, b1, w2, b2, eps: float = 1e-6):
-    """Encoder Block forward through ``vited_block_fwd``: x fp32 [B, N, D] -> y fp32 [B, N, D] (bf16 weights, inference form)."""
+    """Encoder Block forward through ``vited_block_fwd``: x fp32 [B, N, D] -> y fp32 [B, N, D] (bf16 weights, inference form).
+    The whole-block entry has no q/k-norm: a ``qk_norm=True`` model runs its blocks through functions.py (``qk_norm_fwd``)."""
     _need_gpu(x, wqkv, wproj, w1, w2)
     assert x.dtype == torch.float32 and x.dim() == 3 and x.is_contiguous()
     assert all(t.dtype == torch.bfloat16 and t.is_contiguous() for t in (wqkv, wproj, w1, w2))
@@ -698,7 +797,8 @@ def block_fwd(x, heads: int, ln1_g, ln1_b, wqkv, bqkv, wproj, bproj, ln2_g, ln2_
 def cross_block_fwd(x, context, heads: int, ln1, wqkv, bqkv, wproj, bproj, lnq, lnc, wq, bq, wkv, bkv, wcproj, bcproj, ln2, w1, b1, w2, b2,
                     eps: float = 1e-6):
     """Decoder CrossBlock forward through ``vited_cross_block_fwd``: x fp32 [B, N2, D], context fp32 [B, N1, D] -> y fp32 [B, N2, D]
-    (bf16 weights, inference form).  ln1 / lnq / lnc / ln2 = (gamma, beta) of norm1 / norm_cross / norm_context / norm2."""
+    (bf16 weights, inference form).  ln1 / lnq / lnc / ln2 = (gamma, beta) of norm1 / norm_cross / norm_context / norm2.
+    The whole-block entry has no q/k-norm: a ``qk_norm=True`` model runs its blocks through functions.py (``qk_norm_fwd``)."""
     _need_gpu(x, context, wqkv, wproj, wq, wkv, wcproj, w1, w2)
     assert x.dtype == context.dtype == torch.float32 and x.dim() == context.dim() == 3 and x.is_contiguous() and context.is_contiguous()
     assert all(t.dtype == torch.bfloat16 and t.is_contiguous() for t in (wqkv, wproj, wq, wkv, wcproj, w1, w2))
