@@ -74,9 +74,9 @@ def test_out_argument(vited, gpu, small):
     assert _run(vited, small.store, gpu, *args, fc.CASE_S, out=out) is out
     assert np.array_equal(out.cpu().numpy(), small.want[:n])
     strided = torch.zeros(n, 2, 3, 16, 24, dtype=torch.uint8, device=gpu)[:, 0]       # batch stride of two regions: refused, like
-    with pytest.raises(AssertionError):                                                # the `out` of ops.cast
+    with pytest.raises(ValueError, match='out'):                                       # the `out` of ops.cast
         _run(vited, small.store, gpu, *args, fc.CASE_S, out=strided)
-    with pytest.raises(AssertionError):
+    with pytest.raises(ValueError, match='out'):
         _run(vited, small.store, gpu, *args, fc.CASE_S, out=torch.zeros(n, 3, 16, 25, dtype=torch.uint8, device=gpu))
     with pytest.raises(RuntimeError, match='CPU tensor'):
         vited.ops.div2k_regions_u8(small.store.data.cpu(), small.store.offsets, small.store.sizes, *[torch.as_tensor(a) for a in args], fc.CASE_S)

@@ -109,7 +109,7 @@ def test_blur_is_bit_exact(vited, gpu, S):
     assert np.array_equal(got[7], imgs[7]) and all(not np.array_equal(got[k], imgs[k]) for k in range(7))     # both off: unchanged
     off = torch.zeros_like(p['flags'])
     assert torch.equal(vited.ops.hisfrag_blur_u8(x, off, p['blur']), x)
-    with pytest.raises(AssertionError):
+    with pytest.raises(ValueError, match='out'):
         vited.ops.hisfrag_blur_u8(x, p['flags'], p['blur'], out=x)                            # a 3 x 3 filter cannot run in place
 
 
@@ -120,11 +120,11 @@ def test_out_argument(vited, gpu, small):
     assert _windows(vited, small.store, p, fc.CASE_S, out=out) is out
     assert np.array_equal(out.cpu().numpy(), small.want[:n])
     strided = torch.zeros(n, 2, 3, 16, 16, dtype=torch.uint8, device=gpu)[:, 0]               # batch stride of two windows: refused, like
-    with pytest.raises(AssertionError):                                                        # the `out` of ops.div2k_regions_u8
+    with pytest.raises(ValueError, match='out'):                                               # the `out` of ops.div2k_regions_u8
         _windows(vited, small.store, p, fc.CASE_S, out=strided)
-    with pytest.raises(AssertionError):
+    with pytest.raises(ValueError, match='out'):
         _windows(vited, small.store, p, fc.CASE_S, out=torch.zeros(n, 3, 16, 17, dtype=torch.uint8, device=gpu))
-    with pytest.raises(AssertionError):
+    with pytest.raises(ValueError, match='out'):
         vited.ops.hisfrag_jitter_u8(out, p['flags'], p['order'], p['factors'], p['hue'], out=strided)
     with pytest.raises(RuntimeError, match='CPU tensor'):
         _windows(vited, small.store, {k: v.cpu() for k, v in p.items()}, fc.CASE_S)

@@ -99,7 +99,7 @@ def test_blur_and_gray_are_bit_exact(vited, gpu, S):
     assert np.array_equal(got[4][0], got[4][1]) and np.array_equal(got[4][0], got[4][2])       # grey: three equal channels
     off = torch.zeros_like(f)
     assert torch.equal(vited.ops.michigan_blur_gray_u8(x, off, w), x)
-    with pytest.raises(AssertionError):
+    with pytest.raises(ValueError, match='out'):
         vited.ops.michigan_blur_gray_u8(x, f, w, out=x)                                        # the passes cannot run in place
 
 
@@ -141,13 +141,13 @@ def test_out_argument_and_range_checks(vited, gpu, small):
     assert _windows(vited, small.store, p, mc.CASE_S, out=out) is out
     assert np.array_equal(out.cpu().numpy(), small.want[:n])
     strided = torch.zeros(n, 2, 3, 16, 16, dtype=torch.uint8, device=gpu)[:, 0]               # batch stride of two crops: refused, like the
-    with pytest.raises(AssertionError):                                                        # `out` of ops.hisfrag_windows_u8
+    with pytest.raises(ValueError, match='out'):                                               # `out` of ops.hisfrag_windows_u8
         _windows(vited, small.store, p, mc.CASE_S, out=strided)
-    with pytest.raises(AssertionError):
+    with pytest.raises(ValueError, match='out'):
         _windows(vited, small.store, p, mc.CASE_S, out=torch.zeros(n, 3, 16, 17, dtype=torch.uint8, device=gpu))
     blurred = torch.empty_like(out)
     assert vited.ops.michigan_blur_gray_u8(out, p['flags'], p['blur'], out=blurred) is blurred
-    with pytest.raises(AssertionError):
+    with pytest.raises(ValueError, match='out'):
         vited.ops.michigan_blur_gray_u8(out, p['flags'], p['blur'], out=strided)
     with pytest.raises(RuntimeError, match='CPU tensor'):
         _windows(vited, small.store, {k: v.cpu() for k, v in p.items()}, mc.CASE_S)

@@ -521,6 +521,105 @@ def test_ops_refuse_cpu_tensors(vited, gpu):
         vited.ops.cast(torch.zeros(4), torch.bfloat16)
 
 
+def test_refused_calls_launch_nothing_and_the_valid_call_follows(vited, gpu):
+    """A wrong buffer is refused by name before the launch - the NaN-filled destinations of the refused call are untouched - and the
+    valid call after it gives what the parity tests above expect.  Rows 8, dim 384; gemm 8 x 16 x 64; attention B 2, N 5, D 64, 2 heads."""
+    ops = vited.ops
+    rows, dim, K = 8, 384, 64
+
+    def nan(*shape, dtype=torch.float32):
+        return torch.full(shape, float('nan'), dtype=dtype, device=gpu)
+
+    def refused(name, call, *destinations):         # name: 'op: argument', then a space - how every refusal begins
+        with pytest.raises(ValueError, match=f'^{name} '):
+            call()
+        torch.cuda.synchronize()
+        assert all(bool(torch.isnan(t).all()) for t in destinations), name
+
+    # write_cls_row
+    x3, cls, pos = _rand((2, 5, dim), gpu, 1), _rand((dim,), gpu, 2), _rand((5, dim), gpu, 3)
+    blank = nan(2, 5, dim)
+    refused('write_cls_row: cls', lambda: ops.write_cls_row(blank, cls.bfloat16()[:3], pos), blank)
+    refused('write_cls_row: pos', lambda: ops.write_cls_row(blank, cls, pos[0, :1]), blank)
+    y3 = x3.clone()
+    ops.write_cls_row(y3, cls, pos)
+    torch.cuda.synchronize()
+    assert torch.equal(y3[:, 0], (cls + pos[0]).expand(2, -1)) and torch.equal(y3[:, 1:], x3[:, 1:])
+    # layernorm_fwd / layernorm_bwd
+    x, g, b, dy = _rand((rows, dim), gpu, 4, 2.0) + 0.5, _rand((dim,), gpu, 5) * 0.2 + 1, _rand((dim,), gpu, 6) * 0.1, _rand((rows, dim), gpu, 7)
+    out = (nan(rows, dim), nan(rows), nan(rows))
+    refused('layernorm_fwd: gamma', lambda: ops.layernorm_fwd(x, torch.ones(10, device=gpu), b, 1e-6, torch.float32, out=out), *out)
+    refused(r'layernorm_fwd: out\[1\]', lambda: ops.layernorm_fwd(x, g, b, 1e-6, torch.float32, out=(out[0], out[1].double(), out[2])),
+            out[0], out[2])
+    y, mean, rstd = ops.layernorm_fwd(x, g, b, 1e-6, torch.float32, out=out)
+    torch.cuda.synchronize()
+    xr, gr, br = x.clone().requires_grad_(), g.clone().requires_grad_(), b.clone().requires_grad_()
+    yr = F.layer_norm(xr, (dim,), gr, br, 1e-6)
+    yr.backward(dy)
+    torch.testing.assert_close(y, yr.detach(), rtol=1e-5, atol=1e-5)
+    torch.testing.assert_close(mean, x.mean(1), rtol=1e-5, atol=1e-6)
+    dx = nan(rows, dim)
+    refused('layernorm_bwd: mean', lambda: ops.layernorm_bwd(dy, x, g, mean[:rows - 1], rstd, dx_out=dx), dx)
+    refused('layernorm_bwd: dx_out', lambda: ops.layernorm_bwd(dy, x, g, mean, rstd, dx_out=dx.bfloat16()), dx)
+    _, _, dg, db = ops.layernorm_bwd(dy, x, g, mean, rstd, dx_out=dx)
+    torch.cuda.synchronize()
+    torch.testing.assert_close(dx, xr.grad, rtol=1e-4, atol=1e-5)
+    torch.testing.assert_close(dg, gr.grad, rtol=1e-4, atol=1e-4 * math.sqrt(rows))
+    torch.testing.assert_close(db, br.grad, rtol=1e-4, atol=1e-4 * math.sqrt(rows))
+    # linear_residual_layernorm_fwd
+    a, w = _rand((rows, K), gpu, 8, 1.0, torch.bfloat16), _rand((dim, K), gpu, 9, K ** -0.5, torch.bfloat16)
+    bias, res = _rand((dim,), gpu, 10, 0.5), _rand((rows, dim), gpu, 11, 2.0)
+    yo = nan(rows, dim)
+    refused('linear_residual_layernorm_fwd: gamma', lambda: ops.linear_residual_layernorm_fwd(a, w, bias, res, g[:10], b, 1e-6, out=yo), yo)
+    refused('linear_residual_layernorm_fwd: out', lambda: ops.linear_residual_layernorm_fwd(a, w, bias, res, g, b, 1e-6, out=yo[:4]), yo)
+    yl, h, ml, rl = ops.linear_residual_layernorm_fwd(a, w, bias, res, g, b, 1e-6, out=yo)
+    torch.cuda.synchronize()
+    ref = res.double() + a.double() @ w.double().t() + bias.double()
+    torch.testing.assert_close(yl.double(), ref, rtol=1e-5, atol=2e-5 * K ** 0.5)
+    mu, var = ref.mean(dim=1), ref.var(dim=1, unbiased=False)
+    torch.testing.assert_close(ml.double(), mu, rtol=1e-5, atol=1e-5)
+    torch.testing.assert_close(h.double(), (ref - mu[:, None]) * (var[:, None] + 1e-6).rsqrt() * g.double() + b.double(), **BF16_OUT)
+    # linear_layernorm_bwd
+    dyk = _rand((rows, K), gpu, 12, 1.0, torch.bfloat16)
+    xd, gd = x.double().requires_grad_(True), g.double().requires_grad_(True)
+    F.layer_norm(xd, (dim,), gd, None, 1e-6).backward(dyk.double() @ w.double().t())
+    m64, r64 = x.double().mean(dim=1).float(), (x.double().var(dim=1, unbiased=False) + 1e-6).rsqrt().float()
+    dxl = nan(rows, dim)
+    refused('linear_layernorm_bwd: rstd', lambda: ops.linear_layernorm_bwd(dyk, w, x, g, m64, r64[:rows - 1], dx_out=dxl), dxl)
+    refused('linear_layernorm_bwd: gamma', lambda: ops.linear_layernorm_bwd(dyk, w, x, g.double(), m64, r64, dx_out=dxl), dxl)
+    _, _, dgl, _ = ops.linear_layernorm_bwd(dyk, w, x, g, m64, r64, dx_out=dxl)
+    torch.cuda.synchronize()
+    torch.testing.assert_close(dxl.double(), xd.grad, rtol=1e-4, atol=1e-5 * float(xd.grad.abs().max()))
+    torch.testing.assert_close(dgl.double(), gd.grad, rtol=1e-4, atol=1e-5 * float(gd.grad.abs().max()) * rows ** 0.5)
+    # gemm
+    wn, bn = _rand((16, K), gpu, 13, K ** -0.5, torch.bfloat16), _rand((16,), gpu, 14)
+    small = nan(4, 16)
+    refused('gemm: out', lambda: ops.gemm(a, wn, bias=bn, out=small), small)
+    go = nan(rows, 16, dtype=torch.bfloat16)
+    refused('gemm: bias', lambda: ops.gemm(a, wn, bias=bn[:15], out=go), go)
+    assert ops.gemm(a, wn, bias=bn, out=go) is go
+    torch.cuda.synchronize()
+    torch.testing.assert_close(go.double(), _gemm_ref(a, wn, bn), **BF16_OUT)
+    # attention_fwd / attention_bwd
+    B, N, D, H = 2, 5, 64, 2
+    q, k, v, do = (_rand((B, N, D), gpu, 15 + i) for i in range(4))
+    refused('attention_fwd: q', lambda: ops.attention_fwd(q, k, v, 3, 0.2))                                      # 64 columns are not 3 heads
+    scale = (D // H) ** -0.5
+    o, lse = ops.attention_fwd(q, k, v, H, scale)
+    dq, dk, dv = nan(B, N, D), nan(B, N, D), nan(B, N, D)
+    refused('attention_bwd: lse', lambda: ops.attention_bwd(q, k, v, o, do, lse.flatten()[:1], H, scale, dq, dk, dv), dq, dk, dv)
+    refused('attention_bwd: dq', lambda: ops.attention_bwd(q, k, v, o, do, lse, H, scale, dq.bfloat16(), dk.bfloat16(), dv.bfloat16()), dq, dk, dv)
+    ops.attention_bwd(q, k, v, o, do, lse, H, scale, dq, dk, dv)
+    torch.cuda.synchronize()
+    qr, kr, vr = (t.double().clone().requires_grad_() for t in (q, k, v))
+    o_ref, lse_ref = _sdpa_ref(qr, kr, vr, H, scale)
+    o_ref.backward(do.double())
+    torch.testing.assert_close(o.double(), o_ref.detach(), rtol=1e-4, atol=1e-5)
+    torch.testing.assert_close(lse.double(), lse_ref.detach(), rtol=1e-4, atol=1e-4)
+    for got, want in ((dq, qr.grad), (dk, kr.grad), (dv, vr.grad)):
+        torch.testing.assert_close(got.double(), want, rtol=2e-4, atol=2e-5)
+
+
 # ---------------------------------------------------------------------------------------------
 # fused MLP branch (vited_mlp_fwd): y = x + fc2(gelu(fc1(LN(x))))  (vision_transformer.py:126,271; timm Mlp)
 # ---------------------------------------------------------------------------------------------

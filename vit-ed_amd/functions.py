@@ -1044,8 +1044,10 @@ class DecoderFn(torch.autograd.Function):
         if seg is not None:
             if rt.keep_attn or rt.keep_cam:
                 raise NotImplementedError('the attention-map paths (keep_attn / keep_cam) take gathered features, not an image-1 index')
-            assert seg.index.numel() == batch, f'{seg.index.numel()} image-1 indices for {batch} image-2 samples'
-        assert feats.shape == (b1, rt.n1, rt.dim), f'features {tuple(feats.shape)} do not match {b1} context items'
+            if seg.index.numel() != batch:
+                raise ValueError(f'{seg.index.numel()} image-1 indices for {batch} image-2 samples')
+        if feats.shape != (b1, rt.n1, rt.dim):
+            raise ValueError(f'features {tuple(feats.shape)} do not match {b1} context items')
         ctxf = feats.detach().contiguous().float().view(b1 * rt.n1, rt.dim)
         tape = []
         d = rt.dim

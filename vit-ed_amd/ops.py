@@ -1,7 +1,7 @@
 """Functional wrappers over the C ABI: one Python function per entry point of include/vited.h.
 
-These allocate outputs (PyTorch owns every buffer), validate shape/dtype/contiguity BEFORE the
-launch and raise on any non-zero status.  They are not autograd-aware; ``functions.py`` composes
+These allocate outputs (PyTorch owns every buffer), pass every tensor through ``_check`` (dtype, extent,
+strides, device: ValueError BEFORE the launch) and raise on any non-zero status.  They are not autograd-aware; ``functions.py`` composes
 them into the encoder / decoder autograd Functions.  Every op launches on torch's current HIP
 stream, never synchronises and never allocates on the device side, so the whole forward+backward
 is hipGraph-capturable.
@@ -19,6 +19,7 @@ from ._lib import (B_KN, B_NK, BF16, EPI_GELU, EPI_GELU_GRAD, EPI_MUL, EPI_MUL_G
 
 _DTYPE = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16, torch.int32: I32, torch.int64: I64}
 _FLOATS = (torch.float32, torch.bfloat16, torch.float16)       # what the ranking and pair-score entries take
+_ACT = (torch.float32, torch.bfloat16)                         # activations: what _code takes
 
 
 def _code(dtype: torch.dtype) -> int:
@@ -28,11 +29,11 @@ def _code(dtype: torch.dtype) -> int:
     return _DTYPE[dtype]
 
 
-def _need_gpu(*tensors):
+def _need_gpu(*tensors, error=RuntimeError):
     for t in tensors:
         if t is not None and not t.is_cuda:
-            raise RuntimeError('vited ops run on the MI355X HIP kernels only: got a CPU tensor '
-                               '(there is no CPU fallback; the fp32 CPU oracle lives in oracle/ for tests)')
+            raise error('vited ops run on the MI355X HIP kernels only: got a CPU tensor '
+                        '(there is no CPU fallback; the fp32 CPU oracle lives in oracle/ for tests)')
 
 
 def _ptr(t):
@@ -52,11 +53,90 @@ def _host_array(ctype, values, length=None):
     return (ctype * (len(values) if length is None else length))(*values)
 
 
-def _rows2d(t: torch.Tensor):
-    """(tensor, row stride) of a [rows, dim] view whose last dim is dense."""
-    if t.dim() != 2 or t.stride(1) != 1:
-        raise ValueError(f'expected a 2-D tensor with a dense last dim, got shape {tuple(t.shape)} stride {t.stride()}')
-    return t.stride(0)
+# ---- the one argument check: every tensor whose pointer reaches _lib.call goes through _check first ------------------------------
+_f32, _bf16, _i32, _i64, _u8, _f64 = torch.float32, torch.bfloat16, torch.int32, torch.int64, torch.uint8, torch.float64
+CONTIGUOUS = 'contiguous'              # the stride assumptions an entry point can make of a buffer
+DENSE_LAST = 'dense last dim'          # [..., rows, width]: unit column stride, any row / item stride that keeps them apart
+DENSE_ITEMS = 'dense items'            # [B, ...]: every item contiguous, any batch stride
+_ANY2, _ANY3 = (None, None), (None, None, None)      # any 2-D / 3-D extent: recognised by identity, no walk over the sizes
+
+
+class _Min(int):
+    """An extent of ``_check``: at least this many."""
+
+
+def _check(op, name, t, dtype, shape, dev, strides=CONTIGUOUS, optional=False, like=None, ld=None):
+    """Raise ValueError unless ``t`` is a tensor of ``dtype`` (one, a tuple of them, or None: any) on ``dev`` with the extent ``shape``
+    and the stride assumption ``strides`` (None: the caller copies it dense itself); returns ``t``.  ``shape`` is a tuple of sizes
+    (None: any, ``_Min(n)``: at least n), an element count for a buffer of any rank (an int or a ``_Min``), or None.  ``ld``: the row
+    stride it must have.  None passes only where ``optional``.  ``like`` names the operand the expectation was taken from.  An
+    activation (``_ACT``) of another dtype is a TypeError, as from ``_code``.  Host work only: metadata, never device memory."""
+    if t is None and optional:
+        return None
+    try:
+        ok = t.device == dev and (dtype is None or t.dtype == dtype or (type(dtype) is tuple and t.dtype in dtype))
+    except AttributeError:                         # None, or not a tensor
+        ok = False
+    if ok:
+        sizes = t.shape
+        if isinstance(shape, tuple):
+            if sizes != shape:                     # unequal: a wildcard, or a wrong extent
+                ok = len(sizes) == len(shape)
+                for s, e in zip(sizes, shape) if ok and shape is not _ANY2 and shape is not _ANY3 else ():
+                    if e is not None and (s < e if type(e) is _Min else s != e):
+                        ok = False
+        elif shape is not None:
+            ok = t.numel() >= shape if type(shape) is _Min else t.numel() == shape
+    if ok:
+        if strides is CONTIGUOUS:
+            ok = t.is_contiguous()
+        elif strides is DENSE_LAST:
+            if ld is not None or not sizes or not t.is_contiguous():          # a contiguous tensor has dense, disjoint rows
+                st, n = t.stride(), len(sizes)
+                ok = n >= 1 and (sizes[-1] <= 1 or st[-1] == 1) and (
+                    n < 2 or sizes[-2] <= 1 or (st[-2] >= sizes[-1] if ld is None else st[-2] == ld)) and (
+                    n < 3 or sizes[-3] <= 1 or st[-3] >= sizes[-2] * st[-2])          # nor do the [rows, width] items overlap
+        elif strides is DENSE_ITEMS:
+            want = 1
+            for size, stride in zip(reversed(sizes[1:]), reversed(t.stride()[1:])):
+                ok = ok and (size <= 1 or stride == want)
+                want *= size
+    if ok:
+        return t
+    if isinstance(shape, tuple):
+        want = ['*' if e is None else f'>={int(e)}' if type(e) is _Min else str(e) for e in shape]
+        extent = f'vector of length {want[0]}' if len(want) == 1 else '[' + ', '.join(want) + ']'
+    else:
+        extent = 'tensor' if shape is None else f'buffer of {">=" if type(shape) is _Min else ""}{int(shape)} elements'
+    dtypes = 'any dtype' if dtype is None else ' / '.join(str(d).replace('torch.', '') for d in (dtype if type(dtype) is tuple else (dtype,)))
+    want = f'{strides or "strided"} {dtypes} {extent}{f" with row stride {ld}" if ld is not None else ""} on {dev}'
+    got = f'{t.dtype} {list(t.shape)} stride {list(t.stride())} on {t.device}' if torch.is_tensor(t) else type(t).__name__
+    error = TypeError if dtype is _ACT and torch.is_tensor(t) and t.dtype not in _ACT else ValueError
+    raise error(f'{op}: {name} {f"does not match {like}: it " if like else ""}must be a {want}, got {got}')
+
+
+def _out(op, name, t, dtype, shape, dev, strides=CONTIGUOUS):
+    """The ``out=None`` pattern: a fresh ``dtype`` tensor of ``shape`` (a vector where it is an element count), or the given one checked."""
+    return torch.empty(shape, dtype=dtype, device=dev) if t is None else _check(op, name, t, dtype, shape, dev, strides)
+
+
+def _rows(op, name, t, dtype, dev, cols=None, rows=None, like=None):
+    """Row stride of a [rows, cols] operand with a dense last dim, checked."""
+    return _check(op, name, t, dtype, _ANY2 if cols is rows is None else (rows, cols), dev, DENSE_LAST, like=like).stride(0)
+
+
+def _head_dim(op, name, d, heads):
+    if heads <= 0 or d % heads:
+        raise ValueError(f'{op}: {name} has {d} columns, which are not {heads} heads')
+    return d // heads
+
+
+def _head_operand(op, name, t, dtype, shape, dev, optional=False, like=None):
+    """Strides in front of the dense last dim of a q / k / v-like operand [..., heads * head_dim] - a column slice of a packed
+    projection: (row stride,) of [rows, D], (batch stride, token stride) of [B, N, D]; zeros for an absent optional one."""
+    if t is None and optional:
+        return (0,) * (len(shape) - 1)
+    return _check(op, name, t, dtype, shape, dev, DENSE_LAST, like=like).stride()[:-1]
 
 
 _ws_cache = {}
@@ -86,19 +166,18 @@ def workspace(nbytes: int, device) -> torch.Tensor:
     return buf
 
 
-def _scratch(nbytes: int, device):
-    """(pointer, size in bytes) of ``workspace(nbytes, device)``."""
-    ws = workspace(nbytes, device)
-    return ws.data_ptr(), ws.numel() * 4
+def _scratch(nbytes: int, device, align: int = 1):
+    """(pointer, size in bytes) of ``workspace(nbytes, device)``; with ``align``, of one that many bytes larger, the pointer rounded up."""
+    ws = workspace(nbytes + (align if align > 1 else 0), device)
+    base = -(-ws.data_ptr() // align) * align
+    return base, ws.numel() * 4 - (base - ws.data_ptr())
 
 
 # ---------------------------------------------------------------------------------------------
 def cast(src: torch.Tensor, dtype: torch.dtype, out: torch.Tensor | None = None) -> torch.Tensor:
     _need_gpu(src, out)
-    src = src.contiguous()
-    if out is None:
-        out = torch.empty_like(src, dtype=dtype)
-    assert out.dtype == dtype and out.numel() == src.numel() and out.is_contiguous()
+    src = _check('cast', 'src', src, _ACT, None, src.device, None).contiguous()
+    out = torch.empty_like(src, dtype=dtype) if out is None else _check('cast', 'out', out, dtype, src.numel(), src.device)
     _lib.call('vited_cast', _ptr(src), _code(src.dtype), _ptr(out), _code(dtype), src.numel(), _stream())
     return out
 
@@ -106,27 +185,19 @@ def cast(src: torch.Tensor, dtype: torch.dtype, out: torch.Tensor | None = None)
 def scale_rows_cast(src: torch.Tensor, row_scale: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
     """dst[r, :] = dtype(row_scale[r] * src[r, :]) for fp32 ``src`` [rows, dim] (``vited_scale_rows_cast``)."""
     _need_gpu(src, row_scale)
+    ld = _rows('scale_rows_cast', 'src', src, _f32, src.device)
     rows, dim = src.shape
-    _check_row_scale(row_scale, rows)
-    assert src.dtype == torch.float32
+    _check('scale_rows_cast', 'row_scale', row_scale, _f32, (rows,), src.device)
     out = torch.empty((rows, dim), dtype=dtype, device=src.device)
-    _lib.call('vited_scale_rows_cast', _ptr(src), _rows2d(src), _ptr(row_scale), _ptr(out), _code(dtype), dim, rows, dim, _stream())
+    _lib.call('vited_scale_rows_cast', _ptr(src), ld, _ptr(row_scale), _ptr(out), _code(dtype), dim, rows, dim, _stream())
     return out
-
-
-def _check_row_scale(row_scale, rows):
-    """A drop-path scale vector: fp32, one value per row, contiguous."""
-    if row_scale.dtype != torch.float32 or row_scale.dim() != 1 or row_scale.numel() != rows or not row_scale.is_contiguous():
-        raise ValueError(f'row scale: expected a contiguous fp32 vector of {rows} rows, got {row_scale.dtype} {tuple(row_scale.shape)}')
 
 
 def cast_transpose(w: torch.Tensor, dtype: torch.dtype, out: torch.Tensor | None = None) -> torch.Tensor:
     """fp32 [R, C] -> dtype [C, R] (transposed weight shadow)."""
     _need_gpu(w, out)
-    assert w.dtype == torch.float32 and w.dim() == 2 and w.is_contiguous()
-    if out is None:
-        out = torch.empty((w.shape[1], w.shape[0]), dtype=dtype, device=w.device)
-    assert out.dtype == dtype and out.shape == (w.shape[1], w.shape[0]) and out.is_contiguous()
+    _check('cast_transpose', 'w', w, _f32, _ANY2, w.device)
+    out = _out('cast_transpose', 'out', out, dtype, (w.shape[1], w.shape[0]), w.device)
     _lib.call('vited_cast_transpose', _ptr(w), _ptr(out), _code(dtype), w.shape[0], w.shape[1], _stream())
     return out
 
@@ -138,13 +209,14 @@ class WeightShadowPlan:
     def __init__(self, entries):
         """entries: iterable of (w fp32 [rows, cols] contiguous, dst bf16 [rows, cols] | None, dst_t bf16 [cols, rows] | None)."""
         rows_, keep, tile = [], [], 0
-        for w, dst, dst_t in entries:
+        for i, (w, dst, dst_t) in enumerate(entries):
             _need_gpu(w, dst, dst_t)
-            assert w.dtype == torch.float32 and w.dim() == 2 and w.is_contiguous() and w.data_ptr() % 16 == 0
+            _check('WeightShadowPlan', f'entries[{i}] w', w, _f32, _ANY2, w.device)
             r, c = w.shape
-            for t, shape in ((dst, (r, c)), (dst_t, (c, r))):
-                assert t is None or (t.dtype == torch.bfloat16 and tuple(t.shape) == shape and t.is_contiguous()
-                                     and t.data_ptr() % 16 == 0)
+            _check('WeightShadowPlan', f'entries[{i}] dst', dst, _bf16, (r, c), w.device, optional=True)
+            _check('WeightShadowPlan', f'entries[{i}] dst_t', dst_t, _bf16, (c, r), w.device, optional=True)
+            if any(_ptr(t) % 16 for t in (w, dst, dst_t)):
+                raise ValueError(f'WeightShadowPlan: entries[{i}] w, dst and dst_t must be 16-byte aligned')
             if dst is None and dst_t is None:
                 continue
             rows_.append([w.data_ptr(), _ptr(dst), _ptr(dst_t), r, c, tile])
@@ -167,14 +239,14 @@ def patchify(img: torch.Tensor, patch: int, dtype: torch.dtype, batch_index: tor
     u8 = img.dtype == torch.uint8
     if not u8 and img.dtype != torch.float32:
         img = img.float()
-    assert img.dim() == 4 and img.shape[2] == img.shape[3], 'expected [B, C, S, S]'
-    b, c, s, _ = img.shape
-    if img.stride()[1:] != (s * s, s, 1):
+    if img.dim() == 4 and img.stride()[1:] != (img.shape[2] * img.shape[3], img.shape[3], 1):
         img = img.contiguous()
-    nb = b
-    if batch_index is not None:
-        assert batch_index.dtype == torch.int64 and batch_index.is_contiguous()
-        nb = batch_index.numel()
+    _check('patchify', 'img', img, (_u8, _f32), (None, None) + tuple(img.shape[2:3]) * 2, img.device, DENSE_ITEMS)     # [B, C, S, S]
+    b, c, s, _ = img.shape
+    _check('patchify', 'batch_index', batch_index, _i64, None, img.device, optional=True)
+    nb = b if batch_index is None else batch_index.numel()
+    if patch < 1 or s % patch:
+        raise ValueError(f'patchify: img is {s} x {s}, which {patch} x {patch} patches do not tile')
     g = s // patch
     out = torch.empty((nb * g * g, c * patch * patch), dtype=dtype, device=img.device)
     if u8:
@@ -190,37 +262,38 @@ def crop_pairs_u8(regions: torch.Tensor, cells: torch.Tensor, erode: torch.Tenso
     """regions uint8 [B, C, 2 S, 3 S] (any batch stride), cells int32 [B, 2], erode int32 [B] -> uint8 [B, 2, C, S, S]: the pair
     of eroded grid cells resized back to S x S (``vited_crop_pairs_u8``; div2k_patch.py:108-121,155-162)."""
     _need_gpu(regions, cells, erode)
-    s = int(img_size)
-    assert regions.dtype == torch.uint8 and regions.dim() == 4 and regions.shape[2] == 2 * s and regions.shape[3] == 3 * s
-    b, c = regions.shape[:2]
-    if regions.stride()[1:] != (6 * s * s, 3 * s, 1):
+    s, dev = int(img_size), regions.device
+    if regions.dim() == 4 and regions.stride()[1:] != (6 * s * s, 3 * s, 1):
         regions = regions.contiguous()
-    assert cells.dtype == torch.int32 and cells.shape == (b, 2) and cells.is_contiguous()
-    assert erode.dtype == torch.int32 and erode.shape == (b,) and erode.is_contiguous()
+    _check('crop_pairs_u8', 'regions', regions, _u8, (None, None, 2 * s, 3 * s), dev, DENSE_ITEMS)
+    b, c = regions.shape[:2]
+    _check('crop_pairs_u8', 'cells', cells, _i32, (b, 2), dev)
+    _check('crop_pairs_u8', 'erode', erode, _i32, (b,), dev)
     out = torch.empty((b, 2, c, s, s), dtype=torch.uint8, device=regions.device)
     _lib.call('vited_crop_pairs_u8', _ptr(regions), regions.stride(0), _ptr(cells), _ptr(erode), _ptr(out), b, c, s, _stream())
     return out
 
 
-def _store_args(store: torch.Tensor, img_off: torch.Tensor, img_hw: torch.Tensor) -> int:
+def _store_args(op, store: torch.Tensor, img_off: torch.Tensor, img_hw: torch.Tensor) -> int:
     """The resident image store of the feed entry points (``engine.Div2kImageStore``); returns its image count."""
-    assert store.dtype == torch.uint8 and store.dim() == 1 and store.is_contiguous()
-    assert img_off.dtype == torch.int64 and img_off.dim() == 1 and img_off.is_contiguous()
-    assert img_hw.dtype == torch.int32 and img_hw.shape == (img_off.numel(), 2) and img_hw.is_contiguous()
+    _check(op, 'store', store, _u8, (None,), store.device)
+    _check(op, 'img_off', img_off, _i64, (None,), store.device)
+    _check(op, 'img_hw', img_hw, _i32, (img_off.numel(), 2), store.device)
     return img_off.numel()
 
 
-def _batch_args(b: int, *specs):
-    for t, dtype, shape in specs:
-        assert t.dtype == dtype and tuple(t.shape) == (b, *shape) and t.is_contiguous(), (t.dtype, tuple(t.shape), dtype, (b, *shape))
+def _batch_args(op, dev, b: int, **specs):
+    """Per-sample plan columns: name=(tensor, dtype, shape of one sample)."""
+    for name, (t, dtype, shape) in specs.items():
+        _check(op, name, t, dtype, (b, *shape), dev)
 
 
-def _crop_args(img: torch.Tensor, out: torch.Tensor | None, in_place: bool):
+def _crop_args(op, img: torch.Tensor, out: torch.Tensor | None, in_place: bool):
     """(B, S, out) of uint8 crops [B, 3, S, S] and an ``out`` like them (made here when None); it may be ``img`` only with ``in_place``."""
-    assert img.dtype == torch.uint8 and img.dim() == 4 and img.shape[1] == 3 and img.shape[2] == img.shape[3] and img.is_contiguous()
-    if out is None:
-        out = torch.empty_like(img)
-    assert out.dtype == torch.uint8 and out.shape == img.shape and out.is_contiguous() and (in_place or out.data_ptr() != img.data_ptr())
+    _check(op, 'img', img, _u8, (None, 3) + tuple(img.shape[2:3]) * 2, img.device)
+    out = _out(op, 'out', out, _u8, tuple(img.shape), img.device)
+    if not in_place and out.data_ptr() == img.data_ptr():
+        raise ValueError(f'{op}: out must not be img itself (the filter cannot run in place)')
     return img.shape[0], img.shape[2], out
 
 
@@ -233,12 +306,11 @@ def div2k_regions_u8(store: torch.Tensor, img_off: torch.Tensor, img_hw: torch.T
     img_off int64 [n] with sizes img_hw int32 [n, 2] (H, W); the caller guarantees that every image lies inside the store and is
     at least 2 S x 3 S (``engine.Div2kImageStore`` does).  Indices and origins are clamped by the kernel."""
     _need_gpu(store, img_off, img_hw, image, flags, minv, rgb, crop, out)
-    s, n, b = int(img_size), _store_args(store, img_off, img_hw), image.numel()
-    _batch_args(b, (image, torch.int32, ()), (flags, torch.int32, ()), (minv, torch.float64, (6,)), (rgb, torch.float32, (3,)),
-                (crop, torch.int32, (2,)))
-    if out is None:
-        out = torch.empty((b, 3, 2 * s, 3 * s), dtype=torch.uint8, device=store.device)
-    assert out.dtype == torch.uint8 and tuple(out.shape) == (b, 3, 2 * s, 3 * s) and out.is_contiguous()
+    op, dev = 'div2k_regions_u8', store.device
+    s, n, b = int(img_size), _store_args(op, store, img_off, img_hw), image.numel()
+    _batch_args(op, dev, b, image=(image, _i32, ()), flags=(flags, _i32, ()), minv=(minv, _f64, (6,)), rgb=(rgb, _f32, (3,)),
+                crop=(crop, _i32, (2,)))
+    out = _out(op, 'out', out, _u8, (b, 3, 2 * s, 3 * s), dev)
     _lib.call('vited_div2k_regions_u8', _ptr(store), _ptr(img_off), _ptr(img_hw), n, _ptr(image), _ptr(flags), _ptr(minv), _ptr(rgb),
               _ptr(crop), _ptr(out), b, s, _stream())
     return out
@@ -252,12 +324,11 @@ def hisfrag_windows_u8(store: torch.Tensor, img_off: torch.Tensor, img_hw: torch
     the inverse warp map fp64 [B, 6] and the window origin int32 [B, 2] (top, left) in unpadded image coordinates, negative in the
     pad.  store / img_off / img_hw as for ``div2k_regions_u8``.  Everything outside the image is 0; indices are clamped."""
     _need_gpu(store, img_off, img_hw, image, flags, afix, minv, origin, out)
-    s, n, b = int(img_size), _store_args(store, img_off, img_hw), image.numel()
-    _batch_args(b, (image, torch.int32, ()), (flags, torch.int32, ()), (afix, torch.int64, (6,)), (minv, torch.float64, (6,)),
-                (origin, torch.int32, (2,)))
-    if out is None:
-        out = torch.empty((b, 3, s, s), dtype=torch.uint8, device=store.device)
-    assert out.dtype == torch.uint8 and tuple(out.shape) == (b, 3, s, s) and out.is_contiguous()
+    op, dev = 'hisfrag_windows_u8', store.device
+    s, n, b = int(img_size), _store_args(op, store, img_off, img_hw), image.numel()
+    _batch_args(op, dev, b, image=(image, _i32, ()), flags=(flags, _i32, ()), afix=(afix, _i64, (6,)), minv=(minv, _f64, (6,)),
+                origin=(origin, _i32, (2,)))
+    out = _out(op, 'out', out, _u8, (b, 3, s, s), dev)
     _lib.call('vited_hisfrag_windows_u8', _ptr(store), _ptr(img_off), _ptr(img_hw), n, _ptr(image), _ptr(flags), _ptr(afix), _ptr(minv),
               _ptr(origin), _ptr(out), b, s, _stream())
     return out
@@ -270,8 +341,9 @@ def hisfrag_jitter_u8(img: torch.Tensor, flags: torch.Tensor, order: torch.Tenso
     (0 brightness, 1 contrast, 2 saturation, 3 hue), the brightness / contrast / saturation factors fp32 [B, 3] and the uint8 hue
     shift int32 [B].  ``out`` may be ``img`` itself."""
     _need_gpu(img, flags, order, factors, hue, out)
-    b, s, out = _crop_args(img, out, in_place=True)
-    _batch_args(b, (flags, torch.int32, ()), (order, torch.int32, (4,)), (factors, torch.float32, (3,)), (hue, torch.int32, ()))
+    b, s, out = _crop_args('hisfrag_jitter_u8', img, out, in_place=True)
+    _batch_args('hisfrag_jitter_u8', img.device, b, flags=(flags, _i32, ()), order=(order, _i32, (4,)), factors=(factors, _f32, (3,)),
+                hue=(hue, _i32, ()))
     sums = torch.empty(b, dtype=torch.int64, device=img.device)             # the contrast means' L sums; the entry point zeroes them
     _lib.call('vited_hisfrag_jitter_u8', _ptr(img), _ptr(flags), _ptr(order), _ptr(factors), _ptr(hue), _ptr(sums), _ptr(out), b, s, _stream())
     return out
@@ -281,8 +353,8 @@ def hisfrag_blur_u8(img: torch.Tensor, flags: torch.Tensor, weights: torch.Tenso
     """GaussianBlur((3, 3)) on uint8 crops [B, 3, S, S] (``vited_hisfrag_blur_u8``; hisfrag.py:76-78): per sample flag bit 8 (blur on; a
     sample without it is copied) and the 1-D weights (k_edge, k_mid) fp32 [B, 2].  ``out`` must not overlap ``img``."""
     _need_gpu(img, flags, weights, out)
-    b, s, out = _crop_args(img, out, in_place=False)
-    _batch_args(b, (flags, torch.int32, ()), (weights, torch.float32, (2,)))
+    b, s, out = _crop_args('hisfrag_blur_u8', img, out, in_place=False)
+    _batch_args('hisfrag_blur_u8', img.device, b, flags=(flags, _i32, ()), weights=(weights, _f32, (2,)))
     _lib.call('vited_hisfrag_blur_u8', _ptr(img), _ptr(flags), _ptr(weights), _ptr(out), b, s, _stream())
     return out
 
@@ -297,13 +369,11 @@ def michigan_windows_u8(store: torch.Tensor, img_off: torch.Tensor, img_hw: torc
     n_holes int32 [B] count.  store / img_off / img_hw as for ``div2k_regions_u8``.  Everything outside the image, and a tap outside
     the window, is 255; indices and the hole count are clamped."""
     _need_gpu(store, img_off, img_hw, image, flags, origin, x0, kx, y0, ky, holes, n_holes, out)
-    s, n, b = int(img_size), _store_args(store, img_off, img_hw), image.numel()
-    i32 = torch.int32
-    _batch_args(b, (image, i32, ()), (flags, i32, ()), (origin, i32, (2,)), (x0, i32, (s,)), (kx, i32, (s, 3)), (y0, i32, (s,)),
-                (ky, i32, (s, 3)), (holes, i32, (16, 4)), (n_holes, i32, ()))
-    if out is None:
-        out = torch.empty((b, 3, s, s), dtype=torch.uint8, device=store.device)
-    assert out.dtype == torch.uint8 and tuple(out.shape) == (b, 3, s, s) and out.is_contiguous()
+    op, dev = 'michigan_windows_u8', store.device
+    s, n, b = int(img_size), _store_args(op, store, img_off, img_hw), image.numel()
+    _batch_args(op, dev, b, image=(image, _i32, ()), flags=(flags, _i32, ()), origin=(origin, _i32, (2,)), x0=(x0, _i32, (s,)),
+                kx=(kx, _i32, (s, 3)), y0=(y0, _i32, (s,)), ky=(ky, _i32, (s, 3)), holes=(holes, _i32, (16, 4)), n_holes=(n_holes, _i32, ()))
+    out = _out(op, 'out', out, _u8, (b, 3, s, s), dev)
     _lib.call('vited_michigan_windows_u8', _ptr(store), _ptr(img_off), _ptr(img_hw), n, _ptr(image), _ptr(flags), _ptr(origin), _ptr(x0),
               _ptr(kx), _ptr(y0), _ptr(ky), _ptr(holes), _ptr(n_holes), _ptr(out), b, s, _stream())
     return out
@@ -314,8 +384,8 @@ def michigan_blur_gray_u8(img: torch.Tensor, flags: torch.Tensor, weights: torch
     michigan.py:83-85): per sample flag bit 8 (blur), bit 32 (grey; a sample with neither is copied) and the box-blur weights
     (ww, fw) int32 [B, 2].  ``out`` must not overlap ``img``."""
     _need_gpu(img, flags, weights, out)
-    b, s, out = _crop_args(img, out, in_place=False)
-    _batch_args(b, (flags, torch.int32, ()), (weights, torch.int32, (2,)))
+    b, s, out = _crop_args('michigan_blur_gray_u8', img, out, in_place=False)
+    _batch_args('michigan_blur_gray_u8', img.device, b, flags=(flags, _i32, ()), weights=(weights, _i32, (2,)))
     _lib.call('vited_michigan_blur_gray_u8', _ptr(img), _ptr(flags), _ptr(weights), _ptr(out), b, s, _stream())
     return out
 
@@ -323,8 +393,10 @@ def michigan_blur_gray_u8(img: torch.Tensor, flags: torch.Tensor, weights: torch
 def slice_rows_cast(x: torch.Tensor, row_offset: int, rows: int, dtype: torch.dtype) -> torch.Tensor:
     """fp32 [B, R, D] -> dtype [B * rows, D] taking rows [row_offset, row_offset + rows) of every batch."""
     _need_gpu(x)
-    assert x.dtype == torch.float32 and x.dim() == 3 and x.is_contiguous()
+    _check('slice_rows_cast', 'x', x, _f32, _ANY3, x.device)
     b, r, d = x.shape
+    if not 0 <= row_offset <= row_offset + rows <= r:
+        raise ValueError(f'slice_rows_cast: x has {r} rows per batch, rows [{row_offset}, {row_offset + rows}) are not inside them')
     out = torch.empty((b * rows, d), dtype=dtype, device=x.device)
     _lib.call('vited_slice_rows_cast', _ptr(x), _ptr(out), _code(dtype), b, r, row_offset, rows, d, _stream())
     return out
@@ -333,15 +405,17 @@ def slice_rows_cast(x: torch.Tensor, row_offset: int, rows: int, dtype: torch.dt
 def write_cls_row(x: torch.Tensor, cls: torch.Tensor, pos: torch.Tensor):
     """x fp32 [B, R, D]: x[:, 0] = cls + pos[0]."""
     _need_gpu(x, cls, pos)
-    assert x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 3
+    _check('write_cls_row', 'x', x, _f32, _ANY3, x.device)
     b, r, d = x.shape
+    _check('write_cls_row', 'cls', cls, _f32, _Min(d), x.device)
+    _check('write_cls_row', 'pos', pos, _f32, _Min(d), x.device)
     _lib.call('vited_write_cls_row', _ptr(x), _ptr(cls), _ptr(pos), b, r, d, _stream())
 
 
 def sum_rows(x: torch.Tensor) -> torch.Tensor:
     """[batch, width] (fp32 or bf16, dense rows) -> fp32 [width] column sums, deterministic."""
     _need_gpu(x)
-    ld = _rows2d(x)
+    ld = _rows('sum_rows', 'x', x, _ACT, x.device)
     b, w = x.shape
     out = torch.empty(w, dtype=torch.float32, device=x.device)
     ws = _scratch(_lib.load().vited_sum_rows_workspace_bytes(b, w), x.device)
@@ -350,20 +424,26 @@ def sum_rows(x: torch.Tensor) -> torch.Tensor:
 
 
 # ---------------------------------------------------------------------------------------------
+def _ln_grads(op, dev, dim, dgamma, dbeta):
+    """(accumulate, dgamma, dbeta): the given fp32 [dim] pair to add onto, or a fresh pair."""
+    if dgamma is None:
+        return False, torch.empty(dim, dtype=torch.float32, device=dev), torch.empty(dim, dtype=torch.float32, device=dev)
+    return True, _check(op, 'dgamma', dgamma, _f32, dim, dev), _check(op, 'dbeta', dbeta, _f32, dim, dev)
+
+
 def layernorm_fwd(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float, out_dtype: torch.dtype, out=None):
     """x fp32 [rows, dim] (row-strided ok) -> (y [rows, dim] out_dtype, mean, rstd).  ``out`` = (y, mean, rstd) pre-made
     (e.g. row slices of larger tensors)."""
     _need_gpu(x, gamma, beta)
-    assert x.dtype == torch.float32 and gamma.dtype == torch.float32 and beta.dtype == torch.float32
-    ld = _rows2d(x)
+    op, dev = 'layernorm_fwd', x.device
+    ld = _rows(op, 'x', x, _f32, dev)
     rows, dim = x.shape
-    if out is not None:
-        y, mean, rstd = out
-        assert y.shape == (rows, dim) and y.dtype == out_dtype and _rows2d(y) == dim and mean.numel() == rows and rstd.numel() == rows
-    else:
-        y = torch.empty((rows, dim), dtype=out_dtype, device=x.device)
-        mean = torch.empty(rows, dtype=torch.float32, device=x.device)
-        rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
+    _check(op, 'gamma', gamma, _f32, (dim,), dev)
+    _check(op, 'beta', beta, _f32, (dim,), dev)
+    y, mean, rstd = out if out is not None else (None, None, None)
+    y = _out(op, 'out[0] (y)', y, out_dtype, (rows, dim), dev)
+    mean = _out(op, 'out[1] (mean)', mean, _f32, rows, dev)
+    rstd = _out(op, 'out[2] (rstd)', rstd, _f32, rows, dev)
     _lib.call('vited_layernorm_fwd', _ptr(x), ld, _ptr(gamma), _ptr(beta), _ptr(y), _code(out_dtype), dim, _ptr(mean), _ptr(rstd), rows,
               dim, float(eps), _stream())
     return y, mean, rstd
@@ -377,32 +457,27 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, dx_in=None, dx_out=None, want_lp: bo
     dx = (dx_in or 0) + LN'(dy).  ``dx_out`` / ``dx_lp`` may be given as pre-made (row-strided)
     destinations - e.g. the cls rows of a zero-filled token-gradient tensor.
     ``lp_scale`` (fp32 [rows]): dx_lp = lp_dtype(lp_scale[r] * dx[r]) (``vited_layernorm_bwd_scaled``; fp32 allowed then)."""
-    _need_gpu(dy, x, gamma, mean, rstd, dx_in, dx_out, dx_lp, lp_scale)
-    dy_ld, x_ld = _rows2d(dy), _rows2d(x)
+    _need_gpu(dy, x, gamma, mean, rstd, dx_in, dx_out, dx_lp, lp_scale, dgamma, dbeta)
+    op, dev = 'layernorm_bwd', x.device
+    x_ld = _rows(op, 'x', x, _f32, dev)
     rows, dim = x.shape
-    assert dy.shape == x.shape and x.dtype == torch.float32
-    if dx_out is None:
-        dx_out = torch.empty((rows, dim), dtype=torch.float32, device=x.device)
+    dy_ld = _rows(op, 'dy', dy, _ACT, dev, dim, rows)
+    for name, t, size in (('gamma', gamma, dim), ('mean', mean, rows), ('rstd', rstd, rows)):
+        _check(op, name, t, _f32, size, dev)
+    dx_out = _out(op, 'dx_out', dx_out, _f32, (rows, dim), dev, DENSE_LAST)
     if lp_scale is not None:
-        _check_row_scale(lp_scale, rows)
+        _check(op, 'lp_scale', lp_scale, _f32, (rows,), dev)
         want_lp = True
     else:
         lp_dtype = torch.bfloat16
-    if want_lp and dx_lp is None:
-        dx_lp = torch.empty((rows, dim), dtype=lp_dtype, device=x.device)
-    assert dx_lp is None or dx_lp.dtype == lp_dtype
-    if dx_in is not None:
-        assert dx_in.dtype == torch.float32 and dx_in.shape == x.shape
-    accumulate = dgamma is not None
-    if accumulate:
-        assert dbeta is not None and dgamma.dtype == dbeta.dtype == torch.float32 and dgamma.is_contiguous() and dbeta.is_contiguous()
-    else:
-        dgamma = torch.empty(dim, dtype=torch.float32, device=x.device)
-        dbeta = torch.empty(dim, dtype=torch.float32, device=x.device)
+    if want_lp or dx_lp is not None:
+        dx_lp = _out(op, 'dx_lp', dx_lp, lp_dtype, (rows, dim), dev, DENSE_LAST)
+    _check(op, 'dx_in', dx_in, _f32, (rows, dim), dev, DENSE_LAST, optional=True)
+    accumulate, dgamma, dbeta = _ln_grads(op, dev, dim, dgamma, dbeta)
     ws = _scratch(_lib.load().vited_layernorm_bwd_workspace_bytes(rows, dim), x.device)
     head = (_ptr(dy), _code(dy.dtype), dy_ld, _ptr(x), x_ld, _ptr(gamma), _ptr(mean), _ptr(rstd),
-            _ptr(dx_in), _rows2d(dx_in) if dx_in is not None else 0, _ptr(dx_out), _rows2d(dx_out),
-            _ptr(dx_lp), _code(lp_dtype), _rows2d(dx_lp) if dx_lp is not None else 0)
+            _ptr(dx_in), dx_in.stride(0) if dx_in is not None else 0, _ptr(dx_out), dx_out.stride(0),
+            _ptr(dx_lp), _code(lp_dtype), dx_lp.stride(0) if dx_lp is not None else 0)
     tail = (_ptr(dgamma), _ptr(dbeta), int(accumulate), rows, dim, *ws, _stream())
     if lp_scale is not None:
         _lib.call('vited_layernorm_bwd_scaled', *head, _ptr(lp_scale), *tail)
@@ -412,21 +487,6 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, dx_in=None, dx_out=None, want_lp: bo
 
 
 # ---------------------------------------------------------------------------------------------
-def _qkn_operand(name, t, heads, like=None):
-    """(rows, row stride, head_dim) of a q / k operand of the q/k-norm: [rows, heads * head_dim], dense last dim, any row stride."""
-    ld = _rows2d(t)
-    if t.shape[1] % heads:
-        raise ValueError(f'{name}: {t.shape[1]} columns are not {heads} heads')
-    if like is not None and (t.shape != like.shape or t.dtype != like.dtype):
-        raise ValueError(f'{name}: {t.dtype} {tuple(t.shape)} does not match {like.dtype} {tuple(like.shape)}')
-    return t.shape[0], ld, t.shape[1] // heads
-
-
-def _qkn_params(hd, *params):
-    for p in params:
-        assert p.dtype == torch.float32 and p.is_contiguous() and p.numel() == hd, 'q/k-norm parameters are fp32 [head_dim]'
-
-
 def qk_norm_fwd(q, k, gq, bq, gk, bk, heads: int, eps: float, out=None):
     """q_norm / k_norm of the reference's attention (``qk_norm=True``): LayerNorm over the head_dim elements of every head of every
     row, for q and k in ONE launch (``vited_qk_norm_fwd``).  q, k: [rows, heads * head_dim] fp32 or bf16 with a dense last dim and
@@ -436,30 +496,27 @@ def qk_norm_fwd(q, k, gq, bq, gk, bk, heads: int, eps: float, out=None):
     Returns (q_out, k_out, (q_mean, q_rstd), (k_mean, k_rstd)) - None for an absent operand; the statistics are fp32 [rows, heads]."""
     if q is None and k is None:
         raise ValueError('qk_norm_fwd: neither q nor k given')
-    _need_gpu(q, k, gq, bq, gk, bk)
-    ref = q if q is not None else k
+    _need_gpu(q, k, gq, bq, gk, bk, *(out or ()))
+    op, ref = 'qk_norm_fwd', q if q is not None else k
     dtype, dev = ref.dtype, ref.device
-    outs, stats, args, hd = [], [], [], None
+    outs, stats, args, width = [], [], [], None
     for name, t, g, b, o in (('q', q, gq, bq, out[0] if out else None), ('k', k, gk, bk, out[1] if out else None)):
         if t is None:
             outs.append(None)
             stats.append(None)
             args.append((0, 0, 0, 0, 0, 0, 0, 0, 0))
             continue
-        rows, ld, hd_t = _qkn_operand(name, t, heads)
-        assert t.dtype == dtype and (hd is None or hd == hd_t), 'q and k share the dtype and the head width'
-        hd = hd_t
-        _qkn_params(hd, g, b)
-        if o is None:
-            o = torch.empty((rows, heads * hd), dtype=dtype, device=dev)
-        else:
-            _need_gpu(o)
-            _qkn_operand(name + '_out', o, heads, like=t)
+        ld, = _head_operand(op, name, t, _ACT if t is ref else dtype, (None, width), dev, like=None if t is ref else 'q')
+        rows, width = t.shape
+        hd = _head_dim(op, name, width, heads)
+        _check(op, f'g{name}', g, _f32, hd, dev)
+        _check(op, f'b{name}', b, _f32, hd, dev)
+        o = _out(op, f'out[{len(outs)}]', o, dtype, (rows, width), dev, DENSE_LAST)
         mean = torch.empty((rows, heads), dtype=torch.float32, device=dev)
         rstd = torch.empty((rows, heads), dtype=torch.float32, device=dev)
         outs.append(o)
         stats.append((mean, rstd))
-        args.append((_ptr(t), ld, rows, _ptr(g), _ptr(b), _ptr(o), _rows2d(o), _ptr(mean), _ptr(rstd)))
+        args.append((_ptr(t), ld, rows, _ptr(g), _ptr(b), _ptr(o), o.stride(0), _ptr(mean), _ptr(rstd)))
     (qp, qld, qr, gqp, bqp, qop, qold, qm, qs), (kp, kld, kr, gkp, bkp, kop, kold, km, ks) = args
     _lib.call('vited_qk_norm_fwd', qp, qld, qr, kp, kld, kr, gqp, bqp, gkp, bkp, qop, qold, kop, kold, qm, qs, km, ks, _code(dtype), heads, hd,
               float(eps), _stream())
@@ -476,34 +533,32 @@ def qk_norm_bwd(dq, q, q_stats, gq, dk, k, k_stats, gk, heads: int, dgq=None, db
     if dq is None and dk is None:
         raise ValueError('qk_norm_bwd: neither dq nor dk given')
     _need_gpu(dq, q, gq, dk, k, gk, dgq, dbq, dgk, dbk)
-    ref = dq if dq is not None else dk
+    op, ref = 'qk_norm_bwd', dq if dq is not None else dk
     dtype, dev = ref.dtype, ref.device
     given = [t is not None for d, pair in ((dq, (dgq, dbq)), (dk, (dgk, dbk))) if d is not None for t in pair]
     accumulate = all(given)
     if any(given) and not accumulate:
         raise ValueError('qk_norm_bwd: give every gradient destination of the present operands, or none')
-    args, grads, hd, rows_of = [], [], None, []
+    args, grads, width, rows_of = [], [], None, []
     for name, d, x, st, g, dg, db in (('q', dq, q, q_stats, gq, dgq, dbq), ('k', dk, k, k_stats, gk, dgk, dbk)):
         if d is None:
             args.append((0,) * 10)
             grads += [None, None]
             rows_of.append(0)
             continue
-        rows, ld, hd_t = _qkn_operand('d' + name, d, heads)
-        _qkn_operand(name, x, heads, like=d)
-        assert d.dtype == dtype and (hd is None or hd == hd_t), 'q and k share the dtype and the head width'
-        hd = hd_t
+        ld, = _head_operand(op, f'd{name}', d, _ACT if d is ref else dtype, (None, width), dev, like=None if d is ref else 'dq')
+        rows, width = d.shape
+        hd = _head_dim(op, f'd{name}', width, heads)
+        x_ld, = _head_operand(op, name, x, dtype, (rows, width), dev, like=f'd{name}')
         mean, rstd = st
-        assert mean.shape == rstd.shape == (rows, heads) and mean.dtype == rstd.dtype == torch.float32 and mean.is_contiguous() and rstd.is_contiguous()
-        _qkn_params(hd, g)
-        if accumulate:
-            _qkn_params(hd, dg, db)
-        else:
-            dg = torch.empty(hd, dtype=torch.float32, device=dev)
-            db = torch.empty(hd, dtype=torch.float32, device=dev)
+        _check(op, f'{name}_stats[0]', mean, _f32, (rows, heads), dev)
+        _check(op, f'{name}_stats[1]', rstd, _f32, (rows, heads), dev)
+        _check(op, f'g{name}', g, _f32, hd, dev)
+        dg = _out(op, f'dg{name}', dg, _f32, hd, dev)
+        db = _out(op, f'db{name}', db, _f32, hd, dev)
         grads += [dg, db]
         rows_of.append(rows)
-        args.append((_ptr(d), ld, _ptr(x), _rows2d(x), _ptr(mean), _ptr(rstd), _ptr(g), _ptr(dg), _ptr(db), rows))
+        args.append((_ptr(d), ld, _ptr(x), x_ld, _ptr(mean), _ptr(rstd), _ptr(g), _ptr(dg), _ptr(db), rows))
     ws = _scratch(_lib.load().vited_qk_norm_bwd_workspace_bytes(rows_of[0], rows_of[1], heads, hd), dev)
     _lib.call('vited_qk_norm_bwd', *args[0], *args[1], _code(dtype), int(accumulate), heads, hd, *ws, _stream())
     return tuple(grads)
@@ -517,62 +572,60 @@ def gemm(a: torch.Tensor, b: torch.Tensor, *, b_layout: int = B_NK, epilogue: in
     identity row map only): out = residual + row_scale[m] * (acc + bias) (``vited_gemm_scaled``).
 
     Returns ``out`` (and ``out2`` for EPI_GELU)."""
-    _need_gpu(a, b, bias, aux, residual, out)
-    assert a.dtype == b.dtype, f'operand dtypes differ: {a.dtype} vs {b.dtype}'
-    lda, ldb = _rows2d(a), _rows2d(b)
+    _need_gpu(a, b, bias, aux, residual, out, out2, row_scale)
+    op, dev = 'gemm', a.device
+    lda = _rows(op, 'a', a, _ACT, dev)
     m, k = a.shape
+    ldb = _rows(op, 'b', b, a.dtype, dev, *((k, None) if b_layout == B_NK else (None, k)), like='a')
     n = b.shape[0] if b_layout == B_NK else b.shape[1]
-    kb = b.shape[1] if b_layout == B_NK else b.shape[0]
-    if kb != k:
-        raise ValueError(f'contraction mismatch: A is [{m},{k}], B gives K={kb}')
-    f32_out = epilogue in (EPI_RESIDUAL, EPI_STORE_F32)
-    if out is None:
-        rows = m if out_rows is None else out_rows
-        out = torch.empty((rows, n), dtype=torch.float32 if f32_out else a.dtype, device=a.device)
-    ldo = _rows2d(out)
-    if epilogue in (EPI_GELU, EPI_GELU_GRAD):
-        if out2 is None:
-            out2 = torch.empty_like(out)
-        assert out2.dtype == out.dtype and out2.shape == out.shape and _rows2d(out2) == ldo
+    if row_scale is not None and (epilogue != EPI_RESIDUAL or rows_per_batch):
+        raise ValueError('gemm: row_scale goes with EPI_RESIDUAL and the identity row map')
+    # the rows written: m under the identity map, else up to the image of row m - 1 under the RESIDUAL remap of include/vited.h
+    remap = epilogue == EPI_RESIDUAL and rows_per_batch > 0 and m > 0
+    need = (m - 1) // rows_per_batch * out_rows_per_batch + (m - 1) % rows_per_batch + row_offset + 1 if remap else m
+    out_dtype = torch.float32 if epilogue in (EPI_RESIDUAL, EPI_STORE_F32) else a.dtype
+    if out is None and out_rows is None:
+        out = torch.empty((m, n), dtype=out_dtype, device=dev)
+        ldo = out.stride(0)
     else:
-        out2 = None
-    if aux is not None:
-        assert aux.dtype == a.dtype and _rows2d(aux) == ldo
+        out = torch.empty((out_rows, n), dtype=out_dtype, device=dev) if out is None else out
+        ldo = _rows(op, 'out', out, out_dtype, dev, n, m if row_scale is not None else _Min(need))
+    gelu = epilogue in (EPI_GELU, EPI_GELU_GRAD)
+    out2 = (torch.empty_like(out) if out2 is None else out2) if gelu else None
+    _check(op, 'out2', out2, out_dtype, tuple(out.shape), dev, DENSE_LAST, optional=not gelu, ld=ldo)
+    _check(op, 'aux', aux, a.dtype, (m, n), dev, DENSE_LAST, optional=True, ld=ldo)
     if residual is not None:
-        assert residual.dtype == torch.float32 and residual.stride(-1) == 1
-        assert residual.stride(-2) == ldo if residual.dim() >= 2 else True
-    if bias is not None:
-        assert bias.dtype == torch.float32 and bias.numel() == n
+        while residual.dim() > 2 and residual.shape[0] == 1:          # leading unit dims: the same rows
+            residual = residual[0]
+        res_rows = (min(m, rows_per_batch) + row_offset if residual_bcast else need) if remap else m
+        _check(op, 'residual', residual, _f32, (_Min(res_rows), n), dev, DENSE_LAST, ld=ldo)
+    _check(op, 'bias', bias, _f32, n, dev, optional=True)
     if row_scale is not None:
-        _need_gpu(row_scale)
-        _check_row_scale(row_scale, m)
-        if epilogue != EPI_RESIDUAL or rows_per_batch:
-            raise ValueError('row_scale goes with EPI_RESIDUAL and the identity row map')
-        assert out.shape[0] == m
+        _check(op, 'row_scale', row_scale, _f32, (m,), dev)
         _lib.call('vited_gemm_scaled', _ptr(a), lda, _ptr(b), ldb, b_layout, _code(a.dtype), m, n, k, _ptr(bias), _ptr(residual),
                   _ptr(row_scale), _ptr(out), ldo, _stream())
         return out
     _lib.call('vited_gemm', _ptr(a), lda, _ptr(b), ldb, b_layout, _code(a.dtype), m, n, k, epilogue, _ptr(bias), _ptr(aux), _ptr(residual),
               _ptr(out), _ptr(out2), ldo, rows_per_batch, out_rows_per_batch, row_offset, int(bool(residual_bcast)), _stream())
-    return (out, out2) if epilogue in (EPI_GELU, EPI_GELU_GRAD) else out
+    return (out, out2) if gelu else out
 
 
 def linear_bwd_weight(dy: torch.Tensor, x: torch.Tensor, want_bias: bool = True, dw_out=None, db_out=None):
     """dW[N,K] = dy[M,N]^T x[M,K] (fp32), dbias[N] = column sums of dy (fp32) or None.  With ``dw_out``
     (and ``db_out``) the results are ADDED onto those fp32 tensors (a parameter's .grad) instead."""
-    _need_gpu(dy, x)
-    assert dy.dtype == x.dtype and dy.shape[0] == x.shape[0]
-    lddy, ldx = _rows2d(dy), _rows2d(x)
+    _need_gpu(dy, x, dw_out, db_out)
+    op, dev = 'linear_bwd_weight', x.device
+    lddy = _rows(op, 'dy', dy, _ACT, dev)
     m, n = dy.shape
+    ldx = _rows(op, 'x', x, dy.dtype, dev, None, m, like='dy')
     k = x.shape[1]
     accumulate = dw_out is not None
     if accumulate:
-        assert dw_out.dtype == torch.float32 and dw_out.is_contiguous() and dw_out.numel() == n * k
-        dw, db = dw_out, (db_out if want_bias else None)
-        assert db is None or (db.dtype == torch.float32 and db.is_contiguous() and db.numel() == n)
+        dw = _check(op, 'dw_out', dw_out, _f32, n * k, dev)
+        db = _check(op, 'db_out', db_out, _f32, n, dev, optional=True) if want_bias else None
     else:
-        dw = torch.empty((n, k), dtype=torch.float32, device=x.device)
-        db = torch.empty(n, dtype=torch.float32, device=x.device) if want_bias else None
+        dw = torch.empty((n, k), dtype=torch.float32, device=dev)
+        db = torch.empty(n, dtype=torch.float32, device=dev) if want_bias else None
     ws = _scratch(_lib.load().vited_linear_bwd_weight_workspace_bytes(m, n, k), x.device)
     _lib.call('vited_linear_bwd_weight', _ptr(dy), lddy, _ptr(x), ldx, _code(x.dtype), m, n, k, _ptr(dw), _ptr(db), int(accumulate), *ws,
               _stream())
@@ -590,12 +643,15 @@ def linear_bwd_weight_batched(items, accumulate: bool) -> bool:
     n = len(items)
     if n < 1 or n > MAX_BATCHED_WEIGHT_GRADS:
         return False
-    for dy, x, dw, db in items:
+    for i, (dy, x, dw, db) in enumerate(items):
         _need_gpu(dy, x, dw, db)
         if dy.dtype != torch.bfloat16 or x.dtype != torch.bfloat16 or dy.shape[0] != x.shape[0]:
             return False
-        assert dw.dtype == torch.float32 and dw.is_contiguous() and dw.numel() == dy.shape[1] * x.shape[1]
-        assert db is None or (db.dtype == torch.float32 and db.is_contiguous() and db.numel() == dy.shape[1])
+        op, dev = 'linear_bwd_weight_batched', items[0][0].device
+        _rows(op, f'items[{i}][0] (dy)', dy, _bf16, dev)
+        _rows(op, f'items[{i}][1] (x)', x, _bf16, dev)
+        _check(op, f'items[{i}][2] (dw)', dw, _f32, dy.shape[1] * x.shape[1], dev)
+        _check(op, f'items[{i}][3] (db)', db, _f32, dy.shape[1], dev, optional=True)
         if dw.data_ptr() % 16 or (db is not None and db.data_ptr() % 16) or dy.data_ptr() % 16 or x.data_ptr() % 16:
             return False                 # the batched kernels use 16-byte accesses throughout
     dys, xs, dws, dbs = zip(*items)
@@ -605,7 +661,7 @@ def linear_bwd_weight_batched(items, accumulate: bool) -> bool:
     lib = _lib.load()
     if not lib.vited_linear_bwd_weight_batched_supported(n, M, N, K, BF16):
         return False
-    lddy, ldx = _host_array(C.c_int64, map(_rows2d, dys)), _host_array(C.c_int64, map(_rows2d, xs))
+    lddy, ldx = _host_array(C.c_int64, [dy.stride(0) for dy in dys]), _host_array(C.c_int64, [x.stride(0) for x in xs])
     ws = _scratch(lib.vited_linear_bwd_weight_batched_workspace_bytes(n, M, N, K), dys[0].device)
     _lib.call('vited_linear_bwd_weight_batched', n, _host_array(C.c_void_p, dys), lddy, _host_array(C.c_void_p, xs), ldx, M, N, K,
               _host_array(C.c_void_p, dws), _host_array(C.c_void_p, dbs), BF16, int(bool(accumulate)), *ws, _stream())
@@ -623,21 +679,24 @@ def linear_residual_layernorm_fwd(a, w, bias, residual, gamma=None, beta=None, e
     (``vited_linear_residual_layernorm_fwd``).  Returns (y, h | None, mean | None, rstd | None).
     ``row_scale`` (fp32 [M]): y = residual + row_scale[m] * (a w^T + bias) (``vited_linear_residual_layernorm_fwd_scaled``)."""
     _need_gpu(a, w, bias, residual, gamma, beta, out, row_scale)
-    assert a.dtype == w.dtype == torch.bfloat16 and residual.dtype == torch.float32
-    lda, ldw, ldr = _rows2d(a), _rows2d(w), _rows2d(residual)
+    op, dev = 'linear_residual_layernorm_fwd', a.device
+    lda = _rows(op, 'a', a, _bf16, dev)
     m, k = a.shape
+    ldw = _rows(op, 'w', w, _bf16, dev, k)
     n = w.shape[0]
-    assert w.shape[1] == k and residual.shape == (m, n)
-    y = out if out is not None else torch.empty((m, n), dtype=torch.float32, device=a.device)
-    assert y.dtype == torch.float32 and y.shape == (m, n)
+    ldr = _rows(op, 'residual', residual, _f32, dev, n, m)
+    _check(op, 'bias', bias, _f32, n, dev, optional=True)
+    y = _out(op, 'out', out, _f32, (m, n), dev, DENSE_LAST)
     h = mean = rstd = None
     if gamma is not None:
-        h = torch.empty((m, n), dtype=torch.bfloat16, device=a.device)
-        mean = torch.empty(m, dtype=torch.float32, device=a.device)
-        rstd = torch.empty(m, dtype=torch.float32, device=a.device)
-    tail = (_ptr(y), _rows2d(y), _ptr(gamma), _ptr(beta), float(eps), _ptr(h), n, _ptr(mean), _ptr(rstd), m, n, k, _stream())
+        _check(op, 'gamma', gamma, _f32, n, dev)
+        _check(op, 'beta', beta, _f32, n, dev)
+        h = torch.empty((m, n), dtype=torch.bfloat16, device=dev)
+        mean = torch.empty(m, dtype=torch.float32, device=dev)
+        rstd = torch.empty(m, dtype=torch.float32, device=dev)
+    tail = (_ptr(y), y.stride(0), _ptr(gamma), _ptr(beta), float(eps), _ptr(h), n, _ptr(mean), _ptr(rstd), m, n, k, _stream())
     if row_scale is not None:
-        _check_row_scale(row_scale, m)
+        _check(op, 'row_scale', row_scale, _f32, (m,), dev)
         _lib.call('vited_linear_residual_layernorm_fwd_scaled', _ptr(a), lda, _ptr(w), ldw, _ptr(bias), _ptr(residual), ldr, _ptr(row_scale),
                   *tail)
     else:
@@ -653,34 +712,34 @@ def linear_layernorm_bwd(dy, wt, x, gamma, mean, rstd, dx_in=None, dx_out=None, 
     ``defer`` (a list): the column sums are NOT finished here - (partials, rows, dgamma, dbeta, accumulate) is appended and
     ``layernorm_bwd_finish(defer)`` later finishes many LayerNorms with one launch.
     ``lp_scale`` (fp32 [M]): dx_lp = bf16(lp_scale[m] * dx[m]) (``vited_linear_layernorm_bwd_scaled``)."""
-    _need_gpu(dy, wt, x, gamma, mean, rstd, dx_in, dx_out, lp_scale)
-    assert dy.dtype == wt.dtype == torch.bfloat16 and x.dtype == torch.float32
+    _need_gpu(dy, wt, x, gamma, mean, rstd, dx_in, dx_out, lp_scale, dgamma, dbeta)
+    op, dev = 'linear_layernorm_bwd', x.device
     segments = 1
-    if dy.dim() == 3:
+    if torch.is_tensor(dy) and dy.dim() == 3:
         # [L, M, seg_k]: the contraction dim arrives as L tensors (one per decoder block), wt is [N, L * seg_k]
-        assert dy.stride(2) == 1 and dy.stride(0) % 8 == 0
+        _check(op, 'dy', dy, _bf16, _ANY3, dev, DENSE_LAST)
+        if dy.stride(0) % 8:
+            raise ValueError(f'linear_layernorm_bwd: dy must have a segment stride that is a multiple of 8 elements, got {dy.stride(0)}')
         segments, m, seg_k = dy.shape
         lddy, seg_stride, k = dy.stride(1), dy.stride(0), segments * seg_k
     else:
-        lddy = _rows2d(dy)
+        lddy = _rows(op, 'dy', dy, _bf16, dev)
         m, k = dy.shape
-    ldwt, ldx = _rows2d(wt), _rows2d(x)
+    ldwt = _rows(op, 'wt', wt, _bf16, dev, k)
     n = wt.shape[0]
-    assert wt.shape[1] == k and x.shape == (m, n)
+    ldx = _rows(op, 'x', x, _f32, dev, n, m)
+    for name, t, size in (('gamma', gamma, n), ('mean', mean, m), ('rstd', rstd, m)):
+        _check(op, name, t, _f32, size, dev)
     lib = _lib.load()
-    if dx_out is None:
-        dx_out = torch.empty((m, n), dtype=torch.float32, device=x.device)
+    dx_out = _out(op, 'dx_out', dx_out, _f32, (m, n), dev, DENSE_LAST)
+    _check(op, 'dx_in', dx_in, _f32, (m, n), dev, DENSE_LAST, optional=True)
     if lp_scale is not None:
-        _check_row_scale(lp_scale, m)
-        assert segments == 1
+        _check(op, 'lp_scale', lp_scale, _f32, (m,), dev)
+        if segments != 1:
+            raise ValueError('linear_layernorm_bwd: lp_scale does not go with a segmented dy')
         want_lp = True
-    dx_lp = torch.empty((m, n), dtype=torch.bfloat16, device=x.device) if want_lp else None
-    accumulate = dgamma is not None
-    if accumulate:
-        assert dbeta is not None and dgamma.dtype == dbeta.dtype == torch.float32 and dgamma.is_contiguous() and dbeta.is_contiguous()
-    else:
-        dgamma = torch.empty(n, dtype=torch.float32, device=x.device)
-        dbeta = torch.empty(n, dtype=torch.float32, device=x.device)
+    dx_lp = torch.empty((m, n), dtype=torch.bfloat16, device=dev) if want_lp else None
+    accumulate, dgamma, dbeta = _ln_grads(op, dev, n, dgamma, dbeta)
     if defer is not None:
         rows = int(lib.vited_linear_layernorm_bwd_partial_rows(m))
         part = torch.empty(rows * 2 * n, dtype=torch.float32, device=x.device)     # lives until the flush
@@ -688,8 +747,8 @@ def linear_layernorm_bwd(dy, wt, x, gamma, mean, rstd, dx_in=None, dx_out=None, 
         ws = (part.data_ptr(), part.numel() * 4)
     else:
         ws = _scratch(lib.vited_linear_layernorm_bwd_workspace_bytes(m, n), x.device)
-    dx_args = (_ptr(x), ldx, _ptr(gamma), _ptr(mean), _ptr(rstd), _ptr(dx_in), _rows2d(dx_in) if dx_in is not None else 0, _ptr(dx_out),
-               _rows2d(dx_out), _ptr(dx_lp), n)
+    dx_args = (_ptr(x), ldx, _ptr(gamma), _ptr(mean), _ptr(rstd), _ptr(dx_in), dx_in.stride(0) if dx_in is not None else 0, _ptr(dx_out),
+               dx_out.stride(0), _ptr(dx_lp), n)
     sum_args = (0 if defer is not None else _ptr(dgamma), 0 if defer is not None else _ptr(dbeta), int(accumulate))
     tail = dx_args + sum_args
     if lp_scale is not None:          # the scaled prototype takes the scale right after the low-precision copy it applies to
@@ -708,9 +767,14 @@ def layernorm_bwd_finish(entries):
     if not entries:
         return
     parts, rows, dgammas, dbetas, accumulate = zip(*entries)
+    dim, dev = dgammas[0].numel(), dgammas[0].device
+    _need_gpu(*parts, *dgammas, *dbetas)
+    for i, (part, n_rows, dgamma, dbeta) in enumerate(zip(parts, rows, dgammas, dbetas)):
+        for j, t, size in ((0, part, _Min(n_rows * 2 * dim)), (2, dgamma, dim), (3, dbeta, dim)):
+            _check('layernorm_bwd_finish', f'entries[{i}][{j}]', t, _f32, size, dev)
     _lib.call('vited_layernorm_bwd_finish_batched', len(entries), _host_array(C.c_void_p, parts), _host_array(C.c_int, rows),
               _host_array(C.c_void_p, dgammas), _host_array(C.c_void_p, dbetas), _host_array(C.c_int, map(int, accumulate)),
-              dgammas[0].numel(), _stream())
+              dim, _stream())
     entries.clear()
 
 
@@ -718,18 +782,26 @@ def layernorm_bwd_finish(entries):
 MAX_FOLDED_BLOCKS = 16
 
 
+def _block_lists(op, dev, n_blk, **lists):
+    """Per-block fp32 buffers of the context fold: name=(list, shape or element count, whether an entry may be None)."""
+    for name, (ts, shape, optional) in lists.items():
+        if len(ts) != n_blk:
+            raise ValueError(f'{op}: {name} has {len(ts)} entries for {n_blk} blocks')
+        for i, t in enumerate(ts):
+            _check(op, f'{name}[{i}]', t, _f32, shape, dev, optional=optional)
+
+
 def fold_context_weights(ws, biases, gammas, betas, out=None):
     """Folded kv weights of several decoder blocks: W'_l = W_l o gamma_l (bf16, stacked [L N, K] and transposed [K, L N]) and
     b'_l = b_l + W_l beta_l (fp32 [L N]) - ``vited_fold_context_weights``.  ``out`` = (w, wt, b) buffers to refresh in place."""
     n_blk = len(ws)
-    _need_gpu(*ws, *gammas, *betas)
-    n, k = ws[0].shape
-    dev = ws[0].device
-    if out is None:
-        out = (torch.empty((n_blk * n, k), dtype=torch.bfloat16, device=dev), torch.empty((k, n_blk * n), dtype=torch.bfloat16, device=dev),
-               torch.empty(n_blk * n, dtype=torch.float32, device=dev))
-    for t in list(ws) + list(gammas) + list(betas):
-        assert t.dtype == torch.float32 and t.is_contiguous()
+    _need_gpu(*ws, *biases, *gammas, *betas, *(out or ()))
+    op, dev = 'fold_context_weights', ws[0].device
+    n, k = _check(op, 'ws[0]', ws[0], _f32, _ANY2, dev).shape
+    _block_lists(op, dev, n_blk, ws=(ws, (n, k), False), biases=(biases, n, True), gammas=(gammas, k, False), betas=(betas, k, False))
+    w_out, wt_out, b_out = out if out is not None else (None, None, None)
+    out = (_out(op, 'out[0]', w_out, _bf16, (n_blk * n, k), dev), _out(op, 'out[1]', wt_out, _bf16, (k, n_blk * n), dev),
+           _out(op, 'out[2]', b_out, _f32, n_blk * n, dev))
     _lib.call('vited_fold_context_weights', n_blk, *(_host_array(C.c_void_p, ts) for ts in (ws, biases, gammas, betas)), n, k,
               _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _stream())
     return out
@@ -738,9 +810,13 @@ def fold_context_weights(ws, biases, gammas, betas, out=None):
 def unfold_context_grads(dwf, dbf, ws, gammas, betas, dws, dbiases, dgammas, dbetas, accumulate: bool):
     """Gradients of the folded weights / bias -> dW_l, db_l, dgamma_l, dbeta_l (``vited_unfold_context_grads``)."""
     n_blk = len(ws)
-    n, k = ws[0].shape
-    assert dwf.dtype == dbf.dtype == torch.float32 and dwf.is_contiguous() and dbf.is_contiguous()
-    assert dwf.shape == (n_blk * n, k) and dbf.numel() == n_blk * n
+    _need_gpu(dwf, dbf, *ws, *gammas, *betas, *dws, *dbiases, *dgammas, *dbetas)
+    op, dev = 'unfold_context_grads', dwf.device
+    n, k = _check(op, 'ws[0]', ws[0], _f32, _ANY2, dev).shape
+    _check(op, 'dwf', dwf, _f32, (n_blk * n, k), dev)
+    _check(op, 'dbf', dbf, _f32, n_blk * n, dev)
+    _block_lists(op, dev, n_blk, ws=(ws, (n, k), False), gammas=(gammas, k, False), betas=(betas, k, False), dws=(dws, n * k, False),
+                 dbiases=(dbiases, n, True), dgammas=(dgammas, k, False), dbetas=(dbetas, k, False))
     _lib.call('vited_unfold_context_grads', n_blk, _ptr(dwf), _ptr(dbf),
               *(_host_array(C.c_void_p, ts) for ts in (ws, gammas, betas, dws, dbiases, dgammas, dbetas)), n, k, int(bool(accumulate)),
               _stream())
@@ -751,46 +827,46 @@ def mlp_fwd(x, gamma, beta, w1, b1, w2, b2, eps: float, save: bool = True, out=N
     """y = x + fc2(gelu(fc1(LayerNorm(x)))) in one kernel (``vited_mlp_fwd``).  x fp32 [rows, 384]; w1 / w2 the bf16 weights.
     Returns (y, saved) with saved = (mean, rstd, h, gd, u) or None.  ``out`` = (y, mean, rstd, h, gd, u) pre-made outputs
     (row slices of larger tensors are fine for y; the others must be dense)."""
-    _need_gpu(x, gamma, beta, w1, b1, w2, b2)
-    assert x.dtype == torch.float32 and w1.dtype == w2.dtype == torch.bfloat16 and w1.is_contiguous() and w2.is_contiguous()
-    ldx = _rows2d(x)
+    _need_gpu(x, gamma, beta, w1, b1, w2, b2, *(out or ()))
+    op, dev = 'mlp_fwd', x.device
+    ldx = _rows(op, 'x', x, _f32, dev)
     rows, dim = x.shape
-    hidden = w1.shape[0]
-    assert w1.shape == (hidden, dim) and w2.shape == (dim, hidden)
-    dev = x.device
-    if out is not None:
-        y, mean, rstd, h, gd, u = out
-    else:
-        y = torch.empty((rows, dim), dtype=torch.float32, device=dev)
-        mean = rstd = h = gd = u = None
-        if save:
-            mean = torch.empty(rows, dtype=torch.float32, device=dev)
-            rstd = torch.empty(rows, dtype=torch.float32, device=dev)
-            h = torch.empty((rows, dim), dtype=torch.bfloat16, device=dev)
-            gd = torch.empty((rows, hidden), dtype=torch.bfloat16, device=dev)
-            u = torch.empty((rows, hidden), dtype=torch.bfloat16, device=dev)
+    hidden = _check(op, 'w1', w1, _bf16, (None, dim), dev).shape[0]
+    _check(op, 'w2', w2, _bf16, (dim, hidden), dev)
+    for name, t, size in (('gamma', gamma, dim), ('beta', beta, dim), ('b1', b1, hidden), ('b2', b2, dim)):
+        _check(op, name, t, _f32, size, dev)
+    y, mean, rstd, h, gd, u = out if out is not None else (None,) * 6
+    y = _out(op, 'out[0] (y)', y, _f32, (rows, dim), dev, DENSE_LAST)
     if save:
-        assert h.is_contiguous() and gd.is_contiguous() and u.is_contiguous() and h.shape == (rows, dim) and gd.shape == u.shape == (rows, hidden)
-    _lib.call('vited_mlp_fwd', _ptr(x), ldx, _ptr(gamma), _ptr(beta), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), _ptr(y), _rows2d(y),
+        saved = ((mean, _f32, rows), (rstd, _f32, rows), (h, _bf16, (rows, dim)), (gd, _bf16, (rows, hidden)), (u, _bf16, (rows, hidden)))
+        mean, rstd, h, gd, u = (_out(op, f'out[{i + 1}]', t, dtype, shape, dev) for i, (t, dtype, shape) in enumerate(saved))
+    _lib.call('vited_mlp_fwd', _ptr(x), ldx, _ptr(gamma), _ptr(beta), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), _ptr(y), y.stride(0),
               _ptr(h) if save else 0, _ptr(gd) if save else 0, _ptr(u) if save else 0, _ptr(mean) if save else 0, _ptr(rstd) if save else 0,
               rows, dim, hidden, float(eps), _stream())
     return y, ((mean, rstd, h, gd, u) if save else None)
 
 
+def _block_params(op, dev, *params):
+    """Parameters of a whole-block entry: (name, tensor, shape) of a bf16 weight, (name, tensor, length) of an fp32 bias or LayerNorm
+    vector; only the biases of the q / k / v projections (qkv_bias=False) may be absent."""
+    for name, t, shape in params:
+        _check(op, name, t, _bf16 if type(shape) is tuple else _f32, shape, dev, optional=name in ('bqkv', 'bq', 'bkv'))
+
+
 def block_fwd(x, heads: int, ln1_g, ln1_b, wqkv, bqkv, wproj, bproj, ln2_g, ln2_b, w1, b1, w2, b2, eps: float = 1e-6):
     """Encoder Block forward through ``vited_block_fwd``: x fp32 [B, N, D] -> y fp32 [B, N, D] (bf16 weights, inference form).
     The whole-block entry has no q/k-norm: a ``qk_norm=True`` model runs its blocks through functions.py (``qk_norm_fwd``)."""
-    _need_gpu(x, wqkv, wproj, w1, w2)
-    assert x.dtype == torch.float32 and x.dim() == 3 and x.is_contiguous()
-    assert all(t.dtype == torch.bfloat16 and t.is_contiguous() for t in (wqkv, wproj, w1, w2))
-    b, n, d = x.shape
-    hidden = w1.shape[0]
+    _need_gpu(x, ln1_g, ln1_b, wqkv, bqkv, wproj, bproj, ln2_g, ln2_b, w1, b1, w2, b2)
+    op, dev = 'block_fwd', x.device
+    b, n, d = _check(op, 'x', x, _f32, _ANY3, dev).shape
+    _head_dim(op, 'x', d, heads)
+    hidden = _check(op, 'w1', w1, _bf16, (None, d), dev).shape[0]
+    _block_params(op, dev, ('wqkv', wqkv, (3 * d, d)), ('wproj', wproj, (d, d)), ('w2', w2, (d, hidden)), ('ln1_g', ln1_g, d), ('ln1_b', ln1_b, d),
+                  ('bqkv', bqkv, 3 * d), ('bproj', bproj, d), ('ln2_g', ln2_g, d), ('ln2_b', ln2_b, d), ('b1', b1, hidden), ('b2', b2, d))
     y = torch.empty_like(x)
-    ws, nbytes = _scratch(_lib.load().vited_block_workspace_bytes(b, n, d, hidden, heads) + 256, x.device)
-    base = (ws + 255) // 256 * 256
+    ws = _scratch(_lib.load().vited_block_workspace_bytes(b, n, d, hidden, heads), dev, align=256)
     _lib.call('vited_block_fwd', _ptr(x), _ptr(y), b, n, d, heads, hidden, _ptr(ln1_g), _ptr(ln1_b), _ptr(wqkv), _ptr(bqkv), _ptr(wproj),
-              _ptr(bproj), _ptr(ln2_g), _ptr(ln2_b), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), float(eps), base, nbytes - (base - ws),
-              _stream())
+              _ptr(bproj), _ptr(ln2_g), _ptr(ln2_b), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), float(eps), *ws, _stream())
     return y
 
 
@@ -799,28 +875,34 @@ def cross_block_fwd(x, context, heads: int, ln1, wqkv, bqkv, wproj, bproj, lnq, 
     """Decoder CrossBlock forward through ``vited_cross_block_fwd``: x fp32 [B, N2, D], context fp32 [B, N1, D] -> y fp32 [B, N2, D]
     (bf16 weights, inference form).  ln1 / lnq / lnc / ln2 = (gamma, beta) of norm1 / norm_cross / norm_context / norm2.
     The whole-block entry has no q/k-norm: a ``qk_norm=True`` model runs its blocks through functions.py (``qk_norm_fwd``)."""
-    _need_gpu(x, context, wqkv, wproj, wq, wkv, wcproj, w1, w2)
-    assert x.dtype == context.dtype == torch.float32 and x.dim() == context.dim() == 3 and x.is_contiguous() and context.is_contiguous()
-    assert all(t.dtype == torch.bfloat16 and t.is_contiguous() for t in (wqkv, wproj, wq, wkv, wcproj, w1, w2))
-    b, n, d = x.shape
-    nc = context.shape[1]
-    assert context.shape == (b, nc, d)
-    hidden = w1.shape[0]
+    _need_gpu(x, context, *ln1, wqkv, bqkv, wproj, bproj, *lnq, *lnc, wq, bq, wkv, bkv, wcproj, bcproj, *ln2, w1, b1, w2, b2)
+    op, dev = 'cross_block_fwd', x.device
+    b, n, d = _check(op, 'x', x, _f32, _ANY3, dev).shape
+    nc = _check(op, 'context', context, _f32, (b, None, d), dev).shape[1]
+    _head_dim(op, 'x', d, heads)
+    hidden = _check(op, 'w1', w1, _bf16, (None, d), dev).shape[0]
+    _block_params(op, dev, ('wqkv', wqkv, (3 * d, d)), ('wproj', wproj, (d, d)), ('wq', wq, (d, d)), ('wkv', wkv, (2 * d, d)),
+                  ('wcproj', wcproj, (d, d)), ('w2', w2, (d, hidden)), ('bqkv', bqkv, 3 * d), ('bproj', bproj, d), ('bq', bq, d), ('bkv', bkv, 2 * d),
+                  ('bcproj', bcproj, d), ('b1', b1, hidden), ('b2', b2, d), ('ln1[0]', ln1[0], d), ('ln1[1]', ln1[1], d), ('lnq[0]', lnq[0], d),
+                  ('lnq[1]', lnq[1], d), ('lnc[0]', lnc[0], d), ('lnc[1]', lnc[1], d), ('ln2[0]', ln2[0], d), ('ln2[1]', ln2[1], d))
     y = torch.empty_like(x)
-    ws, nbytes = _scratch(_lib.load().vited_cross_block_workspace_bytes(b, n, nc, d, hidden, heads) + 256, x.device)
-    base = (ws + 255) // 256 * 256
+    ws = _scratch(_lib.load().vited_cross_block_workspace_bytes(b, n, nc, d, hidden, heads), dev, align=256)
     _lib.call('vited_cross_block_fwd', _ptr(x), _ptr(context), _ptr(y), b, n, nc, d, heads, hidden, _ptr(ln1[0]), _ptr(ln1[1]), _ptr(wqkv),
               _ptr(bqkv), _ptr(wproj), _ptr(bproj), _ptr(lnq[0]), _ptr(lnq[1]), _ptr(lnc[0]), _ptr(lnc[1]), _ptr(wq), _ptr(bq), _ptr(wkv),
-              _ptr(bkv), _ptr(wcproj), _ptr(bcproj), _ptr(ln2[0]), _ptr(ln2[1]), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), float(eps), base,
-              nbytes - (base - ws), _stream())
+              _ptr(bkv), _ptr(wcproj), _ptr(bcproj), _ptr(ln2[0]), _ptr(ln2[1]), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), float(eps), *ws,
+              _stream())
     return y
 
 
 # ---------------------------------------------------------------------------------------------
-def _head_view(t: torch.Tensor, heads: int, head_dim: int):
-    """t is [B, N, heads*head_dim] (a last-dim slice of the packed projection): (ptr-holder, bs, ts)."""
-    assert t.dim() == 3 and t.stride(2) == 1 and t.shape[2] == heads * head_dim
-    return t.stride(0), t.stride(1)
+def _qkv_operands(op, q, k, v, heads, items=None):
+    """(B, Nq, Nk, D, head_dim) and the (pointer, batch stride, token stride) triples of q [B, Nq, D] and k / v [items or B, Nk, D]."""
+    dev = q.device
+    qs = _head_operand(op, 'q', q, _ACT, _ANY3, dev)
+    b, nq, d = q.shape
+    ks = _head_operand(op, 'k', k, q.dtype, (b if items is None else items, None, d), dev, like='q')
+    vs = _head_operand(op, 'v', v, q.dtype, k.shape, dev, like='k')
+    return (b, nq, k.shape[1], d, _head_dim(op, 'q', d, heads)), (_ptr(q), *qs, _ptr(k), *ks, _ptr(v), *vs)
 
 
 def attention_fwd(q, k, v, heads: int, scale: float, kv_index=None):
@@ -828,20 +910,11 @@ def attention_fwd(q, k, v, heads: int, scale: float, kv_index=None):
     -> (o [B,Nq,D] contiguous, lse fp32 [B,H,Nq]).  With ``kv_index`` (int64 [B]) batch item b attends over
     k[kv_index[b]] / v[kv_index[b]] and k / v may hold any number of items (inference only)."""
     _need_gpu(q, k, v, kv_index)
-    b, nq, d = q.shape
-    nk = k.shape[1]
-    hd = d // heads
-    assert q.dtype == k.dtype == v.dtype and k.shape == v.shape and k.shape[2] == d
-    if kv_index is None:
-        assert k.shape[0] == b
-    else:
-        assert kv_index.dtype == torch.int64 and kv_index.is_contiguous() and kv_index.numel() == b
-    q_bs, q_ts = _head_view(q, heads, hd)
-    k_bs, k_ts = _head_view(k, heads, hd)
-    v_bs, v_ts = _head_view(v, heads, hd)
+    (b, nq, nk, d, hd), qkv = _qkv_operands('attention_fwd', q, k, v, heads, items=None if kv_index is None else k.shape[0])
+    _check('attention_fwd', 'kv_index', kv_index, _i64, b, q.device, optional=True)
     o = torch.empty((b, nq, d), dtype=q.dtype, device=q.device)
     lse = torch.empty((b, heads, nq), dtype=torch.float32, device=q.device)
-    _lib.call('vited_attention_fwd_indexed', _ptr(q), q_bs, q_ts, _ptr(k), k_bs, k_ts, _ptr(v), v_bs, v_ts, _ptr(kv_index), _ptr(o), nq * d,
+    _lib.call('vited_attention_fwd_indexed', *qkv, _ptr(kv_index), _ptr(o), nq * d,
               d, _ptr(lse), _code(q.dtype), b, heads, nq, nk, hd, float(scale), _stream())
     return o, lse
 
@@ -889,26 +962,16 @@ def mine_pairs_max_images() -> int:
 
 def _mine_pairs_args(targets, keys, neg_per_pos, capacity):
     """The argument checks of ``mine_pairs`` (before any launch, also without a GPU).  Returns (n, neg_per_pos, capacity)."""
-    for name, t, dtype in (('targets', targets, torch.int64), ('keys', keys, torch.float32)):
-        if not torch.is_tensor(t) or t.dtype != dtype or t.dim() != 1:
-            raise ValueError(f'mine_pairs: {name} must be a 1-D {dtype} tensor, got '
-                             f'{(t.dtype, tuple(t.shape)) if torch.is_tensor(t) else type(t).__name__}')
-        if not t.is_contiguous():
-            raise ValueError(f'mine_pairs: {name} must be contiguous, got strides {t.stride()}')
+    dev = targets.device if torch.is_tensor(targets) else None
+    _check('mine_pairs', 'targets', targets, _i64, (_Min(1),), dev)
     n = targets.numel()
-    if n < 1:
-        raise ValueError('mine_pairs: no images')
-    if keys.numel() != n * n:
-        raise ValueError(f'mine_pairs: {keys.numel()} keys for {n} images, expected one per ordered cell: {n * n}')
-    if keys.device != targets.device:
-        raise ValueError(f'mine_pairs: keys on {keys.device}, targets on {targets.device}')
+    _check('mine_pairs', 'keys', keys, _f32, (n * n,), dev)                 # one key per ordered cell
     neg_per_pos, capacity = float(neg_per_pos), int(capacity)
     if not 0.0 <= neg_per_pos < float('inf'):
         raise ValueError(f'mine_pairs: neg_per_pos must be a finite number >= 0, got {neg_per_pos}')
     if capacity < 1:
         raise ValueError(f'mine_pairs: capacity must be at least 1, got {capacity}')
-    if not targets.is_cuda:
-        raise ValueError('mine_pairs: the kernel takes device tensors (engine.mine_pairs_device restates the rule for CPU tensors)')
+    _need_gpu(targets, error=ValueError)        # engine.mine_pairs_device restates the rule for CPU tensors
     if n > mine_pairs_max_images():
         raise ValueError(f'mine_pairs: {n} images, the kernel takes at most {mine_pairs_max_images()}')
     if capacity > MINE_MAX_CAPACITY:
@@ -920,12 +983,11 @@ def mine_pairs_out(targets, keys, neg_per_pos, ordered_negatives, groups, labels
     """``mine_pairs`` into the caller's buffers (every element of every one is written): groups int64 [capacity, 2], labels /
     weights fp32 [capacity, 1], seg_index / seg_order int64 [capacity], seg_offsets int64 [n + 1], counts int32 [5]."""
     n, neg_per_pos, capacity = _mine_pairs_args(targets, keys, neg_per_pos, groups.shape[0] if torch.is_tensor(groups) and groups.dim() else 0)
-    for name, t, dtype, shape in (('groups', groups, torch.int64, (capacity, 2)), ('labels', labels, torch.float32, (capacity, 1)),
-                                  ('weights', weights, torch.float32, (capacity, 1)), ('seg_index', seg_index, torch.int64, (capacity,)),
-                                  ('seg_order', seg_order, torch.int64, (capacity,)), ('seg_offsets', seg_offsets, torch.int64, (n + 1,)),
-                                  ('counts', counts, torch.int32, (5,))):
-        if not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != targets.device:
-            raise ValueError(f'mine_pairs: {name} must be a contiguous {dtype} tensor of shape {shape} on {targets.device}')
+    for name, t, dtype, shape in (('groups', groups, _i64, (capacity, 2)), ('labels', labels, _f32, (capacity, 1)),
+                                  ('weights', weights, _f32, (capacity, 1)), ('seg_index', seg_index, _i64, (capacity,)),
+                                  ('seg_order', seg_order, _i64, (capacity,)), ('seg_offsets', seg_offsets, _i64, (n + 1,)),
+                                  ('counts', counts, _i32, (5,))):
+        _check('mine_pairs', name, t, dtype, shape, targets.device)
     _lib.call('vited_mine_pairs', _ptr(targets), n, _ptr(keys), neg_per_pos, int(bool(ordered_negatives)), capacity, _ptr(groups),
               _ptr(labels), _ptr(weights), _ptr(seg_index), _ptr(seg_order), _ptr(seg_offsets), _ptr(counts), _stream())
 
@@ -958,72 +1020,38 @@ def attention_bwd(q, k, v, o, do, lse, heads: int, scale: float, dq, dk, dv, kv_
     dk[g] / dv[g] are the sums over the pairs of item g in ascending pair order - zeros for an item without pairs
     (``vited_attention_bwd_indexed``: per-pair terms in the workspace, then a segmented sum; no atomics)."""
     _need_gpu(q, k, v, o, do, lse, dq, dk, dv)
-    b, nq, d = q.shape
-    nk = k.shape[1]
-    hd = d // heads
-    assert o.is_contiguous() and do.is_contiguous() and o.dtype == do.dtype == q.dtype
+    op, dev = 'attention_bwd', q.device
     if segments is None and kv_index is not None:
         segments = pair_segments(kv_index, k.shape[0])
-    if segments is not None:
-        return _attention_bwd_indexed(q, k, v, o, do, lse, heads, scale, dq, dk, dv, kv_index, segments)
-    q_bs, q_ts = _head_view(q, heads, hd)
-    k_bs, k_ts = _head_view(k, heads, hd)
-    v_bs, v_ts = _head_view(v, heads, hd)
-    dq_bs, dq_ts = _head_view(dq, heads, hd)
-    dk_bs, dk_ts = _head_view(dk, heads, hd)
-    dv_bs, dv_ts = _head_view(dv, heads, hd)
-    delta = torch.empty((b, heads, nq), dtype=torch.float32, device=q.device)
-    _lib.call('vited_attention_bwd',
-              _ptr(q), q_bs, q_ts, _ptr(k), k_bs, k_ts, _ptr(v), v_bs, v_ts, _ptr(o), _ptr(do), nq * d, d, _ptr(lse), _ptr(delta),
-              _ptr(dq), dq_bs, dq_ts, _ptr(dk), dk_bs, dk_ts, _ptr(dv), dv_bs, dv_ts, _code(q.dtype), b, heads, nq, nk, hd,
-              float(scale), _stream())
-    return dq, dk, dv
-
-
-def _attention_bwd_indexed(q, k, v, o, do, lse, heads, scale, dq, dk, dv, kv_index, seg):
-    if not isinstance(seg, PairSegments):
-        raise TypeError(f'attention_bwd: segments must be a PairSegments (ops.pair_segments), got {type(seg).__name__}')
-    b, nq, d = q.shape
-    items, nk = k.shape[0], k.shape[1]
-    hd = d // heads
-    if kv_index is not None and kv_index is not seg.index and not torch.equal(kv_index.to(seg.index.device), seg.index):
+    if segments is not None and not isinstance(segments, PairSegments):
+        raise TypeError(f'attention_bwd: segments must be a PairSegments (ops.pair_segments), got {type(segments).__name__}')
+    items = None if segments is None else k.shape[0]
+    (b, nq, nk, d, hd), qkv = _qkv_operands(op, q, k, v, heads, items)
+    _check(op, 'o', o, q.dtype, q.shape, dev, like='q')
+    _check(op, 'do', do, q.dtype, q.shape, dev, like='q')
+    _check(op, 'lse', lse, _f32, (b, heads, nq), dev)
+    grads = (_ptr(dq), *_head_operand(op, 'dq', dq, q.dtype, q.shape, dev, like='q'),
+             _ptr(dk), *_head_operand(op, 'dk', dk, q.dtype, k.shape, dev, like='k'),
+             _ptr(dv), *_head_operand(op, 'dv', dv, q.dtype, k.shape, dev, like='v'))
+    delta = torch.empty((b, heads, nq), dtype=torch.float32, device=dev)
+    tail = (_ptr(o), _ptr(do), nq * d, d, _ptr(lse), _ptr(delta), *grads, _code(q.dtype), b, heads, nq, nk, hd, float(scale))
+    if segments is None:
+        _lib.call('vited_attention_bwd', *qkv, *tail, _stream())
+        return dq, dk, dv
+    if kv_index is not None and kv_index is not segments.index and not torch.equal(kv_index.to(segments.index.device), segments.index):
         raise ValueError('attention_bwd: kv_index and segments.index differ')
-    for name, t, size in (('index', seg.index, b), ('order', seg.order, b), ('offsets', seg.offsets, items + 1)):
-        if t.dtype != torch.int64 or t.dim() != 1 or t.numel() != size or not t.is_contiguous() or t.device != q.device:
-            raise ValueError(f'attention_bwd: segments.{name} must be a contiguous int64 [{size}] tensor on {q.device}, got {t.dtype} '
-                             f'{tuple(t.shape)} on {t.device} ({b} pairs over {items} key/value items)')
-    assert q.dtype == k.dtype == v.dtype == dq.dtype == dk.dtype == dv.dtype
-    assert k.shape == v.shape == dk.shape == dv.shape and k.shape[2] == d and dq.shape == q.shape
-    q_bs, q_ts = _head_view(q, heads, hd)
-    k_bs, k_ts = _head_view(k, heads, hd)
-    v_bs, v_ts = _head_view(v, heads, hd)
-    dq_bs, dq_ts = _head_view(dq, heads, hd)
-    dk_bs, dk_ts = _head_view(dk, heads, hd)
-    dv_bs, dv_ts = _head_view(dv, heads, hd)
-    delta = torch.empty((b, heads, nq), dtype=torch.float32, device=q.device)
+    for name, t, size in (('index', segments.index, b), ('order', segments.order, b), ('offsets', segments.offsets, items + 1)):
+        _check(op, f'segments.{name}', t, _i64, (size,), dev)
     nbytes = _lib.load().vited_attention_bwd_indexed_workspace_bytes(_code(q.dtype), b, heads, nk, hd)
     if nbytes < 0:
         raise ValueError(f'attention_bwd: empty operands (B {b}, heads {heads}, Nk {nk}, head_dim {hd})')
-    ws, ws_bytes = _scratch(nbytes + 16, q.device)
-    base = (ws + 15) // 16 * 16
-    _lib.call('vited_attention_bwd_indexed',
-              _ptr(q), q_bs, q_ts, _ptr(k), k_bs, k_ts, _ptr(v), v_bs, v_ts, _ptr(seg.index), _ptr(seg.order), _ptr(seg.offsets), items,
-              _ptr(o), _ptr(do), nq * d, d, _ptr(lse), _ptr(delta), _ptr(dq), dq_bs, dq_ts, _ptr(dk), dk_bs, dk_ts, _ptr(dv), dv_bs, dv_ts,
-              _code(q.dtype), b, heads, nq, nk, hd, float(scale), base, ws_bytes - (base - ws), _stream())
+    _lib.call('vited_attention_bwd_indexed', *qkv, _ptr(segments.index), _ptr(segments.order), _ptr(segments.offsets), items, *tail,
+              *_scratch(nbytes, dev, align=16), _stream())
     return dq, dk, dv
 
 
 CAM_GRAD, CAM_PROB = 0, 1          # VITED_CAM_GRAD / VITED_CAM_PROB
 _CAM_MODES = {'grad': CAM_GRAD, 'prob': CAM_PROB, CAM_GRAD: CAM_GRAD, CAM_PROB: CAM_PROB}
-
-
-def _cam_operand(name, t, heads, like=None):
-    if t.dim() != 3 or t.stride(2) != 1 or t.shape[2] % heads:
-        raise ValueError(f'attention_cam: {name} must be [B, N, heads*head_dim] with a dense last dim, got shape {tuple(t.shape)} '
-                         f'stride {t.stride()} for {heads} heads')
-    if like is not None and (t.dtype != like.dtype or t.device != like.device or t.shape[0] != like.shape[0] or t.shape[2] != like.shape[2]):
-        raise ValueError(f'attention_cam: {name} {tuple(t.shape)} {t.dtype} does not match q {tuple(like.shape)} {like.dtype}')
-    return t.stride(0), t.stride(1)
 
 
 def attention_cam(q, k, v, do, lse, heads: int, scale: float, *, mode, head_weight=None, out=None):
@@ -1043,32 +1071,23 @@ def attention_cam(q, k, v, do, lse, heads: int, scale: float, *, mode, head_weig
     if mode == CAM_PROB:
         v = do = None
     _need_gpu(q, k, v, do, lse, head_weight, out)
-    if heads <= 0:
-        raise ValueError(f'attention_cam: heads must be positive, got {heads}')
-    q_bs, q_ts = _cam_operand('q', q, heads)
-    k_bs, k_ts = _cam_operand('k', k, heads, q)
-    v_bs, v_ts = _cam_operand('v', v, heads, q) if v is not None else (0, 0)
-    do_bs, do_ts = _cam_operand('do', do, heads, q) if do is not None else (0, 0)
+    op, dev = 'attention_cam', q.device
+    qs = _head_operand(op, 'q', q, _ACT, _ANY3, dev)
     b, nq, d = q.shape
+    hd = _head_dim(op, 'q', d, heads)
+    ks = _head_operand(op, 'k', k, q.dtype, (b, None, d), dev, like='q')
     nk = k.shape[1]
-    if v is not None and v.shape[1] != nk:
-        raise ValueError(f'attention_cam: v has {v.shape[1]} tokens, k has {nk}')
-    if do is not None and do.shape[1] != nq:
-        raise ValueError(f'attention_cam: do has {do.shape[1]} tokens, q has {nq}')
+    vs = _head_operand(op, 'v', v, q.dtype, (b, nk, d), dev, optional=True, like='q')
+    dos = _head_operand(op, 'do', do, q.dtype, (b, nq, d), dev, optional=True, like='q')
     if b == 0 or nq == 0 or nk == 0:
         raise ValueError(f'attention_cam: empty operands (B {b}, Nq {nq}, Nk {nk})')
-    if lse.dtype != torch.float32 or tuple(lse.shape) != (b, heads, nq) or not lse.is_contiguous():
-        raise ValueError(f'attention_cam: lse must be contiguous float32 [{b}, {heads}, {nq}], got {tuple(lse.shape)} {lse.dtype}')
-    if head_weight is not None and (head_weight.dtype != torch.float32 or tuple(head_weight.shape) != (b, heads) or not head_weight.is_contiguous()):
-        raise ValueError(f'attention_cam: head_weight must be contiguous float32 [{b}, {heads}], got {tuple(head_weight.shape)} {head_weight.dtype}')
+    _check(op, 'lse', lse, _f32, (b, heads, nq), dev)
+    _check(op, 'head_weight', head_weight, _f32, (b, heads), dev, optional=True)
     if out is None:
-        out = torch.empty((b, nq, nk), dtype=torch.float32, device=q.device)
-    elif (out.dtype != torch.float32 or out.dim() != 3 or out.shape[0] != b or out.shape[1] != nq or out.shape[2] < nk or out.stride(2) != 1
-          or out.stride(1) < nk or out.device != q.device):
-        raise ValueError(f'attention_cam: out must be float32 [{b}, {nq}, >= {nk}] with a dense last dim, got {tuple(out.shape)} '
-                         f'stride {out.stride()} {out.dtype}')
-    _lib.call('vited_attention_cam', _ptr(q), q_bs, q_ts, _ptr(k), k_bs, k_ts, _ptr(v), v_bs, v_ts, _ptr(do), do_bs, do_ts, _ptr(lse),
-              _ptr(head_weight), _ptr(out), out.stride(0), out.stride(1), mode, _code(q.dtype), b, heads, nq, nk, d // heads,
+        out = torch.empty((b, nq, nk), dtype=torch.float32, device=dev)
+    _check(op, 'out', out, _f32, (b, nq, _Min(nk)), dev, DENSE_LAST)
+    _lib.call('vited_attention_cam', _ptr(q), *qs, _ptr(k), *ks, _ptr(v), *vs, _ptr(do), *dos, _ptr(lse),
+              _ptr(head_weight), _ptr(out), out.stride(0), out.stride(1), mode, _code(q.dtype), b, heads, nq, nk, hd,
               float(scale), _stream())
     return out[:, :, :nk] if out.shape[2] != nk else out
 
@@ -1081,26 +1100,18 @@ def last_paths():
 # ---------------------------------------------------------------------------------------------
 # evaluation: retrieval metrics of a distance matrix (misc/wi19_evaluate.get_metrics)
 # ---------------------------------------------------------------------------------------------
-def _int32_vector(name, t, device, size=None):
-    if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() or (size is not None and t.numel() != size):
-        raise ValueError(f'{name} must be a contiguous int32 vector{f" of length {size}" if size else ""}, '
-                         f'got {t.dtype} of shape {tuple(t.shape)}')
-    if t.device != device:
-        raise ValueError(f'{name} is on {t.device}, the matrix on {device}')
-
-
-def _ranking_args(what, matrix, labels, rows):
+def _ranking_args(op, what, matrix, labels, rows):
     """(dtype code, ld, n, r0, r1) of the [n, n] matrix a ranking-metrics entry takes, after the checks both entries share."""
     if matrix.dtype not in _FLOATS:
-        raise TypeError(f'{what} metrics take float32, bfloat16 or float16 matrices, got {matrix.dtype}')
+        raise TypeError(f'{op}: matrix must be float32, bfloat16 or float16 for the {what} metrics, got {matrix.dtype}')
     if matrix.dim() != 2 or matrix.shape[0] != matrix.shape[1]:
-        raise ValueError(f'expected a square [n, n] matrix, got shape {tuple(matrix.shape)}')
-    ld = _rows2d(matrix)
+        raise ValueError(f'{op}: matrix must be a square [n, n] matrix, got shape {tuple(matrix.shape)}')
     n = matrix.shape[0]
-    _int32_vector('labels', labels, matrix.device, n)
+    ld = _rows(op, 'matrix', matrix, _FLOATS, matrix.device, n, n)
+    _check(op, 'labels', labels, _i32, (n,), matrix.device)
     r0, r1 = int(rows[0]), int(rows[1])
     if not 0 <= r0 < r1 <= n:
-        raise ValueError(f'rows ({r0}, {r1}) is not a non-empty range inside [0, {n})')
+        raise ValueError(f'{op}: rows ({r0}, {r1}) is not a non-empty range inside [0, {n})')
     return _DTYPE[matrix.dtype], ld, n, r0, r1
 
 
@@ -1110,9 +1121,9 @@ def retrieval_metrics_rows(matrix: torch.Tensor, labels: torch.Tensor, offsets: 
     their sums (float64 [7], see include/vited.h) for the rows [r0, r1) of the [n, n] matrix.  ``labels`` int32 [n] in
     [0, C) with the class CSR ``offsets`` int32 [C + 1] / ``members`` int32 [n] built from them (engine.class_members)."""
     _need_gpu(matrix, labels, offsets, members)
-    dt, ld, n, r0, r1 = _ranking_args('retrieval', matrix, labels, rows)
-    _int32_vector('members', members, matrix.device, n)
-    _int32_vector('offsets', offsets, matrix.device)
+    dt, ld, n, r0, r1 = _ranking_args('retrieval_metrics_rows', 'retrieval', matrix, labels, rows)
+    _check('retrieval_metrics_rows', 'members', members, _i32, (n,), matrix.device)
+    _check('retrieval_metrics_rows', 'offsets', offsets, _i32, (None,), matrix.device)
     rows_out = torch.empty((r1 - r0, 5), dtype=torch.float64, device=matrix.device)
     sums = torch.empty(7, dtype=torch.float64, device=matrix.device)
     _lib.call('vited_retrieval_metrics', _ptr(matrix), dt, ld, n, r0, r1, _ptr(labels), _ptr(offsets), _ptr(members), offsets.numel() - 1,
@@ -1130,11 +1141,12 @@ def group_retrieval_metrics_rows(matrix: torch.Tensor, labels: torch.Tensor, col
     ``pos_csr`` / ``neg_csr`` = (offsets int32 [L + 1], label ids int32), every row ascending and without duplicates; ``neg_csr``
     may be None.  ``ks``: 1 to 8 ints >= 1."""
     _need_gpu(matrix, labels, *col_csr, *pos_csr, *(neg_csr or ()))
-    dt, ld, n, r0, r1 = _ranking_args('group retrieval', matrix, labels, rows)
+    op = 'group_retrieval_metrics_rows'
+    dt, ld, n, r0, r1 = _ranking_args(op, 'group retrieval', matrix, labels, rows)
     num_labels = col_csr[0].numel() - 1
-    for name, (off, vals) in (('col', col_csr), ('pos', pos_csr)) + ((('neg', neg_csr),) if neg_csr is not None else ()):
-        _int32_vector(f'{name} offsets', off, matrix.device, num_labels + 1)
-        _int32_vector(f'{name} members', vals, matrix.device)
+    for name, (off, vals) in (('col_csr', col_csr), ('pos_csr', pos_csr)) + ((('neg_csr', neg_csr),) if neg_csr is not None else ()):
+        _check(op, f'{name}[0] (offsets)', off, _i32, (num_labels + 1,), matrix.device)
+        _check(op, f'{name}[1] (members)', vals, _i32, (n if name == 'col_csr' else None,), matrix.device)
     ks = [int(k) for k in ks]
     if not 1 <= len(ks) <= 8 or min(ks) < 1:
         raise ValueError(f'ks must be 1 to 8 cut-offs >= 1, got {ks}')
@@ -1147,24 +1159,25 @@ def group_retrieval_metrics_rows(matrix: torch.Tensor, labels: torch.Tensor, col
     return rows_out, sums
 
 
+def _pair_score_buffers(op, dev, n, m, counts, rec_cells, rec_values, bad):
+    """The accumulator state both pair-score entries take: counts int32 [n, n], m records, the flag word."""
+    for name, t, dtype, shape in (('counts', counts, _i32, (n, n)), ('rec_cells', rec_cells, _i32, (m, 2)), ('rec_values', rec_values, _f32, (m,)),
+                                  ('bad', bad, _i32, (1,))):
+        _check(op, name, t, dtype, shape, dev)
+
+
 def pair_scores_add(pairs: torch.Tensor, scores: torch.Tensor, n: int, counts: torch.Tensor, rec_cells: torch.Tensor,
                     rec_values: torch.Tensor, bad: torch.Tensor):
     """Stores the records (pairs[r, 0], pairs[r, 1], 1 - scores[r]) into rec_cells int32 [m, 2] / rec_values float32 [m] and
     counts them into counts int32 [n, n] (both cells (i, j) and (j, i)).  Ids outside [0, n) set bit 0 of bad int32 [1]."""
     _need_gpu(pairs, scores, counts, rec_cells, rec_values, bad)
-    if pairs.dtype not in (torch.int32, torch.int64) or pairs.dim() != 2 or pairs.shape[1] != 2:
-        raise ValueError(f'pairs must be int32 / int64 [m, 2], got {pairs.dtype} of shape {tuple(pairs.shape)}')
-    if pairs.stride(1) != 1:
+    op, dev = 'pair_scores_add', pairs.device
+    if torch.is_tensor(pairs) and pairs.dim() == 2 and pairs.stride(1) != 1:
         pairs = pairs.contiguous()
-    if scores.dtype not in _FLOATS or scores.dim() != 1 or scores.numel() != pairs.shape[0]:
-        raise ValueError(f'scores must be a float32 / bfloat16 / float16 vector of {pairs.shape[0]}, '
-                         f'got {scores.dtype} of shape {tuple(scores.shape)}')
-    scores = scores.contiguous()
+    _check(op, 'pairs', pairs, (_i32, _i64), (None, 2), dev, DENSE_LAST)
     m = pairs.shape[0]
-    for name, t, dtype, shape in (('counts', counts, torch.int32, (n, n)), ('rec_cells', rec_cells, torch.int32, (m, 2)),
-                                  ('rec_values', rec_values, torch.float32, (m,)), ('bad', bad, torch.int32, (1,))):
-        if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != pairs.device:
-            raise ValueError(f'{name} must be contiguous {dtype} {shape} on {pairs.device}, got {t.dtype} {tuple(t.shape)} on {t.device}')
+    scores = _check(op, 'scores', scores, _FLOATS, (m,), dev, None).contiguous()
+    _pair_score_buffers(op, dev, n, m, counts, rec_cells, rec_values, bad)
     if m == 0:
         return
     _lib.call('vited_pair_scores_add', _ptr(pairs), _DTYPE[pairs.dtype], pairs.stride(0), _ptr(scores), _DTYPE[scores.dtype], m, n,
@@ -1176,6 +1189,7 @@ def pair_scores_finish(rec_cells: torch.Tensor, rec_values: torch.Tensor, n: int
     record; see include/vited.h."""
     _need_gpu(rec_cells, rec_values, counts, bad)
     m = rec_values.numel()
+    _pair_score_buffers('pair_scores_finish', counts.device, n, m, counts, rec_cells, rec_values, bad)
     ws_bytes = _lib.load().vited_pair_scores_workspace_bytes(n, m)
     if ws_bytes < 0:
         raise ValueError(f'{n} fragments / {m} records is outside what vited_pair_scores_finish takes')
@@ -1191,22 +1205,15 @@ def pair_scores_finish(rec_cells: torch.Tensor, rec_values: torch.Tensor, n: int
 
 
 # ---- puzzle solving: Paikin-Tal compatibility stage (include/vited.h) ------------------------------------------------------------
-def _puzzle_check(name, t, dtype, shape, dev):
-    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous() or t.device != dev:
-        raise ValueError(f'{name} must be contiguous {dtype} {tuple(shape)} on {dev}, got {t.dtype} {tuple(t.shape)} on {t.device}')
-
-
 def puzzle_distances_from_logits(logits: torch.Tensor, pi: torch.Tensor, pj: torch.Tensor, dq: torch.Tensor, bad: torch.Tensor):
     """dq[s, pi[r], pj[r]] = uint32(trunc(fp32(fp32(1 - sigmoid(logits[r, (s + 3) % 4])) * 1000))) for s = 0..3 (top, right, bottom,
     left).  logits float32 [m, 4], pi / pj int64 [m], dq int32 [4, n, n]; a pair outside [0, n) or with i == j sets bad int32 [1]."""
     _need_gpu(logits, pi, pj, dq, bad)
     m, dev = pi.numel(), dq.device
     n = dq.shape[1]
-    _puzzle_check('logits', logits, torch.float32, (m, 4), dev)
-    _puzzle_check('pi', pi, torch.int64, (m,), dev)
-    _puzzle_check('pj', pj, torch.int64, (m,), dev)
-    _puzzle_check('dq', dq, torch.int32, (4, n, n), dev)
-    _puzzle_check('bad', bad, torch.int32, (1,), dev)
+    for name, t, dtype, shape in (('logits', logits, _f32, (m, 4)), ('pi', pi, _i64, (m,)), ('pj', pj, _i64, (m,)), ('dq', dq, _i32, (4, n, n)),
+                                  ('bad', bad, _i32, (1,))):
+        _check('puzzle_distances_from_logits', name, t, dtype, shape, dev)
     _lib.call('vited_puzzle_distances_from_logits', _ptr(logits), _ptr(pi), _ptr(pj), m, n, _ptr(dq), _ptr(bad), _stream())
 
 
@@ -1215,7 +1222,7 @@ def puzzle_compat_init(dq: torch.Tensor) -> dict:
     mutual, start_count, start_total, start_order) of the distances dq int32 [4, n, n]."""
     _need_gpu(dq)
     n, dev = dq.shape[1], dq.device
-    _puzzle_check('dq', dq, torch.int32, (4, n, n), dev)
+    _check('puzzle_compat_init', 'dq', dq, _i32, (4, n, n), dev)
     st = {'min_d': torch.empty((n, 4), dtype=torch.int64, device=dev), 'second_d': torch.empty((n, 4), dtype=torch.int64, device=dev),
           'candidate': torch.empty((n, 4), dtype=torch.int32, device=dev), 'best_buddy': torch.empty((n, 4), dtype=torch.int32, device=dev),
           'compat': torch.empty((4, n, n), dtype=torch.float32, device=dev), 'mutual': torch.empty((4, n, n), dtype=torch.float32, device=dev),
@@ -1230,11 +1237,12 @@ def puzzle_compat_init(dq: torch.Tensor) -> dict:
 def puzzle_compat_recalc(dq: torch.Tensor, placed: torch.Tensor, st: dict, changed: torch.Tensor):
     """recalculate_remaining_piece_compatibilities(placed) on the state ``st`` of puzzle_compat_init, in place; changed int32 [n]
     receives 1 for every piece whose min / second-best distances moved.  placed int32 [n] (0 / 1)."""
-    _need_gpu(dq, placed, changed)
-    n, dev = dq.shape[1], dq.device
-    _puzzle_check('dq', dq, torch.int32, (4, n, n), dev)
-    _puzzle_check('placed', placed, torch.int32, (n,), dev)
-    _puzzle_check('changed', changed, torch.int32, (n,), dev)
+    _need_gpu(dq, placed, changed, *(st[key] for key in ('min_d', 'second_d', 'compat', 'mutual')))
+    op, n, dev = 'puzzle_compat_recalc', dq.shape[1], dq.device
+    for name, t, dtype, shape in (('dq', dq, _i32, (4, n, n)), ('placed', placed, _i32, (n,)), ('changed', changed, _i32, (n,)),
+                                  ("st['min_d']", st['min_d'], _i64, (n, 4)), ("st['second_d']", st['second_d'], _i64, (n, 4)),
+                                  ("st['compat']", st['compat'], _f32, (4, n, n)), ("st['mutual']", st['mutual'], _f32, (4, n, n))):
+        _check(op, name, t, dtype, shape, dev)
     _lib.call('vited_puzzle_compat_recalc', _ptr(dq), n, _ptr(placed), _ptr(st['min_d']), _ptr(st['second_d']), _ptr(st['compat']),
               _ptr(st['mutual']), _ptr(changed), _stream())
 
@@ -1243,13 +1251,12 @@ def puzzle_best_slot(mutual: torch.Tensor, placed: torch.Tensor, slot_piece: tor
                      out: torch.Tensor | None = None) -> torch.Tensor:
     """The packed int64 [1] word of the first maximum of mutual[(slot_side[k] + 2) % 4, p, slot_piece[k]] over unplaced p ascending
     x slot k (see include/vited.h; decode with puzzle_unpack_slot).  placed, slot_piece, slot_side int32."""
-    _need_gpu(mutual, placed, slot_piece, slot_side)
-    n, dev, k = mutual.shape[1], mutual.device, slot_piece.numel()
-    _puzzle_check('mutual', mutual, torch.float32, (4, n, n), dev)
-    _puzzle_check('placed', placed, torch.int32, (n,), dev)
-    _puzzle_check('slot_piece', slot_piece, torch.int32, (k,), dev)
-    _puzzle_check('slot_side', slot_side, torch.int32, (k,), dev)
-    out = torch.empty(1, dtype=torch.int64, device=dev) if out is None else out
+    _need_gpu(mutual, placed, slot_piece, slot_side, out)
+    op, n, dev, k = 'puzzle_best_slot', mutual.shape[1], mutual.device, slot_piece.numel()
+    for name, t, dtype, shape in (('mutual', mutual, _f32, (4, n, n)), ('placed', placed, _i32, (n,)), ('slot_piece', slot_piece, _i32, (k,)),
+                                  ('slot_side', slot_side, _i32, (k,))):
+        _check(op, name, t, dtype, shape, dev)
+    out = _out(op, 'out', out, _i64, (1,), dev)
     _lib.call('vited_puzzle_best_slot', _ptr(mutual), n, _ptr(placed), _ptr(slot_piece), _ptr(slot_side), k, _ptr(out), _stream())
     return out
 
@@ -1272,25 +1279,18 @@ def cls_metrics_update(logits: torch.Tensor, targets: torch.Tensor, meters: torc
     cast to fp32.  ``meters`` fp64 [10]: (sum, count) of loss, acc, f1, precision, recall; ``last`` fp64 [5] receives the batch's
     values; a target other than 0 / 1 sets ``bad`` int32 [1].  One launch, no host sync."""
     _need_gpu(logits, targets, meters, last, bad)
-    dev = meters.device
-    if logits.dim() != 2 or tuple(targets.shape) != tuple(logits.shape):
-        raise ValueError(f'logits and targets must be [B, C] of the same shape, got {tuple(logits.shape)} and {tuple(targets.shape)}')
+    op, dev = 'cls_metrics_update', meters.device
+    if logits.dtype not in _FLOATS:
+        raise TypeError(f'cls_metrics_update: logits must be float32 / bfloat16 / float16, got {logits.dtype}')
+    if targets.dtype == torch.bool or targets.is_complex():
+        raise TypeError(f'cls_metrics_update: targets must be real numbers 0 / 1, got {targets.dtype}')
+    logits = _check(op, 'logits', logits.float(), _f32, _ANY2, dev, DENSE_LAST)
     b, c = logits.shape
     if b < 1 or not 1 <= c <= 64:
-        raise ValueError(f'need B >= 1 rows and 1 <= C <= 64 columns, got [{b}, {c}]')
-    if logits.device != dev or targets.device != dev:
-        raise ValueError(f'logits ({logits.device}) and targets ({targets.device}) must be on the meters\' device {dev}')
-    if logits.dtype not in _FLOATS:
-        raise TypeError(f'logits must be float32 / bfloat16 / float16, got {logits.dtype}')
-    if targets.dtype == torch.bool or targets.is_complex():
-        raise TypeError(f'targets must be real numbers 0 / 1, got {targets.dtype}')
-    logits, targets = logits.float(), targets.float()
-    for name, t in (('logits', logits), ('targets', targets)):
-        if (c > 1 and t.stride(1) != 1) or (b > 1 and t.stride(0) < c):
-            raise ValueError(f'{name} must have a unit column stride and a row stride >= {c}, got strides {t.stride()}')
-    _puzzle_check('meters', meters, torch.float64, (10,), dev)
-    _puzzle_check('last', last, torch.float64, (5,), dev)
-    _puzzle_check('bad', bad, torch.int32, (1,), dev)
+        raise ValueError(f'cls_metrics_update: logits: need B >= 1 rows and 1 <= C <= 64 columns, got [{b}, {c}]')
+    targets = _check(op, 'targets', targets.float(), _f32, (b, c), dev, DENSE_LAST, like='logits')
+    for name, t, dtype, size in (('meters', meters, _f64, 10), ('last', last, _f64, 5), ('bad', bad, _i32, 1)):
+        _check(op, name, t, dtype, (size,), dev)
     ld = lambda t: t.stride(0) if b > 1 else c
     _lib.call('vited_cls_metrics_update', _ptr(logits), ld(logits), _ptr(targets), ld(targets), b, c, _ptr(meters), _ptr(last), _ptr(bad),
               _stream())

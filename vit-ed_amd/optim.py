@@ -129,7 +129,8 @@ class _FlatOptimizer(torch.optim.Optimizer):
         state = [self._bufs[n].data_ptr() for n in self._state_names] + [None] * (2 - len(self._state_names))
         rows_, tile = [], 0
         for p, v, off in zip(self.flat.params, self.flat.views, self.flat.offsets):
-            assert p.is_contiguous() and p.dtype == torch.float32, f'{type(self).__name__}: parameters must be contiguous fp32'
+            if not p.is_contiguous() or p.dtype != torch.float32:
+                raise ValueError(f'{type(self).__name__}: parameters must be contiguous fp32')
             r = p.shape[0] if p.dim() >= 2 else 1
             c = p.numel() // r
             sh = shadows.get(id(p), {})
