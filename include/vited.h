@@ -193,6 +193,48 @@ int vited_slice_rows_cast(const float* in, void* out, int out_dtype, int64_t bat
 int vited_write_cls_row(float* x, const float* cls, const float* pos, int64_t batch, int64_t rows_per_batch,
                         int64_t dim, void* stream);
 
+/* ---- patch dropout (timm PatchDropout(prob, num_prefix_tokens=1, ordered=False) as the reference's model constructs it and calls
+ * it at vision_transformer.py:385,393; csrc/patch_keep.hip) ----------------------------------------------------
+ * A keep table is a DEVICE int32 [batch, K]: per sample the K token indices timm's argsort(randn)[:, :K] kept, counted behind the
+ * prefix slot, in keep order (not sorted), distinct within a row.  `lead` says where the prefix slot falls:
+ *   lead = 0 (prepare_x2): the prefix is the cls token; the kept patch rows are patch(b, r) = keep[b, r], r < K.
+ *   lead = 1 (forward_first_part): no cls token exists, the slot falls on patch 0, which is always kept and leads:
+ *            patch(b, 0) = 0, patch(b, r) = 1 + keep[b, r - 1]; R = 1 + K rows.
+ * R = K + lead below.  An index outside its range is clamped by the kernels, never followed out of bounds.
+ * VITED_ERR_BAD_ARG everywhere: a null pointer, a non-positive size, lead other than 0 / 1, K + lead above the number of patches,
+ * a pointer that is not aligned to its element (16 bytes for the fp32 token rows of vited_tokens_kept / _bwd, whose dim is a
+ * multiple of 4).
+ *
+ * keep[b, 0..K) = the indices of the K smallest of keys[b, 0..L), in ascending key order, equal keys by ascending index (NaN after
+ * every number): torch.argsort(keys, dim=-1, stable=True)[:, :K].  One workgroup per row, the keys in LDS; L > 4096 is
+ * VITED_ERR_UNSUPPORTED, K > L VITED_ERR_BAD_ARG.  No host read: capturable. */
+int vited_keep_from_keys(const float* keys, int32_t* keep, int64_t batch, int L, int K, void* stream);
+
+/* vited_patchify / vited_patchify_u8 for the kept patches alone: out[(b * R + r), :] = the patch row of patch(b, r), bit-equal to
+ * the row the full kernels write for that patch; a dropped patch is never read.  keep is indexed by the OUTPUT sample b (with
+ * batch_index: by the pair, not by the gathered image).  R above 65535 is VITED_ERR_UNSUPPORTED. */
+int vited_patchify_kept(const float* img, int64_t img_bs, const int64_t* batch_index, const int32_t* keep, int K, int lead, void* out,
+                        int out_dtype, int64_t batch, int chans, int img_size, int patch, void* stream);
+int vited_patchify_kept_u8(const uint8_t* img, int64_t img_bs, const int64_t* batch_index, const int32_t* keep, int K, int lead,
+                           void* out, int out_dtype, int64_t batch, int chans, int img_size, int patch, const float* mean,
+                           const float* std, void* stream);
+
+/* timm _pos_embed for kept tokens: tok fp32 [batch * R, dim] is the patch-embedding product + bias of the kept rows, pos fp32
+ * [1 + n_patches, dim].  Without cls (null): x fp32 [batch, R, dim], x[b, r] = tok[b, r] + pos[1 + patch(b, r)].  With cls fp32
+ * [dim]: x [batch, 1 + R, dim], x[b, 0] = cls + pos[0] and x[b, 1 + r] as before.  One fp32 add per element. */
+int vited_tokens_kept(const float* tok, const float* pos, const float* cls, const int32_t* keep, int K, int lead, float* x,
+                      int64_t batch, int n_patches, int dim, void* stream);
+
+/* inv int32 [batch, n_patches]: inv[b, p] = r where patch(b, r) == p, -1 where sample b dropped patch p. */
+int vited_keep_inverse(const int32_t* keep, int K, int lead, int32_t* inv, int64_t batch, int n_patches, void* stream);
+
+/* Backward of vited_tokens_kept with respect to pos and cls: dx fp32 [batch, rows, dim] with rows = R + with_cls.
+ * dpos[1 + p] = sum over the samples b with inv[b, p] >= 0, in ascending b, of dx[b, with_cls + inv[b, p]] - exact zeros for a patch
+ * nobody kept; dpos[0] (and dcls fp32 [dim], nullable, with_cls only) = sum_b dx[b, 0] with a cls row, exact zeros without.  Every
+ * element of dpos [1 + n_patches, dim] is written once, without atomics: bitwise reproducible. */
+int vited_tokens_kept_bwd(const float* dx, const int32_t* inv, float* dpos, float* dcls, int64_t batch, int rows, int with_cls,
+                          int n_patches, int dim, void* stream);
+
 /* out[r] = sum_b in[b, r] (fp32 out; in is `in_dtype` [batch, width]).  Deterministic two-pass;
  * workspace >= vited_sum_rows_workspace_bytes().  Serves bias gradients (column sums) and the
  * pos_embed / cls_token gradients (batch sums). */

@@ -192,7 +192,11 @@ class TrainStep:
       which torch registers with the graph: every replay draws anew, and ``model.last_drop_path`` is a static buffer that holds
       the latest replay's scales.  A custom ``model.drop_path_generator`` raises at capture.  ``step.drop_path`` = a
       ``DropPathScales`` of static tensors forces the scales instead (tests, reproducing a step): a captured graph reads those
-      tensors in place."""
+      tensors in place.
+    * Patch dropout (``patch_drop_rate`` > 0, training mode) works the same way: the keys and the ranking kernel that turns them into
+      keep indices are part of the captured graph, ``model.last_patch_keep`` is a static buffer that holds the latest replay's
+      indices, and ``step.patch_keep`` = a ``PatchKeep`` of static tensors forces them.  The shortened sequences have a fixed length
+      (the rate is the model's), so the captured shapes never change."""
 
     def __init__(self, model, optimizer, *, clip_grad=5.0, amp=True, criterion=None, use_graph=False,
                  compress_bf16=False, forward_fn=None, accumulation_steps=1, lr_scheduler=None, overlap=True, group=None,
@@ -207,7 +211,8 @@ class TrainStep:
         if hasattr(model, 'direct_param_grads') or hasattr(model, 'runtime'):
             model.direct_param_grads = True     # HIP model: weight-gradient kernels add straight into the flat buffer
         self.drop_path = None       # forced stochastic-depth scales (a DropPathScales); None: the model draws when it should
-        self.forward_fn = forward_fn or (lambda m, x: m(x) if self.drop_path is None else m(x, drop_path=self.drop_path))
+        self.patch_keep = None      # forced patch-dropout indices (a PatchKeep); None: the model draws when it should
+        self.forward_fn = forward_fn or (lambda m, x: m(x, **self._forced()))
         self.use_graph = use_graph and torch.cuda.is_available()
         self.hip_opt = hasattr(optimizer, 'bind_flat')       # optim.FlatAdamW / FlatSGD: clip + update + shadow refresh in one kernel
         if self.hip_opt:
@@ -265,6 +270,13 @@ class TrainStep:
         loss = self.criterion(out.float(), y)
         return loss / self.accum if self.accum > 1 else loss
 
+    def _forced(self):
+        """The keyword arguments that hand the forced scales / indices of this step to the model (none: it draws for itself)."""
+        forced = {} if self.drop_path is None else dict(drop_path=self.drop_path)
+        if self.patch_keep is not None:
+            forced['patch_keep'] = self.patch_keep
+        return forced
+
     def _fwd_bwd(self, x, y):
         """One-stage form (any model / forward_fn)."""
         with torch.autocast(self.device_type, dtype=torch.bfloat16, enabled=self.amp):
@@ -277,7 +289,7 @@ class TrainStep:
         """Stage 1 of the split backward: encoder forward, decoder + head forward, loss, decoder backward.
         Returns (loss, features, d loss / d features)."""
         with torch.autocast(self.device_type, dtype=torch.bfloat16, enabled=self.amp):
-            forced = {} if self.drop_path is None else dict(drop_path=self.drop_path)
+            forced = self._forced()
             feats = self.model(x[:, 0], forward_first_part=True, **forced)
             leaf = feats.detach().requires_grad_(True)
             out = self.model(leaf, x[:, 1], **forced)

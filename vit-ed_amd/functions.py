@@ -120,6 +120,8 @@ class Runtime:
         self._unit_ln = None        # (ones, zeros) for the affine-free LayerNorm of the features
         self.drop_path = None       # (encoder scales fp32 [depth, 2, B] | None, decoder scales fp32 [c_depth, 3, B] | None, (live encoder
                                     # branches, live decoder branches)): set by the model around a call, read by the Functions' forward
+        self.patch_keep = None      # (image-1 keep table int32 [B1, K1] | None, image-2 table [B2, K2] | None): patch dropout of this call, set by
+                                    # the model around it
         self.tap = None             # test/diagnostic: a dict that receives clones of per-block activations and gradients
         self.block_events = None    # measurement (bench.py): a list that receives (kind, block, 'fwd' | 'bwd', start event, end event)
         self.pinned = False         # a captured hipGraph reads the shadow buffers: never free one, only refresh in place
@@ -623,8 +625,23 @@ def _attn_branch_bwd(rt, dy, dy_lp, x, P, saved, batch, n, key=None, lp_scale=No
     return dx, dx_lp, dict(g1=dg1, b1=db1, wqkv=dwqkv, bqkv=dbqkv, wproj=dwproj, bproj=dbproj, **gn)
 
 
-def _patch_tokens_fwd(rt, img, S, with_cls, batch_index=None):
-    """timm PatchEmbed + pos-embed (+ cls row, S: a DecShared) : returns x fp32 [B*rows, D] and the saved patch matrix."""
+def _take_patch_keep(rt, which):
+    """The keep table of this call's half (0: image 1, 1: image 2) from ``rt.patch_keep``; None: no patch dropout in this call."""
+    return rt.patch_keep[which] if rt.patch_keep is not None else None
+
+
+def _patch_tokens_fwd(rt, img, S, with_cls, batch_index=None, keep=None):
+    """timm PatchEmbed + pos-embed (+ cls row, S: a DecShared) : returns x fp32 [B*rows, D] and the saved patch matrix.
+    ``keep`` (int32 [B, K]; patch dropout): only the kept patches are extracted, embedded and given their
+    position - rows = K + 1 either way: patch 0 leads without a cls row (the reference's prefix slot falls on it), the cls row with
+    one.  Without it the launches are exactly those of a model that has no patch dropout."""
+    if keep is not None:
+        lead = not with_cls
+        patches = ops.patchify_kept(img, rt.patch_size, rt.act_dtype, keep, lead, batch_index, mean=rt.input_mean, std=rt.input_std)
+        tok = ops.gemm(patches, rt.weight(S.pw), epilogue=EPI_STORE_F32, bias=S.pb)
+        x = ops.tokens_kept(tok, S.pos.view(rt.n2, rt.dim), S.cls.view(-1) if with_cls else None, keep, lead)
+        batch, rows = x.shape[0], x.shape[1]
+        return x.view(batch * rows, rt.dim), patches, batch, rows
     patches = ops.patchify(img, rt.patch_size, rt.act_dtype, batch_index, mean=rt.input_mean, std=rt.input_std)
     batch = patches.shape[0] // rt.n1
     pos2 = S.pos.view(rt.n2, rt.dim)
@@ -636,8 +653,22 @@ def _patch_tokens_fwd(rt, img, S, with_cls, batch_index=None):
     return x, patches, batch, rows
 
 
-def _patch_tokens_bwd(rt, dx, patches, S, with_cls, batch):
-    """dx fp32 [B*rows, D] -> the gradients of pw, pb, pos (and cls) by field name."""
+def _patch_tokens_bwd(rt, dx, patches, S, with_cls, batch, keep=None):
+    """dx fp32 [B*rows, D] -> the gradients of pw, pb, pos (and cls) by field name.  ``keep``: the table the forward embedded through;
+    d pos then sums every patch's row over the samples that kept it (ops.tokens_kept_bwd: fixed order, no atomics) and the
+    weight gradient runs on the kept rows."""
+    if keep is not None:
+        rows = dx.shape[0] // batch
+        dx3 = dx.view(batch, rows, rt.dim)
+        dpos, dcls = ops.tokens_kept_bwd(dx3, ops.keep_inverse(keep, not with_cls, rt.n1), with_cls)
+        grads = dict(pos=dpos.view_as(S.pos))
+        if with_cls:
+            grads['cls'] = dcls.view_as(S.cls)
+            dtok = ops.slice_rows_cast(dx3, 1, rows - 1, rt.act_dtype)
+        else:
+            dtok = dx if rt.exact else ops.cast(dx, rt.act_dtype)
+        grads['pw'], grads['pb'] = _weight_grads(rt, dtok, patches, S.pw, S.pb)
+        return grads
     rows = rt.n2 if with_cls else rt.n1
     dx3 = dx.view(batch, rows, rt.dim)
     dpos_rows = ops.sum_rows(dx3.view(batch, rows * rt.dim)).view(rows, rt.dim)
@@ -667,7 +698,8 @@ class EncoderFn(torch.autograd.Function):
     def forward(ctx, rt: Runtime, img, *params):
         shared, blocks = split_params(params, EncShared, rt.enc_block)
         grad = any(ctx.needs_input_grad)  # False under no_grad: nothing is saved for inference
-        x, patches, batch, n = _patch_tokens_fwd(rt, img, shared, with_cls=False)
+        keep = _take_patch_keep(rt, 0)
+        x, patches, batch, n = _patch_tokens_fwd(rt, img, shared, with_cls=False, keep=keep)
         drop = _take_drop_rows(rt, 0, len(blocks), 2, batch, n, x.device)      # stochastic depth: per-row scales of (attn, mlp) per block
         tape = []
         ln1 = None          # (h, mean, rstd) of this block's norm1 when the previous block's fc2 kernel already produced it
@@ -685,12 +717,12 @@ class EncoderFn(torch.autograd.Function):
                 rt.tap[f'enc.x.{len(tape) - 1 if grad else 0}'] = x.clone()
         if grad:
             ctx.rt, ctx.tape, ctx.patches, ctx.batch, ctx.params = rt, tape, patches, batch, (shared, blocks)
-            ctx.drop = drop
+            ctx.drop, ctx.n, ctx.keep = drop, n, keep
         return x.view(batch, n, rt.dim)
 
     @staticmethod
     def backward(ctx, dout):
-        rt, batch, n = ctx.rt, ctx.batch, ctx.rt.n1
+        rt, batch, n = ctx.rt, ctx.batch, ctx.n      # n: the call's token count (fewer than rt.n1 under patch dropout)
         shared, blocks = ctx.params
         dx = dout.contiguous().view(batch * n, rt.dim).float()
         drop = ctx.drop
@@ -708,8 +740,8 @@ class EncoderFn(torch.autograd.Function):
                 if rt.tap is not None:
                     rt.tap[f'enc.dx.{i}'] = dx.clone()      # gradient w.r.t. the INPUT of encoder block i
                 gblocks[i] = rt.enc_block(**ga, **gm)
-        gshared = EncShared(**_patch_tokens_bwd(rt, dx, ctx.patches, shared, with_cls=False, batch=batch))
-        ctx.tape = ctx.patches = ctx.drop = None
+        gshared = EncShared(**_patch_tokens_bwd(rt, dx, ctx.patches, shared, with_cls=False, batch=batch, keep=ctx.keep))
+        ctx.tape = ctx.patches = ctx.drop = ctx.keep = None
         return (None, None, *_cam_only(rt, flatten_params(gshared, gblocks)))
 
 
@@ -811,10 +843,11 @@ def _dec_cross_fwd(rt, xa, P, batch, lnq=None, q=None, kv3=None, ctxf=None, kv_i
     if kv3 is None:
         hc, mc, rc = ops.layernorm_fwd(ctxf, P.gx, P.bx, LN_EPS, rt.act_dtype)
         kv = ops.gemm(hc, rt.weight(P.wkv), bias=P.bkv)              # [Mc, 2D], columns [2][h][hd] (:178)
-        kv3 = kv.view(batch if items is None else items, rt.n1, 2 * d)
+        items = batch if items is None else items
+        kv3 = kv.view(items, kv.shape[0] // items, 2 * d)      # the context's length is the call's: the features' token count
         if rt.qk_norm:
             kn = _k_norm_cross(rt, kv, P)
-    k3 = kv3[:, :, 0:d] if kn is None else kn[0].view(kv3.shape[0], rt.n1, d)
+    k3 = kv3[:, :, 0:d] if kn is None else kn[0].view(kv3.shape[0], kv3.shape[1], d)
     oc, lse_c = ops.attention_fwd(q.view(batch, nq, d), k3, kv3[:, :, d:2 * d], rt.heads, rt.scale, kv_index=kv_index)
     if rt.keep_attn and key is not None:
         _keep_attention(rt, key, q.view(batch, nq, d), k3)
@@ -839,8 +872,8 @@ def _dec_cross_bwd(rt, dx, dx_lp, xa, P, saved, ctxf, dctx, batch, index, dkv3=N
         kv3, dkv = kv, dkv3                 # views of the all-blocks kv / d(kv) tensors
     else:
         dkv = torch.empty_like(kv)
-        kv3, dkv3 = kv.view(items, rt.n1, 2 * d), dkv.view(items, rt.n1, 2 * d)
-    k3 = kv3[:, :, 0:d] if kn is None else kn[0].view(items, rt.n1, d)       # what the attention read: the normalised keys
+        kv3, dkv3 = kv.view(items, kv.shape[0] // items, 2 * d), dkv.view(items, kv.shape[0] // items, 2 * d)
+    k3 = kv3[:, :, 0:d] if kn is None else kn[0].view(items, kv3.shape[1], d)       # what the attention read: the normalised keys
     if rt.keep_attn:
         _keep_attention_grad(rt, ('cross_blocks', index, 'cross_attn'), doc.view(batch, nq, d), kv3[:, :, d:2 * d])
     if rt.keep_cam:
@@ -1038,7 +1071,8 @@ class DecoderFn(torch.autograd.Function):
         image's d(kv) over its pairs before the per-image kv / norm_context backward (hisfrag.py:117-159 without its two gathers)."""
         shared, blocks = split_params(params, DecShared, rt.dec_block)
         grad = any(ctx.needs_input_grad)
-        x, patches, batch, n = _patch_tokens_fwd(rt, img2, shared, with_cls=True, batch_index=img2_index)
+        keep = _take_patch_keep(rt, 1)
+        x, patches, batch, n = _patch_tokens_fwd(rt, img2, shared, with_cls=True, batch_index=img2_index, keep=keep)
         seg = img1_index
         b1 = batch if seg is None else seg.items
         if seg is not None:
@@ -1046,9 +1080,10 @@ class DecoderFn(torch.autograd.Function):
                 raise NotImplementedError('the attention-map paths (keep_attn / keep_cam) take gathered features, not an image-1 index')
             if seg.index.numel() != batch:
                 raise ValueError(f'{seg.index.numel()} image-1 indices for {batch} image-2 samples')
-        if feats.shape != (b1, rt.n1, rt.dim):
-            raise ValueError(f'features {tuple(feats.shape)} do not match {b1} context items')
-        ctxf = feats.detach().contiguous().float().view(b1 * rt.n1, rt.dim)
+        nc = feats.shape[1] if feats.dim() == 3 else 0      # the context's tokens: rt.n1, or what the encoder kept under patch dropout
+        if feats.dim() != 3 or feats.shape != (b1, nc, rt.dim) or not 1 <= nc <= rt.n1:
+            raise ValueError(f'features {tuple(feats.shape)} do not match {b1} context items of 1 to {rt.n1} tokens')
+        ctxf = feats.detach().contiguous().float().view(b1 * nc, rt.dim)
         tape = []
         d = rt.dim
         cls_tail = rt.cls_tail and rt.c_depth > 0 and not (rt.keep_attn or rt.keep_cam)    # the visualisation paths want every query row's map
@@ -1062,7 +1097,7 @@ class DecoderFn(torch.autograd.Function):
                 kn_all = [_k_norm_cross(rt, kv_all[l], P) for l, P in enumerate(blocks)]
         for i, P in enumerate(blocks):
             x, entry, ln1 = _dec_block_fwd(rt, x, ctxf, P, batch, n, grad, cls_tail and i == rt.c_depth - 1, index=i, ln1=ln1,
-                                           next_ln=_norm1_of(blocks, i + 1), kv3=kv_all[i].view(b1, rt.n1, 2 * d) if fold else None,
+                                           next_ln=_norm1_of(blocks, i + 1), kv3=kv_all[i].view(b1, nc, 2 * d) if fold else None,
                                            scales=drop.block(i) if drop is not None else (None, None, None), seg=seg,
                                            kn=kn_all[i] if kn_all is not None else None)
             if grad:
@@ -1079,12 +1114,12 @@ class DecoderFn(torch.autograd.Function):
             ctx.feats_needs_grad = feats.requires_grad
             ctx.fold = (kv_all, kv_saved, fold_bufs) if fold else None
             ctx.drop = drop
-            ctx.seg = seg
+            ctx.seg, ctx.n, ctx.nc, ctx.keep = seg, n, nc, keep
         return logits
 
     @staticmethod
     def backward(ctx, dlogits):
-        rt, batch, n, d = ctx.rt, ctx.batch, ctx.rt.n2, ctx.rt.dim
+        rt, batch, n, nc, d = ctx.rt, ctx.batch, ctx.n, ctx.nc, ctx.rt.dim      # n, nc: the call's image-2 and context token counts
         shared, blocks = ctx.params
         xcls, y, mN, rN = ctx.final
         # head: logits = y Wh^T + bh
@@ -1132,7 +1167,7 @@ class DecoderFn(torch.autograd.Function):
                     with dwg.block():
                         dx, dx_lp, dctx, gblocks[i] = _dec_block_bwd(rt, dx, dx_lp, ctx.ctxf, dctx, blocks[i], entry, batch, n,
                                                                      ctx.cls_tail and i == rt.c_depth - 1, i,
-                                                                     dkv3=dkv_all[i].view(b1, rt.n1, 2 * d) if dkv_all is not None else None,
+                                                                     dkv3=dkv_all[i].view(b1, nc, 2 * d) if dkv_all is not None else None,
                                                                      lp_scales=(scale_of(i, 1), scale_of(i, 0), scale_of(i - 1, 2)), seg=seg)
                     if rt.tap is not None:
                         rt.tap[f'dec.dx.{i}'] = dx.clone()      # gradient w.r.t. the INPUT of decoder block i
@@ -1142,7 +1177,7 @@ class DecoderFn(torch.autograd.Function):
                 dctx, kv_grads = _context_kv_folded_bwd(rt, dkv_all, ctx.ctxf, ctx.fold[1], ctx.fold[2], blocks)
                 gblocks = [g._replace(**kv) for g, kv in zip(gblocks, kv_grads)]
                 ctx.fold = None
-        gshared = DecShared(**_patch_tokens_bwd(rt, dx, ctx.patches, shared, with_cls=True, batch=batch), gN=dgN, bN=dbN, wh=dwh, bh=dbh)
-        dfeats = dctx.view(b1, rt.n1, d) if ctx.feats_needs_grad and dctx is not None else None
-        ctx.tape = ctx.patches = ctx.ctxf = ctx.final = ctx.drop = ctx.seg = None
+        gshared = DecShared(**_patch_tokens_bwd(rt, dx, ctx.patches, shared, with_cls=True, batch=batch, keep=ctx.keep), gN=dgN, bN=dbN, wh=dwh, bh=dbh)
+        dfeats = dctx.view(b1, nc, d) if ctx.feats_needs_grad and dctx is not None else None
+        ctx.tape = ctx.patches = ctx.ctxf = ctx.final = ctx.drop = ctx.seg = ctx.keep = None
         return (None, dfeats, None, None, None, *_cam_only(rt, flatten_params(gshared, gblocks)))

@@ -15,6 +15,10 @@ Drop-in surface kept:
     cross-attention, with the reference's ``state_dict`` keys (``*.attn.q_norm.weight`` ...); a HIP kernel of its own between the
     projection and the attention kernels.  Off by default: no such module, key or launch exists then.
 
+  * ``patch_drop_rate``: timm PatchDropout as the reference constructs it (prob, num_prefix_tokens=1, ordered=False) - in training mode
+    a random subset of the patch tokens of each image is embedded and runs through the blocks; the others are never read
+    (``draw_patch_keep`` / ``forward(..., patch_keep=...)`` / ``last_patch_keep``).  Off by default.
+
 Precision follows the caller exactly like the reference follows ``torch.cuda.amp.autocast``
 (misc/engine.py:208): inside an autocast region the bf16 MFMA kernels run, outside it the fp32
 kernels run; ``model.compute_dtype = torch.bfloat16 | torch.float32`` pins it.
@@ -40,6 +44,21 @@ LN_EPS = F_.LN_EPS
 # [c_depth, 3, B] for the (self, cross, mlp) branches of every decoder block; each value 0 (the sample skips the branch) or
 # 1 / keep.  Either field may be None for a call that runs only the other half.
 DropPathScales = namedtuple('DropPathScales', 'enc dec')
+
+# Patch-dropout keep indices of one forward (timm PatchDropout): int32 / int64 tables, per sample the token
+# indices that argsort(randn)[:, :K] kept, counted behind the prefix slot, in keep order, distinct within a row.
+#   x1 [B1, K1]: the image-1 path has no cls token, so the prefix slot falls on patch 0, which is always kept: the encoder runs on
+#                patch 0 followed by the patches 1 + x1[b, :] - 1 + K1 tokens.
+#   x2 [B2, K2]: the prefix is the cls token: the decoder runs on cls followed by the patches x2[b, :] - 1 + K2 tokens; one row per
+#                pair of the call.
+# Either field may be None for a call that does not run that half.
+PatchKeep = namedtuple('PatchKeep', 'x1 x2')
+
+
+def patch_keep_count(tokens: int, rate: float) -> int:
+    """How many of ``tokens`` tokens behind the prefix timm's PatchDropout keeps: max(1, int(L * (1. - p))), in Python float
+    arithmetic as timm writes it."""
+    return max(1, int(tokens * (1. - rate)))
 
 
 class _Holder(nn.Module):
@@ -173,11 +192,14 @@ def _get(module, dotted):
 class VisionTransformerCustom(nn.Module):
     def __init__(self, img_size=224, patch_size=16, in_chans=3, num_classes=1000, embed_dim=768, depth=12, c_depth=12,
                  num_heads=12, mlp_ratio=4., qkv_bias=True, keep_attn=False, arch_version='v1', compute_dtype=None,
-                 drop_path_rate=0., qk_norm=False, **unsupported):
+                 drop_path_rate=0., qk_norm=False, patch_drop_rate=0., **unsupported):
         super().__init__()
         drop_path_rate = float(drop_path_rate or 0.)
         if not 0. <= drop_path_rate < 1.:
             raise ValueError(f'drop_path_rate={drop_path_rate}: stochastic depth takes a rate in [0, 1)')
+        patch_drop_rate = float(patch_drop_rate or 0.)
+        if not 0. <= patch_drop_rate < 1.:
+            raise ValueError(f'patch_drop_rate={patch_drop_rate}: patch dropout takes a rate in [0, 1)')
         live = {k: v for k, v in unsupported.items() if v not in (None, False, 0, 0., '', 'token')}
         if live:
             raise NotImplementedError(f'options outside the shipped pjs configs are not on the HIP hot path: {sorted(live)}')
@@ -210,6 +232,10 @@ class VisionTransformerCustom(nn.Module):
         self.drop_path_generator = None     # torch.Generator of the draws in training mode (None: the device's default generator)
         self.last_drop_path = None          # DropPathScales of the latest forward (None: it ran without stochastic depth)
         self._keep_cache = {}
+        # patch dropout (timm PatchDropout(prob, num_prefix_tokens=1, ordered=False)): no parameters either
+        self.patch_drop_rate = patch_drop_rate
+        self.patch_drop_generator = None    # torch.Generator of the keys in training mode (None: the device's default generator)
+        self.last_patch_keep = None         # PatchKeep of the latest forward (None: it ran on every patch)
         # uint8 inputs are normalised inside the patch-embedding kernel: ToTensor + Normalize(0.5, 0.5) of data/transforms.py:14-18
         self.input_mean, self.input_std = (0.5,) * in_chans, (0.5,) * in_chans
         hidden = int(embed_dim * mlp_ratio)
@@ -352,22 +378,78 @@ class VisionTransformerCustom(nn.Module):
         self.last_drop_path = DropPathScales(used.enc if batch_enc is not None else prev.enc, used.dec if batch_dec is not None else prev.dec)
         return used.enc, used.dec, live
 
-    def _run_fn(self, fn, drop, *args):
+    # -- patch dropout ------------------------------------------------------------------------
+    @property
+    def patch_keep_counts(self):
+        """(K1, K2): the columns of PatchKeep.x1 / .x2 at the model's rate - the image-1 path keeps K1 of its n1 - 1 patches behind
+        patch 0, the image-2 path K2 of its n1 patches behind the cls token (the streams then hold 1 + K1 and 1 + K2 tokens)."""
+        n1 = self.patch_embed.num_patches
+        if n1 < 2:
+            raise ValueError('patch dropout needs at least 2 patches per image: on the image-1 path patch 0 takes the prefix slot')
+        return patch_keep_count(n1 - 1, self.patch_drop_rate), patch_keep_count(n1, self.patch_drop_rate)
+
+    def draw_patch_keep(self, batch_x1, batch_x2, generator=None, device=None):
+        """Draw the keep indices of one forward as timm does: PatchKeep(x1 [batch_x1, K1], x2 [batch_x2, K2]) with
+        row = argsort(randn(L))[:K], independently per sample and per half; a batch of None leaves that field None.  On the GPU
+        the keys are torch's randn and the K smallest of every row come from one ranking kernel (ops.keep_from_keys; int32, no host
+        read: capturable); on the CPU plain torch.argsort(stable=True) (int64)."""
+        device = torch.device(device) if device is not None else self.pos_embed.device
+        if generator is not None and device.type == 'cuda' and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('patch-dropout draws inside a graph capture use the device\'s default generator (torch registers it with '
+                               'the graph, so every replay draws anew); a custom generator would freeze one set of indices into the graph')
+        n1 = self.patch_embed.num_patches
+        out = []
+        for batch, tokens, k in zip((batch_x1, batch_x2), (n1 - 1, n1), self.patch_keep_counts):
+            if batch is None:
+                out.append(None)
+                continue
+            keys = torch.randn(int(batch), tokens, generator=generator, device=device if generator is None else generator.device).to(device)
+            out.append(ops.keep_from_keys(keys, k) if device.type == 'cuda' else torch.argsort(keys, dim=-1, stable=True)[:, :k])
+        return PatchKeep(*out)
+
+    def _resolve_patch_keep(self, patch_keep, batch_x1, batch_x2, device):
+        """What a forward passes on to the Functions: (x1 table | None, x2 table | None) or None.  Explicit tables hold in any mode;
+        otherwise training mode with a live rate draws - never under keep_attn / keep_cam, whose maps are over all patches."""
+        if patch_keep is not None:
+            used = PatchKeep(patch_keep[0] if batch_x1 is not None else None, patch_keep[1] if batch_x2 is not None else None)
+        elif self.training and self.patch_drop_rate > 0. and not (self.keep_attn or self.keep_cam):
+            used = self.draw_patch_keep(batch_x1, batch_x2, generator=self.patch_drop_generator, device=device)
+        else:
+            self.last_patch_keep = None
+            return None
+        n1 = self.patch_embed.num_patches
+        for name, t, b, tokens in (('x1', used.x1, batch_x1, n1 - 1), ('x2', used.x2, batch_x2, n1)):
+            if b is None:
+                continue
+            if t is None:
+                raise ValueError(f'patch_keep.{name} is missing for a call that runs that half of the model')
+            if (not torch.is_tensor(t) or t.dtype not in (torch.int32, torch.int64) or t.dim() != 2 or t.shape[0] != b
+                    or not 1 <= t.shape[1] <= tokens or t.device != device):
+                got = f'{t.dtype} {tuple(t.shape)} on {t.device}' if torch.is_tensor(t) else type(t).__name__
+                raise ValueError(f'patch_keep.{name}: expected int32 / int64 [{b}, 1..{tokens}] on {device}, got {got}')
+        # a two-stage step is two calls: each records its half and leaves the other call's half in place
+        prev = self.last_patch_keep or PatchKeep(None, None)
+        self.last_patch_keep = PatchKeep(used.x1 if batch_x1 is not None else prev.x1, used.x2 if batch_x2 is not None else prev.x2)
+        return used.x1, used.x2
+
+    def _run_fn(self, fn, drop, keep, *args):
         rt = self.runtime()
-        rt.drop_path = drop
+        rt.drop_path, rt.patch_keep = drop, keep
         try:
             return fn.apply(rt, *args)
         finally:
-            rt.drop_path = None
+            rt.drop_path = rt.patch_keep = None
 
     # -- the reference's forward surface -----------------------------------------------------
-    def forward_first_part(self, x1, drop_path=None):
+    def forward_first_part(self, x1, drop_path=None, patch_keep=None):
+        """[B, N1, D] features; under patch dropout [B, 1 + K1, D] in keep order (patch 0 first), as the reference returns them."""
         self._check_images(x1)
-        return self._encode(x1, self._resolve_drop_path(drop_path, x1.shape[0], None, x1.device))
+        return self._encode(x1, self._resolve_drop_path(drop_path, x1.shape[0], None, x1.device),
+                            self._resolve_patch_keep(patch_keep, x1.shape[0], None, x1.device))
 
-    def _encode(self, x1, drop):
-        """The encoder with what ``_resolve_drop_path`` returned."""
-        return self._run_fn(F_.EncoderFn, drop, x1, *self._encoder_params())
+    def _encode(self, x1, drop, keep=None):
+        """The encoder with what ``_resolve_drop_path`` and ``_resolve_patch_keep`` returned."""
+        return self._run_fn(F_.EncoderFn, drop, keep, x1, *self._encoder_params())
 
     supports_x2_index = True   # engine.pairwise_similarity gathers image-2 rows inside the patch-embed kernel
 
@@ -403,17 +485,18 @@ class VisionTransformerCustom(nn.Module):
             raise ValueError(f'x1_index names {seg.index.numel()} pairs, the image-2 side {pairs}')
         return seg
 
-    def forward_second_part_head(self, x1_feats, x2, x2_index=None, drop_path=None, x1_index=None):
+    def forward_second_part_head(self, x1_feats, x2, x2_index=None, drop_path=None, x1_index=None, patch_keep=None):
         """``x1_index`` (int64 [P] or ``ops.PairSegments``): ``x1_feats`` holds one item per IMAGE and pair p reads
         x1_feats[x1_index[p]] - == self(x1_feats[x1_index], x2[x2_index]) (hisfrag.py:153-159) without the two gathers and with
         norm_context + the kv projections once per image; under autograd and under no_grad.  Returns [P, C] logits."""
         x2_index, pairs = self._check_x2(x2, x2_index, indexed_features=x1_index is not None)
         x1_index = self._check_x1(x1_feats, x1_index, pairs)
-        return self._decode_head(x1_feats, x2, x2_index, self._resolve_drop_path(drop_path, None, pairs, x2.device), x1_index)
+        return self._decode_head(x1_feats, x2, x2_index, self._resolve_drop_path(drop_path, None, pairs, x2.device), x1_index,
+                                 self._resolve_patch_keep(patch_keep, None, pairs, x2.device))
 
-    def _decode_head(self, x1_feats, x2, x2_index, drop, x1_index=None):
-        """The decoder and head with what ``_resolve_drop_path`` returned."""
-        return self._run_fn(F_.DecoderFn, drop, x1_feats, x2, x2_index, x1_index, *self._decoder_params())
+    def _decode_head(self, x1_feats, x2, x2_index, drop, x1_index=None, keep=None):
+        """The decoder and head with what ``_resolve_drop_path`` and ``_resolve_patch_keep`` returned."""
+        return self._run_fn(F_.DecoderFn, drop, keep, x1_feats, x2, x2_index, x1_index, *self._decoder_params())
 
     # -- pair-cached inference (engine.pairwise_similarity; SURVEY.md section 8(f) rank 2) ---------------------------------
     supports_pair_cache = True
@@ -438,24 +521,28 @@ class VisionTransformerCustom(nn.Module):
         i_idx = i_idx.to(device=dev, dtype=torch.int64).contiguous()
         return F_.decoder_cached(self.runtime(), tokens2, j_idx, kvs, i_idx, self._decoder_params(), q0)
 
-    def forward(self, x, x2=None, forward_first_part=False, x2_index=None, drop_path=None, x1_index=None):
+    def forward(self, x, x2=None, forward_first_part=False, x2_index=None, drop_path=None, x1_index=None, patch_keep=None):
         """``drop_path``: explicit DropPathScales for this call (any mode; tests, reproducing a step).  None: training mode with a
         live ``drop_path_rate`` draws them for the batch of the call - the images of ``forward_first_part``, the pairs of
         ``(feats, x2)``, the B pairs of a one-shot call for both halves - and ``eval()`` or rate 0 runs without.  The scales used
-        are kept in ``last_drop_path``."""
+        are kept in ``last_drop_path``.
+        ``patch_keep``: explicit PatchKeep indices for this call (any mode).  None: training mode with a live ``patch_drop_rate``
+        draws them - one set per image of ``forward_first_part``, one per pair of ``(feats, x2)``, both for a one-shot call - and
+        ``eval()``, rate 0, ``keep_attn`` and ``keep_cam`` run on every patch.  The indices used are kept in ``last_patch_keep``."""
         if forward_first_part:
-            return self.forward_first_part(x, drop_path)
+            return self.forward_first_part(x, drop_path, patch_keep)
         if x2 is not None:
-            return self.forward_second_part_head(x, x2, x2_index, drop_path, x1_index)
+            return self.forward_second_part_head(x, x2, x2_index, drop_path, x1_index, patch_keep)
         if x1_index is not None:
             raise ValueError('x1_index belongs to the two-stage form model(feats, x2, x1_index=...)')
         if x.dim() != 5 or x.shape[1] != 2:
             raise AssertionError(f'expected stacked pairs [B, 2, C, S, S], got {tuple(x.shape)}')
         drop = self._resolve_drop_path(drop_path, x.shape[0], x.shape[0], x.device)
+        keep = self._resolve_patch_keep(patch_keep, x.shape[0], x.shape[0], x.device)
         x1, x2 = x[:, 0], x[:, 1]                                           # strided views: the kernels take a batch stride
         self._check_images(x1)
         self._check_images(x2)
-        return self._decode_head(self._encode(x1, drop), x2, None, drop)
+        return self._decode_head(self._encode(x1, drop, keep), x2, None, drop, keep=keep)
 
     def flops_parts(self):
         """Algorithmic forward FLOPs (2MNK per contraction) of (the encoder on ONE image incl. its

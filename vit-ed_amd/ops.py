@@ -1294,3 +1294,8 @@ def cls_metrics_update(logits: torch.Tensor, targets: torch.Tensor, meters: torc
     ld = lambda t: t.stride(0) if b > 1 else c
     _lib.call('vited_cls_metrics_update', _ptr(logits), ld(logits), _ptr(targets), ld(targets), b, c, _ptr(meters), _ptr(last), _ptr(bad),
               _stream())
+
+
+# ---- patch dropout: the wrappers of csrc/patch_keep.hip live in ops_patchdrop.py, on this module's checker and call path ------------
+from .ops_patchdrop import (MAX_KEEP_KEYS, keep_from_keys, keep_inverse, patchify_kept, tokens_kept,  # noqa: E402,F401
+                            tokens_kept_bwd)
