@@ -72,7 +72,7 @@ def main():
     adamw.bind_flat(flat_a, model_a)
     forms['flat_adamw'] = lambda: adamw.step_flat(5.0)
     forms = {name: forms[name] for name in args.forms.split(',') if name in forms}
-    shadows = sum(len(rt._shadow) for rt in model_a._runtimes.values())
+    shadows = sum(len(cache) for cache in v.functions.shadows_of(model_a))
     assert shadows > 0, 'no bf16 weight shadows: the probe would not measure their refresh'
 
     for f in forms.values():                                 # warm-up

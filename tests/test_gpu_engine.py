@@ -538,19 +538,17 @@ def test_graphs_are_recaptured_when_the_shadow_set_changes(vited, gpu):
     assert steps[1]._g_opt is not None and steps[1].recaptures == 0
     rt = models[1].runtime(torch.bfloat16)
     w = models[1].blocks[0].mlp.fc1.weight
-    before = {k: v[2].data_ptr() for k, v in rt._shadow.items() if k[0] == id(w)}
-    assert set(t for _, t in before) == {'n', 't'}
-    for k in before:
-        old = rt._shadow.pop(k)
-        rt._retired.append(old[2])
+    before = {tag: buf.data_ptr() for tag, buf in rt.shadows.buffers()[id(w)].items()}
+    assert set(before) == {'n', 't'}
+    rt.shadows.discard(w)           # (pinned by the capture: the old buffers are retired, not freed)
     rt.weight(w), rt.weight_t(w)
-    after = {k: v[2].data_ptr() for k, v in rt._shadow.items() if k[0] == id(w)}
+    after = {tag: buf.data_ptr() for tag, buf in rt.shadows.buffers()[id(w)].items()}
     assert all(after[k] != before[k] for k in before)
     run(1)
     assert steps[1].recaptures == 1 and steps[1]._g1 is None, 'the changed shadow set must drop the graphs (this step ran eagerly)'
     # the update refreshed the NEW buffers: they hold the current weights
-    assert torch.equal(rt._shadow[(id(w), 'n')][2], w.detach().to(torch.bfloat16))
-    assert torch.equal(rt._shadow[(id(w), 't')][2], w.detach().t().contiguous().to(torch.bfloat16))
+    assert torch.equal(rt.shadows.buffers()[id(w)]['n'], w.detach().to(torch.bfloat16))
+    assert torch.equal(rt.shadows.buffers()[id(w)]['t'], w.detach().t().contiguous().to(torch.bfloat16))
     run(3)
     assert steps[1].recaptures == 1 and steps[1]._g1 is not None, 'graphs are captured again and replayed'
     for (n, pe), (_, pg) in zip(models[0].named_parameters(), models[1].named_parameters()):

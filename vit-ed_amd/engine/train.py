@@ -6,6 +6,7 @@ import torch
 import torch.distributed as dist
 
 from .. import ops
+from ..functions import shadows_of
 from .distributed import FlatGradients
 from .metrics import MeterValue
 
@@ -316,11 +317,11 @@ class TrainStep:
         return norm
 
     def _refresh_shadows(self):
-        rts = getattr(self.model, '_runtimes', None)
-        if rts:
+        caches = shadows_of(self.model)
+        if caches:
             params = list(self.model.parameters())
-            for rt in rts.values():
-                rt.refresh_shadows(params)
+            for cache in caches:
+                cache.refresh(params)
 
     def _after_update(self):
         # misc/engine.py:228: lr_scheduler.step_update((epoch * num_steps + idx) // ACCUMULATION_STEPS) runs AFTER the update of
@@ -402,8 +403,8 @@ class TrainStep:
         self._sync_lr()
         torch.cuda.synchronize()
         ops.pin_workspace()               # captured kernels bake buffer addresses in: later growth must not free them
-        for rt in getattr(self.model, '_runtimes', {}).values():
-            rt.pinned = True
+        for cache in shadows_of(self.model):
+            cache.pin()
         split = self.split and torch.is_tensor(x) and x.dim() == 5
         self._g1 = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self._g1, capture_error_mode=_CAPTURE_MODE):

@@ -22,6 +22,7 @@ import torch
 
 from . import ops
 from ._lib import (B_KN, B_NK, EPI_GELU_GRAD, EPI_MUL, EPI_RESIDUAL, EPI_STORE, EPI_STORE_F32)
+from .shadows import WeightShadows
 
 LN_EPS = 1e-6  # partial(nn.LayerNorm, eps=1e-6), vision_transformer.py:348
 
@@ -118,15 +119,9 @@ class Runtime:
         self.fold_context = os.environ.get('VITED_FOLD_CONTEXT', '1') != '0'   # norm_context + kv of all decoder blocks as one GEMM
         self._fold_bufs = None      # (folded W [L 2D, D], its transpose, folded bias): refreshed in place every forward
         self._unit_ln = None        # (ones, zeros) for the affine-free LayerNorm of the features
-        self.drop_path = None       # (encoder scales fp32 [depth, 2, B] | None, decoder scales fp32 [c_depth, 3, B] | None, (live encoder
-                                    # branches, live decoder branches)): set by the model around a call, read by the Functions' forward
-        self.patch_keep = None      # (image-1 keep table int32 [B1, K1] | None, image-2 table [B2, K2] | None): patch dropout of this call, set by
-                                    # the model around it
         self.tap = None             # test/diagnostic: a dict that receives clones of per-block activations and gradients
         self.block_events = None    # measurement (bench.py): a list that receives (kind, block, 'fwd' | 'bwd', start event, end event)
-        self.pinned = False         # a captured hipGraph reads the shadow buffers: never free one, only refresh in place
-        self._retired = []
-        self._shadow = {}
+        self.shadows = WeightShadows()   # the bf16 copies of the weights, and what a captured hipGraph needs kept alive
         if not self.exact:
             _install_optimizer_step_hook()
 
@@ -139,7 +134,7 @@ class Runtime:
         w2 = w.detach().reshape(w.shape[0], -1)
         if self.exact:
             return w2
-        return self._cached(w, 'n', lambda out=None: ops.cast(w2, self.act_dtype, out=out))
+        return self.shadows.get(w, 'n', lambda out=None: ops.cast(w2, self.act_dtype, out=out))
 
     def weight_t(self, w: torch.Tensor):
         """Operand + layout of the input-gradient GEMM dX = dY . W: the transposed bf16 shadow (NT
@@ -147,45 +142,15 @@ class Runtime:
         w2 = w.detach().reshape(w.shape[0], -1)
         if self.exact:
             return w2, B_KN
-        return self._cached(w, 't', lambda out=None: ops.cast_transpose(w2.contiguous(), self.act_dtype, out=out)), B_NK
-
-    def _cached(self, w, tag, make):
-        key = (id(w), tag)
-        ent = self._shadow.get(key)
-        if ent is None or ent[0] != w._version or ent[1] != w.data_ptr():
-            if ent is not None and ent[1] == w.data_ptr():
-                # refresh IN PLACE: a captured graph keeps reading the same shadow buffer
-                ent = (w._version, w.data_ptr(), make(ent[2]))
-            else:
-                if ent is not None and self.pinned:
-                    self._retired.append(ent[2])     # the graph still reads the old buffer: keep it alive
-                ent = (w._version, w.data_ptr(), make())
-            self._shadow[key] = ent
-        return ent[2]
+        return self.shadows.get(w, 't', lambda out=None: ops.cast_transpose(w2.contiguous(), self.act_dtype, out=out)), B_NK
 
     def refresh_shadows(self, params):
-        """Recast every cached shadow in place with ONE multi-tensor launch (call after an optimizer step when
-        replaying a graph: the captured kernels keep reading the same shadow buffers)."""
-        by_id = {id(p): p for p in params}
-        per_param = {}
-        for (pid, tag), ent in self._shadow.items():
-            if pid in by_id:
-                per_param.setdefault(pid, {})[tag] = ent[2]
-        entries = []
-        for pid, tags in per_param.items():
-            p = by_id[pid]
-            entries.append((p.detach().reshape(p.shape[0], -1), tags.get('n'), tags.get('t')))
-        if not entries:
-            return
-        key = tuple((w.data_ptr(), 0 if n is None else n.data_ptr(), 0 if t is None else t.data_ptr()) for w, n, t in entries)
-        plan = getattr(self, '_shadow_plan', None)
-        if plan is None or plan.key != key:
-            plan = self._shadow_plan = ops.WeightShadowPlan(entries)
-        plan.run()
-        for pid, tags in per_param.items():
-            p = by_id[pid]
-            for tag, buf in tags.items():
-                self._shadow[(pid, tag)] = (p._version, p.data_ptr(), buf)
+        self.shadows.refresh(params)
+
+
+def shadows_of(model):
+    """The WeightShadows of every Runtime of ``model`` (anything with a ``_runtimes`` dict; none without one)."""
+    return [rt.shadows for rt in getattr(model, '_runtimes', {}).values()]
 
 
 class _BlockSpan:
@@ -240,9 +205,10 @@ class _DropRows:
         return tuple(self.get(i, j) for j in range(self.per_sample.shape[1]))
 
 
-def _take_drop_rows(rt, which, nblk, nbr, batch, n, device, cls_block=None):
-    """The _DropRows of this call from ``rt.drop_path`` (None: no stochastic depth in this call)."""
-    dp = rt.drop_path
+def _take_drop_rows(dp, which, nblk, nbr, batch, n, device, cls_block=None):
+    """The _DropRows of half ``which`` (0: encoder, 1: decoder) of this call from the Function's ``drop_path`` argument = (encoder scales
+    fp32 [depth, 2, B] | None, decoder scales fp32 [c_depth, 3, B] | None, (live encoder branches, live decoder branches)) as
+    model._resolve_drop_path returns it; None: no stochastic depth in this call."""
     if dp is None or dp[which] is None:
         return None
     scales, live = dp[which], dp[2][which]
@@ -476,36 +442,40 @@ def _cam_only(rt, grads):
 
 
 _QKN_FIELDS = ('gqn', 'bqn', 'gkn', 'bkn')
+# what a self-attention's q/k-norm saves: the normalised q [batch, nq, D] and k [batch, n, D] as the attention read them (two views
+# of one buffer; buffers of their own when cls_only) and the two norms' statistics
+QkNormSaved = namedtuple('QkNormSaved', 'qn kn sq sk')
 
 
 def _qk_norm_self(rt, qkv, P, batch, n, cls_only=False):
     """q_norm / k_norm of a self-attention on the packed projection qkv [batch n, 3D] (vision_transformer.py:60): the pre-norm q / k
     stay where the GEMM wrote them (the backward recomputes xhat from them), the normalised ones go to a buffer of their own that
     the attention kernels read.  ``cls_only``: the query is row 0 of every sample alone.
-    Returns (q view [batch, nq, D], k view [batch, n, D], saved = (normalised buffers, q statistics, k statistics))."""
+    Returns (q view [batch, nq, D], k view [batch, n, D], a QkNormSaved whose qn / kn are these two views)."""
     d = rt.dim
     if cls_only:
         qn = torch.empty((batch, d), dtype=qkv.dtype, device=qkv.device)
         kn = torch.empty((batch * n, d), dtype=qkv.dtype, device=qkv.device)
         _, _, sq, sk = ops.qk_norm_fwd(qkv.view(batch, n * 3 * d)[:, 0:d], qkv[:, d:2 * d], P.gqn, P.bqn, P.gkn, P.bkn, rt.heads, LN_EPS,
                                        out=(qn, kn))
-        return qn.view(batch, 1, d), kn.view(batch, n, d), ((qn, kn), sq, sk)
-    qk = torch.empty((batch * n, 2 * d), dtype=qkv.dtype, device=qkv.device)
-    _, _, sq, sk = ops.qk_norm_fwd(qkv[:, 0:d], qkv[:, d:2 * d], P.gqn, P.bqn, P.gkn, P.bkn, rt.heads, LN_EPS,
-                                   out=(qk[:, 0:d], qk[:, d:2 * d]))
-    qk3 = qk.view(batch, n, 2 * d)
-    return qk3[:, :, 0:d], qk3[:, :, d:2 * d], (qk, sq, sk)
+        q3, k3 = qn.view(batch, 1, d), kn.view(batch, n, d)
+    else:
+        qk = torch.empty((batch * n, 2 * d), dtype=qkv.dtype, device=qkv.device)
+        _, _, sq, sk = ops.qk_norm_fwd(qkv[:, 0:d], qkv[:, d:2 * d], P.gqn, P.bqn, P.gkn, P.bkn, rt.heads, LN_EPS,
+                                       out=(qk[:, 0:d], qk[:, d:2 * d]))
+        qk3 = qk.view(batch, n, 2 * d)
+        q3, k3 = qk3[:, :, 0:d], qk3[:, :, d:2 * d]
+    return q3, k3, QkNormSaved(q3, k3, sq, sk)
 
 
 def _qk_norm_self_bwd(rt, dqkv, qkv, P, qkn, batch, n, cls_only=False):
     """Backward of _qk_norm_self, in place on the q and k columns of dqkv (they then are the gradient of the qkv projection's output).
     Returns the four norm-parameter gradients by field name - None when accumulated in place."""
     d = rt.dim
-    _, sq, sk = qkn
     rows = (lambda t: t.view(batch, n * 3 * d)[:, 0:d]) if cls_only else (lambda t: t[:, 0:d])
     targets = [_gtarget(rt, p) for p in (P.gqn, P.bqn, P.gkn, P.bkn)]
     direct = all(t is not None for t in targets)
-    got = ops.qk_norm_bwd(rows(dqkv), rows(qkv), sq, P.gqn, dqkv[:, d:2 * d], qkv[:, d:2 * d], sk, P.gkn, rt.heads,
+    got = ops.qk_norm_bwd(rows(dqkv), rows(qkv), qkn.sq, P.gqn, dqkv[:, d:2 * d], qkv[:, d:2 * d], qkn.sk, P.gkn, rt.heads,
                           *(targets if direct else ()))
     return dict.fromkeys(_QKN_FIELDS) if direct else dict(zip(_QKN_FIELDS, got))
 
@@ -530,8 +500,7 @@ def _self_attn_bwd(rt, do, qkv, o, lse, batch, n, key=None, P=None, qkn=None):
     qkv3 = qkv.view(batch, n, 3 * d)
     q3, k3 = qkv3[:, :, 0:d], qkv3[:, :, d:2 * d]
     if qkn is not None:                                 # the attention saw the normalised q / k
-        qk3 = qkn[0].view(batch, n, 2 * d)
-        q3, k3 = qk3[:, :, 0:d], qk3[:, :, d:2 * d]
+        q3, k3 = qkn.qn, qkn.kn
     if rt.keep_attn and key is not None:
         _keep_attention_grad(rt, key, do.view(batch, n, d), qkv3[:, :, 2 * d:3 * d])
     if rt.keep_cam and key is not None:
@@ -572,6 +541,11 @@ def _hand_over_ln(rt, x, P, grad):
     return grad or not _fused_mlp_rows(rt, x, P.w1, grad)
 
 
+# what a stage's forward saves for its backward
+MlpSaved = namedtuple('MlpSaved', 'mean rstd h gd u')                   # norm2's statistics and output, gelu'(z), gelu(z)
+AttnSaved = namedtuple('AttnSaved', 'mean rstd h qkv o lse qkn')        # norm1's ...; qkn: what _qk_norm_self saved | None
+
+
 def _mlp_fwd(rt, x, P, grad=True, ln=None, next_ln=None, scale=None):
     """x + fc2(gelu(fc1(LayerNorm(x)))) with the block's norm2 / mlp parameters (P: an EncBlock or a DecBlock).  ``ln`` = (h, mean,
     rstd) when the LayerNorm was already produced by the kernel that wrote x; ``next_ln`` = (gamma, beta) of the LayerNorm that
@@ -593,16 +567,16 @@ def _mlp_fwd(rt, x, P, grad=True, ln=None, next_ln=None, scale=None):
     # fc1 saves gelu'(z) and gelu(z) (one exponential serves both): the backward of the activation is then one multiply
     gd, u = ops.gemm(h, rt.weight(w1), epilogue=EPI_GELU_GRAD, bias=b1)
     y, nxt = _res_linear(rt, u, w2, b2, x, next_ln, scale)
-    return y, (mean, rstd, h, gd, u), nxt
+    return y, MlpSaved(mean, rstd, h, gd, u), nxt
 
 
 def _mlp_bwd(rt, dy, dy_lp, x, P, saved, lp_scale=None):
     """Backward of _mlp_fwd.  Under stochastic depth ``dy_lp`` arrives scaled by this branch's scale (so everything inside the branch
     sees s dy, the residual path dy) and ``lp_scale`` is the scale of the branch whose backward runs next: the returned copy carries it.
     Returns (dx, its low-precision copy, the six parameter gradients by field name)."""
-    mean, rstd, h, gd, u = saved
-    dz, dw2, dbb2 = _linear_bwd(rt, dy_lp, u, P.w2, P.bb2, aux=gd)
-    dx, dx_lp, dg2, db2, dw1, dbb1 = _linear_ln_bwd(rt, dz, h, P.w1, P.bb1, x, P.g2, P.b2, mean, rstd, dx_in=dy, lp_scale=lp_scale)
+    s = saved
+    dz, dw2, dbb2 = _linear_bwd(rt, dy_lp, s.u, P.w2, P.bb2, aux=s.gd)
+    dx, dx_lp, dg2, db2, dw1, dbb1 = _linear_ln_bwd(rt, dz, s.h, P.w1, P.bb1, x, P.g2, P.b2, s.mean, s.rstd, dx_in=dy, lp_scale=lp_scale)
     return dx, dx_lp, dict(g2=dg2, b2=db2, w1=dw1, bb1=dbb1, w2=dw2, bb2=dbb2)
 
 
@@ -612,22 +586,23 @@ def _attn_branch_fwd(rt, x, P, batch, n, key=None, ln=None, next_ln=None, scale=
     h, mean, rstd = ln if ln is not None else ops.layernorm_fwd(x, P.g1, P.b1, LN_EPS, rt.act_dtype)
     qkv, o, lse, qkn = _self_attn_fwd(rt, h, P, batch, n, key)
     y, nxt = _res_linear(rt, o, P.wproj, P.bproj, x, next_ln, scale)
-    return y, (mean, rstd, h, qkv, o, lse, qkn), nxt
+    return y, AttnSaved(mean, rstd, h, qkv, o, lse, qkn), nxt
 
 
 def _attn_branch_bwd(rt, dy, dy_lp, x, P, saved, batch, n, key=None, lp_scale=None):
     """Backward of _attn_branch_fwd (``lp_scale`` as in _mlp_bwd).  Returns (dx, its low-precision copy, the six parameter gradients by
     field name)."""
-    mean, rstd, h, qkv, o, lse, qkn = saved
-    do, dwproj, dbproj = _linear_bwd(rt, dy_lp, o, P.wproj, P.bproj)
-    dqkv, gn = _self_attn_bwd(rt, do, qkv, o, lse, batch, n, key, P, qkn)
-    dx, dx_lp, dg1, db1, dwqkv, dbqkv = _linear_ln_bwd(rt, dqkv, h, P.wqkv, P.bqkv, x, P.g1, P.b1, mean, rstd, dx_in=dy, lp_scale=lp_scale)
+    s = saved
+    do, dwproj, dbproj = _linear_bwd(rt, dy_lp, s.o, P.wproj, P.bproj)
+    dqkv, gn = _self_attn_bwd(rt, do, s.qkv, s.o, s.lse, batch, n, key, P, s.qkn)
+    dx, dx_lp, dg1, db1, dwqkv, dbqkv = _linear_ln_bwd(rt, dqkv, s.h, P.wqkv, P.bqkv, x, P.g1, P.b1, s.mean, s.rstd, dx_in=dy, lp_scale=lp_scale)
     return dx, dx_lp, dict(g1=dg1, b1=db1, wqkv=dwqkv, bqkv=dbqkv, wproj=dwproj, bproj=dbproj, **gn)
 
 
-def _take_patch_keep(rt, which):
-    """The keep table of this call's half (0: image 1, 1: image 2) from ``rt.patch_keep``; None: no patch dropout in this call."""
-    return rt.patch_keep[which] if rt.patch_keep is not None else None
+def _take_patch_keep(patch_keep, which):
+    """The keep table of this call's half (0: image 1, 1: image 2) from the Function's ``patch_keep`` argument = (image-1 table int32
+    [B1, K1] | None, image-2 table [B2, K2] | None) as model._resolve_patch_keep returns it; None: no patch dropout in this call."""
+    return patch_keep[which] if patch_keep is not None else None
 
 
 def _patch_tokens_fwd(rt, img, S, with_cls, batch_index=None, keep=None):
@@ -693,14 +668,20 @@ def _norm1_of(blocks, i):
 # ---------------------------------------------------------------------------------------------
 # encoder: forward_first_part (vision_transformer.py:382-388)
 # ---------------------------------------------------------------------------------------------
+# an encoder block's tape entry: the inputs of its two branches (x, xa) and what each saved (AttnSaved, MlpSaved)
+EncTape = namedtuple('EncTape', 'x sa xa sm')
+
+
 class EncoderFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, rt: Runtime, img, *params):
+    def forward(ctx, rt: Runtime, drop_path, patch_keep, img, *params):
+        """``drop_path`` / ``patch_keep``: this call's stochastic-depth scales and keep tables as the model resolved them (_take_drop_rows,
+        _take_patch_keep), or None."""
         shared, blocks = split_params(params, EncShared, rt.enc_block)
         grad = any(ctx.needs_input_grad)  # False under no_grad: nothing is saved for inference
-        keep = _take_patch_keep(rt, 0)
+        keep = _take_patch_keep(patch_keep, 0)
         x, patches, batch, n = _patch_tokens_fwd(rt, img, shared, with_cls=False, keep=keep)
-        drop = _take_drop_rows(rt, 0, len(blocks), 2, batch, n, x.device)      # stochastic depth: per-row scales of (attn, mlp) per block
+        drop = _take_drop_rows(drop_path, 0, len(blocks), 2, batch, n, x.device)      # stochastic depth: per-row scales of (attn, mlp) per block
         tape = []
         ln1 = None          # (h, mean, rstd) of this block's norm1 when the previous block's fc2 kernel already produced it
         for i, P in enumerate(blocks):
@@ -711,7 +692,7 @@ class EncoderFn(torch.autograd.Function):
                                                scale=s_attn)
                 xb, sm, ln1 = _mlp_fwd(rt, xa, P, grad, ln=ln2, next_ln=_norm1_of(blocks, i + 1) if chain else None, scale=s_mlp)
             if grad:
-                tape.append((x, sa, xa, sm))
+                tape.append(EncTape(x, sa, xa, sm))
             x = xb
             if rt.tap is not None:
                 rt.tap[f'enc.x.{len(tape) - 1 if grad else 0}'] = x.clone()
@@ -731,18 +712,18 @@ class EncoderFn(torch.autograd.Function):
         gblocks = [None] * len(blocks)
         with _ln_sums(rt), _DwBatch(rt, kind='enc') as dwg:      # the encoder's 2 x depth LayerNorm column sums
             for i in reversed(range(len(blocks))):
-                x, sa, xa, sm = ctx.tape[i]
+                t = ctx.tape[i]
                 ctx.tape[i] = None
                 with _BlockSpan(rt, 'enc', i, 'bwd'), dwg.block():
-                    dx, dx_lp, gm = _mlp_bwd(rt, dx, dx_lp, xa, blocks[i], sm, lp_scale=scale_of(i, 0))
-                    dx, dx_lp, ga = _attn_branch_bwd(rt, dx, dx_lp, x, blocks[i], sa, batch, n, key=('blocks', i, 'attn'),
+                    dx, dx_lp, gm = _mlp_bwd(rt, dx, dx_lp, t.xa, blocks[i], t.sm, lp_scale=scale_of(i, 0))
+                    dx, dx_lp, ga = _attn_branch_bwd(rt, dx, dx_lp, t.x, blocks[i], t.sa, batch, n, key=('blocks', i, 'attn'),
                                                      lp_scale=scale_of(i - 1, 1))
                 if rt.tap is not None:
                     rt.tap[f'enc.dx.{i}'] = dx.clone()      # gradient w.r.t. the INPUT of encoder block i
                 gblocks[i] = rt.enc_block(**ga, **gm)
         gshared = EncShared(**_patch_tokens_bwd(rt, dx, ctx.patches, shared, with_cls=False, batch=batch, keep=ctx.keep))
         ctx.tape = ctx.patches = ctx.drop = ctx.keep = None
-        return (None, None, *_cam_only(rt, flatten_params(gshared, gblocks)))
+        return (None, None, None, None, *_cam_only(rt, flatten_params(gshared, gblocks)))
 
 
 # ---------------------------------------------------------------------------------------------
@@ -779,7 +760,7 @@ def _dec_self_fwd(rt, x, P, batch, n, cls_only, key=None, ln1=None, fuse_ln=True
     o0 = o0.view(batch, d)
     x0 = _dense_rows(x.view(batch, n, d)[:, 0, :])
     xa, lnq = _res_linear(rt, o0, P.wproj, P.bproj, x0, next_ln, scale)
-    return xa, (m1, r1, h1, qkv, o0, lse0, qkn), lnq
+    return xa, AttnSaved(m1, r1, h1, qkv, o0, lse0, qkn), lnq
 
 
 def _dec_self_bwd(rt, dx, dx_lp, x, P, saved, batch, n, cls_only, key=None, lp_scale=None):
@@ -789,41 +770,48 @@ def _dec_self_bwd(rt, dx, dx_lp, x, P, saved, batch, n, cls_only, key=None, lp_s
     if not cls_only:
         return _attn_branch_bwd(rt, dx, dx_lp, x, P, saved, batch, n, key=key, lp_scale=lp_scale)
     d = rt.dim
-    m1, r1, h1, qkv, o0, lse0, qkn = saved
-    do0, dwproj, dbproj = _linear_bwd(rt, dx_lp, o0, P.wproj, P.bproj)
+    s, qkv, qkn = saved, saved.qkv, saved.qkn        # (o and lse: of query 0 alone)
+    do0, dwproj, dbproj = _linear_bwd(rt, dx_lp, s.o, P.wproj, P.bproj)
     qkv3 = qkv.view(batch, n, 3 * d)
     q0, k3 = qkv3[:, 0:1, 0:d], qkv3[:, :, d:2 * d]
     if qkn is not None:
-        q0, k3 = qkn[0][0].view(batch, 1, d), qkn[0][1].view(batch, n, d)
+        q0, k3 = qkn.qn, qkn.kn
     dqkv = torch.zeros_like(qkv)                 # d(q) of the rows that never queried is zero
     dqkv3 = dqkv.view(batch, n, 3 * d)
-    ops.attention_bwd(q0, k3, qkv3[:, :, 2 * d:3 * d], o0.view(batch, 1, d), do0.view(batch, 1, d),
-                      lse0, rt.heads, rt.scale, dqkv3[:, 0:1, 0:d], dqkv3[:, :, d:2 * d], dqkv3[:, :, 2 * d:3 * d])
+    ops.attention_bwd(q0, k3, qkv3[:, :, 2 * d:3 * d], s.o.view(batch, 1, d), do0.view(batch, 1, d),
+                      s.lse, rt.heads, rt.scale, dqkv3[:, 0:1, 0:d], dqkv3[:, :, d:2 * d], dqkv3[:, :, 2 * d:3 * d])
     gn = _qk_norm_self_bwd(rt, dqkv, qkv, P, qkn, batch, n, cls_only=True) if qkn is not None else {}
     dres = torch.zeros((batch * n, d), dtype=torch.float32, device=dx.device)   # the residual path carries gradient on the cls rows only
     dres.view(batch, n, d)[:, 0, :].copy_(dx)
-    dx, dx_lp, dg1, db1, dwqkv, dbqkv = _linear_ln_bwd(rt, dqkv, h1, P.wqkv, P.bqkv, x, P.g1, P.b1, m1, r1, dx_in=dres, lp_scale=lp_scale)
+    dx, dx_lp, dg1, db1, dwqkv, dbqkv = _linear_ln_bwd(rt, dqkv, s.h, P.wqkv, P.bqkv, x, P.g1, P.b1, s.mean, s.rstd, dx_in=dres, lp_scale=lp_scale)
     return dx, dx_lp, dict(g1=dg1, b1=db1, wqkv=dwqkv, bqkv=dbqkv, wproj=dwproj, bproj=dbproj, **gn)
+
+
+# a cross-attention's q/k-norm: a tensor beside the norm's statistics - ``qraw``: the PRE-norm queries, ``kn``: the NORMALISED keys
+Normed = namedtuple('Normed', 't stats')
+# what the cross stage saves: norm_cross's (mq, rq, hq), norm_context's (mc, rc, hc: None when the keys / values were computed ahead), q
+# as the attention read it, kv (``folded``: this block's view of _context_kv_folded's all-blocks tensor), the attention's output and lse
+CrossSaved = namedtuple('CrossSaved', 'mq rq hq mc rc hc q kv oc lse qraw kn folded')
 
 
 def _cross_q(rt, xa, P, lnq=None):
     """q = Linear_q(norm_cross(xa)) of the cross-attention (:176); ``lnq`` = (h, mean, rstd) of norm_cross(xa) when the self
     stage's proj kernel produced it.  Returns (q in the activation dtype as the attention reads it, (h, mean, rstd), qraw): with the
-    q/k-norm q is q_norm(Linear_q(...)) (:180) and ``qraw`` = (the pre-norm q, its statistics) for the backward, else qraw is None."""
+    q/k-norm q is q_norm(Linear_q(...)) (:180) and ``qraw`` = Normed(the pre-norm q, its statistics) for the backward, else None."""
     hq, mq, rq = lnq if lnq is not None else ops.layernorm_fwd(xa, P.gc, P.bc, LN_EPS, rt.act_dtype)
     q = ops.gemm(hq, rt.weight(P.wq), bias=P.bq)
     if not rt.qk_norm:
         return q, (hq, mq, rq), None
     qn, _, sq, _ = ops.qk_norm_fwd(q, None, P.gcqn, P.bcqn, None, None, rt.heads, LN_EPS)
-    return qn, (hq, mq, rq), (q, sq)
+    return qn, (hq, mq, rq), Normed(q, sq)
 
 
 def _k_norm_cross(rt, kv, P, in_place=False):
-    """k_norm of a cross-attention on the K half of kv [Mc, 2D] (:180).  Returns (normalised keys [Mc, D], their statistics); ``in_place``
-    (the inference caches: nothing is saved for a backward) writes them over the K half itself."""
+    """k_norm of a cross-attention on the K half of kv [Mc, 2D] (:180).  Returns Normed(normalised keys [Mc, D], their statistics);
+    ``in_place`` (the inference caches: nothing is saved for a backward) writes them over the K half itself."""
     k = kv[:, 0:rt.dim]
     _, kn, _, sk = ops.qk_norm_fwd(None, k, None, None, P.gckn, P.bckn, rt.heads, LN_EPS, out=(None, k) if in_place else None)
-    return kn, sk
+    return Normed(kn, sk)
 
 
 def _dec_cross_fwd(rt, xa, P, batch, lnq=None, q=None, kv3=None, ctxf=None, kv_index=None, key=None, fuse_ln=True, scale=None, items=None,
@@ -839,21 +827,21 @@ def _dec_cross_fwd(rt, xa, P, batch, lnq=None, q=None, kv3=None, ctxf=None, kv_i
     hq = mq = rq = hc = mc = rc = qraw = None
     if q is None:
         q, (hq, mq, rq), qraw = _cross_q(rt, xa, P, lnq)
-    kv = kv3                    # computed ahead: a view, nothing of norm_context is saved here
-    if kv3 is None:
+    kv, ahead = kv3, kv3 is not None       # computed ahead: a view, nothing of norm_context is saved here
+    if not ahead:
         hc, mc, rc = ops.layernorm_fwd(ctxf, P.gx, P.bx, LN_EPS, rt.act_dtype)
         kv = ops.gemm(hc, rt.weight(P.wkv), bias=P.bkv)              # [Mc, 2D], columns [2][h][hd] (:178)
         items = batch if items is None else items
         kv3 = kv.view(items, kv.shape[0] // items, 2 * d)      # the context's length is the call's: the features' token count
         if rt.qk_norm:
             kn = _k_norm_cross(rt, kv, P)
-    k3 = kv3[:, :, 0:d] if kn is None else kn[0].view(kv3.shape[0], kv3.shape[1], d)
+    k3 = kv3[:, :, 0:d] if kn is None else kn.t.view(kv3.shape[0], kv3.shape[1], d)
     oc, lse_c = ops.attention_fwd(q.view(batch, nq, d), k3, kv3[:, :, d:2 * d], rt.heads, rt.scale, kv_index=kv_index)
     if rt.keep_attn and key is not None:
         _keep_attention(rt, key, q.view(batch, nq, d), k3)
     oc = oc.view(batch * nq, d)
     xb, ln2 = _res_linear(rt, oc, P.wcp, P.bcp, xa, (P.g2, P.b2) if fuse_ln else None, scale)
-    return xb, (mq, rq, hq, mc, rc, hc, q, kv, oc, lse_c, qraw, kn), ln2
+    return xb, CrossSaved(mq, rq, hq, mc, rc, hc, q, kv, oc, lse_c, qraw, kn, folded=ahead), ln2
 
 
 def _dec_cross_bwd(rt, dx, dx_lp, xa, P, saved, ctxf, dctx, batch, index, dkv3=None, lp_scale=None, seg=None):
@@ -864,23 +852,22 @@ def _dec_cross_bwd(rt, dx, dx_lp, xa, P, saved, ctxf, dctx, batch, index, dkv3=N
     item the sum of its pairs' terms (ops.attention_bwd(segments=...)), and so is everything that follows it."""
     d, nq = rt.dim, xa.shape[0] // batch
     items = batch if seg is None else seg.items
-    mq, rq, hq, mc, rc, hc, q, kv, oc, lse_c, qraw, kn = saved
+    s, q, kv, oc, kn = saved, saved.q, saved.kv, saved.oc, saved.kn
     doc, dwcp, dbcp = _linear_bwd(rt, dx_lp, oc, P.wcp, P.bcp)
     dq = torch.empty_like(q)
-    folded = hc is None
-    if folded:
+    if s.folded:
         kv3, dkv = kv, dkv3                 # views of the all-blocks kv / d(kv) tensors
     else:
         dkv = torch.empty_like(kv)
         kv3, dkv3 = kv.view(items, kv.shape[0] // items, 2 * d), dkv.view(items, kv.shape[0] // items, 2 * d)
-    k3 = kv3[:, :, 0:d] if kn is None else kn[0].view(items, kv3.shape[1], d)       # what the attention read: the normalised keys
+    k3 = kv3[:, :, 0:d] if kn is None else kn.t.view(items, kv3.shape[1], d)       # what the attention read: the normalised keys
     if rt.keep_attn:
         _keep_attention_grad(rt, ('cross_blocks', index, 'cross_attn'), doc.view(batch, nq, d), kv3[:, :, d:2 * d])
     if rt.keep_cam:
         _keep_attention_cam(rt, ('cross_blocks', index, 'cross_attn'), q.view(batch, nq, d), k3, kv3[:, :, d:2 * d],
-                            doc.view(batch, nq, d), lse_c)
+                            doc.view(batch, nq, d), s.lse)
     ops.attention_bwd(q.view(batch, nq, d), k3, kv3[:, :, d:2 * d], oc.view(batch, nq, d),
-                      doc.view(batch, nq, d), lse_c, rt.heads, rt.scale, dq.view(batch, nq, d), dkv3[:, :, 0:d],
+                      doc.view(batch, nq, d), s.lse, rt.heads, rt.scale, dq.view(batch, nq, d), dkv3[:, :, 0:d],
                       dkv3[:, :, d:2 * d], segments=seg)
     if rt.tap is not None:
         i = index
@@ -893,16 +880,20 @@ def _dec_cross_bwd(rt, dx, dx_lp, xa, P, saved, ctxf, dctx, batch, index, dkv3=N
         fields = ('gcqn', 'bcqn', 'gckn', 'bckn')
         targets = [_gtarget(rt, getattr(P, f)) for f in fields]
         direct = all(t is not None for t in targets)
-        got = ops.qk_norm_bwd(dq, qraw[0], qraw[1], P.gcqn, dkv3.reshape(-1, 2 * d)[:, 0:d], kv3.reshape(-1, 2 * d)[:, 0:d], kn[1], P.gckn,
+        got = ops.qk_norm_bwd(dq, s.qraw.t, s.qraw.stats, P.gcqn, dkv3.reshape(-1, 2 * d)[:, 0:d], kv3.reshape(-1, 2 * d)[:, 0:d], kn.stats, P.gckn,
                               rt.heads, *(targets if direct else ()))
         gn = dict.fromkeys(fields) if direct else dict(zip(fields, got))
     # q = Linear(norm_cross(x')), kv = Linear(norm_context(features)): input-gradient GEMM + LayerNorm backward fused
-    dx, dx_lp, dgc, dbc, dwq, dbq = _linear_ln_bwd(rt, dq, hq, P.wq, P.bq, xa, P.gc, P.bc, mq, rq, dx_in=dx, lp_scale=lp_scale)
+    dx, dx_lp, dgc, dbc, dwq, dbq = _linear_ln_bwd(rt, dq, s.hq, P.wq, P.bq, xa, P.gc, P.bc, s.mq, s.rq, dx_in=dx, lp_scale=lp_scale)
     dgx = dbx = dwkv = dbkv = None
-    if not folded:
+    if not s.folded:
         # d(context) accumulates over the c_depth blocks in fp32, in place
-        dctx, _, dgx, dbx, dwkv, dbkv = _linear_ln_bwd(rt, dkv, hc, P.wkv, P.bkv, ctxf, P.gx, P.bx, mc, rc, dx_in=dctx, dx_out=dctx, want_lp=False)
+        dctx, _, dgx, dbx, dwkv, dbkv = _linear_ln_bwd(rt, dkv, s.hc, P.wkv, P.bkv, ctxf, P.gx, P.bx, s.mc, s.rc, dx_in=dctx, dx_out=dctx, want_lp=False)
     return dx, dx_lp, dctx, dict(gc=dgc, bc=dbc, gx=dgx, bx=dbx, wq=dwq, bq=dbq, wkv=dwkv, bkv=dbkv, wcp=dwcp, bcp=dbcp, **gn)
+
+
+# a decoder block's tape entry: the inputs of its three stages (x, xa, xb) and what each stage saved (AttnSaved, CrossSaved, MlpSaved)
+DecTape = namedtuple('DecTape', 'x sa xa sc xb sm')
 
 
 def _dec_block_fwd(rt, x, ctxf, P, batch, n, grad, cls_only, index=0, ln1=None, next_ln=None, kv3=None, scales=(None, None, None),
@@ -916,7 +907,7 @@ def _dec_block_fwd(rt, x, ctxf, P, batch, n, grad, cls_only, index=0, ln1=None, 
                                  fuse_ln=_hand_over_ln(rt, xa, P, grad or scales[2] is not None), scale=scales[1],
                                  kv_index=seg.index if seg is not None else None, items=seg.items if seg is not None else None, kn=kn)
     xc, sm, nxt = _mlp_fwd(rt, xb, P, grad, ln=ln2, next_ln=next_ln, scale=scales[2])
-    return xc, ((x, sa, xa, sc, xb, sm) if grad else None), nxt
+    return xc, (DecTape(x, sa, xa, sc, xb, sm) if grad else None), nxt
 
 
 def _dec_block_bwd(rt, dx, dx_lp, ctxf, dctx, P, entry, batch, n, cls_only, index, dkv3=None, lp_scales=(None, None, None), seg=None):
@@ -924,10 +915,10 @@ def _dec_block_bwd(rt, dx, dx_lp, ctxf, dctx, P, entry, batch, n, cls_only, inde
     ``lp_scales``: the stochastic-depth scales carried by the low-precision copies that leave the MLP, cross and self stage - those
     of this block's cross branch, of its self branch and of the PREVIOUS block's MLP branch.
     Returns (d input fp32, its low-precision copy, d context (accumulated in place), the parameter gradients as a DecBlock)."""
-    x, sa, xa, sc, xb, sm = entry
-    dx, dx_lp, gm = _mlp_bwd(rt, dx, dx_lp, xb, P, sm, lp_scale=lp_scales[0])
-    dx, dx_lp, dctx, gc = _dec_cross_bwd(rt, dx, dx_lp, xa, P, sc, ctxf, dctx, batch, index, dkv3, lp_scale=lp_scales[1], seg=seg)
-    dx, dx_lp, ga = _dec_self_bwd(rt, dx, dx_lp, x, P, sa, batch, n, cls_only, key=('cross_blocks', index, 'attn'), lp_scale=lp_scales[2])
+    t = entry
+    dx, dx_lp, gm = _mlp_bwd(rt, dx, dx_lp, t.xb, P, t.sm, lp_scale=lp_scales[0])
+    dx, dx_lp, dctx, gc = _dec_cross_bwd(rt, dx, dx_lp, t.xa, P, t.sc, ctxf, dctx, batch, index, dkv3, lp_scale=lp_scales[1], seg=seg)
+    dx, dx_lp, ga = _dec_self_bwd(rt, dx, dx_lp, t.x, P, t.sa, batch, n, cls_only, key=('cross_blocks', index, 'attn'), lp_scale=lp_scales[2])
     return dx, dx_lp, dctx, rt.dec_block(**ga, **gc, **gm)
 
 
@@ -1007,18 +998,21 @@ def _kv_params(blocks):
     return [P.wkv for P in blocks], [P.bkv for P in blocks], [P.gx for P in blocks], [P.bx for P in blocks]
 
 
+FoldSaved = namedtuple('FoldSaved', 'kv_all xhat mean rstd wt')      # what _context_kv_folded leaves for _context_kv_folded_bwd
+FinalSaved = namedtuple('FinalSaved', 'xcls y mean rstd')            # the final norm on the cls rows: its input, output, statistics
+
+
 def _context_kv_folded(rt, ctxf, blocks):
     """Keys / values of EVERY decoder block from one LayerNorm and one GEMM (csrc/context_fold.hip): xhat = LayerNorm(features; 1, 0),
     kv_all = xhat W'^T + b' with W'_l = W_l o gamma_l, b'_l = b_l + W_l beta_l stacked over the blocks.
-    Returns (kv_all [L, Mc, 2D], (xhat, mean, rstd), folded buffers)."""
+    Returns FoldSaved(kv_all [L, Mc, 2D], xhat, mean, rstd, wt = the folded weights' transpose [D, L 2D])."""
     dev = ctxf.device
     if rt._unit_ln is None or rt._unit_ln[0].device != dev:
         rt._unit_ln = (torch.ones(rt.dim, dtype=torch.float32, device=dev), torch.zeros(rt.dim, dtype=torch.float32, device=dev))
     ws, bs, gs, bes = _kv_params(blocks)
     bufs = rt._fold_bufs
     if bufs is not None and (bufs[0].shape[0] != len(blocks) * 2 * rt.dim or bufs[0].device != dev):
-        if rt.pinned:
-            rt._retired.append(bufs)        # a captured graph still reads them
+        rt.shadows.retire(bufs)             # a captured graph may still read them
         bufs = None
     rt._fold_bufs = bufs = ops.fold_context_weights([w.detach() for w in ws], [b.detach() if b is not None else None for b in bs],
                                                     [g.detach() for g in gs], [b.detach() for b in bes], out=bufs)
@@ -1027,26 +1021,27 @@ def _context_kv_folded(rt, ctxf, blocks):
     # weights - 4.7 MB at 8 blocks - out of an XCD's L2: measured 690 us for the single GEMM against 8 x 55 us)
     n2 = 2 * rt.dim
     kv_all = torch.empty((len(blocks), ctxf.shape[0], n2), dtype=rt.act_dtype, device=dev)
+    wf, wft, bf = bufs
     for l in range(len(blocks)):
-        ops.gemm(xhat, bufs[0][l * n2:(l + 1) * n2], bias=bufs[2][l * n2:(l + 1) * n2], out=kv_all[l])
-    return kv_all, (xhat, mean, rstd), bufs
+        ops.gemm(xhat, wf[l * n2:(l + 1) * n2], bias=bf[l * n2:(l + 1) * n2], out=kv_all[l])
+    return FoldSaved(kv_all, xhat, mean, rstd, wt=wft)
 
 
-def _context_kv_folded_bwd(rt, dkv_all, ctxf, saved, bufs, blocks):
+def _context_kv_folded_bwd(rt, dkv_all, ctxf, saved, blocks):
     """Backward of _context_kv_folded once every block has written its d(kv) slice: d(features) from ONE row-complete kernel
     (input-gradient GEMM with K = L 2D + the affine-free LayerNorm's backward), the folded weights' gradient from one
     weight-gradient GEMM, unfolded into dW_kv, db_kv, d(norm_context.weight / bias) of every block.
     Returns (d features fp32, per block the gradients of gx, bx, wkv, bkv by field name - None when accumulated straight into .grad)."""
-    xhat, mean, rstd = saved
+    xhat, wt = saved.xhat, saved.wt
     ones = rt._unit_ln[0]
     nblk, mc, n2 = dkv_all.shape
-    if _row_kernel_ok(rt, mc, bufs[1].shape[0], nblk * n2, dkv_all.dtype, ctxf):
-        dctx, _, _, _ = ops.linear_layernorm_bwd(dkv_all, bufs[1], ctxf, ones, mean, rstd)      # contraction over all blocks' d(kv)
+    if _row_kernel_ok(rt, mc, wt.shape[0], nblk * n2, dkv_all.dtype, ctxf):
+        dctx, _, _, _ = ops.linear_layernorm_bwd(dkv_all, wt, ctxf, ones, saved.mean, saved.rstd)      # contraction over all blocks' d(kv)
     else:
         dh = torch.zeros((mc, rt.dim), dtype=torch.float32, device=ctxf.device)
         for l in range(nblk):
-            dh = ops.gemm(dkv_all[l], bufs[1][:, l * n2:(l + 1) * n2], epilogue=EPI_RESIDUAL, residual=dh)
-        dctx, _, _, _ = ops.layernorm_bwd(dh, ctxf, ones, mean, rstd)
+            dh = ops.gemm(dkv_all[l], wt[:, l * n2:(l + 1) * n2], epilogue=EPI_RESIDUAL, residual=dh)
+        dctx, _, _, _ = ops.layernorm_bwd(dh, ctxf, ones, saved.mean, saved.rstd)
     dwf = torch.empty((nblk * n2, rt.dim), dtype=torch.float32, device=ctxf.device)
     dbf = torch.empty(nblk * n2, dtype=torch.float32, device=ctxf.device)
     _launch_weight_grads([(dkv_all[l], xhat, dwf[l * n2:(l + 1) * n2], dbf[l * n2:(l + 1) * n2]) for l in range(nblk)], False)
@@ -1062,16 +1057,39 @@ def _context_kv_folded_bwd(rt, dkv_all, ctxf, saved, bufs, blocks):
     return dctx, [dict.fromkeys(('gx', 'bx', 'wkv', 'bkv')) if direct else dict(gx=tg, bx=tbe, wkv=tw, bkv=tb) for tw, tb, tg, tbe in targets]
 
 
+def _final_norm_bwd(rt, dy, final, S, s_head, cls_tail, batch, n):
+    """Backward of the final norm (on the cls rows) given dy [B, D].  Returns (d x fp32, its low-precision copy, d gN, d bN) over the rows
+    of the last block's output: the cls rows when it ran on them alone (``cls_tail``), else all rows, zero but for the cls rows.
+    ``s_head``: the per-sample stochastic-depth scale the low-precision copy carries (see the caller), or None."""
+    d = rt.dim
+    kw = dict(lp_scale=s_head, lp_dtype=rt.act_dtype) if s_head is not None else {}
+    if cls_tail:
+        if s_head is None:
+            kw = dict(want_lp=not rt.exact)
+        dx, dx_lp, dgN, dbN = _ln_bwd(rt, dy, final.xcls, S.gN, S.bN, final.mean, final.rstd, **kw)
+    else:
+        dx = torch.zeros((batch * n, d), dtype=torch.float32, device=dy.device)
+        dx_lp = dx_lp0 = None
+        if s_head is not None or not rt.exact:
+            dx_lp = torch.zeros((batch * n, d), dtype=rt.act_dtype, device=dy.device)
+            dx_lp0 = dx_lp.view(batch, n, d)[:, 0, :]
+        _, _, dgN, dbN = _ln_bwd(rt, dy, final.xcls, S.gN, S.bN, final.mean, final.rstd, dx_out=dx.view(batch, n, d)[:, 0, :], dx_lp=dx_lp0, **kw)
+    if rt.exact and s_head is None:
+        dx_lp = dx
+    return dx, dx_lp, dgN, dbN
+
+
 class DecoderFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, rt: Runtime, feats, img2, img2_index, img1_index, *params):
-        """``img2_index`` (int64 [P] | None): pair p embeds img2[img2_index[p]] (gathered inside the patch-embedding kernel).
+    def forward(ctx, rt: Runtime, drop_path, patch_keep, feats, img2, img2_index, img1_index, *params):
+        """``drop_path`` / ``patch_keep``: as in EncoderFn.forward.
+        ``img2_index`` (int64 [P] | None): pair p embeds img2[img2_index[p]] (gathered inside the patch-embedding kernel).
         ``img1_index`` (ops.PairSegments | None): ``feats`` holds one item per IMAGE and pair p attends over feats[index[p]]: norm_context
         and the kv projections run once per image, the cross-attention reads them through the index, and the backward sums every
         image's d(kv) over its pairs before the per-image kv / norm_context backward (hisfrag.py:117-159 without its two gathers)."""
         shared, blocks = split_params(params, DecShared, rt.dec_block)
         grad = any(ctx.needs_input_grad)
-        keep = _take_patch_keep(rt, 1)
+        keep = _take_patch_keep(patch_keep, 1)
         x, patches, batch, n = _patch_tokens_fwd(rt, img2, shared, with_cls=True, batch_index=img2_index, keep=keep)
         seg = img1_index
         b1 = batch if seg is None else seg.items
@@ -1087,12 +1105,13 @@ class DecoderFn(torch.autograd.Function):
         tape = []
         d = rt.dim
         cls_tail = rt.cls_tail and rt.c_depth > 0 and not (rt.keep_attn or rt.keep_cam)    # the visualisation paths want every query row's map
-        drop = _take_drop_rows(rt, 1, len(blocks), 3, batch, n, x.device, cls_block=rt.c_depth - 1 if cls_tail else None)
+        drop = _take_drop_rows(drop_path, 1, len(blocks), 3, batch, n, x.device, cls_block=rt.c_depth - 1 if cls_tail else None)
         ln1 = None
         fold = rt.fold_context and not rt.exact and rt.c_depth > 1 and rt.c_depth <= ops.MAX_FOLDED_BLOCKS and rt.dim % 32 == 0
-        kv_all = kv_saved = fold_bufs = kn_all = None
+        folded = kv_all = kn_all = None
         if fold:
-            kv_all, kv_saved, fold_bufs = _context_kv_folded(rt, ctxf, blocks)
+            folded = _context_kv_folded(rt, ctxf, blocks)
+            kv_all = folded.kv_all
             if rt.qk_norm:          # k_norm per block on its keys, once per context item (per image under an image-1 index)
                 kn_all = [_k_norm_cross(rt, kv_all[l], P) for l, P in enumerate(blocks)]
         for i, P in enumerate(blocks):
@@ -1110,9 +1129,9 @@ class DecoderFn(torch.autograd.Function):
         logits = ops.gemm(y, rt.weight(shared.wh), epilogue=EPI_STORE_F32, bias=shared.bh)
         if grad:
             ctx.rt, ctx.tape, ctx.patches, ctx.batch, ctx.params = rt, tape, patches, batch, (shared, blocks)
-            ctx.ctxf, ctx.final, ctx.cls_tail = ctxf, (xcls, y, mN, rN), cls_tail
+            ctx.ctxf, ctx.final, ctx.cls_tail = ctxf, FinalSaved(xcls, y, mN, rN), cls_tail
             ctx.feats_needs_grad = feats.requires_grad
-            ctx.fold = (kv_all, kv_saved, fold_bufs) if fold else None
+            ctx.fold = folded           # a FoldSaved; None when every block computes its own keys / values
             ctx.drop = drop
             ctx.seg, ctx.n, ctx.nc, ctx.keep = seg, n, nc, keep
         return logits
@@ -1121,12 +1140,12 @@ class DecoderFn(torch.autograd.Function):
     def backward(ctx, dlogits):
         rt, batch, n, nc, d = ctx.rt, ctx.batch, ctx.n, ctx.nc, ctx.rt.dim      # n, nc: the call's image-2 and context token counts
         shared, blocks = ctx.params
-        xcls, y, mN, rN = ctx.final
+        final = ctx.final
         # head: logits = y Wh^T + bh
         dl = _lp(rt, dlogits.contiguous().float())
         wh_act = rt.weight(shared.wh)
         dy = ops.gemm(dl, wh_act, b_layout=B_KN)                         # [B, D]
-        dwh, dbh = _weight_grads(rt, dl, y, shared.wh, shared.bh)
+        dwh, dbh = _weight_grads(rt, dl, final.y, shared.wh, shared.bh)
         drop, last = ctx.drop, len(blocks) - 1
         seg = ctx.seg
         b1 = batch if seg is None else seg.items
@@ -1134,31 +1153,10 @@ class DecoderFn(torch.autograd.Function):
         # the low-precision copy that leaves the final norm feeds the last block's MLP branch: it carries that branch's scale, per
         # sample (the final norm runs on the cls rows)
         s_head = drop.per_sample[last, 2] if drop is not None and drop.live[last][2] else None
-        if s_head is not None:
-            lp_dtype = rt.act_dtype
-            if ctx.cls_tail:
-                dx, dx_lp, dgN, dbN = _ln_bwd(rt, dy, xcls, shared.gN, shared.bN, mN, rN, lp_scale=s_head, lp_dtype=lp_dtype)
-            else:
-                dx = torch.zeros((batch * n, d), dtype=torch.float32, device=dy.device)
-                dx_lp = torch.zeros((batch * n, d), dtype=lp_dtype, device=dy.device)
-                _, _, dgN, dbN = _ln_bwd(rt, dy, xcls, shared.gN, shared.bN, mN, rN, dx_out=dx.view(batch, n, d)[:, 0, :],
-                                         dx_lp=dx_lp.view(batch, n, d)[:, 0, :], lp_scale=s_head, lp_dtype=lp_dtype)
-        elif ctx.cls_tail:
-            # the last block ran on the cls rows only: so does its gradient
-            dx, dx_lp, dgN, dbN = _ln_bwd(rt, dy, xcls, shared.gN, shared.bN, mN, rN, want_lp=not rt.exact)
-        else:
-            # final LayerNorm touches the cls rows only; every other row of d(x) is zero
-            dx = torch.zeros((batch * n, d), dtype=torch.float32, device=dy.device)
-            dx_lp = dx_lp3 = None
-            if not rt.exact:
-                dx_lp = torch.zeros((batch * n, d), dtype=rt.act_dtype, device=dy.device)
-                dx_lp3 = dx_lp.view(batch, n, d)[:, 0, :]
-            _, _, dgN, dbN = _ln_bwd(rt, dy, xcls, shared.gN, shared.bN, mN, rN, dx_out=dx.view(batch, n, d)[:, 0, :], dx_lp=dx_lp3)
-        if rt.exact and s_head is None:
-            dx_lp = dx
+        dx, dx_lp, dgN, dbN = _final_norm_bwd(rt, dy, final, shared, s_head, ctx.cls_tail, batch, n)
         dctx = None
         gblocks = [None] * len(blocks)
-        dkv_all = torch.empty_like(ctx.fold[0]) if ctx.fold is not None else None       # ctx.fold: (kv_all, saved, folded buffers)
+        dkv_all = torch.empty_like(ctx.fold.kv_all) if ctx.fold else None
         with _ln_sums(rt):                              # the decoder's 4 x c_depth LayerNorm column sums
             with _DwBatch(rt, kind='dec') as dwg:
                 for i in reversed(range(len(blocks))):
@@ -1167,17 +1165,17 @@ class DecoderFn(torch.autograd.Function):
                     with dwg.block():
                         dx, dx_lp, dctx, gblocks[i] = _dec_block_bwd(rt, dx, dx_lp, ctx.ctxf, dctx, blocks[i], entry, batch, n,
                                                                      ctx.cls_tail and i == rt.c_depth - 1, i,
-                                                                     dkv3=dkv_all[i].view(b1, nc, 2 * d) if dkv_all is not None else None,
+                                                                     dkv3=dkv_all[i].view(b1, nc, 2 * d) if ctx.fold else None,
                                                                      lp_scales=(scale_of(i, 1), scale_of(i, 0), scale_of(i - 1, 2)), seg=seg)
                     if rt.tap is not None:
                         rt.tap[f'dec.dx.{i}'] = dx.clone()      # gradient w.r.t. the INPUT of decoder block i
                         if dctx is not None:
                             rt.tap[f'dec.dctx.{i}'] = dctx.clone()  # running d(features) after blocks c_depth-1 .. i
-            if dkv_all is not None:
-                dctx, kv_grads = _context_kv_folded_bwd(rt, dkv_all, ctx.ctxf, ctx.fold[1], ctx.fold[2], blocks)
+            if ctx.fold:
+                dctx, kv_grads = _context_kv_folded_bwd(rt, dkv_all, ctx.ctxf, ctx.fold, blocks)
                 gblocks = [g._replace(**kv) for g, kv in zip(gblocks, kv_grads)]
                 ctx.fold = None
         gshared = DecShared(**_patch_tokens_bwd(rt, dx, ctx.patches, shared, with_cls=True, batch=batch, keep=ctx.keep), gN=dgN, bN=dbN, wh=dwh, bh=dbh)
         dfeats = dctx.view(b1, nc, d) if ctx.feats_needs_grad and dctx is not None else None
         ctx.tape = ctx.patches = ctx.ctxf = ctx.final = ctx.drop = ctx.seg = ctx.keep = None
-        return (None, dfeats, None, None, None, *_cam_only(rt, flatten_params(gshared, gblocks)))
+        return (None, None, None, dfeats, None, None, None, *_cam_only(rt, flatten_params(gshared, gblocks)))

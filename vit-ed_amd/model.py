@@ -283,6 +283,7 @@ class VisionTransformerCustom(nn.Module):
                          num_classes=self.num_classes, embed_dim=self.embed_dim, depth=self.depth, c_depth=self.c_depth,
                          num_heads=self.num_heads, act_dtype=dt, qk_norm=self.qk_norm)
             self._runtimes[dt] = rt
+        # the model's settings are re-synchronised onto the Runtime on every call
         rt.direct_grads = bool(getattr(self, 'direct_param_grads', False))
         rt.input_mean, rt.input_std = self.input_mean, self.input_std
         rt.keep_attn, rt.attn_store = self.keep_attn, self._attn_store
@@ -433,12 +434,7 @@ class VisionTransformerCustom(nn.Module):
         return used.x1, used.x2
 
     def _run_fn(self, fn, drop, keep, *args):
-        rt = self.runtime()
-        rt.drop_path, rt.patch_keep = drop, keep
-        try:
-            return fn.apply(rt, *args)
-        finally:
-            rt.drop_path = rt.patch_keep = None
+        return fn.apply(self.runtime(), drop, keep, *args)
 
     # -- the reference's forward surface -----------------------------------------------------
     def forward_first_part(self, x1, drop_path=None, patch_keep=None):

@@ -16,6 +16,7 @@ from __future__ import annotations
 import torch
 
 from . import _lib
+from .functions import shadows_of
 
 HYPER_HEADER, GROUP_WORDS, DESC_WORDS = 8, 8, 10
 HYPER_STEP, HYPER_SKIP_FLAG, HYPER_SKIPPED = 0, 1, 2
@@ -116,15 +117,11 @@ class _FlatOptimizer(torch.optim.Optimizer):
             self._hyper[HYPER_HEADER:].copy_(torch.tensor(vals, dtype=torch.float32))
             self._hyper_seen = vals
 
-    def _shadows(self):
-        out = {}
-        for rt in getattr(self._model, '_runtimes', {}).values():
-            for (pid, tag), ent in rt._shadow.items():
-                out.setdefault(pid, {})[tag] = ent[2]
-        return out
-
     def _descriptors(self):
-        shadows = self._shadows()
+        shadows = {}
+        for cache in shadows_of(self._model):
+            for pid, tags in cache.buffers().items():
+                shadows.setdefault(pid, {}).update(tags)
         group_of = {id(p): gi for gi, g in enumerate(self.param_groups) for p in g['params']}
         state = [self._bufs[n].data_ptr() for n in self._state_names] + [None] * (2 - len(self._state_names))
         rows_, tile = [], 0
@@ -164,8 +161,7 @@ class _FlatOptimizer(torch.optim.Optimizer):
 
     def shadow_signature(self):
         """What a captured update graph baked in besides this optimizer's own buffers: the set of weight-shadow buffers."""
-        return tuple(sorted((pid, tag, ent[2].data_ptr()) for rt in getattr(self._model, '_runtimes', {}).values()
-                            for (pid, tag), ent in rt._shadow.items()))
+        return tuple(sorted(item for cache in shadows_of(self._model) for item in cache.signature()))
 
     def _publish_update(self):
         """The kernel raw-wrote the fp32 parameters (and the shadows listed in its descriptor table).  Bump every
@@ -174,12 +170,8 @@ class _FlatOptimizer(torch.optim.Optimizer):
         params = self.flat.params
         torch.autograd.graph.increment_version(params)
         refreshed = {ptr for row in (self._desc_key or ()) for ptr in row[4:6] if ptr}
-        by_id = {id(p): p for p in params}
-        for rt in getattr(self._model, '_runtimes', {}).values():
-            for (pid, tag), ent in list(rt._shadow.items()):
-                p = by_id.get(pid)
-                if p is not None and ent[2].data_ptr() in refreshed:
-                    rt._shadow[(pid, tag)] = (p._version, ent[1], ent[2])
+        for cache in shadows_of(self._model):
+            cache.mark_current(params, only_buffers=refreshed)
 
     @torch.no_grad()
     def step(self, closure=None):
