@@ -301,6 +301,39 @@ int vited_qk_norm_bwd(void* dq, int64_t dq_ld, const void* q, int64_t q_ld, cons
                       float* dgamma_k, float* dbeta_k, int64_t k_rows, int dtype, int accumulate, int64_t heads,
                       int64_t head_dim, float* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- pooled head (timm global_pool='avg': forward_head's x[:, 1:].mean(dim=1); csrc/pool_head.hip) ---- */
+
+/* x fp32 [items, tokens, dim] through an item stride and a token stride (in elements; dense last dim), `first` prefix tokens that
+ * take no part (1: the cls row).  Without gamma: pooled[b, :] = (sum over t >= first of x[b, t, :]) / (tokens - first).  With gamma
+ * and beta (fp32 [dim]): the same mean over LayerNorm(x[b, t, :]; gamma, beta, eps) - the normalised rows are never written - and,
+ * when mean / rstd (fp32 [items * tokens], both or neither) are given, the statistics of row t >= first of item b at [b * tokens +
+ * t] for the backward (the prefix rows' entries are left alone).  pooled fp32 [items, dim] with row stride pooled_ld.  fp32
+ * accumulation in ONE order fixed by the shape: the tokens of an item are cut into chunks of 64 (a workgroup each), a chunk's rows
+ * are added by 8 row owners whose sums are added in ascending order, the chunks' sums - through `workspace` - in ascending order;
+ * no atomics, two runs give the same bits.  dim a multiple of 4 up to 1024 (else VITED_ERR_UNSUPPORTED); a null operand, tokens <=
+ * first, a stride that lets rows or items overlap, a pointer that is not 16-byte aligned or a stride that is no multiple of 4 is
+ * VITED_ERR_BAD_ARG.  workspace >= vited_token_pool_workspace_bytes() (one query serves both entries), 16-byte aligned; the forward
+ * needs none while an item is one chunk. */
+int64_t vited_token_pool_workspace_bytes(int64_t items, int64_t tokens, int64_t first, int64_t dim);
+int vited_token_pool_fwd(const float* x, int64_t x_is, int64_t x_ts, const float* gamma, const float* beta, float eps,
+                         float* pooled, int64_t pooled_ld, float* mean, float* rstd, int64_t items, int64_t tokens,
+                         int64_t first, int64_t dim, float* workspace, int64_t workspace_bytes, void* stream);
+
+/* Backward of vited_token_pool_fwd given g fp32 [items, dim] (row stride g_ld), the gradient at pooled.  Writes EVERY element of dx
+ * fp32 [items, tokens, dim] (item / token strides) exactly once - the caller clears nothing: rows t < first get zero, the others
+ * dy = g[b, :] / (tokens - first), or with gamma the LayerNorm backward of that row gradient, rstd * (dy gamma - mean_c(dy gamma) -
+ * xhat * mean_c(dy gamma xhat)) with xhat recomputed from x and the saved mean / rstd.  Without gamma x, mean and rstd are not read
+ * and may be null.  dx_lp (optional; VITED_BF16 or VITED_F32, strides of its own) receives the copy T(lp_scale[b] * dx[b, t, :]) in
+ * the same pass; lp_scale (optional, fp32 [items], needs dx_lp) means what vited_layernorm_bwd_scaled means by it, one value per
+ * item, and dx stays unscaled.  With gamma, dgamma += / = sum dy * xhat and dbeta += / = sum dy over the pooled rows of all items
+ * (fp32 [dim]; `accumulate` != 0 adds onto their content) from per-workgroup partial rows in `workspace` added in a fixed order
+ * (vited_layernorm_bwd's finishing pass).  Errors as in the forward; a bf16 dx_lp needs 8-byte alignment. */
+int vited_token_pool_bwd(const float* g, int64_t g_ld, const float* x, int64_t x_is, int64_t x_ts, const float* gamma,
+                         const float* mean, const float* rstd, float* dx, int64_t dx_is, int64_t dx_ts, void* dx_lp,
+                         int dx_lp_dtype, int64_t dx_lp_is, int64_t dx_lp_ts, const float* lp_scale, float* dgamma,
+                         float* dbeta, int accumulate, int64_t items, int64_t tokens, int64_t first, int64_t dim,
+                         float* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- Linear / GEMM (nn.Linear: qkv :34, proj :38, q :151, kv :152, timm Mlp fc1/fc2, head) ---- */
 
 /* acc[m, n] = sum_k A[m, k] * B(n, k), fp32 accumulation; A is `dtype` [M, K] (row stride lda);

@@ -101,7 +101,7 @@ def _decoder_only_parameters(model):
     encoder too, vision_transformer.py:379,391-392)."""
     out = []
     for name, p in model.named_parameters():
-        if name.startswith(('cross_blocks.', 'norm.', 'head.')) or name == 'cls_token':
+        if name.startswith(('cross_blocks.', 'norm.', 'fc_norm.', 'head.')) or name == 'cls_token':
             out.append(p)
     return out
 

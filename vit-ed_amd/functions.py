@@ -49,6 +49,8 @@ EncBlockQK, ENC_BLOCK_QK_KEYS = _bundle('EncBlockQK', _ATTN + _QKN + _MLP)      
 DecBlockQK, DEC_BLOCK_QK_KEYS = _bundle('DecBlockQK', _ATTN + _QKN + _CROSS + _CQKN + _MLP)
 EncShared, ENC_SHARED_KEYS = _bundle('EncShared', _PATCH)
 DecShared, DEC_SHARED_KEYS = _bundle('DecShared', _PATCH + 'cls=cls_token gN=norm.weight bN=norm.bias wh=head.weight bh=head.bias')
+# the decoder's shared bundle of a model whose head norm is fc_norm (behind the pooling) instead of norm: the same fields, other keys
+DecSharedFc, DEC_SHARED_FC_KEYS = _bundle('DecSharedFc', _PATCH + 'cls=cls_token gN=fc_norm.weight bN=fc_norm.bias wh=head.weight bh=head.bias')
 
 
 def split_params(params, shared_type, block_type):
@@ -93,7 +95,13 @@ class Runtime:
     """Per-model launch context: static shape, activation dtype and the low-precision weight shadows."""
 
     def __init__(self, *, img_size, patch_size, in_chans, num_classes, embed_dim, depth, c_depth, num_heads,
-                 act_dtype=torch.bfloat16, qk_norm=False):
+                 act_dtype=torch.bfloat16, qk_norm=False, global_pool='token', fc_norm=False):
+        if global_pool not in ('token', 'avg'):
+            raise NotImplementedError(f'global_pool={global_pool!r}: the head pools the cls token (\'token\') or averages the patch tokens (\'avg\')')
+        # the head (timm forward_head; DESIGN.md section 26): 'avg' pools the mean of the tokens behind the cls row (ops.token_pool_fwd /
+        # _bwd) instead of the cls row; fc_norm: the head's LayerNorm sits behind the pooling (fc_norm.*) instead of in front of it (norm.*)
+        self.pool_avg, self.fc_norm = global_pool == 'avg', bool(fc_norm)
+        self.dec_shared = DecSharedFc if self.fc_norm else DecShared
         self.qk_norm = bool(qk_norm)   # q_norm / k_norm in every attention (ops.qk_norm_fwd / _bwd; DESIGN.md section 24)
         self.enc_block, self.dec_block = (EncBlockQK, DecBlockQK) if self.qk_norm else (EncBlock, DecBlock)   # the blocks' bundles
         self.img_size, self.patch_size, self.in_chans = img_size, patch_size, in_chans
@@ -109,7 +117,8 @@ class Runtime:
         self.keep_cam = False       # record the head-averaged relevancy map of every attention in the backward (ops.attention_cam): no
                                     # per-head map is formed, and the backward leaves every parameter gradient alone (see _cam_only)
         self.attn_store = {}        # (kind, block index, 'attn' | 'cross_attn') -> {'attn': ..., 'grad': ..., 'cam': [B, Nq, Nk]}
-        self.cls_tail = os.environ.get('VITED_CLS_TAIL', '1') != '0'   # last decoder block on the cls rows only (exact; see _dec_self_fwd)
+        # last decoder block on the cls rows only (exact; see _dec_self_fwd) - never under 'avg', where every token row reaches the loss
+        self.cls_tail = os.environ.get('VITED_CLS_TAIL', '1') != '0' and not self.pool_avg
         self.fused_mlp = os.environ.get('VITED_FUSED_MLP', '1') != '0'   # vited_mlp_fwd on the no-grad paths
         self.fused_ln = os.environ.get('VITED_FUSED_LN', '1') != '0'     # LayerNorm inside the neighbouring Linear's kernel (gemm_row.hip)
         self.batch_dw = os.environ.get('VITED_BATCH_DW', '1') != '0'     # a block's weight gradients in one launch (vited_linear_bwd_weight_batched)
@@ -939,7 +948,7 @@ def image2_tokens(rt: Runtime, img, params):
              cross-attention that follows, vision_transformer.py:269-270) - unless that block is also the last one (cls-only);
       * q  = Linear_q(norm_cross(x')) of that block's cross-attention (:176), activation dtype.
     Returns (x' or x as [n, N2, D] fp32, q [n, N2, D] or None)."""
-    shared, blocks = split_params(params, DecShared, rt.dec_block)
+    shared, blocks = split_params(params, rt.dec_shared, rt.dec_block)
     x, _, batch, _ = _patch_tokens_fwd(rt, img, shared, with_cls=True)
     if not blocks or (rt.cls_tail and rt.c_depth == 1):
         return x.view(batch, rt.n2, rt.dim), None
@@ -952,7 +961,7 @@ def image2_tokens(rt: Runtime, img, params):
 def context_kv(rt: Runtime, feats, params):
     """Per decoder block: kv = Linear_kv(norm_context(features)) as [b1, N1, 2 D] in the activation dtype (columns [2][h][hd]); with the
     q/k-norm the K half is k_norm of it, which is what decoder_cached's attention reads."""
-    _, blocks = split_params(params, DecShared, rt.dec_block)
+    _, blocks = split_params(params, rt.dec_shared, rt.dec_block)
     b1 = feats.shape[0]
     ctxf = feats.detach().contiguous().float().view(b1 * rt.n1, rt.dim)
     out = []
@@ -970,7 +979,7 @@ def decoder_cached(rt: Runtime, tokens2, j_idx, kvs, i_idx, params, q0=None):
     """Logits [P, C] of the pairs (image-1 row i_idx[p] of the cached block, image j_idx[p]): forward_second_part + forward_head
     (vision_transformer.py:397-405,417) on cached image-2 tokens and cached cross-attention keys / values.  With ``q0`` the cache
     already holds block 0's self-attention branch and cross-attention queries (image2_tokens)."""
-    shared, blocks = split_params(params, DecShared, rt.dec_block)
+    shared, blocks = split_params(params, rt.dec_shared, rt.dec_block)
     d, n = rt.dim, rt.n2
     batch = j_idx.numel()
     x = tokens2.index_select(0, j_idx).view(batch * n, d)
@@ -985,9 +994,7 @@ def decoder_cached(rt: Runtime, tokens2, j_idx, kvs, i_idx, params, q0=None):
             xa, _, lnq = _dec_self_fwd(rt, x, P, batch, n, cls_only, fuse_ln=not cls_only)
         xb, _, _ = _dec_cross_fwd(rt, xa, P, batch, lnq=lnq, q=q, kv3=kv3, kv_index=i_idx, fuse_ln=False)
         x, _, _ = _mlp_fwd(rt, xb, P, grad=False)
-    xcls = x if (rt.cls_tail and rt.c_depth > 0) else x.view(batch, n, d)[:, 0, :]
-    y, _, _ = ops.layernorm_fwd(xcls, shared.gN, shared.bN, LN_EPS, rt.act_dtype)
-    return ops.gemm(y, rt.weight(shared.wh), epilogue=EPI_STORE_F32, bias=shared.bh)
+    return _head_fwd(rt, x, shared, batch, n, rt.cls_tail and rt.c_depth > 0, save=False)[0]
 
 
 # ---------------------------------------------------------------------------------------------
@@ -999,7 +1006,11 @@ def _kv_params(blocks):
 
 
 FoldSaved = namedtuple('FoldSaved', 'kv_all xhat mean rstd wt')      # what _context_kv_folded leaves for _context_kv_folded_bwd
-FinalSaved = namedtuple('FinalSaved', 'xcls y mean rstd')            # the final norm on the cls rows: its input, output, statistics
+# the head's norm: its input rows (the cls rows, or under 'avg' + fc_norm the pooled rows), its output in the activation dtype, its statistics
+FinalSaved = namedtuple('FinalSaved', 'xcls y mean rstd')
+# 'avg' without fc_norm, where norm and pooling are one kernel: the last block's output [B, n, D], the pooled rows in the activation dtype
+# (the head GEMM's operand), the statistics of norm on every pooled row [B n]
+PoolSaved = namedtuple('PoolSaved', 'x y mean rstd')
 
 
 def _context_kv_folded(rt, ctxf, blocks):
@@ -1057,10 +1068,53 @@ def _context_kv_folded_bwd(rt, dkv_all, ctxf, saved, blocks):
     return dctx, [dict.fromkeys(('gx', 'bx', 'wkv', 'bkv')) if direct else dict(gx=tg, bx=tbe, wkv=tw, bkv=tb) for tw, tb, tg, tbe in targets]
 
 
+def _head_fwd(rt, x, S, batch, n, cls_rows, save=True):
+    """norm, pooling and head on the last block's output x - fp32 [batch n, D], or [batch, D] when that block ran on the cls rows alone
+    (``cls_rows``) - as cross_part's last line and timm's forward_head order them (vision_transformer.py:400,417):
+      'token':           norm on the cls rows alone (LayerNorm is row-wise), head; with fc_norm the same arithmetic under the other keys;
+      'avg' + fc_norm:   mean of the rows behind the cls row (ops.token_pool_fwd), fc_norm on [batch, D], head;
+      'avg' alone:       norm on every row and the mean of the rows behind the cls row in ONE kernel - the normalised rows never exist.
+    Returns (logits fp32 [batch, C], a FinalSaved or PoolSaved for _final_norm_bwd / _pool_bwd)."""
+    d = rt.dim
+    if rt.pool_avg and not rt.fc_norm:
+        x3 = x.view(batch, n, d)
+        pooled, mean, rstd = ops.token_pool_fwd(x3, 1, S.gN, S.bN, LN_EPS, save_stats=save)
+        saved = PoolSaved(x3, _lp(rt, pooled), mean, rstd)
+    else:
+        if rt.pool_avg:
+            rows, _, _ = ops.token_pool_fwd(x.view(batch, n, d), 1)
+        else:
+            rows = x if cls_rows else x.view(batch, n, d)[:, 0, :]
+        saved = FinalSaved(rows, *ops.layernorm_fwd(rows, S.gN, S.bN, LN_EPS, rt.act_dtype))
+    return ops.gemm(saved.y, rt.weight(S.wh), epilogue=EPI_STORE_F32, bias=S.bh), saved
+
+
+def _pool_bwd(rt, dy, final, S, s_head, batch, n):
+    """_final_norm_bwd under 'avg': (d x fp32 [batch n, D], its low-precision copy, d gN, d bN) given dy [B, D] at the head GEMM's operand.
+    ops.token_pool_bwd writes every row of d x and of the copy itself, the zero cls rows included; the copy carries ``s_head``."""
+    d = rt.dim
+    lp_dtype = rt.act_dtype if (s_head is not None or not rt.exact) else None
+    if rt.fc_norm:
+        dpool, _, dgN, dbN = _ln_bwd(rt, dy, final.xcls, S.gN, S.bN, final.mean, final.rstd)
+        dx, dx_lp, _, _ = ops.token_pool_bwd(dpool, n, 1, lp_dtype=lp_dtype, lp_scale=s_head)
+    else:
+        gg, gb = _gtarget(rt, S.gN), _gtarget(rt, S.bN)
+        direct = gg is not None and gb is not None
+        dx, dx_lp, dgN, dbN = ops.token_pool_bwd(dy if rt.exact else ops.cast(dy, torch.float32), n, 1, x=final.x, gamma=S.gN, mean=final.mean,
+                                                 rstd=final.rstd, lp_dtype=lp_dtype, lp_scale=s_head, dgamma=gg if direct else None,
+                                                 dbeta=gb if direct else None)
+        if direct:
+            dgN = dbN = None
+    dx = dx.view(batch * n, d)
+    return dx, (dx if dx_lp is None else dx_lp.view(batch * n, d)), dgN, dbN
+
+
 def _final_norm_bwd(rt, dy, final, S, s_head, cls_tail, batch, n):
     """Backward of the final norm (on the cls rows) given dy [B, D].  Returns (d x fp32, its low-precision copy, d gN, d bN) over the rows
     of the last block's output: the cls rows when it ran on them alone (``cls_tail``), else all rows, zero but for the cls rows.
     ``s_head``: the per-sample stochastic-depth scale the low-precision copy carries (see the caller), or None."""
+    if rt.pool_avg:
+        return _pool_bwd(rt, dy, final, S, s_head, batch, n)
     d = rt.dim
     kw = dict(lp_scale=s_head, lp_dtype=rt.act_dtype) if s_head is not None else {}
     if cls_tail:
@@ -1087,7 +1141,7 @@ class DecoderFn(torch.autograd.Function):
         ``img1_index`` (ops.PairSegments | None): ``feats`` holds one item per IMAGE and pair p attends over feats[index[p]]: norm_context
         and the kv projections run once per image, the cross-attention reads them through the index, and the backward sums every
         image's d(kv) over its pairs before the per-image kv / norm_context backward (hisfrag.py:117-159 without its two gathers)."""
-        shared, blocks = split_params(params, DecShared, rt.dec_block)
+        shared, blocks = split_params(params, rt.dec_shared, rt.dec_block)
         grad = any(ctx.needs_input_grad)
         keep = _take_patch_keep(patch_keep, 1)
         x, patches, batch, n = _patch_tokens_fwd(rt, img2, shared, with_cls=True, batch_index=img2_index, keep=keep)
@@ -1123,13 +1177,11 @@ class DecoderFn(torch.autograd.Function):
                 tape.append(entry)
             if rt.tap is not None:
                 rt.tap[f'dec.x.{i}'] = x.clone()
-        # final norm on the cls rows only (LayerNorm is row-wise; only x[:, 0] reaches the head, :400,:417)
-        xcls = x if cls_tail else x.view(batch, n, d)[:, 0, :]
-        y, mN, rN = ops.layernorm_fwd(xcls, shared.gN, shared.bN, LN_EPS, rt.act_dtype)
-        logits = ops.gemm(y, rt.weight(shared.wh), epilogue=EPI_STORE_F32, bias=shared.bh)
+        # final norm on the cls rows only (LayerNorm is row-wise; only x[:, 0] reaches the head, :400,:417); under 'avg' the pooled head
+        logits, final = _head_fwd(rt, x, shared, batch, n, cls_tail, save=grad)
         if grad:
             ctx.rt, ctx.tape, ctx.patches, ctx.batch, ctx.params = rt, tape, patches, batch, (shared, blocks)
-            ctx.ctxf, ctx.final, ctx.cls_tail = ctxf, FinalSaved(xcls, y, mN, rN), cls_tail
+            ctx.ctxf, ctx.final, ctx.cls_tail = ctxf, final, cls_tail
             ctx.feats_needs_grad = feats.requires_grad
             ctx.fold = folded           # a FoldSaved; None when every block computes its own keys / values
             ctx.drop = drop
@@ -1175,7 +1227,7 @@ class DecoderFn(torch.autograd.Function):
                 dctx, kv_grads = _context_kv_folded_bwd(rt, dkv_all, ctx.ctxf, ctx.fold, blocks)
                 gblocks = [g._replace(**kv) for g, kv in zip(gblocks, kv_grads)]
                 ctx.fold = None
-        gshared = DecShared(**_patch_tokens_bwd(rt, dx, ctx.patches, shared, with_cls=True, batch=batch, keep=ctx.keep), gN=dgN, bN=dbN, wh=dwh, bh=dbh)
+        gshared = rt.dec_shared(**_patch_tokens_bwd(rt, dx, ctx.patches, shared, with_cls=True, batch=batch, keep=ctx.keep), gN=dgN, bN=dbN, wh=dwh, bh=dbh)
         dfeats = dctx.view(b1, nc, d) if ctx.feats_needs_grad and dctx is not None else None
         ctx.tape = ctx.patches = ctx.ctxf = ctx.final = ctx.drop = ctx.seg = ctx.keep = None
         return (None, None, None, dfeats, None, None, None, *_cam_only(rt, flatten_params(gshared, gblocks)))

@@ -19,6 +19,12 @@ Drop-in surface kept:
     a random subset of the patch tokens of each image is embedded and runs through the blocks; the others are never read
     (``draw_patch_keep`` / ``forward(..., patch_keep=...)`` / ``last_patch_keep``).  Off by default.
 
+  * ``global_pool`` / ``fc_norm``: timm's head options.  ``global_pool='avg'`` feeds the head the mean of the patch tokens instead of the cls
+    token, ``fc_norm`` (None: on exactly under 'avg', timm's rule) moves the head's LayerNorm behind the pooling - the model then has
+    ``fc_norm.weight`` / ``fc_norm.bias`` and no ``norm.*``, as the reference's ``state_dict`` does.  Under 'avg' every row of the last
+    decoder block reaches the loss, so that block runs on all rows, and the pooling and its backward are HIP kernels of their own
+    (csrc/pool_head.hip).  Off by default: same modules, keys and launches as before.
+
 Precision follows the caller exactly like the reference follows ``torch.cuda.amp.autocast``
 (misc/engine.py:208): inside an autocast region the bf16 MFMA kernels run, outside it the fp32
 kernels run; ``model.compute_dtype = torch.bfloat16 | torch.float32`` pins it.
@@ -35,8 +41,8 @@ import torch.nn as nn
 
 from . import functions as F_
 from . import ops
-from .functions import (DEC_BLOCK_KEYS, DEC_BLOCK_QK_KEYS, DEC_SHARED_KEYS, ENC_BLOCK_KEYS, ENC_BLOCK_QK_KEYS, ENC_SHARED_KEYS,
-                        Runtime)
+from .functions import (DEC_BLOCK_KEYS, DEC_BLOCK_QK_KEYS, DEC_SHARED_FC_KEYS, DEC_SHARED_KEYS, ENC_BLOCK_KEYS, ENC_BLOCK_QK_KEYS,
+                        ENC_SHARED_KEYS, Runtime)
 
 LN_EPS = F_.LN_EPS
 
@@ -192,8 +198,12 @@ def _get(module, dotted):
 class VisionTransformerCustom(nn.Module):
     def __init__(self, img_size=224, patch_size=16, in_chans=3, num_classes=1000, embed_dim=768, depth=12, c_depth=12,
                  num_heads=12, mlp_ratio=4., qkv_bias=True, keep_attn=False, arch_version='v1', compute_dtype=None,
-                 drop_path_rate=0., qk_norm=False, patch_drop_rate=0., **unsupported):
+                 drop_path_rate=0., qk_norm=False, patch_drop_rate=0., global_pool='token', fc_norm=None, **unsupported):
         super().__init__()
+        if global_pool not in ('token', 'avg'):
+            # timm also takes '' (no pooling: forward_head returns per-token logits), which nothing here computes
+            raise NotImplementedError(f'global_pool={global_pool!r} is not on the HIP hot path: the head pools the cls token '
+                                      "(global_pool='token') or averages the patch tokens (global_pool='avg')")
         drop_path_rate = float(drop_path_rate or 0.)
         if not 0. <= drop_path_rate < 1.:
             raise ValueError(f'drop_path_rate={drop_path_rate}: stochastic depth takes a rate in [0, 1)')
@@ -223,6 +233,8 @@ class VisionTransformerCustom(nn.Module):
                                             # such a backward leaves every parameter gradient untouched
         self.arch_version = arch_version.lower()
         self.qk_norm = bool(qk_norm)        # q_norm / k_norm = LayerNorm(head_dim) in every attention
+        self.global_pool = global_pool      # what the head reads: the cls row ('token') or the mean of the rows behind it ('avg')
+        self.use_fc_norm = (global_pool == 'avg') if fc_norm is None else bool(fc_norm)     # timm's rule
         self.compute_dtype = compute_dtype
         # stochastic depth (timm DropPath, scale_by_keep): the reference's two decay rules, fp32 linspace as it computes them
         # (vision_transformer.py:351 for the decoder, timm's VisionTransformer for the encoder); DropPath has no parameters
@@ -244,7 +256,10 @@ class VisionTransformerCustom(nn.Module):
         self.cls_token = nn.Parameter(torch.zeros(1, 1, embed_dim))
         self.pos_embed = nn.Parameter(torch.zeros(1, n1 + 1, embed_dim))
         self.blocks = nn.Sequential(*[Block(embed_dim, num_heads, hidden, qkv_bias, self.qk_norm) for _ in range(depth)])
-        self.norm = _Norm(embed_dim)
+        if self.use_fc_norm:
+            self.fc_norm = _Norm(embed_dim)     # behind the pooling; the reference's norm is then a parameter-free Identity
+        else:
+            self.norm = _Norm(embed_dim)
         self.head = _Linear(embed_dim, num_classes)
         self._init_like_timm()  # runs before the decoder exists, exactly as in the reference ctor (:344-347)
         self.cross_blocks = nn.ModuleList([CrossBlock(embed_dim, num_heads, hidden, qkv_bias, self.qk_norm) for _ in range(c_depth)])
@@ -281,13 +296,17 @@ class VisionTransformerCustom(nn.Module):
         if rt is None:
             rt = Runtime(img_size=self.img_size, patch_size=self.patch_size, in_chans=self.in_chans,
                          num_classes=self.num_classes, embed_dim=self.embed_dim, depth=self.depth, c_depth=self.c_depth,
-                         num_heads=self.num_heads, act_dtype=dt, qk_norm=self.qk_norm)
+                         num_heads=self.num_heads, act_dtype=dt, qk_norm=self.qk_norm, global_pool=self.global_pool,
+                         fc_norm=self.use_fc_norm)
             self._runtimes[dt] = rt
         # the model's settings are re-synchronised onto the Runtime on every call
         rt.direct_grads = bool(getattr(self, 'direct_param_grads', False))
         rt.input_mean, rt.input_std = self.input_mean, self.input_std
         rt.keep_attn, rt.attn_store = self.keep_attn, self._attn_store
         rt.keep_cam = bool(self.keep_cam)
+        if rt.keep_cam and self.global_pool == 'avg':
+            raise NotImplementedError("keep_cam / engine.pair_relevancy read the cls row's attention maps, which a model with global_pool='avg' "
+                                      'does not classify from')
         if rt.keep_cam:
             rt.direct_grads = False         # nothing of that backward may reach a p.grad or the flat gradient buffer behind it
         return rt
@@ -299,7 +318,7 @@ class VisionTransformerCustom(nn.Module):
         return ps
 
     def _decoder_params(self):
-        ps = [_get(self, k) for k in DEC_SHARED_KEYS]
+        ps = [_get(self, k) for k in (DEC_SHARED_FC_KEYS if self.use_fc_norm else DEC_SHARED_KEYS)]
         for blk in self.cross_blocks:
             ps += [_get(blk, k) for k in (DEC_BLOCK_QK_KEYS if self.qk_norm else DEC_BLOCK_KEYS)]
         return ps

@@ -1299,3 +1299,6 @@ def cls_metrics_update(logits: torch.Tensor, targets: torch.Tensor, meters: torc
 # ---- patch dropout: the wrappers of csrc/patch_keep.hip live in ops_patchdrop.py, on this module's checker and call path ------------
 from .ops_patchdrop import (MAX_KEEP_KEYS, keep_from_keys, keep_inverse, patchify_kept, tokens_kept,  # noqa: E402,F401
                             tokens_kept_bwd)
+
+# ---- pooled head: the wrappers of csrc/pool_head.hip live in ops_poolhead.py, on this module's checker and call path ---------------
+from .ops_poolhead import POOL_MAX_DIM, token_pool_bwd, token_pool_fwd  # noqa: E402,F401
