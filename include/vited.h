@@ -235,6 +235,30 @@ int vited_keep_inverse(const int32_t* keep, int K, int lead, int32_t* inv, int64
 int vited_tokens_kept_bwd(const float* dx, const int32_t* inv, float* dpos, float* dcls, int64_t batch, int rows, int with_cls,
                           int n_patches, int dim, void* stream);
 
+/* ---- elementwise token dropout (timm's pos_drop = nn.Dropout(pos_drop_rate) at the end of _pos_embed, vision_transformer.py:378-380;
+ * csrc/token_dropout.hip, the rule in csrc/token_dropout.h) ------------------------------------------------------
+ * out[b, r, d] = keep ? x[b, r, d] * scale : 0 over a stream [batch, rows, dim] of `dtype` (VITED_F32 / VITED_BF16), x and out each with
+ * a batch and a row stride (elements); out may be x itself with x's strides (in place), otherwise the two lie apart.  The mask comes
+ * from a counter-based generator and is never stored: element e = (b * tokens + t) * dim + d (int64; t = the ORIGINAL token of row
+ * r) reads word e & 3 of Philox4x32-10 with the counter (lo32(e >> 2), hi32(e >> 2), stream_id, 0) and the key (lo32, hi32) of
+ * *seed, and is kept iff word >= thr.  The backward is the same call on the gradient with the same seed.
+ *   tokens     the stream's full token count T; without a keep table rows == tokens and t = r
+ *   keep       optional DEVICE int32 [batch, K] patch-dropout table with K + 1 == rows: row 0 is the prefix token 0 and row r the
+ *              token of the patch vited_tokens_kept put there (lead = 1: 1 + keep[b, r - 1] of a stream without a cls token; lead = 0:
+ *              the patch keep[b, r - 1] behind the cls token, token keep[b, r - 1] + 1); indices are clamped, never followed outside
+ *   stream_id  0 (image-1 stream) or 1 (image-2 stream): two streams of one seed get unrelated masks
+ *   seed       DEVICE pointer to one int64, read by the kernel: a captured graph sees the value written for each replay
+ *   thr        min(2^32 - 1, int(p * 2^32)) in [0, 2^32 - 1];  scale = float(1 / (1 - p))
+ * A kept element is one fp32 multiply rounded once to `dtype`; a dropped one is 0 by selection (also for inf / NaN inputs).  Every
+ * output element is written; no allocation, copy or synchronisation.
+ * VITED_ERR_BAD_ARG: a null x / out / seed, a non-positive size, dim % 4 != 0, a row stride below dim or a batch stride below a
+ * sample's span (rows or samples would overlap), x and out overlapping without being the same layout, a stride that is no multiple
+ * of 4 or a pointer not aligned to four elements (seed: 8 bytes, keep: 4), thr outside [0, 2^32 - 1], stream_id or lead outside
+ * {0, 1}, K + 1 != rows or rows > tokens with a table, rows != tokens without.  VITED_ERR_UNSUPPORTED: another dtype, dim > 1024. */
+int vited_token_dropout(const void* x, int64_t x_bs, int64_t x_rs, void* out, int64_t out_bs, int64_t out_rs, int dtype, int64_t batch,
+                        int rows, int dim, int tokens, int stream_id, const int32_t* keep, int K, int lead, const int64_t* seed,
+                        int64_t thr, float scale, void* stream);
+
 /* out[r] = sum_b in[b, r] (fp32 out; in is `in_dtype` [batch, width]).  Deterministic two-pass;
  * workspace >= vited_sum_rows_workspace_bytes().  Serves bias gradients (column sums) and the
  * pos_embed / cls_token gradients (batch sums). */

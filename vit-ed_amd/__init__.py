@@ -9,6 +9,6 @@ kernels as PyTorch custom operators, ``custom_ops.py``).
 from . import _lib, config, custom_ops, engine, functions, ops, optim  # noqa: F401  (custom_ops registers torch.ops.vited.*)
 from .build import build_model  # noqa: F401
 from .config import config_from_yaml, get_config  # noqa: F401
-from .model import DropPathScales, PatchKeep, VisionTransformerCustom  # noqa: F401
+from .model import DropPathScales, PatchKeep, PosDropSeeds, VisionTransformerCustom  # noqa: F401
 
-__all__ = ['build_model', 'get_config', 'config_from_yaml', 'VisionTransformerCustom', 'DropPathScales', 'PatchKeep', 'ops', 'functions', 'config']
+__all__ = ['build_model', 'get_config', 'config_from_yaml', 'VisionTransformerCustom', 'DropPathScales', 'PatchKeep', 'PosDropSeeds', 'ops', 'functions', 'config']

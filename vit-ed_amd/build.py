@@ -7,7 +7,8 @@ part of the ViT-ED hot path and are rejected with a clear message.
 from .model import VisionTransformerCustom
 
 
-def build_model(config, is_pretrain=False, drop_path_rate=None, qk_norm=None, patch_drop_rate=None, global_pool='token', fc_norm=None):
+def build_model(config, is_pretrain=False, drop_path_rate=None, qk_norm=None, patch_drop_rate=None, global_pool='token', fc_norm=None,
+                pos_drop_rate=None):
     """``drop_path_rate``: stochastic depth.  The default (None) reads exactly the keys the reference reads, and the reference's
     factory does not forward ``MODEL.DROP_PATH_RATE`` to the pjs model - the shipped YAMLs set it to 0.1 without effect.  Pass
     ``drop_path_rate=config.MODEL.DROP_PATH_RATE`` to train the regularised model those configs describe.
@@ -16,7 +17,9 @@ def build_model(config, is_pretrain=False, drop_path_rate=None, qk_norm=None, pa
     ``patch_drop_rate``: timm PatchDropout in training mode, which the reference's class inherits and its factory has no key for
     either; the default (None) leaves it off.
     ``global_pool`` / ``fc_norm``: timm's head options ('token' | 'avg'; None | bool), inherited by the reference's class and without a
-    config key too; the defaults are the reference's own and build the shipped model."""
+    config key too; the defaults are the reference's own and build the shipped model.
+    ``pos_drop_rate``: timm's dropout behind the position embedding, training mode only; the reference's factory has no key for it
+    either, and the default (None) leaves it off."""
     model_type = config.MODEL.TYPE
     if model_type != 'pjs':
         raise NotImplementedError(
@@ -41,4 +44,5 @@ def build_model(config, is_pretrain=False, drop_path_rate=None, qk_norm=None, pa
         patch_drop_rate=0. if patch_drop_rate is None else patch_drop_rate,
         global_pool=global_pool,
         fc_norm=fc_norm,
+        pos_drop_rate=0. if pos_drop_rate is None else pos_drop_rate,
     )

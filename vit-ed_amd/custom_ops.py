@@ -16,6 +16,7 @@ These are the op-level building blocks of the reference's layers, usable from or
   ``vited::patchify``          im2col of timm ``PatchEmbed``'s Conv2d(k=s=p) (:383)   vited_patchify
   ``vited::linear_residual_layernorm``  ``x = x + proj(...)`` followed by the next      vited_linear_residual_layernorm_fwd,
                                sub-block's ``norm(x)`` (:124-127, 268-272)             vited_linear_layernorm_bwd
+  ``vited::token_dropout``     ``self.pos_drop(x)`` = ``nn.Dropout(p)`` (:378-380)      vited_token_dropout (forward and backward)
   ===========================  =====================================================  ==============================
 
 The model itself (``model.VisionTransformerCustom``) drives the same C entry points through two coarser
@@ -446,6 +447,37 @@ def _(img, patch, lowp):
 
 
 # ---------------------------------------------------------------------------------------------
+# elementwise dropout of a token stream from a counter-based generator: the backward is the operator itself on the gradient
+# ---------------------------------------------------------------------------------------------
+@custom_op('vited::token_dropout', mutates_args=(), device_types='cuda')
+def token_dropout(x: Tensor, seed: Tensor, p: float, tokens: int, stream: int, keep: Optional[Tensor], lead: bool) -> Tensor:
+    """``nn.Dropout(p)`` on x fp32 / bf16 [batch, rows, dim] with the mask of ``ops.token_dropout``: ``seed`` one int64 on x's device,
+    ``tokens`` the stream's full token count, ``stream`` 0 / 1, ``keep`` / ``lead`` an optional patch-dropout table [batch, rows - 1]."""
+    xd = x if x.dtype in (torch.float32, _LOWP) else x.to(_LOWP)
+    return ops.token_dropout(xd.contiguous(), seed, p, tokens, stream, keep=keep, lead=lead).to(x.dtype)
+
+
+@token_dropout.register_fake
+def _(x, seed, p, tokens, stream, keep, lead):
+    return x.new_empty(x.shape)
+
+
+def _tokdrop_setup(ctx, inputs, output):
+    _x, seed, ctx.p, ctx.tokens, ctx.stream, keep, ctx.lead = inputs
+    ctx.has_keep = keep is not None
+    ctx.save_for_backward(seed, *([keep] if keep is not None else []))
+
+
+def _tokdrop_backward(ctx, dy):
+    seed, *keep = ctx.saved_tensors
+    dx = torch.ops.vited.token_dropout(dy, seed, ctx.p, ctx.tokens, ctx.stream, keep[0] if ctx.has_keep else None, ctx.lead)
+    return dx, None, None, None, None, None, None
+
+
+register_autograd('vited::token_dropout', _tokdrop_backward, setup_context=_tokdrop_setup)
+
+
+# ---------------------------------------------------------------------------------------------
 # autocast: inside torch.autocast('cuda', bfloat16) the GEMM / attention operators take bf16 activations,
 # exactly as F.linear / SDPA do in the reference under torch.cuda.amp.autocast (misc/engine.py:208)
 # ---------------------------------------------------------------------------------------------
@@ -453,4 +485,4 @@ for _name in ('vited::linear', 'vited::mlp', 'vited::attention'):
     torch.library.register_autocast(_name, 'cuda', _LOWP)
 
 OPERATORS = ('layernorm', 'layernorm_backward', 'qk_norm', 'qk_norm_backward', 'linear', 'linear_backward', 'mlp', 'mlp_backward', 'attention',
-             'attention_backward', 'patchify', 'linear_residual_layernorm', 'linear_layernorm_backward')
+             'attention_backward', 'patchify', 'linear_residual_layernorm', 'linear_layernorm_backward', 'token_dropout')

@@ -197,7 +197,11 @@ class TrainStep:
     * Patch dropout (``patch_drop_rate`` > 0, training mode) works the same way: the keys and the ranking kernel that turns them into
       keep indices are part of the captured graph, ``model.last_patch_keep`` is a static buffer that holds the latest replay's
       indices, and ``step.patch_keep`` = a ``PatchKeep`` of static tensors forces them.  The shortened sequences have a fixed length
-      (the rate is the model's), so the captured shapes never change."""
+      (the rate is the model's), so the captured shapes never change.
+    * Position dropout (``pos_drop_rate`` > 0, training mode) likewise: the draw of the two seeds is part of the captured graph, the
+      dropout kernel reads them from device memory, so every replay masks anew, ``model.last_pos_drop`` is a static buffer that holds
+      the latest replay's seeds, and ``step.pos_drop`` = a ``PosDropSeeds`` of static tensors forces them.  No mask is stored between
+      the forward and the backward graph: the encoder's backward regenerates it from the seed."""
 
     def __init__(self, model, optimizer, *, clip_grad=5.0, amp=True, criterion=None, use_graph=False,
                  compress_bf16=False, forward_fn=None, accumulation_steps=1, lr_scheduler=None, overlap=True, group=None,
@@ -213,6 +217,7 @@ class TrainStep:
             model.direct_param_grads = True     # HIP model: weight-gradient kernels add straight into the flat buffer
         self.drop_path = None       # forced stochastic-depth scales (a DropPathScales); None: the model draws when it should
         self.patch_keep = None      # forced patch-dropout indices (a PatchKeep); None: the model draws when it should
+        self.pos_drop = None        # forced position-dropout seeds (a PosDropSeeds); None: the model draws when it should
         self.forward_fn = forward_fn or (lambda m, x: m(x, **self._forced()))
         self.use_graph = use_graph and torch.cuda.is_available()
         self.hip_opt = hasattr(optimizer, 'bind_flat')       # optim.FlatAdamW / FlatSGD: clip + update + shadow refresh in one kernel
@@ -276,6 +281,8 @@ class TrainStep:
         forced = {} if self.drop_path is None else dict(drop_path=self.drop_path)
         if self.patch_keep is not None:
             forced['patch_keep'] = self.patch_keep
+        if self.pos_drop is not None:
+            forced['pos_drop'] = self.pos_drop
         return forced
 
     def _fwd_bwd(self, x, y):

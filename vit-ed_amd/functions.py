@@ -614,6 +614,28 @@ def _take_patch_keep(patch_keep, which):
     return patch_keep[which] if patch_keep is not None else None
 
 
+def _take_pos_drop(pos_drop, which):
+    """(seed int64 [1], rate) of this call's half (0: image 1, 1: image 2) from the Function's ``pos_drop`` argument = (image-1 seed | None,
+    image-2 seed | None, rate) as model._resolve_pos_drop returns it; None: no position dropout in this call."""
+    if pos_drop is None or pos_drop[which] is None:
+        return None
+    return pos_drop[which], pos_drop[2]
+
+
+def _pos_drop(rt, x, batch, rows, with_cls, pos_drop, keep, in_place):
+    """timm's pos_drop on a stream x fp32 [B*rows, D]: the elementwise mask of this call's seed, regenerated by the
+    kernel wherever it is needed - on the tokens in the forward and, with the same arguments, on their gradient in the backward.
+    Stream 0 is the image-1 path (n1 tokens), stream 1 the image-2 path (cls + n1 tokens); under patch dropout the rows carry the
+    masks of their original tokens (``keep``: the table the stream was embedded through).  ``in_place`` only where nothing else reads x."""
+    if pos_drop is None:
+        return x
+    seed, rate = pos_drop
+    x3 = x.view(batch, rows, rt.dim)
+    y = ops.token_dropout(x3, seed, rate, rt.n2 if with_cls else rt.n1, int(with_cls), keep=keep, lead=not with_cls,
+                          out=x3 if in_place else None)
+    return y.view(batch * rows, rt.dim)
+
+
 def _patch_tokens_fwd(rt, img, S, with_cls, batch_index=None, keep=None):
     """timm PatchEmbed + pos-embed (+ cls row, S: a DecShared) : returns x fp32 [B*rows, D] and the saved patch matrix.
     ``keep`` (int32 [B, K]; patch dropout): only the kept patches are extracted, embedded and given their
@@ -683,13 +705,15 @@ EncTape = namedtuple('EncTape', 'x sa xa sm')
 
 class EncoderFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, rt: Runtime, drop_path, patch_keep, img, *params):
-        """``drop_path`` / ``patch_keep``: this call's stochastic-depth scales and keep tables as the model resolved them (_take_drop_rows,
-        _take_patch_keep), or None."""
+    def forward(ctx, rt: Runtime, drop_path, patch_keep, pos_drop, img, *params):
+        """``drop_path`` / ``patch_keep`` / ``pos_drop``: this call's stochastic-depth scales, keep tables and position-dropout seeds as the
+        model resolved them (_take_drop_rows, _take_patch_keep, _take_pos_drop), or None."""
         shared, blocks = split_params(params, EncShared, rt.enc_block)
         grad = any(ctx.needs_input_grad)  # False under no_grad: nothing is saved for inference
         keep = _take_patch_keep(patch_keep, 0)
+        pdrop = _take_pos_drop(pos_drop, 0)
         x, patches, batch, n = _patch_tokens_fwd(rt, img, shared, with_cls=False, keep=keep)
+        x = _pos_drop(rt, x, batch, n, False, pdrop, keep, in_place=True)      # the stream was just written and nothing else holds it
         drop = _take_drop_rows(drop_path, 0, len(blocks), 2, batch, n, x.device)      # stochastic depth: per-row scales of (attn, mlp) per block
         tape = []
         ln1 = None          # (h, mean, rstd) of this block's norm1 when the previous block's fc2 kernel already produced it
@@ -707,7 +731,7 @@ class EncoderFn(torch.autograd.Function):
                 rt.tap[f'enc.x.{len(tape) - 1 if grad else 0}'] = x.clone()
         if grad:
             ctx.rt, ctx.tape, ctx.patches, ctx.batch, ctx.params = rt, tape, patches, batch, (shared, blocks)
-            ctx.drop, ctx.n, ctx.keep = drop, n, keep
+            ctx.drop, ctx.n, ctx.keep, ctx.pos_drop = drop, n, keep, pdrop
         return x.view(batch, n, rt.dim)
 
     @staticmethod
@@ -730,9 +754,11 @@ class EncoderFn(torch.autograd.Function):
                 if rt.tap is not None:
                     rt.tap[f'enc.dx.{i}'] = dx.clone()      # gradient w.r.t. the INPUT of encoder block i
                 gblocks[i] = rt.enc_block(**ga, **gm)
+        # position dropout: the same mask on the stream's gradient, into a tensor of its own (dx may be the caller's gradient)
+        dx = _pos_drop(rt, dx, batch, n, False, ctx.pos_drop, ctx.keep, in_place=False)
         gshared = EncShared(**_patch_tokens_bwd(rt, dx, ctx.patches, shared, with_cls=False, batch=batch, keep=ctx.keep))
-        ctx.tape = ctx.patches = ctx.drop = ctx.keep = None
-        return (None, None, None, None, *_cam_only(rt, flatten_params(gshared, gblocks)))
+        ctx.tape = ctx.patches = ctx.drop = ctx.keep = ctx.pos_drop = None
+        return (None, None, None, None, None, *_cam_only(rt, flatten_params(gshared, gblocks)))
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1135,8 +1161,8 @@ def _final_norm_bwd(rt, dy, final, S, s_head, cls_tail, batch, n):
 
 class DecoderFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, rt: Runtime, drop_path, patch_keep, feats, img2, img2_index, img1_index, *params):
-        """``drop_path`` / ``patch_keep``: as in EncoderFn.forward.
+    def forward(ctx, rt: Runtime, drop_path, patch_keep, pos_drop, feats, img2, img2_index, img1_index, *params):
+        """``drop_path`` / ``patch_keep`` / ``pos_drop``: as in EncoderFn.forward.
         ``img2_index`` (int64 [P] | None): pair p embeds img2[img2_index[p]] (gathered inside the patch-embedding kernel).
         ``img1_index`` (ops.PairSegments | None): ``feats`` holds one item per IMAGE and pair p attends over feats[index[p]]: norm_context
         and the kv projections run once per image, the cross-attention reads them through the index, and the backward sums every
@@ -1144,7 +1170,9 @@ class DecoderFn(torch.autograd.Function):
         shared, blocks = split_params(params, rt.dec_shared, rt.dec_block)
         grad = any(ctx.needs_input_grad)
         keep = _take_patch_keep(patch_keep, 1)
+        pdrop = _take_pos_drop(pos_drop, 1)
         x, patches, batch, n = _patch_tokens_fwd(rt, img2, shared, with_cls=True, batch_index=img2_index, keep=keep)
+        x = _pos_drop(rt, x, batch, n, True, pdrop, keep, in_place=True)       # per pair of the call, also under an image-2 index
         seg = img1_index
         b1 = batch if seg is None else seg.items
         if seg is not None:
@@ -1185,7 +1213,7 @@ class DecoderFn(torch.autograd.Function):
             ctx.feats_needs_grad = feats.requires_grad
             ctx.fold = folded           # a FoldSaved; None when every block computes its own keys / values
             ctx.drop = drop
-            ctx.seg, ctx.n, ctx.nc, ctx.keep = seg, n, nc, keep
+            ctx.seg, ctx.n, ctx.nc, ctx.keep, ctx.pos_drop = seg, n, nc, keep, pdrop
         return logits
 
     @staticmethod
@@ -1227,7 +1255,8 @@ class DecoderFn(torch.autograd.Function):
                 dctx, kv_grads = _context_kv_folded_bwd(rt, dkv_all, ctx.ctxf, ctx.fold, blocks)
                 gblocks = [g._replace(**kv) for g, kv in zip(gblocks, kv_grads)]
                 ctx.fold = None
+        dx = _pos_drop(rt, dx, batch, n, True, ctx.pos_drop, ctx.keep, in_place=False)     # position dropout on the stream's gradient
         gshared = rt.dec_shared(**_patch_tokens_bwd(rt, dx, ctx.patches, shared, with_cls=True, batch=batch, keep=ctx.keep), gN=dgN, bN=dbN, wh=dwh, bh=dbh)
         dfeats = dctx.view(b1, nc, d) if ctx.feats_needs_grad and dctx is not None else None
-        ctx.tape = ctx.patches = ctx.ctxf = ctx.final = ctx.drop = ctx.seg = ctx.keep = None
-        return (None, None, None, dfeats, None, None, None, *_cam_only(rt, flatten_params(gshared, gblocks)))
+        ctx.tape = ctx.patches = ctx.ctxf = ctx.final = ctx.drop = ctx.seg = ctx.keep = ctx.pos_drop = None
+        return (None, None, None, None, dfeats, None, None, None, *_cam_only(rt, flatten_params(gshared, gblocks)))

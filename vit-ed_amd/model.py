@@ -25,6 +25,12 @@ Drop-in surface kept:
     decoder block reaches the loss, so that block runs on all rows, and the pooling and its backward are HIP kernels of their own
     (csrc/pool_head.hip).  Off by default: same modules, keys and launches as before.
 
+  * ``pos_drop_rate``: timm's ``pos_drop = nn.Dropout(pos_drop_rate)`` at the end of ``_pos_embed`` and of the reference's
+    ``_pos_embed_no_cls`` - in training mode every element of both token streams is zeroed with that probability and the others are
+    scaled by 1 / (1 - p), directly behind the position embedding.  The mask comes from a counter-based generator inside a HIP kernel
+    (csrc/token_dropout.hip) and is regenerated from a per-call seed in the backward: no mask is ever stored
+    (``draw_pos_drop`` / ``forward(..., pos_drop=...)`` / ``last_pos_drop``).  No parameter, no key.  Off by default.
+
 Precision follows the caller exactly like the reference follows ``torch.cuda.amp.autocast``
 (misc/engine.py:208): inside an autocast region the bf16 MFMA kernels run, outside it the fp32
 kernels run; ``model.compute_dtype = torch.bfloat16 | torch.float32`` pins it.
@@ -59,6 +65,12 @@ DropPathScales = namedtuple('DropPathScales', 'enc dec')
 #                pair of the call.
 # Either field may be None for a call that does not run that half.
 PatchKeep = namedtuple('PatchKeep', 'x1 x2')
+
+# Position-dropout seeds of one forward (timm's pos_drop): each field an int64 tensor of ONE element on the
+# model's device, from which the kernel regenerates the elementwise mask of that stream in the forward and in the backward
+# (x1: the image-1 stream [B1, n1, D], x2: the image-2 stream [B2, 1 + n1, D], one sample per pair of the call).  Either field may
+# be None for a call that does not run that half.
+PosDropSeeds = namedtuple('PosDropSeeds', 'x1 x2')
 
 
 def patch_keep_count(tokens: int, rate: float) -> int:
@@ -198,7 +210,8 @@ def _get(module, dotted):
 class VisionTransformerCustom(nn.Module):
     def __init__(self, img_size=224, patch_size=16, in_chans=3, num_classes=1000, embed_dim=768, depth=12, c_depth=12,
                  num_heads=12, mlp_ratio=4., qkv_bias=True, keep_attn=False, arch_version='v1', compute_dtype=None,
-                 drop_path_rate=0., qk_norm=False, patch_drop_rate=0., global_pool='token', fc_norm=None, **unsupported):
+                 drop_path_rate=0., qk_norm=False, patch_drop_rate=0., global_pool='token', fc_norm=None, pos_drop_rate=0.,
+                 **unsupported):
         super().__init__()
         if global_pool not in ('token', 'avg'):
             # timm also takes '' (no pooling: forward_head returns per-token logits), which nothing here computes
@@ -210,6 +223,9 @@ class VisionTransformerCustom(nn.Module):
         patch_drop_rate = float(patch_drop_rate or 0.)
         if not 0. <= patch_drop_rate < 1.:
             raise ValueError(f'patch_drop_rate={patch_drop_rate}: patch dropout takes a rate in [0, 1)')
+        pos_drop_rate = float(pos_drop_rate or 0.)
+        if not 0. <= pos_drop_rate < 1.:
+            raise ValueError(f'pos_drop_rate={pos_drop_rate}: position dropout takes a rate in [0, 1)')
         live = {k: v for k, v in unsupported.items() if v not in (None, False, 0, 0., '', 'token')}
         if live:
             raise NotImplementedError(f'options outside the shipped pjs configs are not on the HIP hot path: {sorted(live)}')
@@ -248,6 +264,10 @@ class VisionTransformerCustom(nn.Module):
         self.patch_drop_rate = patch_drop_rate
         self.patch_drop_generator = None    # torch.Generator of the keys in training mode (None: the device's default generator)
         self.last_patch_keep = None         # PatchKeep of the latest forward (None: it ran on every patch)
+        # position dropout (timm's pos_drop = nn.Dropout(pos_drop_rate)): no parameters either
+        self.pos_drop_rate = pos_drop_rate
+        self.pos_drop_generator = None      # torch.Generator of the seeds in training mode (None: the device's default generator)
+        self.last_pos_drop = None           # PosDropSeeds of the latest forward (None: it ran without position dropout)
         # uint8 inputs are normalised inside the patch-embedding kernel: ToTensor + Normalize(0.5, 0.5) of data/transforms.py:14-18
         self.input_mean, self.input_std = (0.5,) * in_chans, (0.5,) * in_chans
         hidden = int(embed_dim * mlp_ratio)
@@ -452,19 +472,64 @@ class VisionTransformerCustom(nn.Module):
         self.last_patch_keep = PatchKeep(used.x1 if batch_x1 is not None else prev.x1, used.x2 if batch_x2 is not None else prev.x2)
         return used.x1, used.x2
 
+    # -- position dropout --------------------------------------------------------------------
+    def draw_pos_drop(self, run_x1, run_x2, generator=None, device=None):
+        """Draw the seeds of one forward: PosDropSeeds(x1, x2), each one int64 over the whole int64 range on ``device`` (the model's), or
+        None for a half the call does not run (``run_x1`` / ``run_x2`` false or None).  One torch.randint per half: no host read, so it
+        can be captured."""
+        device = torch.device(device) if device is not None else self.pos_embed.device
+        if generator is not None and device.type == 'cuda' and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('position-dropout draws inside a graph capture use the device\'s default generator (torch registers it with '
+                               'the graph, so every replay draws anew); a custom generator would freeze one seed into the graph')
+        lo, hi = -2 ** 63, 2 ** 63 - 1
+        out = []
+        for run in (run_x1, run_x2):
+            if not run:
+                out.append(None)
+                continue
+            out.append(torch.randint(lo, hi, (1,), dtype=torch.int64, generator=generator,
+                                     device=device if generator is None else generator.device).to(device))
+        return PosDropSeeds(*out)
+
+    def _resolve_pos_drop(self, pos_drop, run_x1, run_x2, device):
+        """What a forward passes on to the Functions: (x1 seed | None, x2 seed | None, rate) or None.  Explicit seeds hold in any mode;
+        otherwise training mode with a live rate draws - never under keep_cam (a relevancy backward never drops).  A model whose rate
+        is 0 never drops.  The tensors are handed over as they are and never written afterwards."""
+        if self.pos_drop_rate > 0. and pos_drop is not None:
+            used = PosDropSeeds(pos_drop[0] if run_x1 else None, pos_drop[1] if run_x2 else None)
+        elif self.pos_drop_rate > 0. and self.training and not self.keep_cam:
+            used = self.draw_pos_drop(run_x1, run_x2, generator=self.pos_drop_generator, device=device)
+        else:
+            self.last_pos_drop = None
+            return None
+        for name, t, run in (('x1', used.x1, run_x1), ('x2', used.x2, run_x2)):
+            if not run:
+                continue
+            if t is None:
+                raise ValueError(f'pos_drop.{name} is missing for a call that runs that half of the model')
+            if not torch.is_tensor(t) or t.dtype != torch.int64 or t.numel() != 1 or t.device != device:
+                got = f'{t.dtype} {tuple(t.shape)} on {t.device}' if torch.is_tensor(t) else type(t).__name__
+                raise ValueError(f'pos_drop.{name}: expected one int64 on {device}, got {got}')
+        # a two-stage step is two calls: each records its half and leaves the other call's half in place
+        prev = self.last_pos_drop or PosDropSeeds(None, None)
+        self.last_pos_drop = PosDropSeeds(used.x1 if run_x1 else prev.x1, used.x2 if run_x2 else prev.x2)
+        return used.x1, used.x2, self.pos_drop_rate
+
     def _run_fn(self, fn, drop, keep, *args):
+        """``args``: the Function's remaining arguments, the position-dropout seeds (``_resolve_pos_drop``) first."""
         return fn.apply(self.runtime(), drop, keep, *args)
 
     # -- the reference's forward surface -----------------------------------------------------
-    def forward_first_part(self, x1, drop_path=None, patch_keep=None):
+    def forward_first_part(self, x1, drop_path=None, patch_keep=None, pos_drop=None):
         """[B, N1, D] features; under patch dropout [B, 1 + K1, D] in keep order (patch 0 first), as the reference returns them."""
         self._check_images(x1)
         return self._encode(x1, self._resolve_drop_path(drop_path, x1.shape[0], None, x1.device),
-                            self._resolve_patch_keep(patch_keep, x1.shape[0], None, x1.device))
+                            self._resolve_patch_keep(patch_keep, x1.shape[0], None, x1.device),
+                            self._resolve_pos_drop(pos_drop, True, False, x1.device))
 
-    def _encode(self, x1, drop, keep=None):
-        """The encoder with what ``_resolve_drop_path`` and ``_resolve_patch_keep`` returned."""
-        return self._run_fn(F_.EncoderFn, drop, keep, x1, *self._encoder_params())
+    def _encode(self, x1, drop, keep=None, pdrop=None):
+        """The encoder with what ``_resolve_drop_path``, ``_resolve_patch_keep`` and ``_resolve_pos_drop`` returned."""
+        return self._run_fn(F_.EncoderFn, drop, keep, pdrop, x1, *self._encoder_params())
 
     supports_x2_index = True   # engine.pairwise_similarity gathers image-2 rows inside the patch-embed kernel
 
@@ -500,18 +565,19 @@ class VisionTransformerCustom(nn.Module):
             raise ValueError(f'x1_index names {seg.index.numel()} pairs, the image-2 side {pairs}')
         return seg
 
-    def forward_second_part_head(self, x1_feats, x2, x2_index=None, drop_path=None, x1_index=None, patch_keep=None):
+    def forward_second_part_head(self, x1_feats, x2, x2_index=None, drop_path=None, x1_index=None, patch_keep=None, pos_drop=None):
         """``x1_index`` (int64 [P] or ``ops.PairSegments``): ``x1_feats`` holds one item per IMAGE and pair p reads
         x1_feats[x1_index[p]] - == self(x1_feats[x1_index], x2[x2_index]) (hisfrag.py:153-159) without the two gathers and with
         norm_context + the kv projections once per image; under autograd and under no_grad.  Returns [P, C] logits."""
         x2_index, pairs = self._check_x2(x2, x2_index, indexed_features=x1_index is not None)
         x1_index = self._check_x1(x1_feats, x1_index, pairs)
         return self._decode_head(x1_feats, x2, x2_index, self._resolve_drop_path(drop_path, None, pairs, x2.device), x1_index,
-                                 self._resolve_patch_keep(patch_keep, None, pairs, x2.device))
+                                 self._resolve_patch_keep(patch_keep, None, pairs, x2.device),
+                                 self._resolve_pos_drop(pos_drop, False, True, x2.device))
 
-    def _decode_head(self, x1_feats, x2, x2_index, drop, x1_index=None, keep=None):
-        """The decoder and head with what ``_resolve_drop_path`` and ``_resolve_patch_keep`` returned."""
-        return self._run_fn(F_.DecoderFn, drop, keep, x1_feats, x2, x2_index, x1_index, *self._decoder_params())
+    def _decode_head(self, x1_feats, x2, x2_index, drop, x1_index=None, keep=None, pdrop=None):
+        """The decoder and head with what ``_resolve_drop_path``, ``_resolve_patch_keep`` and ``_resolve_pos_drop`` returned."""
+        return self._run_fn(F_.DecoderFn, drop, keep, pdrop, x1_feats, x2, x2_index, x1_index, *self._decoder_params())
 
     # -- pair-cached inference (engine.pairwise_similarity; SURVEY.md section 8(f) rank 2) ---------------------------------
     supports_pair_cache = True
@@ -536,18 +602,21 @@ class VisionTransformerCustom(nn.Module):
         i_idx = i_idx.to(device=dev, dtype=torch.int64).contiguous()
         return F_.decoder_cached(self.runtime(), tokens2, j_idx, kvs, i_idx, self._decoder_params(), q0)
 
-    def forward(self, x, x2=None, forward_first_part=False, x2_index=None, drop_path=None, x1_index=None, patch_keep=None):
+    def forward(self, x, x2=None, forward_first_part=False, x2_index=None, drop_path=None, x1_index=None, patch_keep=None, pos_drop=None):
         """``drop_path``: explicit DropPathScales for this call (any mode; tests, reproducing a step).  None: training mode with a
         live ``drop_path_rate`` draws them for the batch of the call - the images of ``forward_first_part``, the pairs of
         ``(feats, x2)``, the B pairs of a one-shot call for both halves - and ``eval()`` or rate 0 runs without.  The scales used
         are kept in ``last_drop_path``.
         ``patch_keep``: explicit PatchKeep indices for this call (any mode).  None: training mode with a live ``patch_drop_rate``
         draws them - one set per image of ``forward_first_part``, one per pair of ``(feats, x2)``, both for a one-shot call - and
-        ``eval()``, rate 0, ``keep_attn`` and ``keep_cam`` run on every patch.  The indices used are kept in ``last_patch_keep``."""
+        ``eval()``, rate 0, ``keep_attn`` and ``keep_cam`` run on every patch.  The indices used are kept in ``last_patch_keep``.
+        ``pos_drop``: explicit PosDropSeeds for this call (any mode, on a model with a live ``pos_drop_rate``).  None: training mode
+        draws one seed per stream of the call; ``eval()``, rate 0 and ``keep_cam`` never drop.  The seeds used are kept in
+        ``last_pos_drop``; the pair caches (``cache_image2_tokens`` ...) never drop."""
         if forward_first_part:
-            return self.forward_first_part(x, drop_path, patch_keep)
+            return self.forward_first_part(x, drop_path, patch_keep, pos_drop)
         if x2 is not None:
-            return self.forward_second_part_head(x, x2, x2_index, drop_path, x1_index, patch_keep)
+            return self.forward_second_part_head(x, x2, x2_index, drop_path, x1_index, patch_keep, pos_drop)
         if x1_index is not None:
             raise ValueError('x1_index belongs to the two-stage form model(feats, x2, x1_index=...)')
         if x.dim() != 5 or x.shape[1] != 2:
@@ -557,7 +626,8 @@ class VisionTransformerCustom(nn.Module):
         x1, x2 = x[:, 0], x[:, 1]                                           # strided views: the kernels take a batch stride
         self._check_images(x1)
         self._check_images(x2)
-        return self._decode_head(self._encode(x1, drop, keep), x2, None, drop, keep=keep)
+        pdrop = self._resolve_pos_drop(pos_drop, True, True, x.device)
+        return self._decode_head(self._encode(x1, drop, keep, pdrop), x2, None, drop, keep=keep, pdrop=pdrop)
 
     def flops_parts(self):
         """Algorithmic forward FLOPs (2MNK per contraction) of (the encoder on ONE image incl. its

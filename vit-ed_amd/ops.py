@@ -1302,3 +1302,7 @@ from .ops_patchdrop import (MAX_KEEP_KEYS, keep_from_keys, keep_inverse, patchif
 
 # ---- pooled head: the wrappers of csrc/pool_head.hip live in ops_poolhead.py, on this module's checker and call path ---------------
 from .ops_poolhead import POOL_MAX_DIM, token_pool_bwd, token_pool_fwd  # noqa: E402,F401
+
+# ---- elementwise token dropout: the wrapper of csrc/token_dropout.hip and the CPU statement of its mask rule live in ops_tokendrop.py --
+from .ops_tokendrop import (TOKEN_DROPOUT_MAX_DIM, dropout_threshold, philox4x32, token_dropout,  # noqa: E402,F401
+                            token_dropout_mask)
