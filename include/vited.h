@@ -558,6 +558,21 @@ int vited_sgd_step(const int64_t* desc, int count, int64_t total_tiles, const fl
                    float* hyper, float max_norm, int zero_grad, float* norm_out, float* workspace,
                    int64_t workspace_bytes, void* stream);
 
+/* One step of a per-iteration learning-rate schedule on the device (misc/lr_scheduler.py through misc/engine.py:228; the rules are
+ * csrc/lr_schedule.h, in fp64): one launch of one workgroup, queued behind the update it follows.
+ *   t = *counter;  for g < groups: dst[first + stride * g] = (float)(lr_schedule_value(table, base[g], t) * scale[g]);  *counter = t + 1
+ *   table      DEVICE fp64 [44]: kind (0 cosine, 1 linear, 2 step, 3 multistep), warmup_t, warmup_lr_init, t_initial, lr_min,
+ *              cycle_limit, warmup_prefix, lr_min_rate, decay_t, decay_rate, gamma, the milestone count, up to 32 ascending milestones
+ *   base       DEVICE fp64 [groups]: every group's initial_lr;  scale  DEVICE fp64 [groups]: its lr_scale (1 where it has none)
+ *   counter    DEVICE int64 [1]: the index of the update just done, advanced by the launch
+ *   dst        DEVICE fp32 [dst_words]; the hyper array of vited_adamw_step / vited_sgd_step takes first = 8, stride = 8
+ *   last_lr    DEVICE fp32 [groups] or null: receives the same values; may not overlap the words written in dst
+ * Everything is read from device memory, so a captured hipGraph follows a schedule or a counter that was copied into these buffers.
+ * No other word of dst is touched.  VITED_ERR_BAD_ARG: a null table, base, scale, counter or dst; groups outside [1, 4096];
+ * first < 0, stride < 1 or a last word outside dst; fp64 / int64 pointers not 8-byte aligned, fp32 ones not 4-byte aligned. */
+int vited_lr_schedule_step(const double* table, const double* base, const double* scale, int groups, int64_t* counter,
+                           float* dst, int64_t dst_words, int64_t first, int64_t stride, float* last_lr, void* stream);
+
 /* ---- attention core (F.scaled_dot_product_attention, vision_transformer.py:63-66,183-186) ----- */
 
 /* o[b, i, h, :] = softmax_j(scale * q[b,i,h,:] . k[b,j,h,:]) v[b,j,h,:]   (no mask, no dropout)

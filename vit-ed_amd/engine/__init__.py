@@ -22,4 +22,4 @@ from .puzzle import (PUZZLE_SIDES, PuzzleCompatibility, PuzzleSolution, puzzle_a
 from .relevancy import pair_relevancy, relevancy_from_cams  # noqa: F401
 from .similarity import pairwise_similarity, shard_rows_by_pair_count  # noqa: F401
 from .train import (NativeScalerWithGradNormCount, TrainMeters, TrainStep, _decoder_only_parameters, build_optimizer,  # noqa: F401
-                    param_groups_no_decay_1d)
+                    build_scheduler, param_groups_no_decay_1d)

@@ -7,6 +7,7 @@ import torch.distributed as dist
 
 from .. import ops
 from ..functions import shadows_of
+from ..lr_scheduler import Scheduler, build_scheduler  # noqa: F401  (build_scheduler: misc/lr_scheduler.py, re-exported by engine)
 from .distributed import FlatGradients
 from .metrics import MeterValue
 
@@ -182,6 +183,11 @@ class TrainStep:
     * ``num_updates`` (the index handed to ``lr_scheduler.step_update``) counts iterations, whether or not an optimizer built
       with ``skip_nonfinite=True`` left an update out - the reference's index does the same; ``optimizer.num_updates`` counts
       the updates that were applied.
+    * ``lr_scheduler``: one of ``lr_scheduler.py``'s classes (``engine.build_scheduler``) on ``optim.FlatAdamW`` / ``optim.FlatSGD`` is
+      stepped on the device: a one-workgroup launch behind the update (part of the captured update graph) computes ``_get_lr(n)`` from a
+      device counter that starts at ``start_update`` and writes it into the optimizer's device array, so no rate is uploaded per
+      iteration; ``step_update(n)`` on the host then only keeps ``param_groups`` current for the log line and checkpoints.
+      ``lr_scheduler.on_device = False``, any other scheduler object and the torch optimizers are stepped by the host.
     * ``meters=True`` keeps the loop's loss and gradient-norm meters (``TrainMeters``) on the device, eagerly and in replay,
       without a host read; what ``step`` returns does not change.
     * ``use_graph=True`` replays hipGraphs (forward + decoder backward | encoder backward | update) captured
@@ -244,6 +250,16 @@ class TrainStep:
         self._tensor_lr = (not self.hip_opt) and all(g.get('capturable', False) for g in optimizer.param_groups) \
             and next(model.parameters()).is_cuda
         self.device_type = 'cuda' if next(model.parameters()).is_cuda else 'cpu'
+        # a schedule of lr_scheduler.py on a HIP optimizer is stepped by a launch behind the update (its rates never pass through the
+        # host); every other combination - a scheduler that only has step_update, on_device = False, a torch optimizer, a rule the
+        # device table cannot state - is stepped by the host through param_groups, as before.  After bind_flat: the launch writes
+        # into the hyper-parameter array that binding (re-)allocated.
+        self.lr_on_device = (self.hip_opt and isinstance(lr_scheduler, Scheduler) and lr_scheduler.on_device is not False
+                          and lr_scheduler.device_capable())
+        if self.lr_on_device:
+            lr_scheduler.attach(optimizer, self.num_updates)
+        elif isinstance(lr_scheduler, Scheduler):
+            lr_scheduler.detach()
         # meters=True: the loop's loss / grad-norm meters on the device (read them with ``meters.values()`` when a log line is due)
         self.meters = TrainMeters(next(model.parameters()).device, self.accum) if meters else None
 
@@ -316,6 +332,8 @@ class TrainStep:
     def _update(self):
         if self.hip_opt:
             norm = self.optimizer.step_flat(self.clip_grad)      # clip + update + shadow refresh + zero: one pass
+            if self.lr_on_device:
+                self.lr_scheduler.step_device()                  # the rate of the NEXT update, from the device counter
         else:
             norm = self.flat.clip_(self.clip_grad) if self.clip_grad is not None else torch.linalg.vector_norm(self.flat.flat)
             self.optimizer.step()

@@ -1306,3 +1306,6 @@ from .ops_poolhead import POOL_MAX_DIM, token_pool_bwd, token_pool_fwd  # noqa: 
 # ---- elementwise token dropout: the wrapper of csrc/token_dropout.hip and the CPU statement of its mask rule live in ops_tokendrop.py --
 from .ops_tokendrop import (TOKEN_DROPOUT_MAX_DIM, dropout_threshold, philox4x32, token_dropout,  # noqa: E402,F401
                             token_dropout_mask)
+
+# ---- device-stepped learning-rate schedule: the wrapper of csrc/lr_schedule.hip and its table layout live in ops_lrsched.py -----------
+from .ops_lrsched import LR_MAX_MILESTONES, LR_TABLE_WORDS, lr_schedule_step  # noqa: E402,F401

@@ -39,6 +39,7 @@ class _FlatOptimizer(torch.optim.Optimizer):
         self._bufs = None              # {state name: flat fp32 buffer laid out like the gradient buffer}
         self._desc = self._desc_key = None
         self._hyper = self._hyper_seen = None
+        self.hyper_uploads = 0         # copies sync_hyperparameters really made (a device-stepped lr schedule needs one)
         self._norm = self._ws = None
 
     # -- wiring --------------------------------------------------------------------------------
@@ -116,6 +117,21 @@ class _FlatOptimizer(torch.optim.Optimizer):
             # runs ahead of the device under graph replay)
             self._hyper[HYPER_HEADER:].copy_(torch.tensor(vals, dtype=torch.float32))
             self._hyper_seen = vals
+            self.hyper_uploads += 1
+
+    @staticmethod
+    def hyper_lr_words():
+        """(first word, stride) of the groups' learning rates in the device hyper-parameter array: where a device-stepped schedule
+        (lr_scheduler.Scheduler.step_device) writes."""
+        return HYPER_HEADER, GROUP_WORDS
+
+    def mark_lr_on_device(self):
+        """The rates now in ``param_groups`` are the ones a schedule step on the device already wrote into the hyper-parameter array
+        (lr_scheduler.Scheduler.step_update says so): ``sync_hyperparameters`` does not upload them.  Any other change - a caller's
+        ``set_lr``, another word of a group - still differs from what was seen and is uploaded."""
+        if self._hyper_seen is not None:
+            for gi, g in enumerate(self.param_groups):
+                self._hyper_seen[gi * GROUP_WORDS] = float(g['lr'])
 
     def _descriptors(self):
         shadows = {}
