@@ -783,6 +783,27 @@ int vited_mine_pairs(const int64_t* targets, int n, const float* keys, double ne
                      int64_t* groups, float* labels, float* weights, int64_t* seg_index, int64_t* seg_order, int64_t* seg_offsets,
                      int32_t* counts, void* stream);
 
+/* ---- training: the loss of the two-stage step over a mined pair list, and its gradient, in one launch ---------------------------
+ * BCE-with-logits over the rows of vited_mine_pairs' result: logits fp32 [rows, classes] (dense rows), labels / weights fp32 [rows],
+ * counts int32 [5] as that entry leaves them; loss fp32 [1] and dlogits fp32 [rows, classes] are written in full on every call (they
+ * need not be initialised).  All arrays are DEVICE memory; the pair count is read there, never on the host.  Per element (r, c), with
+ * x = logits[r, c], y = labels[r], w = weights[r]:
+ *   term    = (1 - y) x + m + log(exp(-m) + exp(-x - m)),  m = max(-x, 0)        (the stable form of vited_cls_metrics_update)
+ *   denom   = (float)max(counts[3], 1) * (float)classes  when mean != 0,  1  otherwise (the sum)
+ *   loss    = (scale * sum of (w != 0 ? w * term : +0)) / denom
+ *   dlogits = w != 0 ? ((scale * w) * (sigmoid(x) - y)) / denom : +0,  sigmoid(x) - y formed without cancellation from
+ *             q = e / (1 + e), e = exp(-|x|):  (1 - y) - q  for x >= 0,  q - y  for x < 0
+ * The weight selects: a row with weight 0 (padding) contributes an exact +0 term and an exact +0 gradient whatever its logit holds,
+ * NaN included; a NaN or inf logit in a weighted row makes the loss non-finite, as torch's does.  scale is the 1 / accumulation_steps
+ * of the step.
+ * One workgroup of 256 threads: thread t adds the flattened elements t, t + 256, ... in ascending order in fp32, a butterfly joins
+ * each wave's 64 sums and one lane adds the four wave sums in order.  No atomics: the same bits on every call, and - padding rows
+ * lying behind the pairs - the same loss bits whatever the capacity.
+ * VITED_ERR_BAD_ARG: a null pointer, rows < 1, classes < 1, a scale that is not finite, a pointer not 4-byte aligned.
+ * VITED_ERR_UNSUPPORTED: rows > 24576 (vited_mine_pairs' largest capacity) or classes > 64. */
+int vited_mined_bce(const float* logits, const float* labels, const float* weights, const int32_t* counts, int64_t rows,
+                    int64_t classes, int mean, float scale, float* loss, float* dlogits, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

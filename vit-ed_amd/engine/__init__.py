@@ -16,10 +16,10 @@ from .metrics import (ClassificationMeters, GeshaemMetrics, MeterValue, PairScor
                       class_members, geshaem_pair_metrics, group_relations, hisfrag_retrieval_metrics, map_prak, metrics_from_sums,
                       retrieval_metrics, validate_classifier)
 from .mining import (MinedPairs, hisfrag_prepare_data, hisfrag_prepare_indexed, hisfrag_prepare_mined, mine_pairs,  # noqa: F401
-                     mine_pairs_device, mined_bce_with_logits, mined_pair_capacity)
+                     mine_pairs_device, mined_bce_fused, mined_bce_with_logits, mined_pair_capacity)
 from .puzzle import (PUZZLE_SIDES, PuzzleCompatibility, PuzzleSolution, puzzle_accuracy, puzzle_distances,  # noqa: F401
                      solve_puzzle)
 from .relevancy import pair_relevancy, relevancy_from_cams  # noqa: F401
 from .similarity import pairwise_similarity, shard_rows_by_pair_count  # noqa: F401
-from .train import (NativeScalerWithGradNormCount, TrainMeters, TrainStep, _decoder_only_parameters, build_optimizer,  # noqa: F401
-                    build_scheduler, param_groups_no_decay_1d)
+from .train import (NativeScalerWithGradNormCount, TrainMeters, TrainStep, TwoStageTrainStep, _decoder_only_parameters,  # noqa: F401
+                    build_optimizer, build_scheduler, param_groups_no_decay_1d)

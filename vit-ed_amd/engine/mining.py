@@ -1,5 +1,6 @@
 """Pair mining for the two-stage training step (hisfrag.py:117-159): ``mine_pairs`` with a host read per
-step, ``mine_pairs_device`` with a fixed shape, none, and a rule restated on the CPU; their loss and hand-offs."""
+step, ``mine_pairs_device`` with a fixed shape, none, and a rule restated on the CPU; their loss - as torch ops
+and as one HIP launch (``mined_bce_fused``) - and hand-offs."""
 from __future__ import annotations
 
 import functools
@@ -182,6 +183,32 @@ def mined_bce_with_logits(logits: torch.Tensor, mined: MinedPairs, reduction: st
     if reduction == 'sum':
         return total
     return total / (mined.counts[3].clamp(min=1).to(torch.float32) * x.shape[1])
+
+
+class _MinedBCEFused(torch.autograd.Function):
+    """``ops.mined_bce`` under autograd: the launch that forms the loss also forms d loss / d logits, the backward only scales it."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, weights, counts, reduction, scale):
+        loss, dlogits = ops.mined_bce(logits, labels, weights, counts, reduction, scale)
+        ctx.save_for_backward(dlogits)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        (dlogits,) = ctx.saved_tensors
+        return grad_output * dlogits, None, None, None, None, None
+
+
+def mined_bce_fused(logits: torch.Tensor, mined: MinedPairs, reduction: str = 'mean', scale: float = 1.0) -> torch.Tensor:
+    """``scale * mined_bce_with_logits(logits, mined, reduction)`` from one HIP launch (``ops.mined_bce``, csrc/mined_bce.hip) that writes
+    the loss and its gradient together; the backward is ``grad_output * dlogits``, one elementwise device op.  No host read in either
+    direction (the pair count is read on the device): capturable.  ``logits`` [capacity] or [capacity, C], C <= 64, on the GPU; ``scale``
+    is the step's 1 / accumulation_steps.  The sum runs in a fixed order, so the loss and the gradient are bitwise reproducible and the
+    loss bits do not depend on the capacity.  Usable as ``TrainStep(criterion=mined_bce_fused)`` with ``y = mined``."""
+    x = logits.float()
+    x = x.unsqueeze(1) if x.dim() == 1 else x
+    return _MinedBCEFused.apply(x.contiguous(), mined.labels, mined.weights, mined.counts, reduction, float(scale))
 
 
 def hisfrag_prepare_mined(model, samples: torch.Tensor, targets: torch.Tensor, capacity: int, amp: bool = True, generator=None,

@@ -1,6 +1,9 @@
 """The training step (misc/engine.py:183-257, misc/utils.py:206-232, misc/optimizer.py:10-46): optimizer factory, the reference's
-scaler call shape, ``TrainStep`` (eager or replayed as hipGraphs) and its meters on the device."""
+scaler call shape, ``TrainStep`` (eager or replayed as hipGraphs), its meters on the device, and ``TwoStageTrainStep``, the mined
+two-stage step of hisfrag.py / michigan.py on the same machinery."""
 from __future__ import annotations
+
+import gc
 
 import torch
 import torch.distributed as dist
@@ -10,6 +13,7 @@ from ..functions import shadows_of
 from ..lr_scheduler import Scheduler, build_scheduler  # noqa: F401  (build_scheduler: misc/lr_scheduler.py, re-exported by engine)
 from .distributed import FlatGradients
 from .metrics import MeterValue
+from .mining import mine_pairs_device, mined_bce_fused
 
 
 def param_groups_no_decay_1d(model):
@@ -325,6 +329,10 @@ class TrainStep:
     def _enc_bwd(feats, dfeats):
         feats.backward(dfeats)
 
+    def _two_stage(self, x):
+        """Whether the backward of this batch is driven in two stages (``_fwd_dec_bwd`` + ``_enc_bwd``) or as one (``_fwd_bwd``)."""
+        return self.split and torch.is_tensor(x) and x.dim() == 5
+
     def _meter_loss(self, loss, y):
         if self.meters is not None:
             self.meters.update_loss(loss, y.counts[3] if hasattr(y, 'counts') else y.shape[0])    # MinedPairs: the real pairs
@@ -397,7 +405,7 @@ class TrainStep:
 
     def _eager(self, x, y, last):
         buckets = self.flat.buckets()
-        if self.split and torch.is_tensor(x) and x.dim() == 5:
+        if self._two_stage(x):
             loss, feats, dfeats = self._fwd_dec_bwd(x, y)
             if last and len(buckets) == 2:
                 self.flat.start_all_reduce(*buckets[0], group=self.group)
@@ -426,11 +434,15 @@ class TrainStep:
             raise TypeError('TrainStep(use_graph=True) replays on a static input tensor: pass use_graph=False for structured batches')
         self._static_x, self._static_y = x.clone(), y.clone()
         self._sync_lr()
+        # A dead TrainStep is a reference cycle (its default forward_fn closes over it), so the graphs it holds wait for the cyclic
+        # collector - which may run whenever an allocation tips it, also in the autograd thread in the middle of this capture, where
+        # destroying a hipGraph is not permitted and ends the process.  torch.cuda.graph no longer collects on entry: do it here.
+        gc.collect()
         torch.cuda.synchronize()
         ops.pin_workspace()               # captured kernels bake buffer addresses in: later growth must not free them
         for cache in shadows_of(self.model):
             cache.pin()
-        split = self.split and torch.is_tensor(x) and x.dim() == 5
+        split = self._two_stage(x)
         self._g1 = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self._g1, capture_error_mode=_CAPTURE_MODE):
             if split:
@@ -461,3 +473,93 @@ class TrainStep:
         elif norm.data_ptr() != self._static_norm.data_ptr():
             self._static_norm = norm
         self._g_opt = g
+
+
+class TwoStageTrainStep(TrainStep):
+    """The step ``hisfrag.py`` / ``michigan.py`` train with (hisfrag.py:117-159, michigan.py:120-160) as one object, eager or replayed:
+    ``step(samples [n, C, S, S], targets integer [n])`` - what the loader yields - mines the pairs on the device
+    (``mine_pairs_device``, ``capacity`` rows), runs the encoder once per image, the decoder on the pair indices
+    (``model(feats, samples, x2_index=groups[:, 0], x1_index=segments)``), takes ``mined_bce_fused(..., scale=1 / accumulation_steps)``
+    and runs the decoder's backward; then the encoder's backward from d feats, and from there on everything is ``TrainStep``: the two
+    all-reduce buckets (the decoder-only one under the encoder's backward), the fused update, the device schedule, the meters
+    (``counts[3]``, the real pairs, as ``n``).  ``michigan.py`` is ``neg_per_pos=1.0, ordered_negatives=True, reduction='sum'``.
+
+    * ``use_graph=True`` captures, after two eager updates, mining + encoder forward + decoder forward + loss + decoder backward +
+      loss meter | encoder backward | update, and replays them from static copies of ``samples`` and ``targets``; no host read
+      anywhere, so the host runs ahead of the device.  The batch shape is fixed by the capture.
+    * The keys of the negatives' random subset come from the device's default generator inside the captured region: every replay
+      mines anew.  ``step.mine_keys`` = an fp32 [n * n] tensor forces them (tests, reproducing a step); a captured graph reads that
+      tensor in place.  ``step.last_mined`` is the ``MinedPairs`` of the latest call (static buffers under replay).
+    * Live ``drop_path_rate`` / ``patch_drop_rate`` / ``pos_drop_rate`` draw inside the step, per image in the encoder and per pair in
+      the decoder.  Forcing them per stage is not offered: a non-None ``step.drop_path`` / ``patch_keep`` / ``pos_drop`` raises."""
+
+    def __init__(self, model, optimizer, *, capacity, neg_per_pos=2.0, ordered_negatives=False, reduction='mean', clip_grad=5.0, amp=True,
+                 use_graph=False, compress_bf16=False, accumulation_steps=1, lr_scheduler=None, overlap=True, group=None, start_update=0,
+                 meters=False, forward_fn=None, criterion=None):
+        if forward_fn is not None or criterion is not None:
+            raise ValueError('TwoStageTrainStep: forward_fn and criterion are fixed here (the pair-indexed decoder call and '
+                             'mined_bce_fused); use TrainStep for a forward or a loss of your own')
+        if not getattr(model, 'supports_x1_index', False):
+            raise ValueError('TwoStageTrainStep: model must take the pair-indexed decoder call model(feats, x2, x2_index=..., x1_index=...) '
+                             '(supports_x1_index)')
+        capacity = int(capacity)
+        if not 1 <= capacity <= ops.MINE_MAX_CAPACITY:
+            raise ValueError(f'TwoStageTrainStep: capacity must lie in [1, {ops.MINE_MAX_CAPACITY}] (the mining kernel\'s rows), got {capacity}')
+        if reduction not in ('mean', 'sum'):
+            raise ValueError(f"TwoStageTrainStep: reduction must be 'mean' or 'sum', got {reduction!r}")
+        neg_per_pos = float(neg_per_pos)
+        if not 0.0 <= neg_per_pos < float('inf'):
+            raise ValueError(f'TwoStageTrainStep: neg_per_pos must be a finite number >= 0, got {neg_per_pos}')
+        super().__init__(model, optimizer, clip_grad=clip_grad, amp=amp, use_graph=use_graph, compress_bf16=compress_bf16,
+                         accumulation_steps=accumulation_steps, lr_scheduler=lr_scheduler, overlap=overlap, group=group,
+                         start_update=start_update, meters=meters)
+        self.capacity, self.neg_per_pos, self.ordered_negatives, self.reduction = capacity, neg_per_pos, bool(ordered_negatives), reduction
+        self.mine_keys = None       # forced mining keys (fp32 [n * n]); None: drawn on the device in every call
+        self.last_mined = None      # the MinedPairs of the latest call
+
+    def _two_stage(self, x):
+        return True
+
+    def _check_batch(self, samples, targets):
+        """Everything ``step`` refuses, before any launch."""
+        for name in ('drop_path', 'patch_keep', 'pos_drop'):
+            if getattr(self, name) is not None:
+                raise ValueError(f'TwoStageTrainStep: step.{name} cannot be forced here (the two stages draw per image and per pair); '
+                                 f'leave it None')
+        if not torch.is_tensor(samples) or samples.dim() != 4:
+            raise ValueError(f'TwoStageTrainStep: samples must be images [n, C, S, S], got '
+                             f'{tuple(samples.shape) if torch.is_tensor(samples) else type(samples).__name__}')
+        n = samples.shape[0]
+        if not torch.is_tensor(targets) or targets.dtype.is_floating_point or targets.dtype == torch.bool or targets.numel() != n:
+            raise ValueError(f'TwoStageTrainStep: targets must be {n} integer labels, one per image of samples, got '
+                             f'{f"{targets.dtype} {tuple(targets.shape)}" if torch.is_tensor(targets) else type(targets).__name__}')
+        if samples.is_cuda and n > ops.mine_pairs_max_images():
+            raise ValueError(f'TwoStageTrainStep: samples holds {n} images, the mining kernel takes at most {ops.mine_pairs_max_images()}')
+        k = self.mine_keys
+        if k is not None and (not torch.is_tensor(k) or k.dtype != torch.float32 or k.numel() != n * n or k.device != targets.device
+                              or not k.is_contiguous()):
+            raise ValueError(f'TwoStageTrainStep: mine_keys must be {n * n} contiguous float32 values on {targets.device}, got '
+                             f'{f"{k.dtype} {tuple(k.shape)} on {k.device}" if torch.is_tensor(k) else type(k).__name__}')
+
+    def _fwd_dec_bwd(self, x, y):
+        """Stage 1: mining, encoder forward per image, decoder + head forward per pair, fused loss, decoder backward.
+        Returns (loss, features, d loss / d features)."""
+        with torch.autocast(self.device_type, dtype=torch.bfloat16, enabled=self.amp):
+            mined = mine_pairs_device(y, self.capacity, neg_per_pos=self.neg_per_pos, ordered_negatives=self.ordered_negatives,
+                                      keys=self.mine_keys)
+            feats = self.model(x, forward_first_part=True)
+            leaf = feats.detach().requires_grad_(True)
+            out = self.model(leaf, x, x2_index=mined.groups[:, 0], x1_index=mined.segments)
+            loss = mined_bce_fused(out, mined, self.reduction, scale=1.0 / self.accum)
+        loss.backward()
+        self.last_mined = mined
+        return loss.detach(), feats, leaf.grad
+
+    def _meter_loss(self, loss, y):
+        super()._meter_loss(loss, self.last_mined)        # n = counts[3], the real pairs
+
+    def step(self, samples, targets):
+        """One call of the loop body on what the loader yields.  Returns the (micro-batch) loss; ``last_norm`` holds the gradient norm
+        of the last update, ``last_mined`` the pairs of this call."""
+        self._check_batch(samples, targets)
+        return super().step(samples, targets)

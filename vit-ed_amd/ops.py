@@ -1309,3 +1309,6 @@ from .ops_tokendrop import (TOKEN_DROPOUT_MAX_DIM, dropout_threshold, philox4x32
 
 # ---- device-stepped learning-rate schedule: the wrapper of csrc/lr_schedule.hip and its table layout live in ops_lrsched.py -----------
 from .ops_lrsched import LR_MAX_MILESTONES, LR_TABLE_WORDS, lr_schedule_step  # noqa: E402,F401
+
+# ---- fused mined-pair loss: the wrapper of csrc/mined_bce.hip lives in ops_minedloss.py ---------------------------------------------
+from .ops_minedloss import MINED_BCE_MAX_CLASSES, mined_bce  # noqa: E402,F401
