@@ -38,7 +38,7 @@ extern "C" {
 
 #define VITED_F32 0
 #define VITED_BF16 1
-#define VITED_F16 2 /* vited_retrieval_metrics, vited_group_retrieval_metrics and vited_pair_scores_add only */
+#define VITED_F16 2 /* the ranking entries (vited_retrieval_*, vited_group_retrieval_metrics) and vited_pair_scores_add only */
 #define VITED_I32 3 /* integer index dtypes (vited_pair_scores_add) */
 #define VITED_I64 4
 
@@ -668,6 +668,33 @@ int vited_attention_cam(const void* q, int64_t q_bs, int64_t q_ts, const void* k
 int vited_retrieval_metrics(const void* D, int dtype, int64_t ld, int64_t n, int64_t r0, int64_t r1, const int* labels,
                             const int* offsets, const int* members, int num_classes, int remove_self_column, int from_similarity,
                             double* rows_out, double* sums, void* stream);
+
+/* ---- evaluation: ranked retrieval lists and the wi19 ROC / F-score counts (wi19_evaluate.get_sorted_retrievals, compute_roc,
+ *      compute_fscore; hisfrag_visualize_results.py's nlargest) ------ */
+
+/* The first k retrievals of the rows [r0, r1) of an n x n matrix D (dtype, ld, from_similarity and the order as in
+ * vited_retrieval_metrics: ascending by (value, column), ties to the lower column, NaN after +inf, -0 tied with +0).  With
+ * remove_self_column = 1 (skip = 1) the first element of that order is dropped, whatever column it is; otherwise skip = 0.
+ *   labels int32 [n], read only when hit is given; may be null otherwise
+ *   idx    int32   [(r1 - r0) x k]: the columns at positions skip .. skip + k - 1 of the row's order
+ *   val    float32 [(r1 - r0) x k]: the value each was ranked by, D[i, j] or dtype(1 - D[i, j]), widened
+ *   hit    uint8   [(r1 - r0) x k], or null (not wanted): labels[idx] == labels[i]
+ * Every output element is written exactly once; identical inputs give bit-identical outputs.  One launch, no workspace.
+ * VITED_ERR_BAD_ARG: D, idx or val null; hit without labels; n < 1 or ld < n; rows not a non-empty range inside [0, n); a flag
+ * other than 0 / 1; k < 1 or k + skip > n; a misaligned D.  VITED_ERR_UNSUPPORTED: an unknown dtype; k > 1024. */
+int vited_retrieval_topk(const void* D, int dtype, int64_t ld, int64_t n, int64_t r0, int64_t r1, const int* labels, int k,
+                         int remove_self_column, int from_similarity, int* idx, float* val, uint8_t* hit, void* stream);
+
+/* The counts behind compute_roc and compute_fscore for the rows [r0, r1): the row kernel of vited_retrieval_metrics (same
+ * arguments, same order, same checks), recording for every correct retrieval of row i its 0-based position pos after the drop.
+ *   estimate int32 [n], or null: the per-row relevant_estimate of compute_fscore
+ *   tp_at    uint64 [n - skip], ADDED onto (zero it before the first share): correct retrievals at each position, i.e.
+ *            sorted_retrievals.sum(axis=0) over the rows of the call.  Integer adds: bit-identical whatever their order.
+ *   rows_out int32 [(r1 - r0) x 2]: correct retrievals of the row, and those at positions pos < estimate[i] (0 without estimate)
+ * One launch, no workspace.  VITED_ERR_BAD_ARG as vited_retrieval_metrics, and for a null or misaligned tp_at or a null rows_out. */
+int vited_retrieval_curves(const void* D, int dtype, int64_t ld, int64_t n, int64_t r0, int64_t r1, const int* labels,
+                           const int* offsets, const int* members, int num_classes, int remove_self_column, int from_similarity,
+                           const int* estimate, uint64_t* tp_at, int* rows_out, void* stream);
 
 /* ---- evaluation: group mAP / Pr@k of a distance matrix (misc/metric.calc_map_prak) ------------- */
 

@@ -13,32 +13,21 @@
 // More than CHUNK correct columns repeat 1-3 per chunk; a second histogram, filled from the correct columns of every chunk,
 // then counts the correct columns ordered before each staged one.  With skip_first the first element of the order (rank 0) is
 // dropped whatever column it is, as the reference drops sorted_indexes[:, 1:].  A second launch sums the row records in a
-// fixed order: the result is bit-identical run to run.
+// fixed order: the result is bit-identical run to run.  vited_retrieval_curves is the wi19 instance of the same kernel under the
+// record policy CurveRecord: the positions of the correct columns counted per position (compute_roc / compute_fscore), one launch.
+// The order itself (order_bits, make_key, rank_value) is rank_key.h's, shared with rank_lists.hip.
 #include "common.h"
+#include "rank_key.h"
+#include "rank_row.h"
 
 namespace {
 
 constexpr int THREADS = 256;
 constexpr int CHUNK = 2048;                  // correct columns per pass: 16 KB of keys + 2 x 8 KB of histograms in LDS
 constexpr int MAX_K = 8;
-constexpr uint64_t PAD_KEY = ~0ull;          // above every real key (a real key's low word is a column index < 2^31)
 
-typedef _Float16 f16;
-
-__device__ __forceinline__ float load_f32(const float* p) { return *p; }
-__device__ __forceinline__ float load_f32(const bf16* p) { return (float)*p; }
-__device__ __forceinline__ float load_f32(const f16* p) { return (float)*p; }
-
-// Order-preserving 32-bit image of a float: every NaN maps above +inf (to one value, so NaNs tie and fall back to the column
-// order), -0 ties with +0.
-__device__ __forceinline__ uint32_t order_bits(float v) {
-    if (v != v) return 0xffffffffu;
-    if (v == 0.0f) v = 0.0f;
-    const uint32_t u = __float_as_uint(v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-__device__ __forceinline__ uint64_t make_key(float v, int64_t j) { return ((uint64_t)order_bits(v) << 32) | (uint32_t)j; }
+using namespace rank_key;                    // order_bits, make_key, rank_value, PAD_KEY
+using namespace rank_row;                    // f16, load_f32, Vec, unpack, unpack_half
 
 // Number of keys[0, p2) that are <= k (keys ascending, padded with PAD_KEY to the power of two p2).
 __device__ __forceinline__ int count_le(const uint64_t* keys, int p2, uint64_t k) {
@@ -46,18 +35,6 @@ __device__ __forceinline__ int count_le(const uint64_t* keys, int p2, uint64_t k
     for (int s = p2; s > 0; s >>= 1)
         if (pos + s <= p2 && keys[pos + s - 1] <= k) pos += s;
     return pos;
-}
-
-template <typename T> struct Vec;          // 16-byte loads: 4 fp32 or 8 half-width values
-template <> struct Vec<float> { static constexpr int N = 4; typedef float4 type; };
-template <> struct Vec<bf16> { static constexpr int N = 8; typedef uint4 type; };
-template <> struct Vec<f16> { static constexpr int N = 8; typedef uint4 type; };
-
-__device__ __forceinline__ void unpack(const float4& v, float* out) { out[0] = v.x; out[1] = v.y; out[2] = v.z; out[3] = v.w; }
-template <typename T> __device__ __forceinline__ void unpack_half(const uint4& v, float* out) {
-    const T* h = reinterpret_cast<const T*>(&v);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) out[e] = (float)h[e];
 }
 
 // Inclusive prefix sum of h[0, cnt) in place (cnt <= CHUNK = THREADS * 8): each thread scans 8 consecutive bins.
@@ -260,15 +237,25 @@ struct LabelSet {
     }
 };
 
-// The value the row is ranked by: D itself, or T(1 - S) (fp32 subtract, one rounding to T) when the matrix holds similarities.
-template <typename T> __device__ __forceinline__ float rank_value(float v, bool from_similarity) {
-    return from_similarity ? (float)(T)(1.0f - v) : v;
-}
+// What else the row kernel records of the positions it finds.  NoRecord: nothing, the row record of the relation is all.
+struct NoRecord {
+    static constexpr bool ON = false;
+};
 
-template <typename T, typename Rel>
+// The wi19 curves (vited_retrieval_curves; compute_roc / compute_fscore of the reference): every correct column at 0-based position
+// pos after the drop adds 1 to tp_at[pos] - 64-bit integer adds, whose sum does not depend on their order - and the row record is
+// the int32 pair (correct retrievals, correct retrievals at positions < estimate[i]) instead of the relation's.
+struct CurveRecord {
+    static constexpr bool ON = true;
+    unsigned long long* tp_at;               // [n - skip], added onto
+    const int* estimate;                     // [n], or null: the second count stays 0
+    int* rows;                               // [(r1 - r0) x 2]
+};
+
+template <typename T, typename Rel, typename Rec>
 __global__ void __launch_bounds__(THREADS) rank_rows_kernel(const T* __restrict__ D, int64_t ld, int64_t n, int64_t r0,
                                                             const int* __restrict__ labels, Rel rel, int skip_first,
-                                                            int from_similarity, double* __restrict__ rows_out) {
+                                                            int from_similarity, double* __restrict__ rows_out, Rec rec) {
     __shared__ uint64_t keys[CHUNK];
     __shared__ uint32_t below_all[CHUNK];      // eligible elements ordered before staged column s (after the scan)
     __shared__ uint32_t below_pos[CHUNK];      // correct columns ordered before staged column s (after the scan)
@@ -295,6 +282,9 @@ __global__ void __launch_bounds__(THREADS) rank_rows_kernel(const T* __restrict_
 #pragma unroll
     for (int q = 0; q < Rel::NH; ++q) hits[q] = 0;
     bool dropped_is_pos = false;
+    int in_estimate = 0;                             // CurveRecord only
+    int64_t estimate = 0;
+    if constexpr (Rec::ON) estimate = rec.estimate ? (int64_t)rec.estimate[i] : 0;
 
     for (int ch = 0; ch < nchunks; ++ch) {
         const int64_t cbeg = (int64_t)ch * CHUNK;
@@ -373,6 +363,10 @@ __global__ void __launch_bounds__(THREADS) rank_rows_kernel(const T* __restrict_
             ++correct;
 #pragma unroll
             for (int q = 0; q < Rel::NH; ++q) hits[q] += pos < rel.cut(q);
+            if constexpr (Rec::ON) {
+                if (pos < n - (skip_first ? 1 : 0)) atomicAdd(&rec.tp_at[pos], 1ull);
+                in_estimate += pos < estimate;
+            }
         }
         __syncthreads();                                  // keys / histograms are rewritten by the next chunk
     }
@@ -399,7 +393,20 @@ __global__ void __launch_bounds__(THREADS) rank_rows_kernel(const T* __restrict_
             a += red_d[w];
             for (int f = 0; f < 1 + Rel::NH; ++f) s[f] += red_i[f][w];
         }
-        rel.write(rows_out + (int64_t)blockIdx.x * rel.rec_len(), a, s);
+        if constexpr (!Rec::ON) rel.write(rows_out + (int64_t)blockIdx.x * rel.rec_len(), a, s);
+        else rec.rows[(int64_t)blockIdx.x * 2] = s[0];
+    }
+    if constexpr (Rec::ON) {                          // the second count, summed like the first
+        __shared__ int red_e[THREADS / 64];
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) in_estimate += __shfl_xor(in_estimate, off, 64);
+        if (lane == 0) red_e[wave] = in_estimate;
+        __syncthreads();
+        if (t == 0) {
+            int e = 0;
+            for (int w = 0; w < THREADS / 64; ++w) e += red_e[w];
+            rec.rows[(int64_t)blockIdx.x * 2 + 1] = e;
+        }
     }
 }
 
@@ -460,10 +467,12 @@ __global__ void __launch_bounds__(THREADS) group_sum_kernel(const double* __rest
 }
 
 // The checks both entries share, then the row kernel for the dtype.  Entry-specific checks (all VITED_ERR_BAD_ARG) come first.
-template <typename Rel>
+template <typename Rel, typename Rec = NoRecord>
 int launch_rows(const void* D, int dtype, int64_t ld, int64_t n, int64_t r0, int64_t r1, const int* labels, int num_labels,
-                const Rel& rel, int skip_first, int from_similarity, double* rows_out, double* sums, hipStream_t st) {
-    if (!D || !labels || !rows_out || !sums) return VITED_ERR_BAD_ARG;
+                const Rel& rel, int skip_first, int from_similarity, double* rows_out, double* sums, hipStream_t st,
+                const Rec& rec = Rec()) {
+    if (!D || !labels) return VITED_ERR_BAD_ARG;
+    if (!Rec::ON && (!rows_out || !sums)) return VITED_ERR_BAD_ARG;
     if (n < 1 || n > INT32_MAX - 1 || ld < n || num_labels < 1 || num_labels > n) return VITED_ERR_BAD_ARG;
     if (r0 < 0 || r1 <= r0 || r1 > n) return VITED_ERR_BAD_ARG;
     const int esize = dtype == VITED_F32 ? 4 : 2;
@@ -471,9 +480,9 @@ int launch_rows(const void* D, int dtype, int64_t ld, int64_t n, int64_t r0, int
     if (r1 - r0 > INT32_MAX) return VITED_ERR_UNSUPPORTED;
     const dim3 grid((unsigned)(r1 - r0));
     switch (dtype) {
-        case VITED_F32: hipLaunchKernelGGL((rank_rows_kernel<float, Rel>), grid, dim3(THREADS), 0, st, static_cast<const float*>(D), ld, n, r0, labels, rel, skip_first, from_similarity, rows_out); break;
-        case VITED_BF16: hipLaunchKernelGGL((rank_rows_kernel<bf16, Rel>), grid, dim3(THREADS), 0, st, static_cast<const bf16*>(D), ld, n, r0, labels, rel, skip_first, from_similarity, rows_out); break;
-        case VITED_F16: hipLaunchKernelGGL((rank_rows_kernel<f16, Rel>), grid, dim3(THREADS), 0, st, static_cast<const f16*>(D), ld, n, r0, labels, rel, skip_first, from_similarity, rows_out); break;
+        case VITED_F32: hipLaunchKernelGGL((rank_rows_kernel<float, Rel, Rec>), grid, dim3(THREADS), 0, st, static_cast<const float*>(D), ld, n, r0, labels, rel, skip_first, from_similarity, rows_out, rec); break;
+        case VITED_BF16: hipLaunchKernelGGL((rank_rows_kernel<bf16, Rel, Rec>), grid, dim3(THREADS), 0, st, static_cast<const bf16*>(D), ld, n, r0, labels, rel, skip_first, from_similarity, rows_out, rec); break;
+        case VITED_F16: hipLaunchKernelGGL((rank_rows_kernel<f16, Rel, Rec>), grid, dim3(THREADS), 0, st, static_cast<const f16*>(D), ld, n, r0, labels, rel, skip_first, from_similarity, rows_out, rec); break;
         default: return VITED_ERR_UNSUPPORTED;
     }
     return vited_check_launch();
@@ -513,4 +522,17 @@ extern "C" int vited_group_retrieval_metrics(const void* D, int dtype, int64_t l
     if (rc != VITED_OK) return rc;
     hipLaunchKernelGGL(group_sum_kernel, dim3(1), dim3(THREADS), 0, st, rows_out, r1 - r0, rel.ks, nk, sums);
     return vited_check_launch();
+}
+
+extern "C" int vited_retrieval_curves(const void* D, int dtype, int64_t ld, int64_t n, int64_t r0, int64_t r1, const int* labels,
+                                      const int* offsets, const int* members, int num_classes, int remove_self_column,
+                                      int from_similarity, const int* estimate, uint64_t* tp_at, int* rows_out, void* stream) {
+    if (!offsets || !members || !tp_at || !rows_out) return VITED_ERR_BAD_ARG;
+    if ((remove_self_column != 0 && remove_self_column != 1) || (from_similarity != 0 && from_similarity != 1)) return VITED_ERR_BAD_ARG;
+    if (remove_self_column && n < 2) return VITED_ERR_BAD_ARG;       // no column would be left to retrieve
+    if (reinterpret_cast<uintptr_t>(tp_at) % 8 != 0) return VITED_ERR_BAD_ARG;
+    ClassSlice rel = {offsets, members, num_classes, 0, 0, 0};
+    CurveRecord rec = {reinterpret_cast<unsigned long long*>(tp_at), estimate, rows_out};
+    return launch_rows(D, dtype, ld, n, r0, r1, labels, num_classes, rel, remove_self_column, from_similarity, nullptr, nullptr,
+                       static_cast<hipStream_t>(stream), rec);
 }

@@ -12,9 +12,10 @@ from .distributed import FlatGradients, broadcast_parameters, configure_ddp  # n
 from .feeds import (HISFRAG_PLAN_COLUMNS, MICHIGAN_MAX_HOLES, MICHIGAN_PLAN_COLUMNS, DevicePrefetcher, Div2kDeviceLoader,  # noqa: F401
                     Div2kImageStore, HisfragDeviceLoader, HisfragPlan, MichiganDeviceLoader, MichiganPlan, assemble_pairs,
                     div2k_augment_plan, div2k_pair_plan, hisfrag_augment_plan, hisfrag_feed, michigan_augment_plan, michigan_feed)
-from .metrics import (ClassificationMeters, GeshaemMetrics, MeterValue, PairScoreAggregator, PairScoreStats, ValidationResult,  # noqa: F401
-                      class_members, geshaem_pair_metrics, group_relations, hisfrag_retrieval_metrics, map_prak, metrics_from_sums,
-                      retrieval_metrics, validate_classifier)
+from .metrics import (ClassificationMeters, GeshaemMetrics, MeterValue, PairScoreAggregator, PairScoreStats, RetrievalCurves,  # noqa: F401
+                      RetrievalLists, ValidationResult, class_members, geshaem_pair_metrics, group_relations,
+                      hisfrag_retrieval_lists, hisfrag_retrieval_metrics, map_prak, metrics_from_sums, retrieval_curves,
+                      retrieval_metrics, retrieval_topk, validate_classifier)
 from .mining import (MinedPairs, hisfrag_prepare_data, hisfrag_prepare_indexed, hisfrag_prepare_mined, mine_pairs,  # noqa: F401
                      mine_pairs_device, mined_bce_fused, mined_bce_with_logits, mined_pair_capacity)
 from .puzzle import (PUZZLE_SIDES, PuzzleCompatibility, PuzzleSolution, puzzle_accuracy, puzzle_distances,  # noqa: F401

@@ -89,6 +89,149 @@ def hisfrag_retrieval_metrics(similarity: torch.Tensor, labels, *, rank: int = 0
                              from_similarity=True, group=group if world > 1 else None)
 
 
+# ---- ranked retrieval lists (wi19_evaluate.get_sorted_retrievals, hisfrag_visualize_results.py) and the ROC / F-score curves
+def _row_range(n, rows):
+    r0, r1 = (0, n) if rows is None else (int(rows[0]), int(rows[1]))
+    if not 0 <= r0 <= r1 <= n:
+        raise ValueError(f'rows ({r0}, {r1}) is not a range inside [0, {n}]')
+    return r0, r1
+
+
+def _class_labels(labels, n, device):
+    labels = torch.as_tensor(labels, device=device)
+    if labels.dim() != 1 or labels.numel() != n:
+        raise ValueError(f'labels must be a vector of length {n}, got shape {tuple(labels.shape)}')
+    if labels.is_floating_point() or labels.is_complex():
+        raise TypeError(f'labels must be integer class ids, got {labels.dtype}')
+    return labels
+
+
+class RetrievalLists(NamedTuple):
+    """``retrieval_topk``: ``indices`` int32 [rows, k] the retrieved columns in rank order, ``values`` float32 [rows, k] the values
+    they were ranked by, ``correct`` uint8 [rows, k] (1 where the hit has the row's label) or None without labels."""
+    indices: torch.Tensor
+    values: torch.Tensor
+    correct: torch.Tensor | None
+
+
+def retrieval_topk(distance: torch.Tensor, k: int, *, labels=None, rows=None, remove_self_column: bool = True,
+                   from_similarity: bool = False) -> RetrievalLists:
+    """The ``k`` nearest columns of every row of ``rows`` (default: all), on the GPU, without the [n, n] matrix on the host.
+
+    The order is the one ``retrieval_metrics`` ranks by: ascending by (value, column) - a STABLE argsort, ties to the lower column,
+    NaN last - of ``distance`` (with ``from_similarity``: of dtype(1 - S)), the first element dropped with ``remove_self_column``
+    whatever column it is.  Without ties it is ``np.argsort(D, axis=1)[:, skip:skip + k]``; with ``labels`` (int class ids [n])
+    ``correct`` is ``wi19_evaluate.get_sorted_retrievals(D, labels, remove_self_column)[:, :k]``.  1 <= k <= 1024, k + skip <= n."""
+    n = distance.shape[0]
+    r0, r1 = _row_range(n, rows)
+    ids = None
+    if labels is not None:
+        ids = torch.unique(_class_labels(labels, n, distance.device), return_inverse=True)[1].to(torch.int32)
+    if r1 == r0:
+        k = int(k)
+        empty = lambda dtype: torch.empty((0, k), dtype=dtype, device=distance.device)
+        return RetrievalLists(empty(torch.int32), empty(torch.float32), None if ids is None else empty(torch.uint8))
+    return RetrievalLists(*ops.retrieval_topk_rows(distance, k, (r0, r1), ids, remove_self_column=remove_self_column,
+                                                   from_similarity=from_similarity))
+
+
+@torch.no_grad()
+def hisfrag_retrieval_lists(similarity: torch.Tensor, k: int, labels=None, *, rank: int = 0, world: int = 1,
+                            group=None) -> RetrievalLists:
+    """The ``k`` most similar fragments of every fragment, after ``pairwise_similarity``: every rank holds the [n, n] similarity,
+    ranks the rows ``shard_rows_by_pair_count(n, world)`` gives it by dtype(1 - similarity) behind the dropped first hit (the query
+    itself), and ONE all-reduce (SUM of zero-initialised buffers over disjoint row shares, so gloo works too) gives every rank the
+    lists of all n rows.  Replaces the CSV of the matrix and, per fragment (scripts/hisfrag_visualize_results.py),
+
+        similarity_matrix[col].nlargest(k + 1)[1:]
+
+    with ``hisfrag_retrieval_lists(similarity, k)``: ``indices[i]`` are the columns, ``1 - values[i]`` the similarities."""
+    n = similarity.shape[0]
+    bounds = shard_rows_by_pair_count(n, world)
+    r0, r1 = bounds[rank], bounds[rank + 1]
+    part = retrieval_topk(similarity, k, labels=labels, rows=(r0, r1), remove_self_column=True, from_similarity=True)
+    if world == 1:
+        return part
+    # one int32 buffer [3, n, k]: columns, value bits, hits - integer sums with zeros keep every bit pattern
+    both = torch.zeros((3, n, int(k)), dtype=torch.int32, device=similarity.device)
+    both[0, r0:r1] = part.indices
+    both[1, r0:r1] = part.values.view(torch.int32)
+    if part.correct is not None:
+        both[2, r0:r1] = part.correct
+    dist.all_reduce(both, op=dist.ReduceOp.SUM, group=dist.group.WORLD if group is None else group)
+    return RetrievalLists(both[0], both[1].view(torch.float32), None if part.correct is None else both[2].to(torch.uint8))
+
+
+def _ratio(num, den):
+    """num / den in float64 with numpy's zero rule: 0 / 0 is NaN, x / 0 is +-inf."""
+    return (torch.tensor(float(num), dtype=torch.float64) / torch.tensor(float(den), dtype=torch.float64)).item()
+
+
+class RetrievalCurves(NamedTuple):
+    """``retrieval_curves``: ``tp_at`` int64 [n - skip] = ``sorted_retrievals.sum(axis=0)`` over the ``rows`` ranked rows,
+    ``relevant`` = ``sorted_retrievals.sum()``, and with a ``relevant_estimate`` ``tp_in_estimate`` = the correct retrievals inside
+    each row's estimate and ``retrieved`` = the sum of the estimates (both None without one)."""
+    tp_at: torch.Tensor
+    rows: int
+    relevant: int
+    tp_in_estimate: int | None
+    retrieved: int | None
+
+    def roc(self) -> dict:
+        """``wi19_evaluate.compute_roc(sorted_retrievals)``: {'fallout', 'recall'}, float64 [n - skip] - int64 cumulative sums,
+        converted to float64, one division each; a zero denominator gives NaN."""
+        tp = torch.cumsum(self.tp_at, 0).to(torch.float64)
+        fp_at = self.rows - self.tp_at
+        fp = torch.cumsum(fp_at, 0).to(torch.float64)
+        negatives = fp_at.sum().to(torch.float64)                     # (1 - sorted_retrievals).sum(): FP + TN
+        return {'fallout': fp / negatives, 'recall': tp / torch.full_like(tp, float(self.relevant))}
+
+    def fscore(self) -> tuple:
+        """``wi19_evaluate.compute_fscore(sorted_retrievals, relevant_estimate)``: (fscore, precision, recall)."""
+        if self.tp_in_estimate is None:
+            raise ValueError('fscore() needs the curves of a relevant_estimate: pass one to retrieval_curves')
+        precision = _ratio(self.tp_in_estimate, self.retrieved)
+        recall = _ratio(self.tp_in_estimate, self.relevant)
+        two = torch.tensor([precision, recall], dtype=torch.float64)
+        return (2 * two[0] * two[1] / (two[0] + two[1])).item(), precision, recall
+
+
+def retrieval_curves(distance: torch.Tensor, labels, *, rows=None, remove_self_column: bool = True, from_similarity: bool = False,
+                     relevant_estimate=None, group=None) -> RetrievalCurves:
+    """The counts behind ``wi19_evaluate.compute_roc`` and ``compute_fscore`` of ``get_sorted_retrievals(distance, labels,
+    remove_self_column)``, on the GPU: the row kernel of ``retrieval_metrics`` (same order, same arguments) also counts, per
+    position, the rows with a correct retrieval there.  ``relevant_estimate``: int [n], the per-row estimate of ``compute_fscore``.
+    ``rows=(r0, r1)`` computes this rank's share; with ``group`` ONE int64 SUM all-reduce combines the shares and every rank returns
+    the curves of all rows.  Without a group the result covers ``rows`` only."""
+    n = distance.shape[0]
+    dev = distance.device
+    labels = _class_labels(labels, n, dev)
+    r0, r1 = _row_range(n, rows)
+    skip = 1 if remove_self_column else 0
+    estimate = None
+    if relevant_estimate is not None:
+        estimate = torch.as_tensor(relevant_estimate, device=dev)
+        if estimate.dim() != 1 or estimate.numel() != n or estimate.is_floating_point() or estimate.is_complex():
+            raise ValueError(f'relevant_estimate must be an integer vector of length {n}, got {estimate.dtype} {tuple(estimate.shape)}')
+        estimate = estimate.clamp(-1, n).to(torch.int32)             # beyond [0, n - skip] an estimate selects nothing more
+    # [tp_at (n - skip), rows, relevant, tp_in_estimate, retrieved]
+    state = torch.zeros(max(n - skip, 0) + 4, dtype=torch.int64, device=dev)
+    if r1 > r0:
+        ids, offsets, members = class_members(labels)
+        tp_at, records = ops.retrieval_curve_rows(distance, ids, offsets, members, (r0, r1), remove_self_column=remove_self_column,
+                                                  from_similarity=from_similarity, estimate=estimate)
+        state[:n - skip] = tp_at
+        state[n - skip] = r1 - r0
+        state[n - skip + 1:n - skip + 3] = records.sum(0, dtype=torch.int64)
+        if relevant_estimate is not None:
+            state[n - skip + 3] = torch.as_tensor(relevant_estimate, device=dev)[r0:r1].sum(dtype=torch.int64)
+    if group is not None:
+        dist.all_reduce(state, op=dist.ReduceOp.SUM, group=group)
+    tail = state[n - skip:].tolist()
+    with_estimate = relevant_estimate is not None
+    return RetrievalCurves(state[:n - skip], tail[0], tail[1], tail[2] if with_estimate else None, tail[3] if with_estimate else None)
+
+
 # ---- group mAP / Pr@k (misc/metric.calc_map_prak) and the geshaem evaluation (michigan.py:188-233)
 def _relation_csr(uniq, id_of, relation, row_ids, device):
     """(offsets int32 [L + 1], label ids int32): for every label id a whose label is in ``row_ids``, the ascending, duplicate-free

@@ -1312,3 +1312,7 @@ from .ops_lrsched import LR_MAX_MILESTONES, LR_TABLE_WORDS, lr_schedule_step  # 
 
 # ---- fused mined-pair loss: the wrapper of csrc/mined_bce.hip lives in ops_minedloss.py ---------------------------------------------
 from .ops_minedloss import MINED_BCE_MAX_CLASSES, mined_bce  # noqa: E402,F401
+
+# ---- ranked retrieval lists and the wi19 curve counts: the wrappers of csrc/rank_lists.hip and of the curve record of
+# csrc/rank_metrics.hip live in ops_ranklists.py -----------------------------------------------------------------------------------
+from .ops_ranklists import TOPK_MAX_K, retrieval_curve_rows, retrieval_topk_rows  # noqa: E402,F401
