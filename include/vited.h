@@ -831,6 +831,39 @@ int vited_mine_pairs(const int64_t* targets, int n, const float* keys, double ne
 int vited_mined_bce(const float* logits, const float* labels, const float* weights, const int32_t* counts, int64_t rows,
                     int64_t classes, int mean, float scale, float* loss, float* dlogits, void* stream);
 
+/* ---- puzzle solving: the classical baseline's pixel work (solver_driver.py; paikin_tal_solver/puzzle_importer.py:182-232, :265-321,
+ *      :448-473; puzzle_piece.py:535-609), type-1 puzzles -------------------------------------------------------------------------------
+ * Images, pieces and boards are uint8, HWC with 3 channels, contiguous DEVICE memory; csrc/puzzle_pixels.h states every rule.  n
+ * pieces of eroded_width x eroded_width (We >= 2) cut from cells of piece_width x piece_width (P >= We).  Every output byte is written
+ * exactly once by plain stores: the same bits on every call.  No host read, no synchronisation.
+ *
+ * vited_puzzle_cut == Puzzle.make_pieces: rows = height / P, cols = width / P, n = rows * cols; the grid is centred on the image
+ *   (origin ((height - rows P) / 2, (width - cols P) / 2)); a piece is the centre crop of its cell at offset
+ *   int(round((P - We) / 2.0)) (half to even).  pieces [n, We, We, 3]; piece k is cell order[k] (row-major; order int32 [n], a
+ *   permutation the caller validated - an id outside [0, n) is clamped) or cell k without order.
+ * vited_puzzle_resize_pieces: pieces [n, We, We, 3] -> out [n, 3, size, size], Pillow's 8-bit BILINEAR resize of each piece (22-bit
+ *   fixed-point weights, horizontal pass into 8 bits, then vertical), size >= We (upscaling), size <= 1024: what
+ *   vited_patchify_u8 takes.
+ * vited_puzzle_pixel_distances == calculate_asymmetric_distance over all ordered pairs: dq int32 [4, n, n],
+ *   dq[s, i, j] = sum over the 3 We border values of | 2 B_s(i) - B'_s(i) - B_(s+2)%4(j) |, B the border line of a side and B' the line
+ *   next to it (top / bottom in column order, left / right in row order); the diagonal is 2^31 - 1.  n >= 2.  765 * 3 * We fits int32
+ *   up to We = 935722.  workspace >= vited_puzzle_pixel_distances_workspace_bytes(n, We) bytes (-1: bad n or We), 8-byte aligned.
+ * vited_puzzle_assemble == Puzzle.reconstruct_from_pieces: board [rows P, cols P, 3], rows * cols = n.  cells int32 [rows * cols]:
+ *   -1 for an empty cell (black), else 2 * piece + framed (a piece id outside [0, n) is drawn as empty).  The piece lies at
+ *   (r P + pad, c P + pad), pad = (P - We) / 2; with marker >= 0 (the colour, channel c in bits 8 c .. 8 c + 7) a framed piece gets
+ *   a one-pixel ring of it; marker < 0: no frames.  Everything else is black.
+ * VITED_ERR_BAD_ARG: a null pointer (order may be null), We < 2, P < We, n != rows * cols, size < We, n < 2 for the distances, a
+ *   marker >= 0 with pad < 1 (the frame needs the pixel) or above 0xffffff, a misaligned workspace.  VITED_ERR_UNSUPPORTED: n > 46340,
+ *   We > 935722, size > 1024.  VITED_ERR_WORKSPACE: a workspace too small. */
+int vited_puzzle_cut(const uint8_t* image, int64_t height, int64_t width, int piece_width, int eroded_width, const int* order,
+                     int64_t n, uint8_t* pieces, void* stream);
+int vited_puzzle_resize_pieces(const uint8_t* pieces, int64_t n, int eroded_width, int size, uint8_t* out, void* stream);
+int64_t vited_puzzle_pixel_distances_workspace_bytes(int64_t n, int eroded_width);
+int vited_puzzle_pixel_distances(const uint8_t* pieces, int64_t n, int eroded_width, int* dq, void* workspace,
+                                 int64_t workspace_bytes, void* stream);
+int vited_puzzle_assemble(const uint8_t* pieces, int64_t n, int eroded_width, int piece_width, const int* cells, int64_t rows,
+                          int64_t cols, int marker, uint8_t* board, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,7 @@
 """Puzzle evaluation (evaluation.py:100-133, solver_driver.py, paikin_tal_solver/) for type-1 puzzles of one image, fixed size:
 the piece distances from the model's logits, the Paikin-Tal solver with its compatibilities on the device, and the reference's
-accuracies."""
+accuracies; and the classical baseline of solver_driver.py around the same solver - the image cut into eroded pieces, the
+prediction-based border distances of the pieces' pixels, the solved board as an image."""
 from __future__ import annotations
 
 import heapq
@@ -278,3 +279,58 @@ def puzzle_accuracy(solution: PuzzleSolution, true_locations) -> dict:
             got = int(placed_id[r, c]) if 0 <= r < g_rows and 0 <= c < g_cols else -1
             neighbors += (None if got < 0 else got) == want
     return {'Direct_Standard': standard / n, 'Direct_Modified': modified / n, 'neighbor': neighbors / (4 * n), 'perfect': standard == n}
+
+
+# ---- the classical baseline (solver_driver.py): cut, pixel distances, board --------------------------------------------------------
+class PuzzleCut(NamedTuple):
+    pieces: 'object'            # uint8 [n, We, We, 3] on the device, in the solver's order
+    true_locations: 'object'    # int64 [n, 2] (host): the cell (row, col) each piece was cut from
+    grid_size: tuple            # (rows, cols)
+    piece_width: int            # P, the cell's width before the erosion crop
+
+
+def cut_puzzle(image, piece_width: int, erosion: float = 0., order=None) -> PuzzleCut:
+    """Puzzle(0, path, piece_width, erosion=erosion).pieces on the device (puzzle_importer.py:182-232): ``image`` uint8 [H, W, 3] (any
+    3-channel image: the colour conversion is the caller's) cut into (H // P) x (W // P) cells of the centred grid, each centre-cropped to
+    We = min(ceil(P (1 - erosion)), P).  ``order`` (a permutation of the row-major cells, host integers) is the driver's
+    random.shuffle made explicit: piece k is cell order[k]."""
+    import numpy as np
+    P = int(piece_width)
+    if P < 1:
+        raise ValueError(f'cut_puzzle: piece_width must be positive, got {piece_width}')
+    image = torch.as_tensor(image)
+    if not image.is_cuda and torch.cuda.is_available():        # a host image is uploaded; without a GPU ops refuses it
+        image = image.cuda()
+    image = image.contiguous()
+    rows, cols = (image.shape[0] // P, image.shape[1] // P) if image.dim() == 3 else (0, 0)
+    pieces = ops.puzzle_cut(image, P, ops.puzzle_eroded_width(P, erosion), order)
+    cell = np.arange(rows * cols) if order is None else np.asarray(order.cpu() if isinstance(order, torch.Tensor) else order, dtype=np.int64)
+    return PuzzleCut(pieces, np.stack([cell // cols, cell % cols], axis=1).astype(np.int64), (rows, cols), P)
+
+
+def puzzle_model_pieces(pieces, size: int):
+    """The pieces of ``cut_puzzle`` at the model's size, uint8 [n, 3, size, size]: TwoImgSyncEval's Resize on each piece (Pillow's
+    8-bit bilinear resample, bit for bit), the input of ``puzzle_distances``."""
+    return ops.puzzle_resize_pieces(pieces, size)
+
+
+def puzzle_pixel_distances(pieces):
+    """Dq int32 [4, n, n] of PuzzlePiece.calculate_asymmetric_distance (puzzle_piece.py:535-609) over all ordered pairs and sides of
+    the pieces uint8 [n, We, We, 3] of ``cut_puzzle``: what ``solve_puzzle`` takes, as it takes ``puzzle_distances``' ."""
+    return ops.puzzle_pixel_distances(pieces)
+
+
+def reconstruct_puzzle(pieces, solution, true_locations, piece_width: int, marker=None):
+    """Puzzle.reconstruct_from_pieces (puzzle_importer.py:265-321, :448-473): the board uint8 [R P, C P, 3] of the pieces at
+    ``solution.locations`` (a ``PuzzleSolution``, or the locations themselves).  With ``marker`` (three bytes; the reference's is BGR
+    (0, 0, 255)) every piece away from its true location is framed, which needs (P - We) // 2 >= 1."""
+    return ops.puzzle_assemble(pieces, getattr(solution, 'locations', solution), true_locations, piece_width, marker)
+
+
+def solve_pixel_puzzle(image, piece_width: int, erosion: float = 0., order=None, marker=None):
+    """One pass of solver_driver.py's loop on the device: cut, pixel distances, Paikin-Tal, accuracies, board.  Returns
+    (``PuzzleSolution``, the dict of ``puzzle_accuracy``, board uint8 [R P, C P, 3])."""
+    cut = cut_puzzle(image, piece_width, erosion, order)
+    solution = solve_puzzle(puzzle_pixel_distances(cut.pieces), cut.grid_size)
+    board = reconstruct_puzzle(cut.pieces, solution, cut.true_locations, cut.piece_width, marker)
+    return solution, puzzle_accuracy(solution, cut.true_locations), board

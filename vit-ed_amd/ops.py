@@ -1316,3 +1316,7 @@ from .ops_minedloss import MINED_BCE_MAX_CLASSES, mined_bce  # noqa: E402,F401
 # ---- ranked retrieval lists and the wi19 curve counts: the wrappers of csrc/rank_lists.hip and of the curve record of
 # csrc/rank_metrics.hip live in ops_ranklists.py -----------------------------------------------------------------------------------
 from .ops_ranklists import TOPK_MAX_K, retrieval_curve_rows, retrieval_topk_rows  # noqa: E402,F401
+
+# ---- classical puzzle baseline: the wrappers of csrc/puzzle_pixels.hip (cut, resize, border distances, board) live in ops_puzzlepixels.py
+from .ops_puzzlepixels import (PUZZLE_MAX_ERODED, PUZZLE_MAX_PIECES, PUZZLE_MAX_SIZE, puzzle_assemble, puzzle_cut,  # noqa: E402,F401
+                               puzzle_eroded_width, puzzle_pixel_distances, puzzle_resize_pieces)
