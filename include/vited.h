@@ -741,7 +741,7 @@ int vited_pair_scores_finish(const int* rec_cells, const float* rec_values, int6
                              float* minv, double* stdev, double* stats, int* bad, void* workspace, int64_t workspace_bytes,
                              void* stream);
 
-/* ---- puzzle solving: the Paikin-Tal compatibility stage (paikin_tal_solver/inter_piece_distance.py), type-1 puzzles ---------------
+/* ---- puzzle solving: the Paikin-Tal compatibility stage (paikin_tal_solver/inter_piece_distance.py), type-1 puzzles (type 2: below)
  * n pieces (2 <= n <= 46340), sides top 0, right 1, bottom 2, left 3, s^ = (s + 2) % 4.  All arrays are contiguous device memory:
  *   dq       int32 [4, n, n]: dq[s, i, j] = distance of side s of piece i to side s^ of piece j, >= 0 (the diagonal is not read)
  *   min_d, second_d int64 [n, 4]; candidate, best_buddy int32 [n, 4] (a piece id or -1); compat, mutual float32 [4, n, n]
@@ -832,7 +832,7 @@ int vited_mined_bce(const float* logits, const float* labels, const float* weigh
                     int64_t classes, int mean, float scale, float* loss, float* dlogits, void* stream);
 
 /* ---- puzzle solving: the classical baseline's pixel work (solver_driver.py; paikin_tal_solver/puzzle_importer.py:182-232, :265-321,
- *      :448-473; puzzle_piece.py:535-609), type-1 puzzles -------------------------------------------------------------------------------
+ *      :448-473; puzzle_piece.py:535-609), type-1 puzzles (type 2: the section after this one) ------------------------------------------
  * Images, pieces and boards are uint8, HWC with 3 channels, contiguous DEVICE memory; csrc/puzzle_pixels.h states every rule.  n
  * pieces of eroded_width x eroded_width (We >= 2) cut from cells of piece_width x piece_width (P >= We).  Every output byte is written
  * exactly once by plain stores: the same bits on every call.  No host read, no synchronisation.
@@ -863,6 +863,43 @@ int vited_puzzle_pixel_distances(const uint8_t* pieces, int64_t n, int eroded_wi
                                  int64_t workspace_bytes, void* stream);
 int vited_puzzle_assemble(const uint8_t* pieces, int64_t n, int eroded_width, int piece_width, const int* cells, int64_t rows,
                           int64_t cols, int marker, uint8_t* board, void* stream);
+
+/* ---- puzzle solving, type 2: pieces of unknown rotation (PuzzleType.type2 of paikin_tal_solver/) -----------------
+ * Any side sj of piece j may meet side si of piece i.  dq2, compat and mutual are [4, n, n, 4], indexed [si, i, j, sj], contiguous
+ * device memory, dq2 16-byte aligned; the slice [s, i, j, (s + 2) % 4] is the type-1 array.  Nothing here rotates a piece: the solver
+ * assigns rotations, and only vited_puzzle_assemble2 turns pixels.  Every result is an integer reduction, an elementwise expression or
+ * a max of packed integers, as in type 1: independent of the launch split, the same bits on every call.
+ *
+ * vited_puzzle_pixel_distances2 == calculate_asymmetric_distance over all ordered pairs and all 16 side pairings: dq2[si, i, j, sj] =
+ *   sum over the 3 We border values of | 2 B_si(i) - B'_si(i) - B_sj(j) |, B_sj(j) read in reversed pixel order when si == sj or
+ *   (si, sj) is (right, top), (top, right), (left, bottom) or (bottom, left); dq2[si, i, i, sj] = 2^31 - 1.  workspace >=
+ *   vited_puzzle_pixel_distances2_workspace_bytes(n, We) bytes (-1: bad n or We), 8-byte aligned.
+ * vited_puzzle_compat2_init == InterPieceDistance.__init__ for type 2: per (piece i, side si) the minimum and the second order statistic
+ *   (with multiplicity, seeds (maxsize - 1, maxsize)) of dq2[si, i, j, sj] over j != i and the 4 sj, min_count int32 [n, 4] the
+ *   number of candidates holding the minimum, candidate int32 [n, 4, 2] that (j, sj) when min_count is 1, else (-1, -1); compat as in
+ *   type 1 on each candidate; mutual[si, i, j, sj] = (C[si, i, j, sj] + C[sj, j, i, si]) / 2 in fp32 (inf at j == i, as compat);
+ *   best_buddy int32 [n, 4, 2]: the candidate (j, sj) whose own candidate is (i, si), else (-1, -1); the start keys and ordering of
+ *   type 1 on those best buddies (start_total adds mutual[si, i, j, sj] in side order).
+ * vited_puzzle_compat2_recalc == recalculate_remaining_piece_compatibilities(placed) for type 2, with the quirks of the type-1 entry:
+ *   unplaced rows over unplaced j, compat of changed rows at unplaced j only, mutual of every pair with a changed piece.
+ * vited_puzzle_best_slot2: the first maximum of mutual[side, p, slot_piece[k], slot_side[k]] over unplaced p ascending (outer) x
+ *   k < slots x side 0..3 (inner) - _get_next_piece_from_pool for type 2, slot_side[k] the unrotated side of the placed piece that faces
+ *   slot k.  *best = (key << 32) | (0xffffffff - ((p * slots + k) * 4 + side)); 4 * n * slots < 2^32.
+ * vited_puzzle_assemble2 == Puzzle.reconstruct_from_pieces with rotations: as vited_puzzle_assemble, the piece of cell q entering as
+ *   numpy.rot90(piece, rotations[q]) (int32 [rows * cols], quarter turns; only the low two bits are read).
+ * Errors as in the type-1 entries; VITED_ERR_BAD_ARG also for a dq2 that is not 16-byte aligned. */
+int64_t vited_puzzle_pixel_distances2_workspace_bytes(int64_t n, int eroded_width);
+int vited_puzzle_pixel_distances2(const uint8_t* pieces, int64_t n, int eroded_width, int* dq2, void* workspace,
+                                  int64_t workspace_bytes, void* stream);
+int vited_puzzle_compat2_init(const int* dq2, int64_t n, int64_t* min_d, int64_t* second_d, int* min_count, int* candidate,
+                              int* best_buddy, float* compat, float* mutual, int* start_count, float* start_total, int* start_order,
+                              void* stream);
+int vited_puzzle_compat2_recalc(const int* dq2, int64_t n, const int* placed, int64_t* min_d, int64_t* second_d, float* compat,
+                                float* mutual, int* changed, void* stream);
+int vited_puzzle_best_slot2(const float* mutual, int64_t n, const int* placed, const int* slot_piece, const int* slot_side,
+                            int64_t slots, int64_t* best, void* stream);
+int vited_puzzle_assemble2(const uint8_t* pieces, int64_t n, int eroded_width, int piece_width, const int* cells, const int* rotations,
+                           int64_t rows, int64_t cols, int marker, uint8_t* board, void* stream);
 
 #ifdef __cplusplus
 }

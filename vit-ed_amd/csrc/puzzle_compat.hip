@@ -1,4 +1,5 @@
-// Paikin-Tal compatibility stage of the reference's puzzle solver (paikin_tal_solver/inter_piece_distance.py), type-1 puzzles.
+// Paikin-Tal compatibility stage of the reference's puzzle solver (paikin_tal_solver/inter_piece_distance.py): type-1 puzzles first,
+// then the kernels of type 2 (pieces of unknown rotation) over (piece, side) candidates.
 //
 // State, all on the device and owned by the caller (n pieces, side s: top 0, right 1, bottom 2, left 3; s^ = (s + 2) % 4):
 //   Dq       int32 [4, n, n]  distance of side s of piece i to side s^ of piece j (the diagonal is never read)
@@ -218,6 +219,173 @@ __global__ void __launch_bounds__(THREADS) distances_kernel(const float* __restr
     }
 }
 
+// ---- type 2 (inter_piece_distance.py with PuzzleType.type2): any side sj of piece j may meet side si of piece i ---------------------------
+// Dq2, compat and mutual are [4, n, n, 4], indexed [si, i, j, sj]: the row of (si, i) holds its 4 n candidates (j, sj) contiguously,
+// candidate c = 4 j + sj.  candidate and best_buddy are int32 [n, 4, 2]: (j, sj), or (-1, -1).
+
+// Per (piece i, side si), one wave, each lane one j (its four sj as one 16-byte load): the two smallest distances over the candidates
+// with j != i (RECALC: unplaced j only), with multiplicity, seeded as in type 1.  Init also stores how many candidates hold the minimum
+// and the candidate itself when exactly one does.
+template <bool RECALC>
+__global__ void __launch_bounds__(THREADS) min_second2_kernel(const int* __restrict__ dq2, int n, const int* __restrict__ placed,
+                                                              int64_t* __restrict__ min_d, int64_t* __restrict__ second_d,
+                                                              int* __restrict__ min_count, int* __restrict__ candidate,
+                                                              int* __restrict__ changed) {
+    const int row = blockIdx.x * ROWS_PER_BLOCK + threadIdx.x / VITED_WAVE;
+    const int lane = threadIdx.x % VITED_WAVE;
+    if (row >= 4 * n) return;
+    const int s = row / n, i = row % n;
+    if (RECALC && placed[i]) return;
+    const int4* d_row = reinterpret_cast<const int4*>(dq2 + ((int64_t)s * n + i) * n * 4);
+    int64_t m1 = PY_MAXSIZE, m2 = PY_MAXSIZE;
+    for (int j = lane; j < n; j += VITED_WAVE) {
+        if (j == i || (RECALC && placed[j])) continue;
+        const int4 d = d_row[j];
+        const int v[4] = {d.x, d.y, d.z, d.w};
+#pragma unroll
+        for (int sj = 0; sj < 4; ++sj) {                    // keep_two_smallest as selects: the lanes stay in registers
+            const int64_t x = v[sj];
+            m2 = x < m1 ? m1 : (x < m2 ? x : m2);
+            m1 = x < m1 ? x : m1;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const int64_t b1 = __shfl_xor(m1, off, 64), b2 = __shfl_xor(m2, off, 64);
+        const int64_t lo = m1 < b1 ? m1 : b1, hi = m1 < b1 ? b1 : m1;
+        m1 = lo;
+        m2 = hi < (m2 < b2 ? m2 : b2) ? hi : (m2 < b2 ? m2 : b2);
+    }
+    {
+        const int64_t s1 = PY_MAXSIZE - 1, s2 = PY_MAXSIZE;
+        const int64_t lo = m1 < s1 ? m1 : s1, hi = m1 < s1 ? s1 : m1;
+        const int64_t m2b = m2 < s2 ? m2 : s2;
+        m1 = lo;
+        m2 = hi < m2b ? hi : m2b;
+    }
+    const int64_t at = (int64_t)i * 4 + s;
+    if (!RECALC) {
+        int count = 0, first = 4 * n;
+        for (int j = lane; j < n; j += VITED_WAVE) {
+            if (j == i) continue;
+            const int4 d = d_row[j];
+            const int v[4] = {d.x, d.y, d.z, d.w};
+#pragma unroll
+            for (int sj = 3; sj >= 0; --sj) {
+                if (v[sj] == m1) {
+                    ++count;
+                    first = first < 4 * j + sj ? first : 4 * j + sj;
+                }
+            }
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            count += __shfl_xor(count, off, 64);
+            const int f = __shfl_xor(first, off, 64);
+            first = first < f ? first : f;
+        }
+        if (lane == 0) {
+            min_count[at] = count;
+            candidate[at * 2] = count == 1 ? first / 4 : -1;
+            candidate[at * 2 + 1] = count == 1 ? first % 4 : -1;
+        }
+    }
+    if (lane == 0) {
+        if (RECALC && (min_d[at] != m1 || second_d[at] != m2)) changed[i] = 1;
+        min_d[at] = m1;
+        second_d[at] = m2;
+    }
+}
+
+// C[si, i, j, sj], the type-1 expression on the candidate's distance.  One thread per candidate of the row blockIdx.x (4 n rows: the
+// dimension that may pass 65535).
+template <bool RECALC>
+__global__ void __launch_bounds__(THREADS) compat2_kernel(const int* __restrict__ dq2, int n, const int* __restrict__ placed,
+                                                          const int* __restrict__ changed, const int64_t* __restrict__ second_d,
+                                                          float* __restrict__ compat) {
+    const int c = blockIdx.y * THREADS + threadIdx.x;
+    const int row = blockIdx.x, s = row / n, i = row % n;
+    if (c >= 4 * n) return;
+    const int j = c >> 2;
+    if (RECALC && (!changed[i] || placed[j])) return;
+    const int64_t at = ((int64_t)s * n + i) * n * 4 + c;
+    if (j == i) {
+        if (!RECALC) compat[at] = __builtin_inff();
+        return;
+    }
+    const int64_t d = dq2[at], sec = second_d[(int64_t)i * 4 + s];
+    float v;
+    if (d == 0) v = 1.0f;
+    else if (sec == 0) v = (float)(-PY_MAXSIZE);
+    else v = (float)(1.0 - (double)d / (double)sec);
+    compat[at] = v;
+}
+
+// M[si, i, j, sj] = M[sj, j, i, si] = (C[si, i, j, sj] + C[sj, j, i, si]) / 2 in fp32; inf at j == i.  Recalc: pairs with a changed piece.
+template <bool RECALC>
+__global__ void __launch_bounds__(THREADS) mutual2_kernel(const float* __restrict__ compat, int n, const int* __restrict__ changed,
+                                                          float* __restrict__ mutual) {
+    const int c = blockIdx.y * THREADS + threadIdx.x;
+    const int row = blockIdx.x, s = row / n, i = row % n;
+    if (c >= 4 * n) return;
+    const int j = c >> 2, sj = c & 3;
+    if (RECALC && !changed[i] && !changed[j]) return;
+    const int64_t at = ((int64_t)s * n + i) * n * 4 + c;
+    mutual[at] = j == i ? __builtin_inff() : (compat[at] + compat[(((int64_t)sj * n + j) * n + i) * 4 + s]) / 2.0f;
+}
+
+// Best buddies: the unique candidates (piece, side) that name each other.
+__global__ void __launch_bounds__(THREADS) best_buddy2_kernel(const int* __restrict__ candidate, int n, int* __restrict__ best_buddy) {
+    const int t = blockIdx.x * THREADS + threadIdx.x;
+    if (t >= 4 * n) return;
+    const int i = t / 4, s = t % 4, j = candidate[2 * t], sj = candidate[2 * t + 1];
+    const bool mutual = j >= 0 && candidate[2 * (j * 4 + sj)] == i && candidate[2 * (j * 4 + sj) + 1] == s;
+    best_buddy[2 * t] = mutual ? j : -1;
+    best_buddy[2 * t + 1] = mutual ? sj : -1;
+}
+
+// The start-piece keys of type 1 on (piece, side) best buddies.
+__global__ void __launch_bounds__(THREADS) start_keys2_kernel(const int* __restrict__ best_buddy, const float* __restrict__ mutual, int n,
+                                                              int* __restrict__ start_count, float* __restrict__ start_total) {
+    const int i = blockIdx.x * THREADS + threadIdx.x;
+    if (i >= n) return;
+    int count = 0;
+    float total = 0.0f;
+    for (int s = 0; s < 4; ++s) {
+        const int j = best_buddy[2 * (i * 4 + s)], sj = best_buddy[2 * (i * 4 + s) + 1];
+        if (j < 0) continue;
+        count += 4;
+        for (int t = 0; t < 4; ++t) count += best_buddy[2 * (j * 4 + t)] >= 0;
+        total = total + mutual[(((int64_t)s * n + i) * n + j) * 4 + sj];
+    }
+    start_count[i] = count;
+    start_total[i] = total;
+}
+
+// Slot scan of _get_next_piece_from_pool for type 2: the first maximum of M[side, p, q, sq] over unplaced pieces p ascending x open slots
+// (q, sq) in list order x the piece's side 0..3, sq the unrotated side of the placed piece q that faces the slot.  Packed as in type 1.
+__global__ void __launch_bounds__(THREADS) best_slot2_kernel(const float* __restrict__ mutual, int n, const int* __restrict__ placed,
+                                                             const int* __restrict__ slot_piece, const int* __restrict__ slot_side, int slots,
+                                                             unsigned long long* __restrict__ best) {
+    const int64_t per_piece = (int64_t)slots * 4, total = (int64_t)n * per_piece;
+    unsigned long long word = 0;
+    for (int64_t lin = (int64_t)blockIdx.x * THREADS + threadIdx.x; lin < total; lin += (int64_t)gridDim.x * THREADS) {
+        const int p = (int)(lin / per_piece), rem = (int)(lin % per_piece);
+        const int k = rem >> 2, side = rem & 3;
+        const int q = slot_piece[k];
+        if (placed[p] || q < 0 || q >= n) continue;
+        const float v = mutual[(((int64_t)side * n + p) * n + q) * 4 + (slot_side[k] & 3)];
+        const unsigned long long w = ((unsigned long long)order_key(v) << 32) | (0xffffffffu - (uint32_t)lin);
+        word = w > word ? w : word;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned long long o = __shfl_xor(word, off, 64);
+        word = o > word ? o : word;
+    }
+    if (threadIdx.x % VITED_WAVE == 0 && word != 0) atomicMax(best, word);
+}
+
 inline unsigned blocks_for(int64_t work) { return (unsigned)ceil_div64(work, THREADS); }
 
 }  // namespace
@@ -273,6 +441,58 @@ extern "C" int vited_puzzle_best_slot(const float* mutual, int64_t n, const int*
     if (hipMemsetAsync(best, 0, sizeof(int64_t), st) != hipSuccess) return VITED_ERR_LAUNCH;
     const int64_t want = ceil_div64(n * slots, THREADS), blocks = want < 1024 ? want : 1024;
     hipLaunchKernelGGL(best_slot_kernel, dim3((unsigned)blocks), dim3(THREADS), 0, st, mutual, (int)n, placed, slot_piece, slot_side,
+                       (int)slots, reinterpret_cast<unsigned long long*>(best));
+    return vited_check_launch();
+}
+
+// ---- type 2 --------------------------------------------------------------------------------------------------------------------------
+extern "C" int vited_puzzle_compat2_init(const int* dq2, int64_t n, int64_t* min_d, int64_t* second_d, int* min_count, int* candidate,
+                                         int* best_buddy, float* compat, float* mutual, int* start_count, float* start_total,
+                                         int* start_order, void* stream) {
+    if (!dq2 || !min_d || !second_d || !min_count || !candidate || !best_buddy || !compat || !mutual || !start_count || !start_total ||
+        !start_order)
+        return VITED_ERR_BAD_ARG;
+    if (n < 2 || n > MAX_PIECES || reinterpret_cast<uintptr_t>(dq2) % 16 != 0) return VITED_ERR_BAD_ARG;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int ni = (int)n;
+    const dim3 grid2((unsigned)(4 * n), (unsigned)ceil_div64(4 * n, THREADS));
+    hipLaunchKernelGGL(min_second2_kernel<false>, dim3((unsigned)ceil_div64(4 * n, ROWS_PER_BLOCK)), dim3(THREADS), 0, st, dq2, ni,
+                       (const int*)nullptr, min_d, second_d, min_count, candidate, (int*)nullptr);
+    hipLaunchKernelGGL(compat2_kernel<false>, grid2, dim3(THREADS), 0, st, dq2, ni, (const int*)nullptr, (const int*)nullptr,
+                       (const int64_t*)second_d, compat);
+    hipLaunchKernelGGL(mutual2_kernel<false>, grid2, dim3(THREADS), 0, st, (const float*)compat, ni, (const int*)nullptr, mutual);
+    hipLaunchKernelGGL(best_buddy2_kernel, dim3(blocks_for(4 * n)), dim3(THREADS), 0, st, (const int*)candidate, ni, best_buddy);
+    hipLaunchKernelGGL(start_keys2_kernel, dim3(blocks_for(n)), dim3(THREADS), 0, st, (const int*)best_buddy, (const float*)mutual, ni,
+                       start_count, start_total);
+    hipLaunchKernelGGL(start_order_kernel, dim3(blocks_for(n)), dim3(THREADS), 0, st, (const int*)start_count, (const float*)start_total,
+                       ni, start_order);
+    return vited_check_launch();
+}
+
+extern "C" int vited_puzzle_compat2_recalc(const int* dq2, int64_t n, const int* placed, int64_t* min_d, int64_t* second_d, float* compat,
+                                           float* mutual, int* changed, void* stream) {
+    if (!dq2 || !placed || !min_d || !second_d || !compat || !mutual || !changed || n < 2 || n > MAX_PIECES) return VITED_ERR_BAD_ARG;
+    if (reinterpret_cast<uintptr_t>(dq2) % 16 != 0) return VITED_ERR_BAD_ARG;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int ni = (int)n;
+    const dim3 grid2((unsigned)(4 * n), (unsigned)ceil_div64(4 * n, THREADS));
+    if (hipMemsetAsync(changed, 0, sizeof(int) * n, st) != hipSuccess) return VITED_ERR_LAUNCH;
+    hipLaunchKernelGGL(min_second2_kernel<true>, dim3((unsigned)ceil_div64(4 * n, ROWS_PER_BLOCK)), dim3(THREADS), 0, st, dq2, ni, placed,
+                       min_d, second_d, (int*)nullptr, (int*)nullptr, changed);
+    hipLaunchKernelGGL(compat2_kernel<true>, grid2, dim3(THREADS), 0, st, dq2, ni, placed, (const int*)changed, (const int64_t*)second_d,
+                       compat);
+    hipLaunchKernelGGL(mutual2_kernel<true>, grid2, dim3(THREADS), 0, st, (const float*)compat, ni, (const int*)changed, mutual);
+    return vited_check_launch();
+}
+
+extern "C" int vited_puzzle_best_slot2(const float* mutual, int64_t n, const int* placed, const int* slot_piece, const int* slot_side,
+                                       int64_t slots, int64_t* best, void* stream) {
+    if (!mutual || !placed || !slot_piece || !slot_side || !best || n < 2 || n > MAX_PIECES || slots < 1) return VITED_ERR_BAD_ARG;
+    if (slots > (int64_t)UINT32_MAX || 4 * n * slots > (int64_t)UINT32_MAX) return VITED_ERR_UNSUPPORTED;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (hipMemsetAsync(best, 0, sizeof(int64_t), st) != hipSuccess) return VITED_ERR_LAUNCH;
+    const int64_t want = ceil_div64(4 * n * slots, THREADS), blocks = want < 1024 ? want : 1024;
+    hipLaunchKernelGGL(best_slot2_kernel, dim3((unsigned)blocks), dim3(THREADS), 0, st, mutual, (int)n, placed, slot_piece, slot_side,
                        (int)slots, reinterpret_cast<unsigned long long*>(best));
     return vited_check_launch();
 }

@@ -3,6 +3,7 @@
 // bilinear upscale of a piece (TwoImgSyncEval's Resize) and the reconstructed board (Puzzle.reconstruct_from_pieces), written so that
 // the device kernels (puzzle_pixels.hip) and a host program under the sanitizers (tools/puzzle_pixels_host_check.cpp) compile the
 // same text.  Everything is 8-bit / integer arithmetic, except the resample coefficients, which are Pillow's fp64 expressions.
+// The rules of type-2 puzzles (any side against any side, rotated pieces on the board) follow those of type 1.
 //
 // Images and pieces are uint8, HWC with 3 channels.  Sides: top 0, right 1, bottom 2, left 3; side s faces side (s + 2) % 4.
 #pragma once
@@ -105,6 +106,18 @@ PP_FN int strip_distance(const uint16_t* prediction, const uint16_t* border, int
     return (int)acc;
 }
 
+// ---- type 2: any side of piece i against any side of piece j ---------------------------------------------------------------------------
+// calculate_asymmetric_distance reads j's border in reversed pixel order (channels keep their order) when the two sides are the same,
+// or (si, sj) is (right, top), (top, right), (left, bottom) or (bottom, left); the prediction of i is never reversed.  A pairing
+// (s, (s + 2) % 4) is not reversed: it is the type-1 distance.
+PP_FN bool pairing_reversed(int si, int sj) { return si == sj || (si ^ sj) == 1; }
+
+// The border strip of side s read from its far end: value k is channel k % 3 of position We - 1 - k / 3, the same zero padding behind.
+PP_FN uint16_t strip_border_reversed(const uint8_t* piece, int We, int s, int k) {
+    if (k >= CHANNELS * We) return 0;
+    return (uint16_t)(piece[side_pixel(We, s, We - 1 - k / CHANNELS, 0) * CHANNELS + k % CHANNELS] + 255);
+}
+
 // ---- Pillow's 8-bit bilinear resample, upscaling (libImaging/Resample.c: precompute_coeffs, normalize_coeffs_8bpc, the horizontal
 // pass into an 8-bit intermediate, then the vertical pass) ------------------------------------------------------------------------------
 constexpr int RESAMPLE_TAPS = 3;           // support 1, ksize 3
@@ -169,6 +182,32 @@ PP_FN uint8_t board_byte(const uint8_t* pieces, int64_t n, int We, int P, const 
     const int pad = (P - We) / 2;
     const int y = (int)(Y - r * P) - pad, x = (int)(X - col * P) - pad;
     if (y >= 0 && y < We && x >= 0 && x < We) return pieces[(((int64_t)(cell >> 1) * We + y) * We + x) * CHANNELS + c];
+    if ((cell & 1) && marker >= 0 && y >= -1 && y <= We && x >= -1 && x <= We) return (uint8_t)(marker >> (8 * c));
+    return 0;
+}
+
+// Pixel (y, x) of numpy.rot90(piece, r) (r quarter turns counter-clockwise) as a pixel index y' * We + x' of the piece itself.
+PP_FN int64_t rotated_source(int We, int r, int y, int x) {
+    const int64_t w = We;
+    switch (r & 3) {
+        case 0: return y * w + x;
+        case 1: return x * w + (We - 1 - y);
+        case 2: return (We - 1 - y) * w + (We - 1 - x);
+        default: return (We - 1 - x) * w + y;
+    }
+}
+
+// board_byte for a type-2 solution: the piece of cell (r, col) enters as numpy.rot90(piece, rotations[r * cols + col]).  The padding
+// and the frame are the same on all four sides, so they turn into themselves.
+PP_FN uint8_t board_byte_rotated(const uint8_t* pieces, int64_t n, int We, int P, const int* cells, const int* rotations, int64_t cols,
+                                 int marker, int64_t Y, int64_t X, int c) {
+    const int64_t r = Y / P, col = X / P;
+    const int cell = cells[r * cols + col];
+    if (cell < 0 || (cell >> 1) >= n) return 0;
+    const int pad = (P - We) / 2;
+    const int y = (int)(Y - r * P) - pad, x = (int)(X - col * P) - pad;
+    if (y >= 0 && y < We && x >= 0 && x < We)
+        return pieces[((int64_t)(cell >> 1) * We * We + rotated_source(We, rotations[r * cols + col], y, x)) * CHANNELS + c];
     if ((cell & 1) && marker >= 0 && y >= -1 && y <= We && x >= -1 && x <= We) return (uint8_t)(marker >> (8 * c));
     return 0;
 }

@@ -3,6 +3,8 @@
 // are upscaled to the model's size for the learned path, and the solved board is assembled as an image.  puzzle_pixels.h states every
 // per-element rule; tools/puzzle_pixels_host_check.cpp runs the same text on the host, and tests/puzzle_pixels_cases.py restates it in
 // numpy.  All results are integers formed without atomics: the same bits on every call, whatever the tiling.
+// Type-2 puzzles (pieces of unknown rotation) add the distances of all 16 side pairings, Dq2 int32 [4, n, n, 4],
+// and a board whose pieces enter turned; tools/puzzle_type2_host_check.cpp and tests/puzzle_type2_cases.py restate those.
 #include "common.h"
 #include "puzzle_pixels.h"
 
@@ -109,6 +111,78 @@ puzzle_pixel_distances_kernel(const uint16_t* __restrict__ strips, int64_t n, in
     }
 }
 
+// ---- distances, type 2: all 16 side pairings -------------------------------------------------------------------------------------------
+// Pass 1: the strips of a piece, 4 sides x 3 kinds.  strips[0][s][i] is the prediction of side s of piece i, strips[1][s][i] its border
+// and strips[2][s][i] its border read from the far end (puzzle_pixels.h: pairing_reversed), `padded` uint16 each.
+__global__ void __launch_bounds__(PP_THREADS)
+puzzle_strips2_kernel(const uint8_t* __restrict__ pieces, int64_t n, int We, int padded, uint16_t* __restrict__ strips) {
+    const int64_t idx = (int64_t)blockIdx.x * PP_THREADS + threadIdx.x;
+    const int64_t per_kind = 4 * n * padded;
+    if (idx >= 3 * per_kind) return;
+    const int kind = (int)(idx / per_kind);
+    const int64_t rem = idx - kind * per_kind;
+    const int k = (int)(rem % padded);
+    const int64_t si = rem / padded;                            // s * n + i
+    const int s = (int)(si / n);
+    const uint8_t* piece = pieces + (si - s * n) * We * We * pp::CHANNELS;
+    strips[idx] = kind == 0 ? pp::strip_prediction(piece, We, s, k)
+                            : (kind == 1 ? pp::strip_border(piece, We, s, k) : pp::strip_border_reversed(piece, We, s, k));
+}
+
+// Pass 2: a workgroup owns the PD_TILE x PD_TILE block (i0.., j0..) of one side si of i and all four sides sj of j.  Per stage it puts the
+// predictions of its 32 i and, for each sj, the border strips of its 32 j in the order the pairing (si, sj) reads them into LDS - rows
+// laid out as in the type-1 kernel, so the reads stay conflict-free - and thread (ty, tx) accumulates the 4 x 4 outputs
+// (i0 + ty + 8 a, j0 + tx, sj) with v_sad_u16.  The four sj of one (i, j) leave as one 16-byte store.
+__global__ void __launch_bounds__(PP_THREADS)
+puzzle_pixel_distances2_kernel(const uint16_t* __restrict__ strips, int64_t n, int padded, int* __restrict__ dq2) {
+    __shared__ __attribute__((aligned(16))) uint16_t lds[5][PD_TILE * PD_ROW];       // [0]: predictions, [1 + sj]: borders
+    const int si = blockIdx.z;
+    const int64_t i0 = (int64_t)blockIdx.y * PD_TILE, j0 = (int64_t)blockIdx.x * PD_TILE;
+    const int tx = threadIdx.x % PD_TILE, ty = threadIdx.x / PD_TILE;
+    const int64_t per_side = n * padded, per_kind = 4 * per_side;
+    uint32_t acc[PD_PER_THREAD][4];
+#pragma unroll
+    for (int a = 0; a < PD_PER_THREAD; ++a)
+#pragma unroll
+        for (int sj = 0; sj < 4; ++sj) acc[a][sj] = 0u;
+    for (int k0 = 0; k0 < padded; k0 += PD_STAGE) {
+        const int items = (padded - k0 < PD_STAGE ? padded - k0 : PD_STAGE) / 4;       // 8-byte items of this stage, per row
+        for (int idx = threadIdx.x; idx < 5 * PD_TILE * (PD_STAGE / 4); idx += PP_THREADS) {
+            const int which = idx / (PD_TILE * (PD_STAGE / 4)), rem = idx % (PD_TILE * (PD_STAGE / 4));
+            const int r = rem / (PD_STAGE / 4), q = rem % (PD_STAGE / 4);
+            if (q >= items) continue;
+            const int64_t piece = (which ? j0 : i0) + r;
+            const uint16_t* src = which == 0 ? strips + si * per_side
+                                             : strips + (pp::pairing_reversed(si, which - 1) ? 2 : 1) * per_kind + (which - 1) * per_side;
+            uint2 v = make_uint2(0u, 0u);                       // rows past n: zeros, their outputs are never written
+            if (piece < n) v = *reinterpret_cast<const uint2*>(src + piece * padded + k0 + 4 * q);
+            *reinterpret_cast<uint2*>(&lds[which][r * PD_ROW + 4 * q]) = v;
+        }
+        __syncthreads();
+        for (int q = 0; q < items; ++q) {
+            uint2 b[4];
+#pragma unroll
+            for (int sj = 0; sj < 4; ++sj) b[sj] = *reinterpret_cast<const uint2*>(&lds[1 + sj][tx * PD_ROW + 4 * q]);
+#pragma unroll
+            for (int a = 0; a < PD_PER_THREAD; ++a) {
+                const uint2 p = *reinterpret_cast<const uint2*>(&lds[0][(ty + 8 * a) * PD_ROW + 4 * q]);
+#pragma unroll
+                for (int sj = 0; sj < 4; ++sj) acc[a][sj] = pp::sad2(p.y, b[sj].y, pp::sad2(p.x, b[sj].x, acc[a][sj]));
+            }
+        }
+        __syncthreads();
+    }
+    const int64_t j = j0 + tx;
+#pragma unroll
+    for (int a = 0; a < PD_PER_THREAD; ++a) {
+        const int64_t i = i0 + ty + 8 * a;
+        if (i >= n || j >= n) continue;
+        const int4 out = i == j ? make_int4(pp::DQ_UNSET, pp::DQ_UNSET, pp::DQ_UNSET, pp::DQ_UNSET)
+                                : make_int4((int)acc[a][0], (int)acc[a][1], (int)acc[a][2], (int)acc[a][3]);
+        *reinterpret_cast<int4*>(dq2 + (((int64_t)si * n + i) * n + j) * 4) = out;
+    }
+}
+
 // ---- board: one thread per output pixel, a gather ------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(PP_THREADS)
 puzzle_assemble_kernel(const uint8_t* __restrict__ pieces, int64_t n, int We, int P, const int* __restrict__ cells, int64_t rows,
@@ -119,6 +193,18 @@ puzzle_assemble_kernel(const uint8_t* __restrict__ pieces, int64_t n, int We, in
     const int64_t Y = idx / width, X = idx - Y * width;
 #pragma unroll
     for (int c = 0; c < pp::CHANNELS; ++c) board[idx * pp::CHANNELS + c] = pp::board_byte(pieces, n, We, P, cells, cols, marker, Y, X, c);
+}
+
+__global__ void __launch_bounds__(PP_THREADS)
+puzzle_assemble2_kernel(const uint8_t* __restrict__ pieces, int64_t n, int We, int P, const int* __restrict__ cells,
+                        const int* __restrict__ rotations, int64_t rows, int64_t cols, int marker, uint8_t* __restrict__ board) {
+    const int64_t width = cols * P;
+    const int64_t idx = (int64_t)blockIdx.x * PP_THREADS + threadIdx.x;
+    if (idx >= rows * P * width) return;
+    const int64_t Y = idx / width, X = idx - Y * width;
+#pragma unroll
+    for (int c = 0; c < pp::CHANNELS; ++c)
+        board[idx * pp::CHANNELS + c] = pp::board_byte_rotated(pieces, n, We, P, cells, rotations, cols, marker, Y, X, c);
 }
 
 bool sizes_ok(int64_t n, int We) { return n >= 1 && We >= 2; }
@@ -181,5 +267,42 @@ extern "C" int vited_puzzle_assemble(const uint8_t* pieces, int64_t n, int erode
     if (ceil_div64(pixels, PP_THREADS) > INT32_MAX) return VITED_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(puzzle_assemble_kernel, dim3(blocks_for(pixels)), dim3(PP_THREADS), 0, static_cast<hipStream_t>(stream), pieces, n,
                        eroded_width, piece_width, cells, rows, cols, marker, board);
+    return vited_check_launch();
+}
+
+// ---- type 2 (pieces of unknown rotation) ---------------------------------------------------------------------------------------------
+extern "C" int64_t vited_puzzle_pixel_distances2_workspace_bytes(int64_t n, int eroded_width) {
+    if (!sizes_ok(n, eroded_width) || n < 2 || !sizes_supported(n, eroded_width)) return -1;
+    return 3 * 4 * n * (int64_t)pp::strip_padded(eroded_width) * (int64_t)sizeof(uint16_t);
+}
+
+extern "C" int vited_puzzle_pixel_distances2(const uint8_t* pieces, int64_t n, int eroded_width, int* dq2, void* workspace,
+                                             int64_t workspace_bytes, void* stream) {
+    if (!pieces || !dq2 || !workspace || !sizes_ok(n, eroded_width) || n < 2) return VITED_ERR_BAD_ARG;
+    if (reinterpret_cast<uintptr_t>(workspace) % 8 != 0 || reinterpret_cast<uintptr_t>(dq2) % 16 != 0) return VITED_ERR_BAD_ARG;
+    if (!sizes_supported(n, eroded_width)) return VITED_ERR_UNSUPPORTED;
+    if (workspace_bytes < vited_puzzle_pixel_distances2_workspace_bytes(n, eroded_width)) return VITED_ERR_WORKSPACE;
+    const int padded = pp::strip_padded(eroded_width);
+    const int64_t values = 3 * 4 * n * padded;
+    if (ceil_div64(values, PP_THREADS) > INT32_MAX) return VITED_ERR_UNSUPPORTED;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    uint16_t* strips = static_cast<uint16_t*>(workspace);
+    hipLaunchKernelGGL(puzzle_strips2_kernel, dim3(blocks_for(values)), dim3(PP_THREADS), 0, st, pieces, n, eroded_width, padded, strips);
+    const unsigned tiles = (unsigned)ceil_div64(n, PD_TILE);
+    hipLaunchKernelGGL(puzzle_pixel_distances2_kernel, dim3(tiles, tiles, 4), dim3(PP_THREADS), 0, st, strips, n, padded, dq2);
+    return vited_check_launch();
+}
+
+extern "C" int vited_puzzle_assemble2(const uint8_t* pieces, int64_t n, int eroded_width, int piece_width, const int* cells,
+                                      const int* rotations, int64_t rows, int64_t cols, int marker, uint8_t* board, void* stream) {
+    if (!pieces || !cells || !rotations || !board || !sizes_ok(n, eroded_width) || piece_width < eroded_width) return VITED_ERR_BAD_ARG;
+    if (rows < 1 || cols < 1 || rows > n || cols > n || marker > 0xffffff) return VITED_ERR_BAD_ARG;
+    if (marker >= 0 && (piece_width - eroded_width) / 2 < 1) return VITED_ERR_BAD_ARG;       // the frame needs a pixel of padding
+    if (!sizes_supported(n, eroded_width)) return VITED_ERR_UNSUPPORTED;
+    if (rows * cols != n) return VITED_ERR_BAD_ARG;
+    const int64_t pixels = rows * piece_width * cols * piece_width;
+    if (ceil_div64(pixels, PP_THREADS) > INT32_MAX) return VITED_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(puzzle_assemble2_kernel, dim3(blocks_for(pixels)), dim3(PP_THREADS), 0, static_cast<hipStream_t>(stream), pieces, n,
+                       eroded_width, piece_width, cells, rotations, rows, cols, marker, board);
     return vited_check_launch();
 }

@@ -1,7 +1,9 @@
-"""Puzzle evaluation (evaluation.py:100-133, solver_driver.py, paikin_tal_solver/) for type-1 puzzles of one image, fixed size:
-the piece distances from the model's logits, the Paikin-Tal solver with its compatibilities on the device, and the reference's
-accuracies; and the classical baseline of solver_driver.py around the same solver - the image cut into eroded pieces, the
-prediction-based border distances of the pieces' pixels, the solved board as an image."""
+"""Puzzle evaluation (evaluation.py:100-133, solver_driver.py, paikin_tal_solver/) for puzzles of one image, fixed size: the piece
+distances from the model's logits, the Paikin-Tal solver with its compatibilities on the device, and the reference's accuracies; and
+the classical baseline of solver_driver.py around the same solver - the image cut into eroded pieces, the prediction-based border
+distances of the pieces' pixels, the solved board as an image.  Type-1 puzzles (orientation known) take distances [4, n, n]; type-2
+puzzles (any side of a piece may meet any side of another; the solver assigns each piece a rotation) take distances [4, n, n, 4] of
+the pixel path, and every function here tells the two apart by that rank or by ``PuzzleSolution.rotations``."""
 from __future__ import annotations
 
 import heapq
@@ -79,15 +81,20 @@ def puzzle_distances(model, pieces, *, pair_batch: int = 1024, amp: bool = True,
 
 
 class PuzzleCompatibility:
-    """The Paikin-Tal compatibility state of one puzzle on the device (InterPieceDistance, type 1): built from Dq int32 [4, n, n]
-    by ``vited_puzzle_compat_init``; ``recalc`` and ``best_slot`` are the solver's two pool-empty steps.  Tensors: min_d,
-    second_d int64 [n, 4], candidate, best_buddy int32 [n, 4], compat, mutual float32 [4, n, n], start_count int32 [n],
-    start_total float32 [n], start_order int32 [n]."""
+    """The Paikin-Tal compatibility state of one puzzle on the device (InterPieceDistance): built from Dq int32 [4, n, n] (type 1) by
+    ``vited_puzzle_compat_init`` or from Dq2 int32 [4, n, n, 4] (type 2, ``puzzle_type`` 2) by ``vited_puzzle_compat2_init``;
+    ``recalc`` and ``best_slot`` are the solver's two pool-empty steps.  Tensors, type 1: min_d, second_d int64 [n, 4], candidate,
+    best_buddy int32 [n, 4], compat, mutual float32 [4, n, n], start_count int32 [n], start_total float32 [n], start_order int32 [n].
+    Type 2: compat, mutual float32 [4, n, n, 4] ([si, i, j, sj]), candidate, best_buddy int32 [n, 4, 2] ((piece, side) or (-1, -1)) and
+    min_count int32 [n, 4] beside the others."""
 
     def __init__(self, dq: torch.Tensor):
         self.dq = dq.to(torch.int32).contiguous()
+        if self.dq.dim() not in (3, 4):
+            raise ValueError(f'PuzzleCompatibility: distances must be [4, n, n] or [4, n, n, 4], got shape {list(self.dq.shape)}')
+        self.puzzle_type = 2 if self.dq.dim() == 4 else 1
         self.n = self.dq.shape[1]
-        self.state = ops.puzzle_compat_init(self.dq)
+        self.state = ops.puzzle_compat2_init(self.dq) if self.puzzle_type == 2 else ops.puzzle_compat_init(self.dq)
         dev = self.dq.device
         self._placed = torch.empty(self.n, dtype=torch.int32, device=dev)
         self.changed = torch.zeros(self.n, dtype=torch.int32, device=dev)
@@ -102,16 +109,24 @@ class PuzzleCompatibility:
     def recalc(self, placed) -> torch.Tensor:
         """recalculate_remaining_piece_compatibilities for the boolean mask ``placed`` [n]; returns the changed flags (device)."""
         self._placed.copy_(torch.as_tensor(placed, dtype=torch.int32))
-        ops.puzzle_compat_recalc(self.dq, self._placed, self.state, self.changed)
+        (ops.puzzle_compat2_recalc if self.puzzle_type == 2 else ops.puzzle_compat_recalc)(self.dq, self._placed, self.state, self.changed)
         return self.changed
 
     def best_slot(self, placed, slot_piece, slot_side):
-        """(piece, slot index, value) of the first maximum of mutual[(slot_side[k] + 2) % 4, p, slot_piece[k]] over unplaced p
-        ascending x slots k in list order."""
+        """Type 1: (piece, slot index, value) of the first maximum of mutual[(slot_side[k] + 2) % 4, p, slot_piece[k]] over unplaced p
+        ascending x slots k in list order.  Type 2: (piece, slot index, side of the piece, value) of the first maximum of
+        mutual[side, p, slot_piece[k], slot_side[k]] over unplaced p ascending x slots k in list order x side 0..3."""
         dev = self.dq.device
         self._placed.copy_(torch.as_tensor(placed, dtype=torch.int32))
         sp = torch.as_tensor(slot_piece, dtype=torch.int32).to(dev)
         ss = torch.as_tensor(slot_side, dtype=torch.int32).to(dev)
+        if self.puzzle_type == 2:
+            ops.puzzle_best_slot2(self.mutual, self._placed, sp, ss, out=self._word)
+            hit = ops.puzzle_unpack_slot2(int(self._word.item()), sp.numel())
+            if hit is None:
+                raise RuntimeError('best_slot: no unplaced piece')
+            p, k, side = hit
+            return p, k, side, float(self.mutual[side, p, int(slot_piece[k]), int(slot_side[k])])
         ops.puzzle_best_slot(self.mutual, self._placed, sp, ss, out=self._word)
         hit = ops.puzzle_unpack_slot(int(self._word.item()), sp.numel())
         if hit is None:
@@ -126,6 +141,7 @@ class PuzzleSolution(NamedTuple):
     order: 'object'             # int64 [n]: placement order, the seed first
     recalcs: int                # times the best-buddy pool ran empty and the compatibilities were recalculated
     grid: 'object'              # int64 [rows, cols]: the piece at each cell, -1 for none
+    rotations: 'object' = None  # type 2: int64 [n], the quarter turns 0..3 the solver gave each piece (numpy.rot90's k); type 1: None
 
 
 class _BuddyHeapEntry:
@@ -142,27 +158,41 @@ class _BuddyHeapEntry:
 
 
 def solve_puzzle(distances: torch.Tensor, grid_size) -> PuzzleSolution:
-    """Paikin-Tal placement (PaikinTalSolver, solver.py) of one type-1 puzzle of ``grid_size`` = (rows, cols) pieces from the
-    distances Dq int32 [4, n, n] of ``puzzle_distances``, making the reference's decisions in the reference's order: the seed from
-    the start ordering at the board centre, best buddies pooled as pieces are placed, the best-buddy heap popped until it yields a
-    placeable entry, and - whenever the pool is empty - a device recalculation of the compatibilities followed by a device scan
-    of every unplaced piece against every open slot.  The host keeps a mirror of the mutual compatibility, refreshed by one copy
-    per recalculation, for the heap's lookups."""
+    """Paikin-Tal placement (PaikinTalSolver, solver.py) of one puzzle of ``grid_size`` = (rows, cols) pieces, making the reference's
+    decisions in the reference's order: the seed from the start ordering at the board centre, best buddies pooled as pieces are
+    placed, the best-buddy heap popped until it yields a placeable entry, and - whenever the pool is empty - a device recalculation
+    of the compatibilities followed by a device scan of every unplaced piece against every open slot.  The host keeps a mirror of
+    the mutual compatibility for the heap's lookups, fetched again by the first lookup after a recalculation.
+
+    ``distances`` int32 [4, n, n] (``puzzle_distances``, ``puzzle_pixel_distances``) is a type-1 puzzle: only complementary sides
+    meet.  ``distances`` int32 [4, n, n, 4] (``puzzle_pixel_distances(pieces, puzzle_type=2)``) is a type-2 puzzle: every open slot
+    is tried against all four sides of a piece, the seed lies at rotation 0, each placed piece gets the rotation of
+    PuzzlePiece._calculate_placed_piece_rotation, and the slots it opens carry its unrotated sides
+    (_get_neighbor_locations_and_sides); ``PuzzleSolution.rotations`` holds the quarter turns."""
     import numpy as np
     rows, cols = int(grid_size[0]), int(grid_size[1])
-    n = distances.shape[1]
-    if rows * cols != n or tuple(distances.shape) != (4, n, n):
+    n = distances.shape[1] if distances.dim() > 1 else 0
+    type2 = distances.dim() == 4
+    if rows * cols != n or tuple(distances.shape) != ((4, n, n, 4) if type2 else (4, n, n)):
         raise ValueError(f'distances {tuple(distances.shape)} do not describe a {rows} x {cols} puzzle')
     comp = PuzzleCompatibility(distances)
-    mutual = comp.mutual.cpu().numpy()
-    best_buddy = comp.best_buddy.cpu().numpy()
+    mirror = [None]                                         # M on the host: dropped by a recalculation, fetched again by the next lookup
+    best_buddy = comp.best_buddy.cpu().numpy().reshape(n, 4, -1)[:, :, 0]       # the buddy's piece id, either type
     seed = int(comp.start_order[0].item())
+    # the sides of a piece that may meet a slot whose placed neighbour shows side s, and the mutual compatibility of the pairing
+    sides_for = (lambda s: (0, 1, 2, 3)) if type2 else (lambda s: ((s + 2) % 4,))
+
+    def m(p, ps, q, qs):
+        if mirror[0] is None:
+            mirror[0] = comp.mutual.cpu().numpy()
+        return float(mirror[0][ps, p, q, qs] if type2 else mirror[0][ps, p, q])
 
     placed = np.zeros(n, dtype=bool)
     occupied = np.zeros((n, n), dtype=bool)                # the reference's board: n x n, indexed as numpy indexes it
     board_loc = np.full((n, 2), -1, dtype=np.int64)
+    rotation = np.zeros(n, dtype=np.int64)                 # quarter turns; stays 0 throughout a type-1 puzzle
     top_left, bottom_right = [n // 2, n // 2], [n // 2, n // 2]
-    open_slots = []                                         # (location, piece, side of that piece facing the slot), list order
+    open_slots = []                                         # (location, piece, unrotated side of that piece facing the slot), list order
     pool = {}                                               # best buddies waiting, insertion ordered
     heap = []
     order = []
@@ -190,16 +220,18 @@ def solve_puzzle(distances: torch.Tensor, grid_size) -> PuzzleSolution:
                 continue
             pool[bb] = None
             for loc, q, side in open_slots:
-                heapq.heappush(heap, _BuddyHeapEntry(float(mutual[(side + 2) % 4, bb, q]), bb, (side + 2) % 4, q, side, loc))
+                for bb_side in sides_for(side):
+                    heapq.heappush(heap, _BuddyHeapEntry(m(bb, bb_side, q, side), bb, bb_side, q, side, loc))
 
     def open_slots_around(piece):
         r, c = board_loc[piece]
-        for s, (dr, dc) in enumerate(_SIDE_STEP):
-            loc = (int(r + dr), int(c + dc))
+        for d, (dr, dc) in enumerate(_SIDE_STEP):
+            loc, s = (int(r + dr), int(c + dc)), int(d - rotation[piece]) % 4
             if slot_open(loc):
                 open_slots.append((loc, piece, s))
                 for bb in list(pool):
-                    heapq.heappush(heap, _BuddyHeapEntry(float(mutual[s, piece, bb]), bb, (s + 2) % 4, piece, s, loc))
+                    for bb_side in sides_for(s):
+                        heapq.heappush(heap, _BuddyHeapEntry(m(piece, s, bb, bb_side), bb, bb_side, piece, s, loc))
 
     put(seed, (n // 2, n // 2))
     add_best_buddies(seed)
@@ -210,14 +242,16 @@ def solve_puzzle(distances: torch.Tensor, grid_size) -> PuzzleSolution:
                 e = heapq.heappop(heap)
                 if not placed[e.piece] and slot_open(e.location):
                     break
-            piece, loc, from_pool = e.piece, e.location, True
+            piece, piece_side, neighbor, neighbor_side, loc, from_pool = e.piece, e.piece_side, e.neighbor, e.neighbor_side, e.location, True
         else:
             recalcs += 1
             comp.recalc(placed)
-            mutual = comp.mutual.cpu().numpy()
+            mirror[0] = None
             valid = [k for k, (loc, _, _) in enumerate(open_slots) if slot_open(loc)]
-            piece, k, _ = comp.best_slot(placed, [open_slots[v][1] for v in valid], [open_slots[v][2] for v in valid])
-            loc, from_pool = open_slots[valid[k]][0], False
+            hit = comp.best_slot(placed, [open_slots[v][1] for v in valid], [open_slots[v][2] for v in valid])
+            piece, (loc, neighbor, neighbor_side), from_pool = hit[0], open_slots[valid[hit[1]]], False
+            piece_side = hit[2] if type2 else (neighbor_side + 2) % 4
+        rotation[piece] = (rotation[neighbor] + (neighbor_side + 2) % 4 - piece_side) % 4
         for d in range(2):
             if top_left[d] > loc[d]:
                 top_left[d] = loc[d]
@@ -234,15 +268,20 @@ def solve_puzzle(distances: torch.Tensor, grid_size) -> PuzzleSolution:
     shape = locations.max(axis=0) + 1
     grid = np.full((int(shape[0]), int(shape[1])), -1, dtype=np.int64)
     grid[locations[:, 0], locations[:, 1]] = np.arange(n)
-    return PuzzleSolution(locations, board_loc, np.array(order, dtype=np.int64), recalcs, grid)
+    return PuzzleSolution(locations, board_loc, np.array(order, dtype=np.int64), recalcs, grid, rotation if type2 else None)
 
 
 def puzzle_accuracy(solution: PuzzleSolution, true_locations) -> dict:
     """The accuracies PuzzleResultsCollection.collect_results reports for one solved puzzle (puzzle_importer.py:779-844, the rules
-    of :985-1150 and :1386-1520), every piece from the one original puzzle and unrotated: ``Direct_Standard`` (pieces at their true
-    cell / n), ``Direct_Modified`` (the same, best over the origins the reference's search from the top-left corner offers),
-    ``neighbor`` (sides whose neighbour - or board edge - is the true one / 4n) and ``perfect``.  ``true_locations`` int [n, 2]:
-    where piece i belongs in the original rows x cols grid."""
+    of :985-1150 and :1386-1520), every piece from the one original puzzle: ``Direct_Standard`` (pieces at their true cell / n),
+    ``Direct_Modified`` (the same, best over the origins the reference's search from the top-left corner offers), ``neighbor``
+    (sides whose neighbour - or board edge - is the true one / 4n) and ``perfect``.  ``true_locations`` int [n, 2]: where piece i
+    belongs in the original rows x cols grid.
+
+    A type-2 solution (``solution.rotations`` is not None) follows the reference's type-2 rules (:558-598, :985-1058): a piece at its
+    true cell counts only at rotation 0 - otherwise it is a "wrong rotation", and the dict gains ``'wrong_rotation'``, their number
+    under the standard origin; side s of a piece turned by r looks at the cell in direction (s + r) % 4, and a true neighbour found
+    there counts only when both pieces carry the same rotation."""
     import numpy as np
     true = np.asarray(true_locations, dtype=np.int64)
     loc = np.asarray(solution.locations, dtype=np.int64)
@@ -253,8 +292,11 @@ def puzzle_accuracy(solution: PuzzleSolution, true_locations) -> dict:
     placed_id = np.full((g_rows, g_cols), -1, dtype=np.int64)
     placed_id[loc[:, 0], loc[:, 1]] = orig_id
 
+    rot = None if getattr(solution, 'rotations', None) is None else np.asarray(solution.rotations, dtype=np.int64) % 4
+    upright = np.ones(n, dtype=bool) if rot is None else rot == 0
+
     def correct_at(origin):
-        return int(np.all(loc == true + np.asarray(origin), axis=1).sum())
+        return int((np.all(loc == true + np.asarray(origin), axis=1) & upright).sum())
 
     standard = correct_at((0, 0))
     # the reference's breadth-first search for the candidate origins (puzzle_importer.py:1081-1138)
@@ -270,15 +312,24 @@ def puzzle_accuracy(solution: PuzzleSolution, true_locations) -> dict:
                     frontier.append(nxt)
     modified = max(correct_at(origin) for origin in explored)
 
+    placed_rot = np.zeros((g_rows, g_cols), dtype=np.int64)
+    if rot is not None:
+        placed_rot[loc[:, 0], loc[:, 1]] = rot
     neighbors = 0
     for p in range(n):
         for s, (dr, dc) in enumerate(_SIDE_STEP):
             tr, tc = true[p, 0] + dr, true[p, 1] + dc
             want = int(tr * t_cols + tc) if 0 <= tr < t_rows and 0 <= tc < t_cols else None
-            r, c = loc[p, 0] + dr, loc[p, 1] + dc
-            got = int(placed_id[r, c]) if 0 <= r < g_rows and 0 <= c < g_cols else -1
-            neighbors += (None if got < 0 else got) == want
-    return {'Direct_Standard': standard / n, 'Direct_Modified': modified / n, 'neighbor': neighbors / (4 * n), 'perfect': standard == n}
+            lr, lc = _SIDE_STEP[s if rot is None else int(s + rot[p]) % 4]
+            r, c = loc[p, 0] + lr, loc[p, 1] + lc
+            inside = 0 <= r < g_rows and 0 <= c < g_cols
+            got = int(placed_id[r, c]) if inside else -1
+            same_turn = want is None or rot is None or bool(inside and placed_rot[r, c] == rot[p])
+            neighbors += (None if got < 0 else got) == want and same_turn
+    out = {'Direct_Standard': standard / n, 'Direct_Modified': modified / n, 'neighbor': neighbors / (4 * n), 'perfect': standard == n}
+    if rot is not None:
+        out['wrong_rotation'] = int((np.all(loc == true, axis=1) & ~upright).sum())
+    return out
 
 
 # ---- the classical baseline (solver_driver.py): cut, pixel distances, board --------------------------------------------------------
@@ -314,23 +365,30 @@ def puzzle_model_pieces(pieces, size: int):
     return ops.puzzle_resize_pieces(pieces, size)
 
 
-def puzzle_pixel_distances(pieces):
+def puzzle_pixel_distances(pieces, puzzle_type: int = 1):
     """Dq int32 [4, n, n] of PuzzlePiece.calculate_asymmetric_distance (puzzle_piece.py:535-609) over all ordered pairs and sides of
-    the pieces uint8 [n, We, We, 3] of ``cut_puzzle``: what ``solve_puzzle`` takes, as it takes ``puzzle_distances``' ."""
-    return ops.puzzle_pixel_distances(pieces)
+    the pieces uint8 [n, We, We, 3] of ``cut_puzzle``: what ``solve_puzzle`` takes, as it takes ``puzzle_distances``' .
+    ``puzzle_type=2``: Dq2 int32 [4, n, n, 4] over all 16 side pairings, [si, i, j, sj], which ``solve_puzzle`` solves as a type-2
+    puzzle."""
+    return ops.puzzle_pixel_distances(pieces, puzzle_type=puzzle_type)
 
 
 def reconstruct_puzzle(pieces, solution, true_locations, piece_width: int, marker=None):
     """Puzzle.reconstruct_from_pieces (puzzle_importer.py:265-321, :448-473): the board uint8 [R P, C P, 3] of the pieces at
     ``solution.locations`` (a ``PuzzleSolution``, or the locations themselves).  With ``marker`` (three bytes; the reference's is BGR
-    (0, 0, 255)) every piece away from its true location is framed, which needs (P - We) // 2 >= 1."""
+    (0, 0, 255)) every piece away from its true location is framed, which needs (P - We) // 2 >= 1.  A piece of a type-2 solution
+    enters as numpy.rot90(piece, rotation); the frame still goes by the location alone, as insert_piece_into_image draws it."""
+    rotations = getattr(solution, 'rotations', None)
+    if rotations is not None:
+        return ops.puzzle_assemble2(pieces, solution.locations, rotations, true_locations, piece_width, marker)
     return ops.puzzle_assemble(pieces, getattr(solution, 'locations', solution), true_locations, piece_width, marker)
 
 
-def solve_pixel_puzzle(image, piece_width: int, erosion: float = 0., order=None, marker=None):
+def solve_pixel_puzzle(image, piece_width: int, erosion: float = 0., order=None, marker=None, puzzle_type: int = 1):
     """One pass of solver_driver.py's loop on the device: cut, pixel distances, Paikin-Tal, accuracies, board.  Returns
-    (``PuzzleSolution``, the dict of ``puzzle_accuracy``, board uint8 [R P, C P, 3])."""
+    (``PuzzleSolution``, the dict of ``puzzle_accuracy``, board uint8 [R P, C P, 3]).  ``puzzle_type=2`` solves the pieces as a type-2
+    puzzle (paikin_tal_tester.py's PuzzleType.type2): the pieces are cut upright, the solver is free to turn them."""
     cut = cut_puzzle(image, piece_width, erosion, order)
-    solution = solve_puzzle(puzzle_pixel_distances(cut.pieces), cut.grid_size)
+    solution = solve_puzzle(puzzle_pixel_distances(cut.pieces, puzzle_type), cut.grid_size)
     board = reconstruct_puzzle(cut.pieces, solution, cut.true_locations, cut.piece_width, marker)
     return solution, puzzle_accuracy(solution, cut.true_locations), board

@@ -1320,3 +1320,8 @@ from .ops_ranklists import TOPK_MAX_K, retrieval_curve_rows, retrieval_topk_rows
 # ---- classical puzzle baseline: the wrappers of csrc/puzzle_pixels.hip (cut, resize, border distances, board) live in ops_puzzlepixels.py
 from .ops_puzzlepixels import (PUZZLE_MAX_ERODED, PUZZLE_MAX_PIECES, PUZZLE_MAX_SIZE, puzzle_assemble, puzzle_cut,  # noqa: E402,F401
                                puzzle_eroded_width, puzzle_pixel_distances, puzzle_resize_pieces)
+
+# ---- type-2 puzzles (pieces of unknown rotation): the wrappers of the *2 entry points of csrc/puzzle_pixels.hip and
+# csrc/puzzle_compat.hip live in ops_puzzle2.py ---------------------------------------------------------------------------------------
+from .ops_puzzle2 import (puzzle_assemble2, puzzle_best_slot2, puzzle_compat2_init, puzzle_compat2_recalc,  # noqa: E402,F401
+                          puzzle_pixel_distances2, puzzle_unpack_slot2)

@@ -98,9 +98,14 @@ def puzzle_resize_pieces(pieces: torch.Tensor, size: int, out: torch.Tensor | No
     return out
 
 
-def puzzle_pixel_distances(pieces: torch.Tensor, out: torch.Tensor | None = None):
+def puzzle_pixel_distances(pieces: torch.Tensor, out: torch.Tensor | None = None, puzzle_type: int = 1):
     """PuzzlePiece.calculate_asymmetric_distance over all ordered pairs and sides (``vited_puzzle_pixel_distances``): pieces uint8
-    [n, We, We, 3], n >= 2 -> Dq int32 [4, n, n], Dq[s, i, j] = sum | 2 B_s(i) - B'_s(i) - B_(s+2)%4(j) |; the diagonal is 2^31 - 1."""
+    [n, We, We, 3], n >= 2 -> Dq int32 [4, n, n], Dq[s, i, j] = sum | 2 B_s(i) - B'_s(i) - B_(s+2)%4(j) |; the diagonal is 2^31 - 1.
+    ``puzzle_type=2``: all 16 side pairings, Dq2 int32 [4, n, n, 4] of ``puzzle_pixel_distances2``."""
+    if puzzle_type == 2:
+        return _o.puzzle_pixel_distances2(pieces, out)
+    if puzzle_type != 1:
+        raise ValueError(f'puzzle_pixel_distances: puzzle_type must be 1 or 2, got {puzzle_type!r}')
     _o._need_gpu(pieces, out)
     op = 'puzzle_pixel_distances'
     n, We = _pieces(op, pieces)
@@ -112,17 +117,8 @@ def puzzle_pixel_distances(pieces: torch.Tensor, out: torch.Tensor | None = None
     return out
 
 
-def puzzle_assemble(pieces: torch.Tensor, locations, true_locations, piece_width: int, marker=None, out: torch.Tensor | None = None):
-    """Puzzle.reconstruct_from_pieces on the device (``vited_puzzle_assemble``): the board uint8 [R * P, C * P, 3] of pieces uint8
-    [n, We, We, 3] placed at ``locations`` (host integers [n, 2], distinct cells (row, col) >= 0; R, C their extent, R * C = n), each
-    at (r P + pad, c P + pad), pad = (P - We) // 2, black elsewhere.  With ``marker`` (three bytes) every piece whose location
-    differs from its ``true_locations`` row gets a one-pixel frame of that colour, which needs pad >= 1."""
-    _o._need_gpu(pieces, out)
-    op = 'puzzle_assemble'
-    n, We = _pieces(op, pieces)
-    P, We = _widths(op, piece_width, We)
-    loc = _host_ints(op, 'locations', locations, (n, 2))
-    true = _host_ints(op, 'true_locations', true_locations, (n, 2))
+def _board_cells(op, n, We, P, loc, true, marker):
+    """(cells int32 [R * C], R, C, the marker as one integer or -1) of ``vited_puzzle_assemble`` from validated host locations."""
     if loc.min() < 0:
         raise ValueError(f'{op}: locations must lie inside the board, got a negative cell')
     R, C = int(loc[:, 0].max()) + 1, int(loc[:, 1].max()) + 1
@@ -142,6 +138,21 @@ def puzzle_assemble(pieces: torch.Tensor, locations, true_locations, piece_width
     framed = (loc != true).any(axis=1) if marker is not None else np.zeros(n, bool)
     cells = np.full(R * C, -1, np.int32)
     cells[flat] = 2 * np.arange(n) + framed
+    return cells, R, C, colour
+
+
+def puzzle_assemble(pieces: torch.Tensor, locations, true_locations, piece_width: int, marker=None, out: torch.Tensor | None = None):
+    """Puzzle.reconstruct_from_pieces on the device (``vited_puzzle_assemble``): the board uint8 [R * P, C * P, 3] of pieces uint8
+    [n, We, We, 3] placed at ``locations`` (host integers [n, 2], distinct cells (row, col) >= 0; R, C their extent, R * C = n), each
+    at (r P + pad, c P + pad), pad = (P - We) // 2, black elsewhere.  With ``marker`` (three bytes) every piece whose location
+    differs from its ``true_locations`` row gets a one-pixel frame of that colour, which needs pad >= 1."""
+    _o._need_gpu(pieces, out)
+    op = 'puzzle_assemble'
+    n, We = _pieces(op, pieces)
+    P, We = _widths(op, piece_width, We)
+    loc = _host_ints(op, 'locations', locations, (n, 2))
+    true = _host_ints(op, 'true_locations', true_locations, (n, 2))
+    cells, R, C, colour = _board_cells(op, n, We, P, loc, true, marker)
     cells_dev = torch.from_numpy(cells).to(pieces.device)
     out = _o._out(op, 'out', out, _u8, (R * P, C * P, 3), pieces.device)
     _o._lib.call('vited_puzzle_assemble', _o._ptr(pieces), n, We, P, _o._ptr(cells_dev), R, C, colour, _o._ptr(out), _o._stream())
