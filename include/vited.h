@@ -901,6 +901,25 @@ int vited_puzzle_best_slot2(const float* mutual, int64_t n, const int* placed, c
 int vited_puzzle_assemble2(const uint8_t* pieces, int64_t n, int eroded_width, int piece_width, const int* cells, const int* rotations,
                            int64_t rows, int64_t cols, int marker, uint8_t* board, void* stream);
 
+/* ---- puzzle solving, type 2 from the pair model: turned pieces (csrc/puzzle_turn.h states every index rule) ---------
+ * A turn k in 0..3 is k clockwise quarter turns: turn_k(x) = numpy.rot90(x, -k) over the pixel axes, the border that was side s becomes
+ * side (s + k) % 4.  The model scores the pair (piece i, turn_k(piece j)); its bin b speaks of side si = (b + 1) % 4 of i against side
+ * sj = (si + 2 - k) % 4 of the upright j, so four turns x four bins cover the 16 pairings of (i, j) once each and k = 0 is type 1.
+ *
+ * vited_patchify_turned / _u8: vited_patchify / vited_patchify_u8 of turn_k(image), gathered from the upright image: row (b, patch) of
+ *   out equals, bit for bit, the row those entries write for the physically turned image.  turn int32 [batch] (device, one per OUTPUT
+ *   image b, beside batch_index; only the low two bits are read) or NULL: every image is turned by turn_all in 0..3.
+ * vited_puzzle_distances2_from_logits: m pairs (pi[r], pjt[r]) (int64; pjt = k n + j in [0, 4 n)) and their logits [m, 4] fp32 ->
+ *   dq2[si, i, j, sj] = the quantisation of vited_puzzle_distances_from_logits of logits[r, b] for the 4 bins; dq2 int32 [4, n, n, 4].  A
+ *   pair with i outside [0, n), pjt outside [0, 4 n) or j == i is skipped and sets bit 0 of *bad (int32, device). */
+int vited_patchify_turned(const float* img, int64_t img_batch_stride, const int64_t* batch_index, const int32_t* turn, int turn_all,
+                          void* out, int out_dtype, int64_t batch, int chans, int img_size, int patch, void* stream);
+int vited_patchify_turned_u8(const uint8_t* img, int64_t img_batch_stride, const int64_t* batch_index, const int32_t* turn, int turn_all,
+                             void* out, int out_dtype, int64_t batch, int chans, int img_size, int patch, const float* mean,
+                             const float* std, void* stream);
+int vited_puzzle_distances2_from_logits(const float* logits, const int64_t* pi, const int64_t* pjt, int64_t m, int64_t n, int* dq2,
+                                        int* bad, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,6 +10,7 @@
 // (C in fp64 rounded once to fp32, M = (C + C^) / 2 in fp32, as numpy does it), the start ordering is a rank count, and the slot
 // scan is an integer max over packed (order-preserving key, reversed linear index) words.
 #include "common.h"
+#include "puzzle_turn.h"
 
 #pragma clang fp contract(off)
 
@@ -198,6 +199,13 @@ __global__ void __launch_bounds__(THREADS) best_slot_kernel(const float* __restr
     if (threadIdx.x % VITED_WAVE == 0 && word != 0) atomicMax(best, word);
 }
 
+// uint32(trunc(fp32(fp32(1 - sigmoid(logit)) * 1000))): the one statement of the quantisation, for both puzzle types.
+__device__ __forceinline__ int quantise_logit(float x) {
+    const float sig = 1.0f / (1.0f + expf(-x));
+    const float q = (1.0f - sig) * 1000.0f;
+    return (int)(uint32_t)q;
+}
+
 // Ordered-pair distances from the model's 4 logits (evaluation.py:118-133): side s of i uses bin (s + 3) % 4, and the value is
 // uint32(trunc(fp32(fp32(1 - sigmoid(logit)) * 1000))).
 __global__ void __launch_bounds__(THREADS) distances_kernel(const float* __restrict__ logits, const int64_t* __restrict__ pi,
@@ -211,12 +219,24 @@ __global__ void __launch_bounds__(THREADS) distances_kernel(const float* __restr
         return;
     }
 #pragma unroll
-    for (int s = 0; s < 4; ++s) {
-        const float x = logits[r * 4 + ((s + 3) & 3)];
-        const float sig = 1.0f / (1.0f + expf(-x));
-        const float q = (1.0f - sig) * 1000.0f;
-        dq[((int64_t)s * n + i) * n + j] = (int)(uint32_t)q;
+    for (int s = 0; s < 4; ++s) dq[((int64_t)s * n + i) * n + j] = quantise_logit(logits[r * 4 + ((s + 3) & 3)]);
+}
+
+// The same quantisation for the learned type-2 path: pair r is (piece i, piece j turned by k clockwise quarter
+// turns), jt = k n + j, and its bin b belongs to side (b + 1) % 4 of i against side ((b + 1) % 4 + 2 - k) % 4 of the upright j
+// (puzzle_turn.h).  Four turns x four bins fill the 16 pairings of (i, j) once each; k = 0 stores what distances_kernel stores.
+__global__ void __launch_bounds__(THREADS) distances2_kernel(const float* __restrict__ logits, const int64_t* __restrict__ pi,
+                                                             const int64_t* __restrict__ pjt, int64_t m, int n, int* __restrict__ dq2,
+                                                             int* __restrict__ bad) {
+    const int64_t r = (int64_t)blockIdx.x * THREADS + threadIdx.x;
+    if (r >= m) return;
+    const int64_t i = pi[r], jt = pjt[r];
+    if (!puzzle_turn::pair_in_range(i, jt, n)) {
+        atomicOr(bad, 1);
+        return;
     }
+#pragma unroll
+    for (int b = 0; b < 4; ++b) dq2[puzzle_turn::dq2_slot(n, i, jt, b)] = quantise_logit(logits[r * 4 + b]);
 }
 
 // ---- type 2 (inter_piece_distance.py with PuzzleType.type2): any side sj of piece j may meet side si of piece i ---------------------------
@@ -396,6 +416,15 @@ extern "C" int vited_puzzle_distances_from_logits(const float* logits, const int
     if (m == 0) return VITED_OK;
     hipLaunchKernelGGL(distances_kernel, dim3(blocks_for(m)), dim3(THREADS), 0, static_cast<hipStream_t>(stream), logits, pi, pj, m,
                        (int)n, dq, bad);
+    return vited_check_launch();
+}
+
+extern "C" int vited_puzzle_distances2_from_logits(const float* logits, const int64_t* pi, const int64_t* pjt, int64_t m, int64_t n, int* dq2,
+                                                   int* bad, void* stream) {
+    if (!logits || !pi || !pjt || !dq2 || !bad || m < 0 || n < 2 || n > MAX_PIECES) return VITED_ERR_BAD_ARG;
+    if (m == 0) return VITED_OK;
+    hipLaunchKernelGGL(distances2_kernel, dim3(blocks_for(m)), dim3(THREADS), 0, static_cast<hipStream_t>(stream), logits, pi, pjt, m,
+                       (int)n, dq2, bad);
     return vited_check_launch();
 }
 

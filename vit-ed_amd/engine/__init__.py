@@ -19,7 +19,8 @@ from .metrics import (ClassificationMeters, GeshaemMetrics, MeterValue, PairScor
 from .mining import (MinedPairs, hisfrag_prepare_data, hisfrag_prepare_indexed, hisfrag_prepare_mined, mine_pairs,  # noqa: F401
                      mine_pairs_device, mined_bce_fused, mined_bce_with_logits, mined_pair_capacity)
 from .puzzle import (PUZZLE_SIDES, PuzzleCompatibility, PuzzleCut, PuzzleSolution, cut_puzzle, puzzle_accuracy,  # noqa: F401
-                     puzzle_distances, puzzle_model_pieces, puzzle_pixel_distances, reconstruct_puzzle, solve_pixel_puzzle, solve_puzzle)
+                     puzzle_distances, puzzle_model_pieces, puzzle_pixel_distances, reconstruct_puzzle, solve_model_puzzle, solve_pixel_puzzle,
+                     solve_puzzle)
 from .relevancy import pair_relevancy, relevancy_from_cams  # noqa: F401
 from .similarity import pairwise_similarity, shard_rows_by_pair_count  # noqa: F401
 from .train import (NativeScalerWithGradNormCount, TrainMeters, TrainStep, TwoStageTrainStep, _decoder_only_parameters,  # noqa: F401

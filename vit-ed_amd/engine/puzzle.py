@@ -3,7 +3,8 @@ distances from the model's logits, the Paikin-Tal solver with its compatibilitie
 the classical baseline of solver_driver.py around the same solver - the image cut into eroded pieces, the prediction-based border
 distances of the pieces' pixels, the solved board as an image.  Type-1 puzzles (orientation known) take distances [4, n, n]; type-2
 puzzles (any side of a piece may meet any side of another; the solver assigns each piece a rotation) take distances [4, n, n, 4] of
-the pixel path, and every function here tells the two apart by that rank or by ``PuzzleSolution.rotations``."""
+the pixel path or of the model (``puzzle_type=2``), and every function here tells the two apart by that rank or by
+``PuzzleSolution.rotations``."""
 from __future__ import annotations
 
 import heapq
@@ -29,7 +30,8 @@ def _ordered_block_pairs(a0, a1, n, dev):
 
 
 @torch.no_grad()
-def puzzle_distances(model, pieces, *, pair_batch: int = 1024, amp: bool = True, block: int = 128, return_logits: bool = False):
+def puzzle_distances(model, pieces, *, pair_batch: int = 1024, amp: bool = True, block: int = 128, return_logits: bool = False,
+                     puzzle_type: int = 1):
     """The reference's integer piece distances ``Dq`` int32 [4, n, n] on the device (evaluation.py:100-133 feeding
     inter_piece_distance.py:206-223): Dq[s, i, j] is the distance of side s of piece i (top 0, right 1, bottom 2, left 3) to the
     complementary side of piece j, from the model's logits of the ordered pair (i, j) (bin (s + 3) % 4), quantised as
@@ -38,7 +40,16 @@ def puzzle_distances(model, pieces, *, pair_batch: int = 1024, amp: bool = True,
     ``pieces``: the n pieces of one puzzle at model size, uint8 [n, 3, S, S] (normalised in the patch-embedding kernel) or
     normalised float, on the host or the device.  The encoder and the image-2 token cache run once per piece; the decoder runs on
     all n (n - 1) ordered pairs, ``pair_batch`` at a time, row block by row block of ``block`` pieces, and every batch's logits
-    are quantised and scattered into Dq on the device.  ``return_logits`` also returns the fp32 logits [n, n, 4] (diagonal 0)."""
+    are quantised and scattered into Dq on the device.  ``return_logits`` also returns the fp32 logits [n, n, 4] (diagonal 0).
+
+    ``puzzle_type=2`` (pieces of unknown rotation): Dq2 int32 [4, n, n, 4] over all 16 side pairings, what
+    ``solve_puzzle`` solves as a type-2 puzzle.  Dq2[si, i, j, sj] is bin (si + 3) % 4 of the pair (piece i, piece j turned by
+    k = (si + 2 - sj) % 4 clockwise quarter turns, so that its side sj faces side si), quantised as above; Dq2[s, :, :, (s + 2) % 4]
+    is the type-1 Dq[s], bit for bit at equal ``pair_batch`` and ``block``.  The encoder still runs once per piece; the image-2 token
+    cache is built for the 4 n turned pieces from the upright ones, and within a row block the pairs run turn by turn, each turn
+    batched on its own.  ``return_logits`` then returns fp32 [n, n, 4, 4], indexed [i, j, k, bin] (diagonal 0)."""
+    if puzzle_type not in (1, 2):
+        raise ValueError(f'puzzle_distances: puzzle_type must be 1 or 2, got {puzzle_type!r}')
     if not getattr(model, 'supports_pair_cache', False):
         raise TypeError('puzzle_distances needs the HIP model (VisionTransformerCustom): it runs on the pair caches')
     if getattr(model, 'num_classes', 4) != 4:
@@ -48,15 +59,24 @@ def puzzle_distances(model, pieces, *, pair_batch: int = 1024, amp: bool = True,
     n = src.n
     if n < 2:
         raise ValueError('a puzzle needs at least two pieces')
-    dq = torch.full((4, n, n), _DQ_UNSET, dtype=torch.int32, device=dev)
+    type2 = puzzle_type == 2
+    turns = (0, 1, 2, 3) if type2 else (0,)
+    dq = torch.full((4, n, n, 4) if type2 else (4, n, n), _DQ_UNSET, dtype=torch.int32, device=dev)
     bad = torch.zeros(1, dtype=torch.int32, device=dev)
-    logits = torch.zeros((n, n, 4), dtype=torch.float32, device=dev) if return_logits else None
+    logits = torch.zeros((n, n, 4, 4) if type2 else (n, n, 4), dtype=torch.float32, device=dev) if return_logits else None
     dtype_ctx = lambda: torch.autocast(dev.type, dtype=torch.bfloat16, enabled=amp)
     was_training = model.training
     model.eval()
     try:
         with dtype_ctx():
-            tokens2, q0 = model.cache_image2_tokens(src.block(0, n))        # once per piece
+            if type2:                                                       # once per piece and turn: rows k n + j, from one upright copy
+                upright = src.block(0, n)
+                caches = [model.cache_image2_tokens(upright, turn=k) for k in turns]
+                tokens2 = torch.cat([c[0] for c in caches])
+                q0 = None if caches[0][1] is None else torch.cat([c[1] for c in caches])
+                del caches, upright
+            else:
+                tokens2, q0 = model.cache_image2_tokens(src.block(0, n))    # once per piece
         for a0 in range(0, n, block):
             a1 = min(a0 + block, n)
             with dtype_ctx():
@@ -64,14 +84,22 @@ def puzzle_distances(model, pieces, *, pair_batch: int = 1024, amp: bool = True,
                 kvs = model.cache_context_kv(feats)
             del feats
             ii, jj = _ordered_block_pairs(a0, a1, n, dev)
-            for p0 in range(0, ii.numel(), pair_batch):
-                i_sub, j_sub = ii[p0:p0 + pair_batch], jj[p0:p0 + pair_batch]
-                with dtype_ctx():
-                    out = model.forward_pairs_cached(tokens2, j_sub, kvs, i_sub - a0, q0)
-                out = out.float().reshape(-1, 4).contiguous()
-                ops.puzzle_distances_from_logits(out, i_sub.contiguous(), j_sub.contiguous(), dq, bad)
-                if logits is not None:
-                    logits[i_sub, j_sub] = out
+            for k in turns:                                                 # k = 0: the launches of a type-1 puzzle
+                for p0 in range(0, ii.numel(), pair_batch):
+                    i_sub, j_sub = ii[p0:p0 + pair_batch], jj[p0:p0 + pair_batch]
+                    jt_sub = j_sub + k * n if k else j_sub
+                    with dtype_ctx():
+                        out = model.forward_pairs_cached(tokens2, jt_sub, kvs, i_sub - a0, q0)
+                    out = out.float().reshape(-1, 4).contiguous()
+                    if type2:
+                        ops.puzzle_distances2_from_logits(out, i_sub.contiguous(), jt_sub.contiguous(), dq, bad)
+                    else:
+                        ops.puzzle_distances_from_logits(out, i_sub.contiguous(), j_sub.contiguous(), dq, bad)
+                    if logits is not None:
+                        if type2:
+                            logits[i_sub, j_sub, k] = out
+                        else:
+                            logits[i_sub, j_sub] = out
             del kvs
     finally:
         model.train(was_training)
@@ -390,5 +418,21 @@ def solve_pixel_puzzle(image, piece_width: int, erosion: float = 0., order=None,
     puzzle (paikin_tal_tester.py's PuzzleType.type2): the pieces are cut upright, the solver is free to turn them."""
     cut = cut_puzzle(image, piece_width, erosion, order)
     solution = solve_puzzle(puzzle_pixel_distances(cut.pieces, puzzle_type), cut.grid_size)
+    board = reconstruct_puzzle(cut.pieces, solution, cut.true_locations, cut.piece_width, marker)
+    return solution, puzzle_accuracy(solution, cut.true_locations), board
+
+
+def solve_model_puzzle(model, image, piece_width: int, erosion: float = 0., order=None, marker=None, puzzle_type: int = 1, **distance_kw):
+    """The learned twin of ``solve_pixel_puzzle``, evaluation.py's loop body on the device: cut, the pieces at the model's size, the
+    model's distances, Paikin-Tal, accuracies, board.  Returns (``PuzzleSolution``, the dict of ``puzzle_accuracy``, board uint8
+    [R P, C P, 3]).  ``puzzle_type=2`` scores all 16 side pairings through the model and solves the pieces as a type-2 puzzle;
+    ``distance_kw`` (pair_batch, amp, block) goes to ``puzzle_distances``."""
+    if puzzle_type not in (1, 2):
+        raise ValueError(f'solve_model_puzzle: puzzle_type must be 1 or 2, got {puzzle_type!r}')
+    if distance_kw.get('return_logits'):
+        raise ValueError('solve_model_puzzle: return_logits belongs to puzzle_distances, the driver returns the solution')
+    cut = cut_puzzle(image, piece_width, erosion, order)
+    distances = puzzle_distances(model, puzzle_model_pieces(cut.pieces, model.img_size), puzzle_type=puzzle_type, **distance_kw)
+    solution = solve_puzzle(distances, cut.grid_size)
     board = reconstruct_puzzle(cut.pieces, solution, cut.true_locations, cut.piece_width, marker)
     return solution, puzzle_accuracy(solution, cut.true_locations), board

@@ -636,11 +636,13 @@ def _pos_drop(rt, x, batch, rows, with_cls, pos_drop, keep, in_place):
     return y.view(batch * rows, rt.dim)
 
 
-def _patch_tokens_fwd(rt, img, S, with_cls, batch_index=None, keep=None):
+def _patch_tokens_fwd(rt, img, S, with_cls, batch_index=None, keep=None, turn=None):
     """timm PatchEmbed + pos-embed (+ cls row, S: a DecShared) : returns x fp32 [B*rows, D] and the saved patch matrix.
     ``keep`` (int32 [B, K]; patch dropout): only the kept patches are extracted, embedded and given their
     position - rows = K + 1 either way: patch 0 leads without a cls row (the reference's prefix slot falls on it), the cls row with
-    one.  Without it the launches are exactly those of a model that has no patch dropout."""
+    one.  Without it the launches are exactly those of a model that has no patch dropout.
+    ``turn`` (an int 0..3 or an int tensor [B]; learned type-2 puzzles): the patches of every image turned by
+    that many clockwise quarter turns, gathered from the upright image; None is the upright path, launch for launch."""
     if keep is not None:
         lead = not with_cls
         patches = ops.patchify_kept(img, rt.patch_size, rt.act_dtype, keep, lead, batch_index, mean=rt.input_mean, std=rt.input_std)
@@ -648,7 +650,10 @@ def _patch_tokens_fwd(rt, img, S, with_cls, batch_index=None, keep=None):
         x = ops.tokens_kept(tok, S.pos.view(rt.n2, rt.dim), S.cls.view(-1) if with_cls else None, keep, lead)
         batch, rows = x.shape[0], x.shape[1]
         return x.view(batch * rows, rt.dim), patches, batch, rows
-    patches = ops.patchify(img, rt.patch_size, rt.act_dtype, batch_index, mean=rt.input_mean, std=rt.input_std)
+    if turn is not None:
+        patches = ops.patchify_turned(img, rt.patch_size, rt.act_dtype, turn, batch_index, mean=rt.input_mean, std=rt.input_std)
+    else:
+        patches = ops.patchify(img, rt.patch_size, rt.act_dtype, batch_index, mean=rt.input_mean, std=rt.input_std)
     batch = patches.shape[0] // rt.n1
     pos2 = S.pos.view(rt.n2, rt.dim)
     rows, first = (rt.n2, 1) if with_cls else (rt.n1, 0)        # under a cls row the patch tokens start at row 1 of every image
@@ -967,15 +972,15 @@ def _dec_block_bwd(rt, dx, dx_lp, ctxf, dctx, P, entry, batch, n, cls_only, inde
 # the pair batch then gathers token rows by index j and the attention kernel reads K / V by index i (vited_attention_fwd_indexed).
 # ``params`` is the decoder's flat parameter list (model._decoder_params) throughout.
 @torch.no_grad()
-def image2_tokens(rt: Runtime, img, params):
+def image2_tokens(rt: Runtime, img, params, turn=None):
     """Everything of the decoder that depends on image 2 ALONE, once per image:
       * x  = patch embedding + cls row + pos_embed (timm _pos_embed), the decoder's input stream;
       * x' = x + attn(norm1(x)) of the FIRST CrossBlock (its self-attention sees image 2 only: the features enter at the
              cross-attention that follows, vision_transformer.py:269-270) - unless that block is also the last one (cls-only);
       * q  = Linear_q(norm_cross(x')) of that block's cross-attention (:176), activation dtype.
-    Returns (x' or x as [n, N2, D] fp32, q [n, N2, D] or None)."""
+    Returns (x' or x as [n, N2, D] fp32, q [n, N2, D] or None).  ``turn``: the images enter turned (``_patch_tokens_fwd``)."""
     shared, blocks = split_params(params, rt.dec_shared, rt.dec_block)
-    x, _, batch, _ = _patch_tokens_fwd(rt, img, shared, with_cls=True)
+    x, _, batch, _ = _patch_tokens_fwd(rt, img, shared, with_cls=True, turn=turn)
     if not blocks or (rt.cls_tail and rt.c_depth == 1):
         return x.view(batch, rt.n2, rt.dim), None
     xa, _, lnq = _dec_self_fwd(rt, x, blocks[0], batch, rt.n2, cls_only=False)

@@ -583,11 +583,15 @@ class VisionTransformerCustom(nn.Module):
     supports_pair_cache = True
 
     @torch.no_grad()
-    def cache_image2_tokens(self, images):
+    def cache_image2_tokens(self, images, turn=0):
         """Everything of the decoder that depends on image 2 alone, once per image: prepare_x2 (vision_transformer.py:390-395),
-        the first CrossBlock's self-attention branch and its cross-attention queries.  Returns (tokens [n, N2, D] fp32, q0 | None)."""
+        the first CrossBlock's self-attention branch and its cross-attention queries.  Returns (tokens [n, N2, D] fp32, q0 | None).
+        ``turn`` (an int 0..3, or an int tensor [n] with one per image): the cache of the images turned by that many clockwise quarter
+        turns, ``torch.rot90(images, -turn, (2, 3))``, their patches gathered from the upright images (learned type-2 puzzles);
+        ``turn=0`` makes the launches of the upright cache and no other."""
         self._check_images(images)
-        return F_.image2_tokens(self.runtime(), images, self._decoder_params())
+        upright = type(turn) is int and turn == 0
+        return F_.image2_tokens(self.runtime(), images, self._decoder_params(), turn=None if upright else turn)
 
     @torch.no_grad()
     def cache_context_kv(self, feats):

@@ -1325,3 +1325,7 @@ from .ops_puzzlepixels import (PUZZLE_MAX_ERODED, PUZZLE_MAX_PIECES, PUZZLE_MAX_
 # csrc/puzzle_compat.hip live in ops_puzzle2.py ---------------------------------------------------------------------------------------
 from .ops_puzzle2 import (puzzle_assemble2, puzzle_best_slot2, puzzle_compat2_init, puzzle_compat2_recalc,  # noqa: E402,F401
                           puzzle_pixel_distances2, puzzle_unpack_slot2)
+
+# ---- learned type-2 puzzles (pieces turned under the pair model): the wrappers of csrc/puzzle_turn.hip and of the turned-pair scatter of
+# csrc/puzzle_compat.hip live in ops_puzzlerot.py --------------------------------------------------------------------------------------
+from .ops_puzzlerot import patchify_turned, puzzle_distances2_from_logits  # noqa: E402,F401
