@@ -920,6 +920,17 @@ int vited_patchify_turned_u8(const uint8_t* img, int64_t img_batch_stride, const
 int vited_puzzle_distances2_from_logits(const float* logits, const int64_t* pi, const int64_t* pjt, int64_t m, int64_t n, int* dq2,
                                         int* bad, void* stream);
 
+/* ---- puzzle solving: point lookups of the mutual compatibility (mixed bags and unknown dimensions) ------------------
+ * The placement loop of PaikinTalSolver reads a handful of M entries per placed piece (solver.py:490, :630, :688); these entries fetch
+ * them from the device tensor, so that no host copy of M is needed.  lookups int32 [m, 3] = (side, p, q) reads mutual[side, p, q] of
+ * the type-1 tensor [4, n, n]; vited_puzzle_mutual_gather2 takes lookups int32 [m, 4] = (side_p, p, q, side_q) and reads
+ * mutual[side_p, p, q, side_q] of the type-2 tensor [4, n, n, 4].  out fp32 [m] receives the words of M bit for bit (-0, inf and the
+ * images of -maxsize included).  A lookup with a side outside 0..3 or a piece outside [0, n) writes nothing to its slot and sets bit 0
+ * of *bad (int32, device).  One thread per lookup, plain loads and stores, m >= 0; all arrays are contiguous DEVICE memory.
+ * VITED_ERR_BAD_ARG: a null pointer, m < 0, n < 2 or n > 46340.  VITED_ERR_UNSUPPORTED: m > INT32_MAX. */
+int vited_puzzle_mutual_gather(const float* mutual, int64_t n, const int* lookups, int64_t m, float* out, int* bad, void* stream);
+int vited_puzzle_mutual_gather2(const float* mutual, int64_t n, const int* lookups, int64_t m, float* out, int* bad, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -406,7 +406,37 @@ __global__ void __launch_bounds__(THREADS) best_slot2_kernel(const float* __rest
     if (threadIdx.x % VITED_WAVE == 0 && word != 0) atomicMax(best, word);
 }
 
+// The solver's point lookups of M (solver.py:490, :630, :688) without a host copy of it: lookup r is (side, p, q) -> M[side, p, q]
+// (type 1, WIDTH 3) or (side_p, p, q, side_q) -> M[side_p, p, q, side_q] (type 2, WIDTH 4).  The word moves as an integer, so every
+// bit pattern arrives as it lies in M.  A lookup outside the tensor leaves its slot alone and flags bad.
+template <int WIDTH>
+__global__ void __launch_bounds__(VITED_WAVE) mutual_gather_kernel(const uint32_t* __restrict__ mutual, int n,
+                                                                   const int* __restrict__ lookups, int64_t m,
+                                                                   uint32_t* __restrict__ out, int* __restrict__ bad) {
+    const int64_t r = (int64_t)blockIdx.x * VITED_WAVE + threadIdx.x;
+    if (r >= m) return;
+    const int* look = lookups + r * WIDTH;
+    const int side = look[0], p = look[1], q = look[2], side_q = WIDTH == 4 ? look[3] : 0;
+    if (side < 0 || side > 3 || p < 0 || p >= n || q < 0 || q >= n || side_q < 0 || side_q > 3) {
+        atomicOr(bad, 1);
+        return;
+    }
+    const int64_t at = ((int64_t)side * n + p) * n + q;
+    out[r] = mutual[WIDTH == 4 ? at * 4 + side_q : at];
+}
+
 inline unsigned blocks_for(int64_t work) { return (unsigned)ceil_div64(work, THREADS); }
+
+template <int WIDTH>
+int launch_mutual_gather(const float* mutual, int64_t n, const int* lookups, int64_t m, float* out, int* bad, void* stream) {
+    if (!mutual || !lookups || !out || !bad || m < 0 || n < 2 || n > MAX_PIECES) return VITED_ERR_BAD_ARG;
+    if (m > (int64_t)INT32_MAX) return VITED_ERR_UNSUPPORTED;
+    if (m == 0) return VITED_OK;
+    hipLaunchKernelGGL(mutual_gather_kernel<WIDTH>, dim3((unsigned)ceil_div64(m, VITED_WAVE)), dim3(VITED_WAVE), 0,
+                       static_cast<hipStream_t>(stream), reinterpret_cast<const uint32_t*>(mutual), (int)n, lookups, m,
+                       reinterpret_cast<uint32_t*>(out), bad);
+    return vited_check_launch();
+}
 
 }  // namespace
 
@@ -524,4 +554,15 @@ extern "C" int vited_puzzle_best_slot2(const float* mutual, int64_t n, const int
     hipLaunchKernelGGL(best_slot2_kernel, dim3((unsigned)blocks), dim3(THREADS), 0, st, mutual, (int)n, placed, slot_piece, slot_side,
                        (int)slots, reinterpret_cast<unsigned long long*>(best));
     return vited_check_launch();
+}
+
+// ---- point lookups of M for the placement loop (mixed bags and unknown dimensions) ----------------------------------
+extern "C" int vited_puzzle_mutual_gather(const float* mutual, int64_t n, const int* lookups, int64_t m, float* out, int* bad,
+                                          void* stream) {
+    return launch_mutual_gather<3>(mutual, n, lookups, m, out, bad, stream);
+}
+
+extern "C" int vited_puzzle_mutual_gather2(const float* mutual, int64_t n, const int* lookups, int64_t m, float* out, int* bad,
+                                           void* stream) {
+    return launch_mutual_gather<4>(mutual, n, lookups, m, out, bad, stream);
 }

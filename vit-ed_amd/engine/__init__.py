@@ -5,7 +5,7 @@ and the input pipelines and evaluation paths on the device; loading from disk, l
 
 One concern per module: ``distributed`` (process group, flat gradient exchange), ``train`` (optimizer, ``TrainStep``, meters),
 ``feeds`` (prefetcher; DIV2K, HisFrag and Michigan device loaders), ``mining`` (pair mining and its loss), ``similarity`` (the
-streamed similarity matrix), ``metrics`` (retrieval, group mAP / Pr@k, geshaem, classifier validation), ``puzzle``, ``relevancy``.
+streamed similarity matrix), ``metrics`` (retrieval, group mAP / Pr@k, geshaem, classifier validation), ``puzzle`` (with ``puzzle_mixed``), ``relevancy``.
 Every public name is re-exported here, so callers write ``engine.TrainStep``.  State that is rebound at run time is not: read
 and set ``engine.train._CAPTURE_MODE`` there."""
 from .distributed import FlatGradients, broadcast_parameters, configure_ddp  # noqa: F401
@@ -21,6 +21,7 @@ from .mining import (MinedPairs, hisfrag_prepare_data, hisfrag_prepare_indexed, 
 from .puzzle import (PUZZLE_SIDES, PuzzleCompatibility, PuzzleCut, PuzzleSolution, cut_puzzle, puzzle_accuracy,  # noqa: F401
                      puzzle_distances, puzzle_model_pieces, puzzle_pixel_distances, reconstruct_puzzle, solve_model_puzzle, solve_pixel_puzzle,
                      solve_puzzle)
+from .puzzle_mixed import PuzzleBoards  # noqa: F401
 from .relevancy import pair_relevancy, relevancy_from_cams  # noqa: F401
 from .similarity import pairwise_similarity, shard_rows_by_pair_count  # noqa: F401
 from .train import (NativeScalerWithGradNormCount, TrainMeters, TrainStep, TwoStageTrainStep, _decoder_only_parameters,  # noqa: F401

@@ -4,7 +4,8 @@ the classical baseline of solver_driver.py around the same solver - the image cu
 distances of the pieces' pixels, the solved board as an image.  Type-1 puzzles (orientation known) take distances [4, n, n]; type-2
 puzzles (any side of a piece may meet any side of another; the solver assigns each piece a rotation) take distances [4, n, n, 4] of
 the pixel path or of the model (``puzzle_type=2``), and every function here tells the two apart by that rank or by
-``PuzzleSolution.rotations``."""
+``PuzzleSolution.rotations``.  Puzzles of unknown size and the pooled pieces of several images (``solve_puzzle(dq, None, ...)``) are
+solved by ``puzzle_mixed``."""
 from __future__ import annotations
 
 import heapq
@@ -140,10 +141,40 @@ class PuzzleCompatibility:
         (ops.puzzle_compat2_recalc if self.puzzle_type == 2 else ops.puzzle_compat_recalc)(self.dq, self._placed, self.state, self.changed)
         return self.changed
 
-    def best_slot(self, placed, slot_piece, slot_side):
+    def mutual_at(self, lookups):
+        """The mutual compatibilities the placement loop asks for, float32 [m] (numpy), fetched on the device
+        (``vited_puzzle_mutual_gather``): ``lookups`` host integers [m, 3] = (side, p, q) -> mutual[side, p, q] (type 1) or [m, 4] =
+        (side_p, p, q, side_q) -> mutual[side_p, p, q, side_q] (type 2).  One launch and one read through a small pinned buffer
+        (the flag word in front of the m values); no copy of M is made.  An index outside the tensor raises IndexError."""
+        import numpy as np
+        width = 4 if self.puzzle_type == 2 else 3
+        look = np.ascontiguousarray(lookups, dtype=np.int32).reshape(-1, width)
+        m = look.shape[0]
+        if m == 0:
+            return np.empty(0, dtype=np.float32)
+        room = self.__dict__.get('_gather')
+        if room is None or room[0].shape[0] < m:
+            cap, dev = max(64, 2 * m), self.dq.device
+            room = (torch.empty((cap, width), dtype=torch.int32).pin_memory(), torch.empty((cap, width), dtype=torch.int32, device=dev),
+                    torch.zeros(cap + 1, dtype=torch.float32, device=dev), torch.empty(cap + 1, dtype=torch.float32).pin_memory())
+            self._gather = room
+        look_host, look_dev, words_dev, words_host = room
+        look_host[:m].copy_(torch.from_numpy(look))
+        look_dev[:m].copy_(look_host[:m], non_blocking=True)
+        bad = words_dev[:1].view(torch.int32)                   # stays zero from one call to the next: a set flag raises below
+        ops.puzzle_mutual_gather(self.mutual, look_dev[:m], out=words_dev[1:m + 1], bad=bad)
+        words_host[:m + 1].copy_(words_dev[:m + 1], non_blocking=True)
+        torch.cuda.current_stream(self.dq.device).synchronize()
+        if int(words_host[:1].view(torch.int32)[0]):
+            bad.zero_()
+            raise IndexError(f'mutual_at: a lookup fell outside the {self.n} pieces or the 4 sides')
+        return words_host[1:m + 1].numpy().copy()
+
+    def best_slot(self, placed, slot_piece, slot_side, value: bool = True):
         """Type 1: (piece, slot index, value) of the first maximum of mutual[(slot_side[k] + 2) % 4, p, slot_piece[k]] over unplaced p
         ascending x slots k in list order.  Type 2: (piece, slot index, side of the piece, value) of the first maximum of
-        mutual[side, p, slot_piece[k], slot_side[k]] over unplaced p ascending x slots k in list order x side 0..3."""
+        mutual[side, p, slot_piece[k], slot_side[k]] over unplaced p ascending x slots k in list order x side 0..3.  ``value=False``
+        leaves the value out (the caller fetches it with ``mutual_at``)."""
         dev = self.dq.device
         self._placed.copy_(torch.as_tensor(placed, dtype=torch.int32))
         sp = torch.as_tensor(slot_piece, dtype=torch.int32).to(dev)
@@ -154,12 +185,16 @@ class PuzzleCompatibility:
             if hit is None:
                 raise RuntimeError('best_slot: no unplaced piece')
             p, k, side = hit
+            if not value:
+                return p, k, side
             return p, k, side, float(self.mutual[side, p, int(slot_piece[k]), int(slot_side[k])])
         ops.puzzle_best_slot(self.mutual, self._placed, sp, ss, out=self._word)
         hit = ops.puzzle_unpack_slot(int(self._word.item()), sp.numel())
         if hit is None:
             raise RuntimeError('best_slot: no unplaced piece')
         p, k = hit
+        if not value:
+            return p, k
         return p, k, float(self.mutual[(int(slot_side[k]) + 2) % 4, p, int(slot_piece[k])])
 
 
@@ -185,7 +220,8 @@ class _BuddyHeapEntry:
         return self.compat > other.compat
 
 
-def solve_puzzle(distances: torch.Tensor, grid_size) -> PuzzleSolution:
+def solve_puzzle(distances: torch.Tensor, grid_size=None, *, numb_puzzles: int = 1, new_board_mutual_compatibility: float = 0.5,
+                 mutual_lookup: str | None = None) -> PuzzleSolution:
     """Paikin-Tal placement (PaikinTalSolver, solver.py) of one puzzle of ``grid_size`` = (rows, cols) pieces, making the reference's
     decisions in the reference's order: the seed from the start ordering at the board centre, best buddies pooled as pieces are
     placed, the best-buddy heap popped until it yields a placeable entry, and - whenever the pool is empty - a device recalculation
@@ -196,7 +232,18 @@ def solve_puzzle(distances: torch.Tensor, grid_size) -> PuzzleSolution:
     meet.  ``distances`` int32 [4, n, n, 4] (``puzzle_pixel_distances(pieces, puzzle_type=2)``) is a type-2 puzzle: every open slot
     is tried against all four sides of a piece, the seed lies at rotation 0, each placed piece gets the rotation of
     PuzzlePiece._calculate_placed_piece_rotation, and the slots it opens carry its unrotated sides
-    (_get_neighbor_locations_and_sides); ``PuzzleSolution.rotations`` holds the quarter turns."""
+    (_get_neighbor_locations_and_sides); ``PuzzleSolution.rotations`` holds the quarter turns.
+
+    ``grid_size=None`` solves without dimensions (``fixed_puzzle_dimensions=None``: every slot passes the dimension check), and
+    ``numb_puzzles`` > 1 - which needs ``grid_size=None``, as in the reference - solves the pooled pieces of several images, spawning a
+    board whenever the found piece's mutual compatibility lies below ``new_board_mutual_compatibility`` while boards are left to
+    spawn.  Both return a ``PuzzleBoards`` (a ``PuzzleSolution`` with the boards and their extents) and read the
+    mutual compatibility by device lookups (``mutual_lookup='gather'``, ``PuzzleCompatibility.mutual_at``) instead of the host mirror
+    (``'mirror'``, kept for comparison).  With ``grid_size`` given, nothing of this runs."""
+    from . import puzzle_mixed
+    mutual_lookup = puzzle_mixed.check_solve_arguments(grid_size, numb_puzzles, mutual_lookup)
+    if grid_size is None:
+        return puzzle_mixed.solve_open_puzzle(distances, numb_puzzles, new_board_mutual_compatibility, mutual_lookup)
     import numpy as np
     rows, cols = int(grid_size[0]), int(grid_size[1])
     n = distances.shape[1] if distances.dim() > 1 else 0
@@ -299,7 +346,7 @@ def solve_puzzle(distances: torch.Tensor, grid_size) -> PuzzleSolution:
     return PuzzleSolution(locations, board_loc, np.array(order, dtype=np.int64), recalcs, grid, rotation if type2 else None)
 
 
-def puzzle_accuracy(solution: PuzzleSolution, true_locations) -> dict:
+def puzzle_accuracy(solution: PuzzleSolution, true_locations, *, true_puzzle=None) -> dict:
     """The accuracies PuzzleResultsCollection.collect_results reports for one solved puzzle (puzzle_importer.py:779-844, the rules
     of :985-1150 and :1386-1520), every piece from the one original puzzle: ``Direct_Standard`` (pieces at their true cell / n),
     ``Direct_Modified`` (the same, best over the origins the reference's search from the top-left corner offers), ``neighbor``
@@ -309,8 +356,16 @@ def puzzle_accuracy(solution: PuzzleSolution, true_locations) -> dict:
     A type-2 solution (``solution.rotations`` is not None) follows the reference's type-2 rules (:558-598, :985-1058): a piece at its
     true cell counts only at rotation 0 - otherwise it is a "wrong rotation", and the dict gains ``'wrong_rotation'``, their number
     under the standard origin; side s of a piece turned by r looks at the cell in direction (s + r) % 4, and a true neighbour found
-    there counts only when both pieces carry the same rotation."""
+    there counts only when both pieces carry the same rotation.
+
+    ``true_puzzle`` int [n] (the image each piece came from; ``true_locations`` then lie in that image's grid) scores a mixed-bag
+    solution (``puzzle_mixed.several_puzzle_accuracy``): the same keys, each a list with one entry per scored original puzzle."""
     import numpy as np
+    if true_puzzle is not None:
+        from .puzzle_mixed import several_puzzle_accuracy
+        return several_puzzle_accuracy(solution, true_locations, true_puzzle)
+    if getattr(solution, 'numb_boards', 1) > 1:
+        raise ValueError('puzzle_accuracy: a solution of several boards is scored with true_puzzle, the image each piece came from')
     true = np.asarray(true_locations, dtype=np.int64)
     loc = np.asarray(solution.locations, dtype=np.int64)
     n = true.shape[0]
@@ -364,19 +419,38 @@ def puzzle_accuracy(solution: PuzzleSolution, true_locations) -> dict:
 class PuzzleCut(NamedTuple):
     pieces: 'object'            # uint8 [n, We, We, 3] on the device, in the solver's order
     true_locations: 'object'    # int64 [n, 2] (host): the cell (row, col) each piece was cut from
-    grid_size: tuple            # (rows, cols)
+    grid_size: tuple            # (rows, cols); of several images: a tuple of them
     piece_width: int            # P, the cell's width before the erosion crop
+    true_puzzle: 'object' = None    # several images: int64 [n] (host), the image each piece was cut from; one image: None
+
+
+def _several_images(image):
+    return isinstance(image, (list, tuple)) and len(image) > 0 and getattr(image[0], 'ndim', None) == 3
 
 
 def cut_puzzle(image, piece_width: int, erosion: float = 0., order=None) -> PuzzleCut:
     """Puzzle(0, path, piece_width, erosion=erosion).pieces on the device (puzzle_importer.py:182-232): ``image`` uint8 [H, W, 3] (any
     3-channel image: the colour conversion is the caller's) cut into (H // P) x (W // P) cells of the centred grid, each centre-cropped to
     We = min(ceil(P (1 - erosion)), P).  ``order`` (a permutation of the row-major cells, host integers) is the driver's
-    random.shuffle made explicit: piece k is cell order[k]."""
+    random.shuffle made explicit: piece k is cell order[k].
+
+    A list of images is a mixed bag: every image is cut as above, the pieces are pooled image after image (Puzzle(k, ...,
+    starting_piece_id=...)) and ``order`` permutes the pool; ``true_puzzle`` tells the images apart and ``grid_size`` lists their grids."""
     import numpy as np
     P = int(piece_width)
     if P < 1:
         raise ValueError(f'cut_puzzle: piece_width must be positive, got {piece_width}')
+    if _several_images(image):
+        cuts = [cut_puzzle(one, P, erosion) for one in image]
+        pieces = torch.cat([cut.pieces for cut in cuts])
+        true = np.concatenate([cut.true_locations for cut in cuts])
+        puzzle = np.concatenate([np.full(len(cut.true_locations), k, dtype=np.int64) for k, cut in enumerate(cuts)])
+        if order is not None:
+            pick = np.asarray(order.cpu() if isinstance(order, torch.Tensor) else order, dtype=np.int64)
+            if pick.shape != puzzle.shape or not np.array_equal(np.sort(pick), np.arange(puzzle.size)):
+                raise ValueError(f'cut_puzzle: order must be a permutation of the {puzzle.size} pooled pieces')
+            pieces, true, puzzle = pieces.index_select(0, torch.from_numpy(np.array(pick)).to(pieces.device)).contiguous(), true[pick], puzzle[pick]
+        return PuzzleCut(pieces, true, tuple(cut.grid_size for cut in cuts), P, puzzle)
     image = torch.as_tensor(image)
     if not image.is_cuda and torch.cuda.is_available():        # a host image is uploaded; without a GPU ops refuses it
         image = image.cuda()
@@ -401,38 +475,93 @@ def puzzle_pixel_distances(pieces, puzzle_type: int = 1):
     return ops.puzzle_pixel_distances(pieces, puzzle_type=puzzle_type)
 
 
+def _reconstruct_boards(pieces, solution, true_locations, piece_width, marker):
+    """One board per solved board of a ``PuzzleBoards``, each cropped to its extents.  ``vited_puzzle_assemble`` draws a board that its
+    pieces fill, so every empty cell of the extent gets a black piece whose true location is that cell (no frame): the reference's
+    black background."""
+    import numpy as np
+    true = np.asarray(true_locations, dtype=np.int64)
+    loc_all = np.asarray(solution.locations, dtype=np.int64)
+    boards, out = np.asarray(solution.boards), []
+    for b in range(solution.numb_boards):
+        on = np.flatnonzero(boards == b)
+        loc = loc_all[on]
+        R, C = int(loc[:, 0].max()) + 1, int(loc[:, 1].max()) + 1
+        filled = np.zeros((R, C), dtype=bool)
+        filled[loc[:, 0], loc[:, 1]] = True
+        empty = np.argwhere(~filled).astype(np.int64)
+        sub = pieces.index_select(0, torch.from_numpy(on).to(pieces.device))
+        if len(empty):
+            sub = torch.cat([sub, sub.new_zeros((len(empty),) + tuple(sub.shape[1:]))])
+        sub = sub.contiguous()
+        at, want = np.concatenate([loc, empty]), np.concatenate([true[on], empty])
+        if solution.rotations is not None:
+            turns = np.concatenate([np.asarray(solution.rotations, dtype=np.int64)[on], np.zeros(len(empty), dtype=np.int64)])
+            out.append(ops.puzzle_assemble2(sub, at, turns, want, piece_width, marker))
+        else:
+            out.append(ops.puzzle_assemble(sub, at, want, piece_width, marker))
+    return out
+
+
 def reconstruct_puzzle(pieces, solution, true_locations, piece_width: int, marker=None):
     """Puzzle.reconstruct_from_pieces (puzzle_importer.py:265-321, :448-473): the board uint8 [R P, C P, 3] of the pieces at
     ``solution.locations`` (a ``PuzzleSolution``, or the locations themselves).  With ``marker`` (three bytes; the reference's is BGR
     (0, 0, 255)) every piece away from its true location is framed, which needs (P - We) // 2 >= 1.  A piece of a type-2 solution
-    enters as numpy.rot90(piece, rotation); the frame still goes by the location alone, as insert_piece_into_image draws it."""
+    enters as numpy.rot90(piece, rotation); the frame still goes by the location alone, as insert_piece_into_image draws it.
+
+    A ``PuzzleBoards`` (several boards, or one of unknown extents) gives a list: one board image per solved board, in board order, each
+    cropped to that board's extents, black where no piece lies."""
+    if getattr(solution, 'boards', None) is not None:
+        return _reconstruct_boards(pieces, solution, true_locations, piece_width, marker)
     rotations = getattr(solution, 'rotations', None)
     if rotations is not None:
         return ops.puzzle_assemble2(pieces, solution.locations, rotations, true_locations, piece_width, marker)
     return ops.puzzle_assemble(pieces, getattr(solution, 'locations', solution), true_locations, piece_width, marker)
 
 
-def solve_pixel_puzzle(image, piece_width: int, erosion: float = 0., order=None, marker=None, puzzle_type: int = 1):
+def _solve_cut(cut, distances, marker, grid_size, numb_puzzles, new_board_mutual_compatibility, mutual_lookup):
+    """Solver, accuracies and board(s) of a cut, shared by the two drivers.  One image: ``grid_size`` 'cut' is the cut's own grid, None
+    the unknown-dimension form.  Several images: no dimensions, ``numb_puzzles`` boards (default: one per image)."""
+    if cut.true_puzzle is not None:
+        if grid_size not in ('cut', None):
+            from .puzzle_mixed import SEVERAL_WITH_DIMENSIONS
+            raise ValueError(SEVERAL_WITH_DIMENSIONS)
+        grid_size, numb_puzzles = None, len(cut.grid_size) if numb_puzzles is None else numb_puzzles
+    elif grid_size == 'cut':
+        grid_size = cut.grid_size
+    solution = solve_puzzle(distances, grid_size, numb_puzzles=1 if numb_puzzles is None else numb_puzzles,
+                            new_board_mutual_compatibility=new_board_mutual_compatibility, mutual_lookup=mutual_lookup)
+    board = reconstruct_puzzle(cut.pieces, solution, cut.true_locations, cut.piece_width, marker)
+    return solution, puzzle_accuracy(solution, cut.true_locations, true_puzzle=cut.true_puzzle), board
+
+
+def solve_pixel_puzzle(image, piece_width: int, erosion: float = 0., order=None, marker=None, puzzle_type: int = 1, *, grid_size='cut',
+                       numb_puzzles=None, new_board_mutual_compatibility: float = 0.5, mutual_lookup=None):
     """One pass of solver_driver.py's loop on the device: cut, pixel distances, Paikin-Tal, accuracies, board.  Returns
     (``PuzzleSolution``, the dict of ``puzzle_accuracy``, board uint8 [R P, C P, 3]).  ``puzzle_type=2`` solves the pieces as a type-2
-    puzzle (paikin_tal_tester.py's PuzzleType.type2): the pieces are cut upright, the solver is free to turn them."""
+    puzzle (paikin_tal_tester.py's PuzzleType.type2): the pieces are cut upright, the solver is free to turn them.
+
+    A list of images is solved as a mixed bag (``numb_puzzles`` boards, one per image unless given) and ``grid_size=None`` solves one
+    image without its dimensions: both return (``PuzzleBoards``, the accuracies - per original puzzle for a list -, the list of board
+    images, one per solved board)."""
     cut = cut_puzzle(image, piece_width, erosion, order)
-    solution = solve_puzzle(puzzle_pixel_distances(cut.pieces, puzzle_type), cut.grid_size)
-    board = reconstruct_puzzle(cut.pieces, solution, cut.true_locations, cut.piece_width, marker)
-    return solution, puzzle_accuracy(solution, cut.true_locations), board
+    return _solve_cut(cut, puzzle_pixel_distances(cut.pieces, puzzle_type), marker, grid_size, numb_puzzles, new_board_mutual_compatibility,
+                      mutual_lookup)
 
 
 def solve_model_puzzle(model, image, piece_width: int, erosion: float = 0., order=None, marker=None, puzzle_type: int = 1, **distance_kw):
     """The learned twin of ``solve_pixel_puzzle``, evaluation.py's loop body on the device: cut, the pieces at the model's size, the
     model's distances, Paikin-Tal, accuracies, board.  Returns (``PuzzleSolution``, the dict of ``puzzle_accuracy``, board uint8
     [R P, C P, 3]).  ``puzzle_type=2`` scores all 16 side pairings through the model and solves the pieces as a type-2 puzzle;
-    ``distance_kw`` (pair_batch, amp, block) goes to ``puzzle_distances``."""
+    ``distance_kw`` (pair_batch, amp, block) goes to ``puzzle_distances``.  A list of images and ``grid_size=None`` as in
+    ``solve_pixel_puzzle``, whose solver keywords (grid_size, numb_puzzles, new_board_mutual_compatibility, mutual_lookup) are taken
+    out of ``distance_kw``."""
     if puzzle_type not in (1, 2):
         raise ValueError(f'solve_model_puzzle: puzzle_type must be 1 or 2, got {puzzle_type!r}')
     if distance_kw.get('return_logits'):
         raise ValueError('solve_model_puzzle: return_logits belongs to puzzle_distances, the driver returns the solution')
+    solver_kw = (distance_kw.pop('grid_size', 'cut'), distance_kw.pop('numb_puzzles', None),
+                 distance_kw.pop('new_board_mutual_compatibility', 0.5), distance_kw.pop('mutual_lookup', None))
     cut = cut_puzzle(image, piece_width, erosion, order)
     distances = puzzle_distances(model, puzzle_model_pieces(cut.pieces, model.img_size), puzzle_type=puzzle_type, **distance_kw)
-    solution = solve_puzzle(distances, cut.grid_size)
-    board = reconstruct_puzzle(cut.pieces, solution, cut.true_locations, cut.piece_width, marker)
-    return solution, puzzle_accuracy(solution, cut.true_locations), board
+    return _solve_cut(cut, distances, marker, *solver_kw)

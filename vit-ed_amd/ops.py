@@ -1329,3 +1329,6 @@ from .ops_puzzle2 import (puzzle_assemble2, puzzle_best_slot2, puzzle_compat2_in
 # ---- learned type-2 puzzles (pieces turned under the pair model): the wrappers of csrc/puzzle_turn.hip and of the turned-pair scatter of
 # csrc/puzzle_compat.hip live in ops_puzzlerot.py --------------------------------------------------------------------------------------
 from .ops_puzzlerot import patchify_turned, puzzle_distances2_from_logits  # noqa: E402,F401
+
+# ---- mixed-bag and unknown-dimension puzzles: the wrapper of the point lookups of M of csrc/puzzle_compat.hip lives in ops_puzzlemixed.py
+from .ops_puzzlemixed import puzzle_mutual_gather  # noqa: E402,F401
