@@ -405,14 +405,17 @@ int vited_linear_bwd_weight_batched(int count, const void* const* dY, const int6
                                     float* const* dbias, int dtype, int accumulate, float* workspace, int64_t workspace_bytes,
                                     void* stream);
 
-/* ---- Linear fused with the LayerNorm on the other side of it (row-complete 384-wide tile, bf16 MFMA; gemm_row.hip) ----
+/* ---- Linear fused with the LayerNorm on the other side of it (row-complete tile, bf16 MFMA; gemm_row.hip, gemm_row768.hip) ----
  * The reference's blocks are chains  x = x + f(norm(x))  (Block.forward vision_transformer.py:124-127, CrossBlock.forward
  * :268-272, norm_layer :348): every residual Linear (attn.proj :38, cross_attn.proj :156, timm Mlp fc2) is followed by the next
  * sub-block's LayerNorm, and every Linear that consumes a LayerNorm's output (qkv :34, q :151, kv :152, fc1) is followed, in
  * backward, by that LayerNorm's backward.  These two entries do each pair in ONE kernel so the LayerNorm is not a separate
- * pass over the fp32 residual stream.  bf16 operands, N == 384 (the embed width of every shipped pjs config), K % 64 == 0;
- * vited_linear_layernorm_supported() tells whether a shape is covered - otherwise the caller runs vited_gemm +
- * vited_layernorm_fwd / vited_layernorm_bwd. */
+ * pass over the fp32 residual stream.  bf16 operands, K % 64 == 0, and the embed width one of
+ *   N == 384 (configs/puzzle, configs/hisfrag, configs/test), K >= 64;
+ *   N == 768 (ViT-Base: the reference's michigan base_patch16_384), K >= 768.
+ * The entries take every such shape.  vited_linear_layernorm_supported() tells whether a caller SHOULD use them: at 384 for every
+ * such shape; at 768 only where they measured faster than the two kernels - more than 24,576 rows and K neither N nor 4 N
+ * (DESIGN.md section 35).  Otherwise the caller runs vited_gemm + vited_layernorm_fwd / vited_layernorm_bwd. */
 int vited_linear_layernorm_supported(int64_t M, int64_t N, int64_t K);
 
 /* y = residual + a . w^T + bias   (fp32 [M, N], row stride ldy; residual fp32 row stride ldr, may alias y row for row)
@@ -433,7 +436,7 @@ int vited_linear_residual_layernorm_fwd_scaled(const void* a, int64_t lda, const
 /* dh = dy . wt^T  (wt = the transposed weight shadow, bf16 [N, K]: dX of y = LN(x) W^T), never written anywhere;
  * dx_out = (dx_in ? dx_in : 0) + LN'(dh; x, mean, rstd, gamma)  fp32 (dx_out may alias dx_in), optional bf16 copy dx_lp;
  * dgamma / dbeta: column sums of dh * xhat / dh, overwritten or (accumulate != 0) added.  workspace >= *_workspace_bytes.
- * With dgamma == dbeta == null the column partials stay in `workspace` as [vited_linear_layernorm_bwd_partial_rows(M)][2][N]
+ * With dgamma == dbeta == null the column partials stay in `workspace` as [vited_linear_layernorm_bwd_partial_rows_n(M, N)][2][N]
  * fp32 for vited_layernorm_bwd_finish_batched, which sums the partials of several LayerNorms in one launch. */
 /* The same with the contraction dim cut into `segments` column blocks of seg_k, block j read from the tensor at
  * dy + j * seg_stride (elements): one [M, seg_k] tensor per decoder block (each contiguous for its own attention backward), all
@@ -444,7 +447,8 @@ int vited_linear_layernorm_bwd_segmented(const void* dy, int64_t lddy, int64_t s
                                          float* dx_out, int64_t dx_out_ld, void* dx_lp, int64_t dx_lp_ld, float* dgamma,
                                          float* dbeta, int accumulate, int64_t M, int64_t N, float* workspace,
                                          int64_t workspace_bytes, void* stream);
-int64_t vited_linear_layernorm_bwd_partial_rows(int64_t M);
+int64_t vited_linear_layernorm_bwd_partial_rows(int64_t M);               /* N == 384 */
+int64_t vited_linear_layernorm_bwd_partial_rows_n(int64_t M, int64_t N);  /* either width; 0 for any other N */
 int vited_layernorm_bwd_finish_batched(int count, const float* const* partial, const int* nparts, float* const* dgamma,
                                        float* const* dbeta, const int* accumulate, int64_t dim, void* stream);
 int64_t vited_linear_layernorm_bwd_workspace_bytes(int64_t M, int64_t N);

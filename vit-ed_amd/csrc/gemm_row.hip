@@ -33,6 +33,7 @@
 
 #include "gemm_kernels.h"
 #include "gemm_lds.h"
+#include "gemm_row768.h"
 
 #define ROW_N 384
 #define ROW_LD 388      // floats per scratch row: 16-byte aligned rows; 388 mod 32 = 4 spreads the 8-lane groups of ds_write_b128 over the banks
@@ -483,7 +484,11 @@ static inline int64_t row_tiles(int64_t M) { return ceil_div64(M, 16 * row_mt(M)
 
 static bool row_shape_ok(int64_t M, int64_t N, int64_t K) { return N == ROW_N && K >= 64 && K % 64 == 0 && K <= (1 << 20) && M >= 1 && M < ((int64_t)1 << 31); }
 
-extern "C" int vited_linear_layernorm_supported(int64_t M, int64_t N, int64_t K) { return row_shape_ok(M, N, K) ? 1 : 0; }
+// N == 768: the kernels of gemm_row768.hip, which every extern "C" entry below routes to before anything here sees the shape
+extern "C" int vited_linear_layernorm_supported(int64_t M, int64_t N, int64_t K) {
+    if (N == ROW768_N) return row768_shape_ok(M, N, K) && row768_pays(M, K) ? 1 : 0;
+    return row_shape_ok(M, N, K) ? 1 : 0;
+}
 
 template <int MODE, int MT, bool SCALED>
 static int row_launch_scaled(const RowArgs& a, unsigned tiles, hipStream_t s) {
@@ -538,6 +543,8 @@ extern "C" int vited_linear_residual_layernorm_fwd(const void* a, int64_t lda, c
                                                    const float* residual, int64_t ldr, float* y, int64_t ldy, const float* gamma,
                                                    const float* beta, float eps, void* h, int64_t ldh, float* mean, float* rstd,
                                                    int64_t M, int64_t N, int64_t K, void* stream) {
+    if (N == ROW768_N)
+        return row768_fwd(a, lda, w, ldw, bias, residual, ldr, nullptr, y, ldy, gamma, beta, eps, h, ldh, mean, rstd, M, N, K, stream);
     return linear_residual_layernorm_fwd_impl(a, lda, w, ldw, bias, residual, ldr, nullptr, y, ldy, gamma, beta, eps, h, ldh, mean, rstd,
                                               M, N, K, stream);
 }
@@ -547,6 +554,8 @@ extern "C" int vited_linear_residual_layernorm_fwd_scaled(const void* a, int64_t
                                                           int64_t ldy, const float* gamma, const float* beta, float eps, void* h,
                                                           int64_t ldh, float* mean, float* rstd, int64_t M, int64_t N, int64_t K,
                                                           void* stream) {
+    if (N == ROW768_N)
+        return row768_fwd(a, lda, w, ldw, bias, residual, ldr, row_scale, y, ldy, gamma, beta, eps, h, ldh, mean, rstd, M, N, K, stream);
     return linear_residual_layernorm_fwd_impl(a, lda, w, ldw, bias, residual, ldr, row_scale, y, ldy, gamma, beta, eps, h, ldh, mean,
                                               rstd, M, N, K, stream);
 }
@@ -556,7 +565,13 @@ int ln_bwd_finish(const float* partial, int nparts, int dim, float* dgamma, floa
 
 extern "C" int64_t vited_linear_layernorm_bwd_partial_rows(int64_t M) { return M >= 1 ? row_tiles(M) : 0; }
 
+extern "C" int64_t vited_linear_layernorm_bwd_partial_rows_n(int64_t M, int64_t N) {
+    if (M < 1) return 0;
+    return N == ROW768_N ? row768_tiles(M) : N == ROW_N ? row_tiles(M) : 0;
+}
+
 extern "C" int64_t vited_linear_layernorm_bwd_workspace_bytes(int64_t M, int64_t N) {
+    if (N == ROW768_N) return M >= 1 ? row768_tiles(M) * 2 * ROW768_N * (int64_t)sizeof(float) : 0;
     return N == ROW_N && M >= 1 ? row_tiles(M) * 2 * ROW_N * (int64_t)sizeof(float) : 0;
 }
 
@@ -590,6 +605,9 @@ extern "C" int vited_linear_layernorm_bwd(const void* dy, int64_t lddy, const vo
                                           int64_t dx_in_ld, float* dx_out, int64_t dx_out_ld, void* dx_lp, int64_t dx_lp_ld,
                                           float* dgamma, float* dbeta, int accumulate, int64_t M, int64_t N, int64_t K,
                                           float* workspace, int64_t workspace_bytes, void* stream) {
+    if (N == ROW768_N)
+        return row768_bwd(dy, lddy, K, 0, wt, ldwt, x, ldx, gamma, mean, rstd, dx_in, dx_in_ld, dx_out, dx_out_ld, dx_lp, dx_lp_ld, nullptr,
+                          dgamma, dbeta, accumulate, M, N, K, workspace, workspace_bytes, stream);
     return linear_layernorm_bwd_impl(dy, lddy, K, 0, wt, ldwt, x, ldx, gamma, mean, rstd, dx_in, dx_in_ld, dx_out, dx_out_ld, dx_lp, dx_lp_ld,
                                      nullptr, dgamma, dbeta, accumulate, M, N, K, workspace, workspace_bytes, stream);
 }
@@ -603,6 +621,9 @@ extern "C" int vited_linear_layernorm_bwd_segmented(const void* dy, int64_t lddy
                                                     float* dbeta, int accumulate, int64_t M, int64_t N, float* workspace,
                                                     int64_t workspace_bytes, void* stream) {
     if (segments <= 0) return VITED_ERR_BAD_ARG;
+    if (N == ROW768_N)
+        return row768_bwd(dy, lddy, seg_k, seg_stride, wt, ldwt, x, ldx, gamma, mean, rstd, dx_in, dx_in_ld, dx_out, dx_out_ld, dx_lp, dx_lp_ld,
+                          nullptr, dgamma, dbeta, accumulate, M, N, segments * seg_k, workspace, workspace_bytes, stream);
     return linear_layernorm_bwd_impl(dy, lddy, seg_k, seg_stride, wt, ldwt, x, ldx, gamma, mean, rstd, dx_in, dx_in_ld, dx_out, dx_out_ld, dx_lp,
                                      dx_lp_ld, nullptr, dgamma, dbeta, accumulate, M, N, segments * seg_k, workspace, workspace_bytes, stream);
 }
@@ -612,6 +633,9 @@ extern "C" int vited_linear_layernorm_bwd_scaled(const void* dy, int64_t lddy, c
                                                  int64_t dx_in_ld, float* dx_out, int64_t dx_out_ld, void* dx_lp, int64_t dx_lp_ld,
                                                  const float* lp_scale, float* dgamma, float* dbeta, int accumulate, int64_t M, int64_t N,
                                                  int64_t K, float* workspace, int64_t workspace_bytes, void* stream) {
+    if (N == ROW768_N)
+        return row768_bwd(dy, lddy, K, 0, wt, ldwt, x, ldx, gamma, mean, rstd, dx_in, dx_in_ld, dx_out, dx_out_ld, dx_lp, dx_lp_ld, lp_scale,
+                          dgamma, dbeta, accumulate, M, N, K, workspace, workspace_bytes, stream);
     return linear_layernorm_bwd_impl(dy, lddy, K, 0, wt, ldwt, x, ldx, gamma, mean, rstd, dx_in, dx_in_ld, dx_out, dx_out_ld, dx_lp, dx_lp_ld,
                                      lp_scale, dgamma, dbeta, accumulate, M, N, K, workspace, workspace_bytes, stream);
 }

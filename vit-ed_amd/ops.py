@@ -741,7 +741,7 @@ def linear_layernorm_bwd(dy, wt, x, gamma, mean, rstd, dx_in=None, dx_out=None, 
     dx_lp = torch.empty((m, n), dtype=torch.bfloat16, device=dev) if want_lp else None
     accumulate, dgamma, dbeta = _ln_grads(op, dev, n, dgamma, dbeta)
     if defer is not None:
-        rows = int(lib.vited_linear_layernorm_bwd_partial_rows(m))
+        rows = int(lib.vited_linear_layernorm_bwd_partial_rows_n(m, n))
         part = torch.empty(rows * 2 * n, dtype=torch.float32, device=x.device)     # lives until the flush
         defer.append((part, rows, dgamma, dbeta, accumulate))
         ws = (part.data_ptr(), part.numel() * 4)
