@@ -577,6 +577,26 @@ int vited_sgd_step(const int64_t* desc, int count, int64_t total_tiles, const fl
 int vited_lr_schedule_step(const double* table, const double* base, const double* scale, int groups, int64_t* counter,
                            float* dst, int64_t dst_words, int64_t first, int64_t stride, float* last_lr, void* stream);
 
+/* One record of the learning-rate range test (the reference's lr_finder.py; the rule is csrc/lr_finder.h, in fp64): one launch of one
+ * workgroup, queued behind the training step whose loss it reads.  With i = state[0], while state[1] == 0 and 0 <= i < num_iter:
+ *   s = (i == 0 or smooth_f == 0) ? loss : smooth_f * loss + (1 - smooth_f) * s_prev;   best = (i == 0 or s < best) ? s : best
+ *   history[i] = {start[0] * (end[0] / start[0]) ** (i / num_iter), loss, s};   state[0] = i + 1
+ *   state[1] = 3 where the loss is not finite, else 2 where s > diverge_th * best, else 1 where i + 1 == num_iter, else 0
+ *   dst[first + stride * g] = state[1] == 0 ? (float)(start[g] * (end[g] / start[g]) ** ((i + 1) / num_iter)) : 0.0f
+ * In every other state the launch writes 0.0f into the rate words and touches neither the history nor the state.
+ *   loss       DEVICE fp32 [1]: the loss of the iteration that just ran
+ *   state      DEVICE 4 words of 8 bytes: int64 rows written, int64 halt state (0 running, 1 num_iter reached, 2 diverged, 3 loss not
+ *              finite), fp64 s of the last row, fp64 best; all zero before the first launch
+ *   history    DEVICE fp64 [capacity, 3]
+ *   start, end DEVICE fp64 [groups]: the ends of every group's sweep, positive and finite (the caller's check)
+ *   dst        DEVICE fp32 [dst_words]; the hyper array of vited_adamw_step / vited_sgd_step takes first = 8, stride = 8
+ * Everything is read from device memory, so an eager launch and a replayed one see the same thing.  No other word of dst is touched.
+ * VITED_ERR_BAD_ARG: a null pointer; groups outside [1, 4096]; num_iter < 1 or > capacity; smooth_f outside [0, 1]; diverge_th not
+ * above 1; first < 0, stride < 1 or a last word outside dst; 8-byte words not 8-byte aligned, fp32 ones not 4-byte aligned. */
+int vited_lr_finder_step(const float* loss, int64_t* state, double* history, int64_t capacity, const double* start, const double* end,
+                         int groups, int64_t num_iter, double smooth_f, double diverge_th, float* dst, int64_t dst_words,
+                         int64_t first, int64_t stride, void* stream);
+
 /* ---- attention core (F.scaled_dot_product_attention, vision_transformer.py:63-66,183-186) ----- */
 
 /* o[b, i, h, :] = softmax_j(scale * q[b,i,h,:] . k[b,j,h,:]) v[b,j,h,:]   (no mask, no dropout)

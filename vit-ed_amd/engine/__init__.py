@@ -5,13 +5,15 @@ and the input pipelines and evaluation paths on the device; loading from disk, l
 
 One concern per module: ``distributed`` (process group, flat gradient exchange), ``train`` (optimizer, ``TrainStep``, meters),
 ``feeds`` (prefetcher; DIV2K, HisFrag and Michigan device loaders), ``mining`` (pair mining and its loss), ``similarity`` (the
-streamed similarity matrix), ``metrics`` (retrieval, group mAP / Pr@k, geshaem, classifier validation), ``puzzle`` (with ``puzzle_mixed``), ``relevancy``.
+streamed similarity matrix), ``metrics`` (retrieval, group mAP / Pr@k, geshaem, classifier validation), ``puzzle`` (with ``puzzle_mixed``), ``relevancy``,
+``lr_finder`` (the learning-rate range test).
 Every public name is re-exported here, so callers write ``engine.TrainStep``.  State that is rebound at run time is not: read
 and set ``engine.train._CAPTURE_MODE`` there."""
 from .distributed import FlatGradients, broadcast_parameters, configure_ddp  # noqa: F401
 from .feeds import (HISFRAG_PLAN_COLUMNS, MICHIGAN_MAX_HOLES, MICHIGAN_PLAN_COLUMNS, DevicePrefetcher, Div2kDeviceLoader,  # noqa: F401
                     Div2kImageStore, HisfragDeviceLoader, HisfragPlan, MichiganDeviceLoader, MichiganPlan, assemble_pairs,
                     div2k_augment_plan, div2k_pair_plan, hisfrag_augment_plan, hisfrag_feed, michigan_augment_plan, michigan_feed)
+from .lr_finder import LR_FINDER_MAX_ITER, LRFinderResult, LRRangeTest, find_lr  # noqa: F401
 from .metrics import (ClassificationMeters, GeshaemMetrics, MeterValue, PairScoreAggregator, PairScoreStats, RetrievalCurves,  # noqa: F401
                       RetrievalLists, ValidationResult, class_members, geshaem_pair_metrics, group_relations,
                       hisfrag_retrieval_lists, hisfrag_retrieval_metrics, map_prak, metrics_from_sums, retrieval_curves,

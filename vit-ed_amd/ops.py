@@ -1310,6 +1310,10 @@ from .ops_tokendrop import (TOKEN_DROPOUT_MAX_DIM, dropout_threshold, philox4x32
 # ---- device-stepped learning-rate schedule: the wrapper of csrc/lr_schedule.hip and its table layout live in ops_lrsched.py -----------
 from .ops_lrsched import LR_MAX_MILESTONES, LR_TABLE_WORDS, lr_schedule_step  # noqa: E402,F401
 
+# ---- learning-rate range test: the wrapper of csrc/lr_finder.hip, its rule in numpy and the suggestion live in ops_lrfinder.py ----------
+from .ops_lrfinder import (LRF_DIVERGED, LRF_DONE, LRF_HISTORY_COLS, LRF_NONFINITE, LRF_RUNNING, LRF_STATE_WORDS,  # noqa: E402,F401
+                           lr_finder_rate, lr_finder_step, lr_suggestion)
+
 # ---- fused mined-pair loss: the wrapper of csrc/mined_bce.hip lives in ops_minedloss.py ---------------------------------------------
 from .ops_minedloss import MINED_BCE_MAX_CLASSES, mined_bce  # noqa: E402,F401
 

@@ -89,6 +89,24 @@ class WeightShadows:
         self._plan.run()
         self.mark_current(params)
 
+    def snapshot(self, params):
+        """Copies of the cached shadows of ``params``, with whether each was current: what ``restore`` puts back."""
+        by_id = {id(p): p for p in params}
+        return {key: (ent.version == by_id[key[0]]._version and ent.ptr == by_id[key[0]].data_ptr(), ent.buf.clone())
+                for key, ent in self._entries.items() if key[0] in by_id}
+
+    def restore(self, saved, params):
+        """The parameters were set back in place to what they held at ``snapshot``: so are the shadows, IN PLACE (a captured graph
+        keeps reading the same buffers).  An entry ``saved`` has no copy of (created since) is recast from its parameter; one that was
+        not current at the snapshot holds its old bits again and stays not current."""
+        self.refresh(params)
+        for key, (current, buf) in saved.items():
+            ent = self._entries.get(key)
+            if ent is not None and ent.buf.shape == buf.shape:
+                ent.buf.copy_(buf)
+                if not current:
+                    self._entries[key] = ent._replace(version=-1)
+
     def pin(self):
         """A captured graph reads the buffers from now on: none is freed any more, only refreshed in place or retired."""
         self._pinned = True
