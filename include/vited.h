@@ -66,6 +66,20 @@ const char* vited_strerror(int code);
 int vited_last_gemm_path(void);
 int vited_last_attention_path(void);
 
+/* GEMM path 1 (the fp32 compute mode, and the bf16 shapes the bf16 MFMA kernels do not tile) has two kernels that produce the
+ * same bits: the vector-ALU kernel and, for the shapes vited_gemm_f32_mfma_supported names, one on the f32-input matrix-core
+ * instruction (v_mfma_f32_32x32x2_f32), whose result is the same k-ordered fmaf chain.
+ *   vited_gemm_f32_mfma_supported  1 when vited_gemm of that shape (b_layout VITED_B_*, epilogue VITED_EPI_*) takes the matrix-core
+ *                                  kernel under automatic selection, else 0.  Host-only: needs no GPU.
+ *   vited_last_fp32_gemm_kernel    which one the last path-1 call of vited_gemm / vited_gemm_scaled / vited_linear_bwd_weight on
+ *                                  this thread ran: 0 = none yet, 1 = vector-ALU kernel, 2 = matrix-core kernel.
+ *   vited_fp32_gemm_select         mode 0 = automatic (the default), 1 = vector-ALU kernels only.  Process-wide; returns the
+ *                                  previous mode, or VITED_ERR_BAD_ARG for any other mode (nothing changes).  Test/diagnostic use:
+ *                                  it lets one process run both kernels on the same data. */
+int vited_gemm_f32_mfma_supported(int64_t M, int64_t N, int64_t K, int b_layout, int epilogue);
+int vited_last_fp32_gemm_kernel(void);
+int vited_fp32_gemm_select(int mode);
+
 /* ---- data movement -------------------------------------------------------------------------- */
 
 /* dst[i] = (dst_dtype) src[i].  Used for the bf16 shadow of the fp32 master parameters. */

@@ -1,5 +1,5 @@
 // C-ABI GEMM entry points: argument validation and dispatch between the bf16 MFMA kernels and the
-// portable fp32-FMA kernels.
+// fp32 kernels (portable fp32-FMA, or the same chains on the f32-input matrix-core instruction).
 #include <stdlib.h>
 #include <string.h>
 
@@ -7,6 +7,24 @@
 
 static thread_local int g_last_gemm_path = 0;
 extern "C" int vited_last_gemm_path(void) { return g_last_gemm_path; }
+
+// Path 1 has two kernels that compute the same bits: the vector-ALU ones (gemm_portable.hip) and the matrix-core ones
+// (gemm_f32_mfma.hip).  Which of them the last path-1 call on this thread ran, and a process-wide switch that keeps every call
+// on the vector-ALU ones (tests and the probe run both in one process).
+static thread_local int g_last_fp32_gemm_kernel = 0;
+static int g_fp32_gemm_select = 0;
+extern "C" int vited_last_fp32_gemm_kernel(void) { return g_last_fp32_gemm_kernel; }
+extern "C" int vited_fp32_gemm_select(int mode) {
+    if (mode != 0 && mode != 1) return VITED_ERR_BAD_ARG;
+    return __atomic_exchange_n(&g_fp32_gemm_select, mode, __ATOMIC_RELAXED);
+}
+extern "C" int vited_gemm_f32_mfma_supported(int64_t M, int64_t N, int64_t K, int b_layout, int epilogue) {
+    if (M <= 0 || N <= 0 || K <= 0 || epilogue < VITED_EPI_STORE || epilogue > VITED_EPI_GELU_GRAD) return 0;
+    return gemm_f32_mfma_supported(M, N, K, b_layout, epilogue) ? 1 : 0;
+}
+static inline bool fp32_gemm_on_matrix_cores(int64_t M, int64_t N, int64_t K, int b_layout, int epilogue) {
+    return __atomic_load_n(&g_fp32_gemm_select, __ATOMIC_RELAXED) == 0 && gemm_f32_mfma_supported(M, N, K, b_layout, epilogue);
+}
 
 static int gemm_impl(const void* A, int64_t lda, const void* B, int64_t ldb, int b_layout, int dtype, int64_t M, int64_t N, int64_t K,
                      int epilogue, const float* bias, const void* aux, const float* residual, void* out, void* out2, int64_t ldo,
@@ -44,6 +62,11 @@ static int gemm_impl(const void* A, int64_t lda, const void* B, int64_t ldb, int
         return gemm_nt_mfma(A, lda, B, ldb, M, N, K, epilogue, ep, s);
     }
     g_last_gemm_path = 1;
+    if (fp32_gemm_on_matrix_cores(M, N, K, b_layout, epilogue)) {
+        g_last_fp32_gemm_kernel = 2;
+        return gemm_f32_mfma(A, lda, B, ldb, b_layout, dtype, M, N, K, epilogue, ep, s);
+    }
+    g_last_fp32_gemm_kernel = 1;
     return gemm_portable(A, lda, B, ldb, b_layout, dtype, M, N, K, epilogue, ep, s);
 }
 
@@ -106,7 +129,14 @@ extern "C" int vited_linear_bwd_weight(const void* dY, int64_t lddy, const void*
         return rc;
     }
     g_last_gemm_path = 1;
-    rc = gemm_tn_portable(dY, lddy, X, ldx, dtype, M, N, K, splits, slab, s);
+    // the product is [N, K] with M the reduction: the predicate sees it as the forward GEMM of that shape; same splits, same slabs
+    if (fp32_gemm_on_matrix_cores(N, K, M, VITED_B_KN, VITED_EPI_STORE_F32)) {
+        g_last_fp32_gemm_kernel = 2;
+        rc = gemm_tn_f32_mfma(dY, lddy, X, ldx, dtype, M, N, K, splits, slab, s);
+    } else {
+        g_last_fp32_gemm_kernel = 1;
+        rc = gemm_tn_portable(dY, lddy, X, ldx, dtype, M, N, K, splits, slab, s);
+    }
     if (rc != VITED_OK) return rc;
     if (via_slabs) {
         rc = sum_rows_f32_single_pass(workspace, N * K, dW, splits, N * K, s, accumulate);

@@ -8,6 +8,13 @@ int gemm_portable(const void* A, int64_t lda, const void* B, int64_t ldb, int b_
 int gemm_tn_portable(const void* dY, int64_t lddy, const void* X, int64_t ldx, int dtype, int64_t M, int64_t N, int64_t K,
                      int64_t splits, float* out, hipStream_t s);
 
+// the same products on the f32-input matrix-core instruction, bit for bit (gemm_f32_mfma.hip); the predicate is host-only
+bool gemm_f32_mfma_supported(int64_t M, int64_t N, int64_t K, int b_layout, int epilogue);
+int gemm_f32_mfma(const void* A, int64_t lda, const void* B, int64_t ldb, int b_layout, int dtype, int64_t M, int64_t N,
+                  int64_t K, int epilogue, const EpiParams& ep, hipStream_t s);
+int gemm_tn_f32_mfma(const void* dY, int64_t lddy, const void* X, int64_t ldx, int dtype, int64_t M, int64_t N, int64_t K,
+                     int64_t splits, float* out, hipStream_t s);
+
 // bf16 MFMA kernels (gemm_mfma.hip)
 bool gemm_nt_mfma_supported(const void* A, int64_t lda, const void* B, int64_t ldb, int64_t M, int64_t N, int64_t K,
                             int epilogue, const EpiParams& ep);

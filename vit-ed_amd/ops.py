@@ -8,6 +8,7 @@ is hipGraph-capturable.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from typing import NamedTuple
 
@@ -1095,6 +1096,34 @@ def attention_cam(q, k, v, do, lse, heads: int, scale: float, *, mode, head_weig
 def last_paths():
     lib = _lib.load()
     return lib.vited_last_gemm_path(), lib.vited_last_attention_path()
+
+
+def fp32_gemm_supported(m: int, n: int, k: int, b_layout: int = B_NK, epilogue: int = EPI_STORE) -> bool:
+    """Whether ``gemm`` of that shape on GEMM path 1 (fp32, or bf16 outside the bf16 MFMA tiles) takes the matrix-core kernel
+    (gemm_f32_mfma.hip) under ``'auto'``.  Host-only."""
+    return bool(_lib.load().vited_gemm_f32_mfma_supported(int(m), int(n), int(k), int(b_layout), int(epilogue)))
+
+
+def last_fp32_gemm_kernel() -> int:
+    """Which kernel the last path-1 ``gemm`` / ``linear_bwd_weight`` of this thread ran: 0 none yet, 1 vector-ALU, 2 matrix-core."""
+    return _lib.load().vited_last_fp32_gemm_kernel()
+
+
+_FP32_GEMM_MODES = {'auto': 0, 'valu': 1}
+
+
+@contextlib.contextmanager
+def fp32_gemm_kernels(mode: str):
+    """Within the block, path-1 GEMMs pick their kernel automatically (``'auto'``, the default of the process) or stay on the
+    vector-ALU kernels (``'valu'``); the previous mode returns on exit.  Both give the same bits.  Process-wide."""
+    if mode not in _FP32_GEMM_MODES:
+        raise ValueError(f"fp32_gemm_kernels: mode is 'auto' or 'valu', not {mode!r}")
+    select = _lib.load().vited_fp32_gemm_select          # returns the previous mode, not a status: only valid modes are passed
+    previous = select(_FP32_GEMM_MODES[mode])
+    try:
+        yield
+    finally:
+        select(previous)
 
 
 # ---------------------------------------------------------------------------------------------
