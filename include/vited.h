@@ -80,6 +80,21 @@ int vited_gemm_f32_mfma_supported(int64_t M, int64_t N, int64_t K, int b_layout,
 int vited_last_fp32_gemm_kernel(void);
 int vited_fp32_gemm_select(int mode);
 
+/* Attention path 1 (the fp32 compute mode, and the bf16 operands the bf16 MFMA attention refuses) has two sets of kernels that
+ * produce the same bits as well: the vector-ALU kernels and, for the calls vited_attention_f32_mfma_supported names, kernels on
+ * v_mfma_f32_32x32x2_f32 that walk the same fmaf chains (forward, dQ + delta, dK / dV).
+ *   vited_attention_f32_mfma_supported  1 when vited_attention_fwd* (backward = 0) or vited_attention_bwd* (backward = 1) of that
+ *                                       dtype (VITED_F32 / VITED_BF16) and shape takes the matrix-core kernels under automatic
+ *                                       selection once it is on path 1, else 0.  Host-only: needs no GPU.
+ *   vited_last_fp32_attention_kernel    which set the last path-1 attention call on this thread ran: 0 = none yet, 1 = vector-ALU
+ *                                       kernels, 2 = matrix-core kernels.
+ *   vited_fp32_attention_select         mode 0 = automatic (the default), 1 = vector-ALU kernels only.  Process-wide and separate
+ *                                       from vited_fp32_gemm_select; returns the previous mode, or VITED_ERR_BAD_ARG for any other
+ *                                       mode (nothing changes).  Test/diagnostic use. */
+int vited_attention_f32_mfma_supported(int dtype, int64_t batch, int heads, int64_t nq, int64_t nk, int head_dim, int backward);
+int vited_last_fp32_attention_kernel(void);
+int vited_fp32_attention_select(int mode);
+
 /* ---- data movement -------------------------------------------------------------------------- */
 
 /* dst[i] = (dst_dtype) src[i].  Used for the bf16 shadow of the fp32 master parameters. */

@@ -1,11 +1,30 @@
 // C-ABI attention entry points: validation + dispatch (bf16 MFMA kernels when the shape is
-// covered, portable fp32-VALU kernels otherwise).
+// covered, otherwise the fp32 kernels: portable fp32-VALU, or the same chains on the f32-input matrix-core instruction).
 #include "attention_kernels.h"
 #include "pair_segsum.h"
 
 static thread_local int g_last_attn_path = 0;
 extern "C" int vited_last_attention_path(void) { return g_last_attn_path; }
 void attention_set_last_path(int path) { g_last_attn_path = path; }
+
+// Path 1 has two sets of kernels that compute the same bits: the vector-ALU ones (attention_portable.hip) and the matrix-core ones
+// (attention_f32_mfma.hip).  Which of them the last path-1 call on this thread ran, and a process-wide switch that keeps every call
+// on the vector-ALU ones (tests and the probe run both in one process).
+static thread_local int g_last_fp32_attn_kernel = 0;
+static int g_fp32_attn_select = 0;
+extern "C" int vited_last_fp32_attention_kernel(void) { return g_last_fp32_attn_kernel; }
+extern "C" int vited_fp32_attention_select(int mode) {
+    if (mode != 0 && mode != 1) return VITED_ERR_BAD_ARG;
+    return __atomic_exchange_n(&g_fp32_attn_select, mode, __ATOMIC_RELAXED);
+}
+extern "C" int vited_attention_f32_mfma_supported(int dtype, int64_t batch, int heads, int64_t nq, int64_t nk, int head_dim,
+                                                  int backward) {
+    return attention_f32_mfma_supported(dtype, batch, heads, nq, nk, head_dim, backward != 0) ? 1 : 0;
+}
+static inline bool fp32_attn_on_matrix_cores(const AttnArgs& a, int dtype, bool backward) {
+    return __atomic_load_n(&g_fp32_attn_select, __ATOMIC_RELAXED) == 0 &&
+           attention_f32_mfma_supported(dtype, a.batch, a.heads, a.nq, a.nk, a.head_dim, backward);
+}
 
 static int check_common(const AttnArgs& a, int dtype) {
     if (!a.q || !a.k || !a.v || !a.o || !a.lse) return VITED_ERR_BAD_ARG;
@@ -42,6 +61,11 @@ extern "C" int vited_attention_fwd_indexed(const void* q, int64_t q_bs, int64_t 
         return attention_fwd_mfma(a, s);
     }
     g_last_attn_path = 1;
+    if (fp32_attn_on_matrix_cores(a, dtype, false)) {
+        g_last_fp32_attn_kernel = 2;
+        return attention_fwd_f32_mfma(a, dtype, s);
+    }
+    g_last_fp32_attn_kernel = 1;
     return attention_fwd_portable(a, dtype, s);
 }
 
@@ -51,6 +75,11 @@ static int bwd_dispatch(const AttnArgs& a, int dtype, hipStream_t s) {
         return attention_bwd_mfma(a, s);
     }
     g_last_attn_path = 1;
+    if (fp32_attn_on_matrix_cores(a, dtype, true)) {
+        g_last_fp32_attn_kernel = 2;
+        return attention_bwd_f32_mfma(a, dtype, s);
+    }
+    g_last_fp32_attn_kernel = 1;
     return attention_bwd_portable(a, dtype, s);
 }
 

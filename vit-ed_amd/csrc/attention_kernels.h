@@ -22,6 +22,11 @@ struct AttnArgs {
 int attention_fwd_portable(const AttnArgs& a, int dtype, hipStream_t s);
 int attention_bwd_portable(const AttnArgs& a, int dtype, hipStream_t s);
 
+// the same chains on the f32-input matrix-core instruction, bit for bit (attention_f32_mfma.hip); the predicate is host-only
+bool attention_f32_mfma_supported(int dtype, int64_t batch, int heads, int64_t nq, int64_t nk, int head_dim, bool backward);
+int attention_fwd_f32_mfma(const AttnArgs& a, int dtype, hipStream_t s);
+int attention_bwd_f32_mfma(const AttnArgs& a, int dtype, hipStream_t s);
+
 // bf16 MFMA kernels (attention_mfma.hip)
 bool attention_mfma_supported(const AttnArgs& a, bool backward);
 int attention_fwd_mfma(const AttnArgs& a, hipStream_t s);
