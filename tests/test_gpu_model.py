@@ -74,7 +74,9 @@ def test_against_reference_fixtures(vited, gpu, name, dtype):
         m_ac = vo.fill_closed_form_(vo.OracleViTED(s)).eval()
         with torch.no_grad(), torch.autocast('cpu', dtype=torch.bfloat16):
             err_ac = float(np.abs(m_ac(vo.closed_form_pairs(batch, s)).float().numpy() - fx['logits']).max())
-        assert err <= max(3e-2, 1.5 * err_ac + 1e-2), f'bf16 logits {err:.3e} off the reference fixture; torch bf16 autocast: {err_ac:.3e}'
+        # ... and never beyond 6e-2, whatever the host's autocast does (measured: DESIGN.md section 8)
+        print(f'{name}: bf16 logits err {err:.3e}, torch bf16 autocast on this host err_ac {err_ac:.3e}')
+        assert err <= min(6e-2, max(3e-2, 1.5 * err_ac + 1e-2)), f'bf16 logits {err:.3e} off the reference fixture; torch bf16 autocast: {err_ac:.3e}'
         ltol = dict(rtol=0, atol=float('inf'))
     # structural invariant the reference's only test relies on: two-stage == one-shot
     assert torch.equal(two_stage, logits)

@@ -719,6 +719,8 @@ class EncoderFn(torch.autograd.Function):
         pdrop = _take_pos_drop(pos_drop, 0)
         x, patches, batch, n = _patch_tokens_fwd(rt, img, shared, with_cls=False, keep=keep)
         x = _pos_drop(rt, x, batch, n, False, pdrop, keep, in_place=True)      # the stream was just written and nothing else holds it
+        if rt.tap is not None:
+            rt.tap['enc.in'] = x.clone()        # the input of encoder block 0
         drop = _take_drop_rows(drop_path, 0, len(blocks), 2, batch, n, x.device)      # stochastic depth: per-row scales of (attn, mlp) per block
         tape = []
         ln1 = None          # (h, mean, rstd) of this block's norm1 when the previous block's fc2 kernel already produced it
@@ -744,6 +746,8 @@ class EncoderFn(torch.autograd.Function):
         rt, batch, n = ctx.rt, ctx.batch, ctx.n      # n: the call's token count (fewer than rt.n1 under patch dropout)
         shared, blocks = ctx.params
         dx = dout.contiguous().view(batch * n, rt.dim).float()
+        if rt.tap is not None:
+            rt.tap[f'enc.dx.{len(blocks)}'] = dx.clone()      # gradient w.r.t. the encoder's OUTPUT: what autograd hands over
         drop = ctx.drop
         scale_of = (lambda i, j: drop.get(i, j)) if drop is not None else (lambda i, j: None)
         dx_lp = _lp_scaled(rt, dx, scale_of(len(blocks) - 1, 1))      # the last block's MLP branch consumes it
@@ -923,6 +927,8 @@ def _dec_cross_bwd(rt, dx, dx_lp, xa, P, saved, ctxf, dctx, batch, index, dkv3=N
         got = ops.qk_norm_bwd(dq, s.qraw.t, s.qraw.stats, P.gcqn, dkv3.reshape(-1, 2 * d)[:, 0:d], kv3.reshape(-1, 2 * d)[:, 0:d], kn.stats, P.gckn,
                               rt.heads, *(targets if direct else ()))
         gn = dict.fromkeys(fields) if direct else dict(zip(fields, got))
+    if rt.tap is not None:
+        rt.tap[f'dec.dkvo.{index}'] = dkv.clone()     # gradient of the kv projection's OUTPUT (dec.dkv: before the k_norm backward)
     # q = Linear(norm_cross(x')), kv = Linear(norm_context(features)): input-gradient GEMM + LayerNorm backward fused
     dx, dx_lp, dgc, dbc, dwq, dbq = _linear_ln_bwd(rt, dq, s.hq, P.wq, P.bq, xa, P.gc, P.bc, s.mq, s.rq, dx_in=dx, lp_scale=lp_scale)
     dgx = dbx = dwkv = dbkv = None
@@ -1178,6 +1184,8 @@ class DecoderFn(torch.autograd.Function):
         pdrop = _take_pos_drop(pos_drop, 1)
         x, patches, batch, n = _patch_tokens_fwd(rt, img2, shared, with_cls=True, batch_index=img2_index, keep=keep)
         x = _pos_drop(rt, x, batch, n, True, pdrop, keep, in_place=True)       # per pair of the call, also under an image-2 index
+        if rt.tap is not None:
+            rt.tap['dec.in'] = x.clone()        # the input of decoder block 0
         seg = img1_index
         b1 = batch if seg is None else seg.items
         if seg is not None:
@@ -1239,6 +1247,8 @@ class DecoderFn(torch.autograd.Function):
         # sample (the final norm runs on the cls rows)
         s_head = drop.per_sample[last, 2] if drop is not None and drop.live[last][2] else None
         dx, dx_lp, dgN, dbN = _final_norm_bwd(rt, dy, final, shared, s_head, ctx.cls_tail, batch, n)
+        if rt.tap is not None:
+            rt.tap[f'dec.dx.{len(blocks)}'] = dx.clone()      # gradient w.r.t. the last block's OUTPUT (its cls rows under the cls tail)
         dctx = None
         gblocks = [None] * len(blocks)
         dkv_all = torch.empty_like(ctx.fold.kv_all) if ctx.fold else None
@@ -1260,6 +1270,8 @@ class DecoderFn(torch.autograd.Function):
                 dctx, kv_grads = _context_kv_folded_bwd(rt, dkv_all, ctx.ctxf, ctx.fold, blocks)
                 gblocks = [g._replace(**kv) for g, kv in zip(gblocks, kv_grads)]
                 ctx.fold = None
+        if rt.tap is not None and dctx is not None:
+            rt.tap['dec.dfeats'] = dctx.clone()     # total d(features), whichever way the keys / values were computed
         dx = _pos_drop(rt, dx, batch, n, True, ctx.pos_drop, ctx.keep, in_place=False)     # position dropout on the stream's gradient
         gshared = rt.dec_shared(**_patch_tokens_bwd(rt, dx, ctx.patches, shared, with_cls=True, batch=batch, keep=ctx.keep), gN=dgN, bN=dbN, wh=dwh, bh=dbh)
         dfeats = dctx.view(b1, nc, d) if ctx.feats_needs_grad and dctx is not None else None
