@@ -565,7 +565,8 @@ int vited_cross_block_fwd(const float* x, const float* context, float* y, int64_
  *               first_tile = running sum of ceil(rows/64) * ceil(cols/64); total_tiles the sum over all rows.
  *   grad_flat   the contiguous fp32 gradient buffer every g points into (the L2 norm is taken over all of it)
  *   hyper       DEVICE fp32 array: [0] = number of updates applied so far (an applied update increments it: bias correction
- *               uses the incremented value), [1] = skip flag, [2] = number of updates skipped, [3..7] unused, then 8 floats
+ *               uses the incremented value), [1] = skip flag, [2] = number of updates skipped, [3..5] the EMA words of the *_ema entries below (never
+ *               read or written here), [6..7] unused, then 8 floats
  *               per parameter group {lr, beta1, beta2, eps, weight_decay, 0, 0, 0} - device-resident so that a replayed
  *               hipGraph follows lr_scheduler.step_update (misc/engine.py:228)
  *   max_norm    clip_grad_norm_ threshold (<= 0: no clipping); norm_out (nullable) receives the pre-clip norm
@@ -590,6 +591,32 @@ int vited_adamw_step(const int64_t* desc, int count, int64_t total_tiles, const 
 int vited_sgd_step(const int64_t* desc, int count, int64_t total_tiles, const float* grad_flat, int64_t grad_numel,
                    float* hyper, float max_norm, int zero_grad, float* norm_out, float* workspace,
                    int64_t workspace_bytes, void* stream);
+
+/* The same two updates with an exponential moving average of the parameters (timm's ModelEmaV2, --model-ema) kept in the update
+ * launch; every other output is bit for bit what vited_adamw_step / vited_sgd_step give.  The rule is csrc/optim_update.h's
+ * (ema_decay_at, ema_blend); with d = hyper[3], the warmup flag hyper[4] and n = hyper[5], the EMA updates done so far, an applied
+ * update that produced the new parameter p' also does, per element,
+ *     d_t = warmup ? min(d, (1 + n) / (10 + n)) : d          all fp32, n as fp32
+ *     e'  = fl(fl(d_t * e) + fl((1.0f - d_t) * p'))           two rounded products and a rounded sum, never an fma
+ * and hyper[5] goes up by one.  A skipped update leaves e and hyper[5] alone.  With a momentum of 0 the SGD entry still updates and
+ * averages p.  vited_adamw_step / vited_sgd_step never read or write hyper[3..5].
+ *   ema_flat    DEVICE fp32 [ema_numel], 16-byte aligned, laid out like grad_flat: the average of a row's p lies at the offset its g
+ *               has in grad_flat (the 10-word descriptor row is the one above); it may not overlap any other buffer
+ * VITED_ERR_BAD_ARG before any launch: ema_flat null or not 16-byte aligned, ema_numel < grad_numel, and whatever the entries above
+ * refuse. */
+int vited_adamw_step_ema(const int64_t* desc, int count, int64_t total_tiles, const float* grad_flat, int64_t grad_numel,
+                         float* hyper, float max_norm, int zero_grad, float* norm_out, float* workspace,
+                         int64_t workspace_bytes, float* ema_flat, int64_t ema_numel, void* stream);
+int vited_sgd_step_ema(const int64_t* desc, int count, int64_t total_tiles, const float* grad_flat, int64_t grad_numel,
+                       float* hyper, float max_norm, int zero_grad, float* norm_out, float* workspace,
+                       int64_t workspace_bytes, float* ema_flat, int64_t ema_numel, void* stream);
+
+/* Exchange every parameter of the table with its average, element for element, and rewrite the row's shadow and shadow_t (where not
+ * 0) from the value now in p: one launch over the update's descriptor table and 64 x 64 tiling (words 2, 3 and 9 of a row are not
+ * read).  Evaluation on the averaged weights happens between two calls; the second restores every bit of p, e and (shadows that were
+ * current) both shadows.  ema_flat and grad_flat as above; the caller guarantees that ema_flat covers grad_flat's extent.
+ * VITED_ERR_BAD_ARG before the launch: a null desc, ema_flat or grad_flat, ema_flat not 16-byte aligned, count or total_tiles < 1. */
+int vited_ema_swap(const int64_t* desc, int count, int64_t total_tiles, float* ema_flat, const float* grad_flat, void* stream);
 
 /* One step of a per-iteration learning-rate schedule on the device (misc/lr_scheduler.py through misc/engine.py:228; the rules are
  * csrc/lr_schedule.h, in fp64): one launch of one workgroup, queued behind the update it follows.

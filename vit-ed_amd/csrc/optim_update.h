@@ -1,7 +1,8 @@
 // The per-element update bodies of the fused optimizer kernels (optimizer.hip): torch.optim.AdamW's and torch.optim.SGD's rules
 // on four consecutive elements of one parameter row, and the decision whether an update is applied at all.  Plain C++ (one call =
 // one 4-element piece, the unit a thread of the update kernel handles), so that the same text runs inside the HIP kernels and in a
-// host program under the sanitizers (tools/optim_host_check.cpp).
+// host program under the sanitizers (tools/optim_host_check.cpp, tools/ema_host_check.cpp).  The exponential moving average of the
+// parameters (the *_ema entries, vited_ema_swap) is stated here as well: ema_decay_at / ema_blend are THE rule.
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -161,4 +162,72 @@ OPTIM_FN void skipped_piece(float* g, int64_t o, int n, bool wide, int zero_grad
     if (wide) *(OptimVec4*)(g + o) = OptimVec4{{0.f, 0.f, 0.f, 0.f}};
     else
         for (int e = 0; e < n; ++e) g[o + e] = 0.f;
+}
+
+// ---- exponential moving average of the parameters (timm's ModelEmaV2 / --model-ema) --------------------------------------------------
+// hyper[3] = d (the decay), hyper[4] = warmup flag, hyper[5] = n, the EMA updates done so far.  After an applied update produced p':
+//     d_t = warmup ? min(d, (1 + n) / (10 + n)) : d            all fp32, n as fp32
+//     e'  = fl( fl(d_t * e) + fl((1.0f - d_t) * p') )           both products rounded on their own: never an fma
+// and n advances by one.  A skipped update leaves e and n alone.
+#define OPTIM_EMA_DECAY 3
+#define OPTIM_EMA_WARMUP 4
+#define OPTIM_EMA_COUNT 5
+
+OPTIM_FN float ema_decay_at(float d, float warmup, float n) {
+    if (warmup != 0.f) {
+        const float w = (1.0f + n) / (10.0f + n);
+        d = w < d ? w : d;
+    }
+    return d;
+}
+
+OPTIM_FN float ema_blend(float dt, float e, float p) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    float keep = OPTIM_MUL_RN(dt, e);
+    float take = OPTIM_MUL_RN(1.0f - dt, p);
+#if defined(__HIP_DEVICE_COMPILE__)
+    // -ffp-contract=fast lets the backend fuse a product into the sum whatever the source says (pragma and __fmul_rn included): an
+    // empty statement that "produces" both products makes them values of their own.  No instruction is emitted for it.
+    asm("" : "+v"(keep), "+v"(take));
+#endif
+    return keep + take;
+}
+
+// Beside optim_decide, by the same one thread: an applied update is one EMA update.
+OPTIM_FN void ema_decide(bool applied, float* hyper) {
+    if (applied) hyper[OPTIM_EMA_COUNT] += 1.0f;
+}
+
+// The decay of the update whose decision ema_decide just recorded (every workgroup of the update kernel derives it alike).
+OPTIM_FN float ema_decay_now(const float* hyper) {
+    return ema_decay_at(hyper[OPTIM_EMA_DECAY], hyper[OPTIM_EMA_WARMUP], hyper[OPTIM_EMA_COUNT] - 1.0f);
+}
+
+// Elements [o, o + n) of the average, from the new parameter values pn the update piece just produced (same n / wide as there).
+OPTIM_FN void ema_piece(float* ema, int64_t o, int n, bool wide, float dt, const float* pn) {
+    if (wide) {
+        const OptimVec4 qe = *(const OptimVec4*)(ema + o);
+        *(OptimVec4*)(ema + o) = OptimVec4{{ema_blend(dt, qe.v[0], pn[0]), ema_blend(dt, qe.v[1], pn[1]), ema_blend(dt, qe.v[2], pn[2]),
+                                            ema_blend(dt, qe.v[3], pn[3])}};
+    } else {
+        for (int e = 0; e < n; ++e) ema[o + e] = ema_blend(dt, ema[o + e], pn[e]);
+    }
+}
+
+// vited_ema_swap: p <-> its slice of the average, element for element; pn receives what p now holds (for the bf16 shadows).
+OPTIM_FN void swap_piece(float* p, float* ema, int64_t o, int n, bool wide, float* pn) {
+    if (wide) {
+        const OptimVec4 qp = *(const OptimVec4*)(p + o), qe = *(const OptimVec4*)(ema + o);
+        *(OptimVec4*)(p + o) = qe;
+        *(OptimVec4*)(ema + o) = qp;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) pn[e] = qe.v[e];
+    } else {
+        for (int e = 0; e < n; ++e) {
+            const float pv = p[o + e], ev = ema[o + e];
+            p[o + e] = ev; ema[o + e] = pv; pn[e] = ev;
+        }
+    }
 }

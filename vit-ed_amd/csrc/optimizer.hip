@@ -25,15 +25,21 @@
 // + 4 B of shadows (8 + 8 + 4 without momentum) = the floor for these updates.
 // All hyper-parameters that change between steps (learning rate per group, step count) live in a device array, so a
 // hipGraph replay of the launches follows the scheduler.
+//
+// vited_adamw_step_ema / vited_sgd_step_ema: the same three launches with the exponential moving average of the parameters kept in
+// the third one (optim_update_ema_kernel, the EMA instance of the same tile body: + 4 B read and 4 B written per element, on the
+// fresh p it holds in registers); launch 2 advances the EMA counter hyper[5] beside hyper[0].  vited_ema_swap: the OPT_SWAP instance
+// of that body, p <-> e and both shadows rewritten from the value now in p.  The entries without _ema launch optim_update_kernel,
+// which instantiates the body without any of it.
 #include "common.h"
 #include "optim_update.h"
 
 #define AD_DESC_WORDS 10   // {p, g, m, v, shadow, shadow_t, rows, cols, first_tile, group}
-#define AD_HYPER_HEADER 8  // hyper[0] = updates applied (float), [1] = skip-non-finite flag, [2] = updates skipped, [3..7] reserved; then 8 floats per group
+#define AD_HYPER_HEADER 8  // hyper[0] = updates applied (float), [1] = skip-non-finite flag, [2] = updates skipped, [3..5] = EMA decay, warmup flag, EMA updates (the *_ema entries only), [6..7] reserved; then 8 floats per group
 #define AD_GROUP_WORDS 8   // AdamW {lr, beta1, beta2, eps, weight_decay, -, -, -}; SGD {lr, momentum, nesterov, -, weight_decay, -, -, -}
 #define AD_PARTIALS 1024
 #define AD_RESULT_WORDS 4  // behind the partials: {norm, clip, applied, step count}
-enum { OPT_ADAMW = 0, OPT_SGD = 1 };
+enum { OPT_ADAMW = 0, OPT_SGD = 1, OPT_SWAP = 2 };
 
 __device__ __forceinline__ float block_sum_256(float v, float* red) {
     v = wave_sum(v);
@@ -72,7 +78,7 @@ optim_sumsq_kernel(const float* __restrict__ g, int64_t n, float* __restrict__ p
 }
 
 __global__ void __launch_bounds__(256)
-optim_decide_kernel(float* __restrict__ ws, float* __restrict__ hyper, float max_norm, float* __restrict__ norm_out) {
+optim_decide_kernel(float* __restrict__ ws, float* __restrict__ hyper, float max_norm, float* __restrict__ norm_out, int ema) {
     __shared__ float red[4];
     float s = 0.f;
 #pragma unroll
@@ -80,17 +86,25 @@ optim_decide_kernel(float* __restrict__ ws, float* __restrict__ hyper, float max
     const float norm = sqrtf(block_sum_256(s, red));
     if (threadIdx.x == 0) {
         optim_decide(norm, max_norm, hyper, ws + AD_PARTIALS);
+        if (ema) ema_decide(ws[AD_PARTIALS + 2] != 0.f, hyper);    // the *_ema entries only: the others never touch hyper[3..5]
         if (norm_out) *norm_out = norm;
     }
 }
 
-template <int OPT>
-__global__ void __launch_bounds__(256)
-optim_update_kernel(const int64_t* __restrict__ desc, int count, const float* __restrict__ res,
-                    const float* __restrict__ hyper, int zero_grad) {
+// One 64 x 64 tile of one parameter.  OPT_ADAMW / OPT_SGD: the update; EMA adds e' = ema_blend(d_t, e, p') on the row's slice of
+// ema_flat (at the offset of its g in grad_flat).  OPT_SWAP: p <-> e and the shadows rewritten from the value now in p (vited_ema_swap;
+// res, hyper and zero_grad unused).
+template <int OPT, bool EMA>
+__device__ __forceinline__ void
+optim_update_tile(const int64_t* __restrict__ desc, int count, const float* __restrict__ res, const float* __restrict__ hyper,
+                  int zero_grad, float* __restrict__ ema_flat, const float* grad_flat) {
     __shared__ bf16 tile[64][66];
-    const float clip = res[1], step = res[3];
-    const bool applied = res[2] != 0.f;         // the same word in every workgroup
+    float clip = 1.0f, step = 0.f;
+    bool applied = true;
+    if constexpr (OPT != OPT_SWAP) {
+        clip = res[1]; step = res[3];
+        applied = res[2] != 0.f;                // the same word in every workgroup
+    }
     if (!applied && !zero_grad) return;
 
     const int64_t blk = blockIdx.x;
@@ -107,18 +121,25 @@ optim_update_kernel(const int64_t* __restrict__ desc, int count, const float* __
     bf16* __restrict__ dst = (bf16*)d[4];
     bf16* __restrict__ dst_t = (bf16*)d[5];
     const int64_t rows = d[6], cols = d[7];
-    const float* hg = hyper + AD_HYPER_HEADER + d[9] * AD_GROUP_WORDS;
     AdamWCoef ka = {};
     SgdCoef ks = {};
-    if constexpr (OPT == OPT_ADAMW) ka = adamw_coef(hg, step);
-    else ks = sgd_coef(hg);
+    if constexpr (OPT != OPT_SWAP) {
+        const float* hg = hyper + AD_HYPER_HEADER + d[9] * AD_GROUP_WORDS;
+        if constexpr (OPT == OPT_ADAMW) ka = adamw_coef(hg, step);
+        else ks = sgd_coef(hg);
+    }
+    float* e = nullptr;                         // the row's slice of the average
+    float dt = 0.f;
+    if constexpr (EMA) e = ema_flat + (g - grad_flat);
+    if constexpr (EMA && OPT != OPT_SWAP) dt = applied ? ema_decay_now(hyper) : 0.f;
 
     const int64_t t = blk - d[8], tiles_c = (cols + 63) >> 6;
     const int64_t r0 = (t / tiles_c) << 6, c0 = (t % tiles_c) << 6;
     const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;   // 16 x 16: 4 columns x 4 rows per thread
     uintptr_t ptrs = (uintptr_t)p | (uintptr_t)g;
     if constexpr (OPT == OPT_ADAMW) ptrs |= (uintptr_t)m | (uintptr_t)v;
-    else if (ks.momentum != 0.f) ptrs |= (uintptr_t)m;
+    else if (OPT == OPT_SGD && ks.momentum != 0.f) ptrs |= (uintptr_t)m;
+    if constexpr (EMA) ptrs |= (uintptr_t)e;
     const bool vec = (cols & 3) == 0 && (ptrs & 15) == 0;
     if (!applied) {                             // skipped update: zero the gradient tile, leave p, the state and the shadows alone
 #pragma unroll
@@ -139,7 +160,9 @@ optim_update_kernel(const int64_t* __restrict__ desc, int count, const float* __
         if (r < rows && c < cols) {
             const int n = cols - c < 4 ? (int)(cols - c) : 4;
             if constexpr (OPT == OPT_ADAMW) adamw_piece(p, g, m, v, r * cols + c, n, vec && n == 4, ka, clip, zero_grad, pn);
-            else sgd_piece(p, g, m, r * cols + c, n, vec && n == 4, ks, clip, zero_grad, pn);
+            else if constexpr (OPT == OPT_SGD) sgd_piece(p, g, m, r * cols + c, n, vec && n == 4, ks, clip, zero_grad, pn);
+            else swap_piece(p, e, r * cols + c, n, vec && n == 4, pn);
+            if constexpr (EMA && OPT != OPT_SWAP) ema_piece(e, r * cols + c, n, vec && n == 4, dt, pn);
         }
         if (!dst && !dst_t) continue;
         bf16 b[4];
@@ -172,32 +195,86 @@ optim_update_kernel(const int64_t* __restrict__ desc, int count, const float* __
     }
 }
 
-extern "C" int64_t vited_adamw_workspace_bytes(void) { return (int64_t)(AD_PARTIALS + AD_RESULT_WORDS) * sizeof(float); }
+template <int OPT>
+__global__ void __launch_bounds__(256)
+optim_update_kernel(const int64_t* __restrict__ desc, int count, const float* __restrict__ res,
+                    const float* __restrict__ hyper, int zero_grad) {
+    optim_update_tile<OPT, false>(desc, count, res, hyper, zero_grad, nullptr, nullptr);
+}
 
 template <int OPT>
+__global__ void __launch_bounds__(256)
+optim_update_ema_kernel(const int64_t* __restrict__ desc, int count, const float* __restrict__ res,
+                        const float* __restrict__ hyper, int zero_grad, float* __restrict__ ema_flat, const float* grad_flat) {
+    optim_update_tile<OPT, true>(desc, count, res, hyper, zero_grad, ema_flat, grad_flat);
+}
+
+__global__ void __launch_bounds__(256)
+ema_swap_kernel(const int64_t* __restrict__ desc, int count, float* __restrict__ ema_flat, const float* grad_flat) {
+    optim_update_tile<OPT_SWAP, true>(desc, count, nullptr, nullptr, 0, ema_flat, grad_flat);
+}
+
+extern "C" int64_t vited_adamw_workspace_bytes(void) { return (int64_t)(AD_PARTIALS + AD_RESULT_WORDS) * sizeof(float); }
+
+// ema_flat == nullptr: the update without the average (the instances vited_adamw_step / vited_sgd_step have always reached).
+template <int OPT>
 static int optim_step(const int64_t* desc, int count, int64_t total_tiles, const float* grad_flat, int64_t grad_numel, float* hyper,
-                      float max_norm, int zero_grad, float* norm_out, float* workspace, int64_t workspace_bytes, void* stream) {
+                      float max_norm, int zero_grad, float* norm_out, float* workspace, int64_t workspace_bytes, float* ema_flat,
+                      void* stream) {
     if (!desc || !grad_flat || !hyper || !workspace || count <= 0 || grad_numel <= 0 || total_tiles <= 0 || total_tiles > 0x7fffffff)
         return VITED_ERR_BAD_ARG;
     if (workspace_bytes < vited_adamw_workspace_bytes()) return VITED_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(optim_sumsq_kernel, dim3(AD_PARTIALS), dim3(256), 0, s, grad_flat, grad_numel, workspace);
-    hipLaunchKernelGGL(optim_decide_kernel, dim3(1), dim3(256), 0, s, workspace, hyper, max_norm, norm_out);
-    hipLaunchKernelGGL(optim_update_kernel<OPT>, dim3((unsigned)total_tiles), dim3(256), 0, s, desc, count, workspace + AD_PARTIALS,
-                       hyper, zero_grad);
+    hipLaunchKernelGGL(optim_decide_kernel, dim3(1), dim3(256), 0, s, workspace, hyper, max_norm, norm_out, ema_flat ? 1 : 0);
+    if (ema_flat)
+        hipLaunchKernelGGL(optim_update_ema_kernel<OPT>, dim3((unsigned)total_tiles), dim3(256), 0, s, desc, count,
+                           workspace + AD_PARTIALS, hyper, zero_grad, ema_flat, grad_flat);
+    else
+        hipLaunchKernelGGL(optim_update_kernel<OPT>, dim3((unsigned)total_tiles), dim3(256), 0, s, desc, count, workspace + AD_PARTIALS,
+                           hyper, zero_grad);
     return vited_check_launch();
+}
+
+// The average must cover the gradient buffer and allow the 16-byte accesses the gradient slices allow.
+static bool ema_buffer_ok(const float* ema_flat, int64_t ema_numel, int64_t grad_numel) {
+    return ema_flat && ((uintptr_t)ema_flat & 15) == 0 && ema_numel >= grad_numel;
 }
 
 extern "C" int vited_adamw_step(const int64_t* desc, int count, int64_t total_tiles, const float* grad_flat, int64_t grad_numel,
                                 float* hyper, float max_norm, int zero_grad, float* norm_out, float* workspace,
                                 int64_t workspace_bytes, void* stream) {
     return optim_step<OPT_ADAMW>(desc, count, total_tiles, grad_flat, grad_numel, hyper, max_norm, zero_grad, norm_out, workspace,
-                                 workspace_bytes, stream);
+                                 workspace_bytes, nullptr, stream);
 }
 
 extern "C" int vited_sgd_step(const int64_t* desc, int count, int64_t total_tiles, const float* grad_flat, int64_t grad_numel,
                               float* hyper, float max_norm, int zero_grad, float* norm_out, float* workspace,
                               int64_t workspace_bytes, void* stream) {
     return optim_step<OPT_SGD>(desc, count, total_tiles, grad_flat, grad_numel, hyper, max_norm, zero_grad, norm_out, workspace,
-                               workspace_bytes, stream);
+                               workspace_bytes, nullptr, stream);
+}
+
+extern "C" int vited_adamw_step_ema(const int64_t* desc, int count, int64_t total_tiles, const float* grad_flat, int64_t grad_numel,
+                                    float* hyper, float max_norm, int zero_grad, float* norm_out, float* workspace,
+                                    int64_t workspace_bytes, float* ema_flat, int64_t ema_numel, void* stream) {
+    if (!ema_buffer_ok(ema_flat, ema_numel, grad_numel)) return VITED_ERR_BAD_ARG;
+    return optim_step<OPT_ADAMW>(desc, count, total_tiles, grad_flat, grad_numel, hyper, max_norm, zero_grad, norm_out, workspace,
+                                 workspace_bytes, ema_flat, stream);
+}
+
+extern "C" int vited_sgd_step_ema(const int64_t* desc, int count, int64_t total_tiles, const float* grad_flat, int64_t grad_numel,
+                                  float* hyper, float max_norm, int zero_grad, float* norm_out, float* workspace,
+                                  int64_t workspace_bytes, float* ema_flat, int64_t ema_numel, void* stream) {
+    if (!ema_buffer_ok(ema_flat, ema_numel, grad_numel)) return VITED_ERR_BAD_ARG;
+    return optim_step<OPT_SGD>(desc, count, total_tiles, grad_flat, grad_numel, hyper, max_norm, zero_grad, norm_out, workspace,
+                               workspace_bytes, ema_flat, stream);
+}
+
+extern "C" int vited_ema_swap(const int64_t* desc, int count, int64_t total_tiles, float* ema_flat, const float* grad_flat,
+                              void* stream) {
+    if (!desc || !grad_flat || count <= 0 || total_tiles <= 0 || total_tiles > 0x7fffffff || !ema_buffer_ok(ema_flat, 0, 0))
+        return VITED_ERR_BAD_ARG;
+    hipLaunchKernelGGL(ema_swap_kernel, dim3((unsigned)total_tiles), dim3(256), 0, (hipStream_t)stream, desc, count, ema_flat, grad_flat);
+    return vited_check_launch();
 }

@@ -123,7 +123,8 @@ class _Snapshot:
         self.step, self.params = step, [p for p in step.model.parameters()]
         self.values = [p.detach().clone() for p in self.params]
         self.bufs = {n: b.clone() for n, b in opt._bufs.items()}
-        self.hyper = opt._hyper.clone()
+        self.hyper = opt._hyper.clone()                   # the EMA counter hyper[5] with it
+        self.ema = None if opt.ema is None else opt.ema.clone()
         self.seen = None if opt._hyper_seen is None else list(opt._hyper_seen)
         self.rates = [g['lr'] for g in opt.param_groups]
         self.state_keys = {id(p): set(opt.state[p]) if p in opt.state else None for g in opt.param_groups for p in g['params']}
@@ -140,6 +141,8 @@ class _Snapshot:
         for n, b in self.bufs.items():
             opt._bufs[n].copy_(b)
         opt._hyper.copy_(self.hyper)
+        if self.ema is not None:
+            opt.ema.copy_(self.ema)
         opt._hyper_seen = self.seen
         for g, lr in zip(opt.param_groups, self.rates):
             g['lr'] = lr
@@ -173,7 +176,7 @@ def find_lr(step, loader, num_iter=None, start_lr=1e-7, end_lr=1e-2, smooth_f=0.
     the same decisions and sets the same rates.
 
     ``restore=True`` puts back, in place and bit for bit, the parameters, the optimizer's state with its step and skip counters, the
-    rate words and ``param_groups``, the weight shadows, ``step.num_updates`` and the step's meters; captured graphs stay valid.  Random
+    parameter average (``ema_decay``) with its counter, the rate words and ``param_groups``, the weight shadows, ``step.num_updates`` and the step's meters; captured graphs stay valid.  Random
     draws the step made (mining keys, dropout) are not rewound.  ``restore=False`` leaves the swept state - the rate words at 0 after a
     halt - and after a halt on a non-finite loss (``LRF_NONFINITE``) the parameters are not meaningful: the update that followed the
     loss may have written non-finite values, which a rate of 0 does not undo.

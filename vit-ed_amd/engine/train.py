@@ -25,7 +25,8 @@ def param_groups_no_decay_1d(model):
     return [{'params': decay}, {'params': no_decay, 'weight_decay': 0.}]
 
 
-def build_optimizer(config, model, capturable: bool = False, fused_hip: bool | None = None, skip_nonfinite: bool = False):
+def build_optimizer(config, model, capturable: bool = False, fused_hip: bool | None = None, skip_nonfinite: bool = False,
+                    ema_decay: float | None = None, ema_warmup: bool = False):
     """misc/optimizer.py:10-46: AdamW / Nesterov SGD with the no-decay group for 1-D parameters and ``*.bias``.
 
     On a GPU model they are ``optim.FlatAdamW`` / ``optim.FlatSGD`` (the HIP multi-tensor kernels: clip + update + bf16
@@ -33,7 +34,8 @@ def build_optimizer(config, model, capturable: bool = False, fused_hip: bool | N
     ``torch.optim.AdamW(fused=True)`` / ``torch.optim.SGD`` instead, with ``capturable`` forwarded to AdamW (a torch optimizer
     captured into a hipGraph must be built with capturable=True, and TrainStep keeps its learning rate in a device tensor).
     ``skip_nonfinite=True`` (HIP optimizers only) leaves out an update whose gradient norm is inf or NaN, which is what
-    ``GradScaler.step`` does in the reference's loop (misc/utils.py:206-226)."""
+    ``GradScaler.step`` does in the reference's loop (misc/utils.py:206-226).  ``ema_decay`` / ``ema_warmup`` (HIP optimizers only)
+    keep timm's ``--model-ema`` average of the parameters inside the update launch (optim.py); None keeps none."""
     name = config.TRAIN.OPTIMIZER.NAME.lower()
     groups = param_groups_no_decay_1d(model)
     on_gpu = all(p.is_cuda for g in groups for p in g['params'])
@@ -43,20 +45,24 @@ def build_optimizer(config, model, capturable: bool = False, fused_hip: bool | N
     if skip_nonfinite and not hip:
         raise ValueError('skip_nonfinite=True needs the HIP optimizers (a GPU model and fused_hip in (None, True)): the torch '
                          'optimizers have no such check')
+    if ema_decay is not None and not hip:
+        raise ValueError('ema_decay needs the HIP optimizers (a GPU model and fused_hip in (None, True)): the average is kept by their '
+                         'update kernel')
+    ema = dict(ema_decay=ema_decay, ema_warmup=ema_warmup)
     if name == 'adamw':
         kw = dict(eps=config.TRAIN.OPTIMIZER.EPS, betas=tuple(config.TRAIN.OPTIMIZER.BETAS), lr=config.TRAIN.BASE_LR,
                   weight_decay=config.TRAIN.WEIGHT_DECAY)
         if hip:
             from ..optim import FlatAdamW     # here, not at the top: optim imports this package (FlatGradients)
             # the model's bf16 weight shadows are refreshed by the update kernel
-            return FlatAdamW(groups, model=model, skip_nonfinite=skip_nonfinite, **kw)
+            return FlatAdamW(groups, model=model, skip_nonfinite=skip_nonfinite, **ema, **kw)
         if on_gpu:
             return torch.optim.AdamW(groups, fused=True, capturable=capturable, **kw)
         return torch.optim.AdamW(groups, **kw)
     kw = dict(momentum=config.TRAIN.OPTIMIZER.MOMENTUM, nesterov=True, lr=config.TRAIN.BASE_LR, weight_decay=config.TRAIN.WEIGHT_DECAY)
     if hip:
         from ..optim import FlatSGD
-        return FlatSGD(groups, model=model, skip_nonfinite=skip_nonfinite, **kw)
+        return FlatSGD(groups, model=model, skip_nonfinite=skip_nonfinite, **ema, **kw)
     return torch.optim.SGD(groups, **kw)
 
 
@@ -192,6 +198,10 @@ class TrainStep:
       device counter that starts at ``start_update`` and writes it into the optimizer's device array, so no rate is uploaded per
       iteration; ``step_update(n)`` on the host then only keeps ``param_groups`` current for the log line and checkpoints.
       ``lr_scheduler.on_device = False``, any other scheduler object and the torch optimizers are stepped by the host.
+    * An optimizer built with ``ema_decay`` averages the parameters inside its update launch, eagerly and in replay alike: the flat
+      average is one more buffer the captured update graph bakes in (allocated once, when the optimizer is bound here), and a changed
+      ``optimizer.ema_decay`` reaches a replayed update through ``sync_hyperparameters``.  ``with optimizer.swap_ema():`` evaluates on
+      the averaged weights; ``step`` raises inside it.
     * ``meters=True`` keeps the loop's loss and gradient-norm meters (``TrainMeters``) on the device, eagerly and in replay,
       without a host read; what ``step`` returns does not change.
     * ``use_graph=True`` replays hipGraphs (forward + decoder backward | encoder backward | update) captured
@@ -367,6 +377,8 @@ class TrainStep:
     def step(self, x, y):
         """One call of the loop body.  Returns the (micro-batch) loss; ``last_norm`` holds the gradient norm of the
         last update."""
+        if self.hip_opt and self.optimizer.ema_swapped:
+            raise RuntimeError('TrainStep.step: not inside `with optimizer.swap_ema():` (the parameters hold the averaged weights)')
         last = (self._micro + 1) % self.accum == 0
         self._micro += 1
         if (self._g1 is not None and self.hip_opt and (self._micro - 1) % self.accum == 0

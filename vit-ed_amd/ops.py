@@ -1366,5 +1366,8 @@ from .ops_puzzlerot import patchify_turned, puzzle_distances2_from_logits  # noq
 # ---- mixed-bag and unknown-dimension puzzles: the wrapper of the point lookups of M of csrc/puzzle_compat.hip lives in ops_puzzlemixed.py
 from .ops_puzzlemixed import puzzle_mutual_gather  # noqa: E402,F401
 
+# ---- parameter EMA: the wrapper of vited_ema_swap (csrc/optimizer.hip) lives in ops_ema.py ---------------------------------------------
+from .ops_ema import ema_swap  # noqa: E402,F401
+
 # matrix-core fp32 attention: predicate, per-thread record and kernel selection (csrc/attention_f32_mfma.hip); ops_f32attn.py
 from .ops_f32attn import fp32_attention_kernels, fp32_attention_supported, last_fp32_attention_kernel  # noqa: E402,F401

@@ -10,16 +10,36 @@ drives them through ``step_flat``.  There is no CPU path: parameters must live o
 (misc/utils.py:206-226): parameters, optimizer state and shadows keep their bits, the gradients are zeroed, the step count
 stays and ``skipped_updates`` goes up.  The norm is that of the all-reduced flat buffer, so every data-parallel rank decides
 alike.
+
+``ema_decay=d`` keeps an exponential moving average of the parameters (timm's ``ModelEmaV2``, ``--model-ema``) inside the update
+launch (``vited_adamw_step_ema`` / ``vited_sgd_step_ema``): one more flat fp32 buffer, ``optimizer.ema``, laid out like the gradient
+buffer and equal to the parameters, bit for bit, until the first update.  ``ema_warmup=True`` uses ``min(d, (1 + n) / (10 + n))``
+with ``n`` the EMA updates done so far; a skipped update leaves the average and ``n`` alone.  ``with optimizer.swap_ema():``
+exchanges parameters and averages in place (``vited_ema_swap``, shadows included) for an evaluation on the averaged weights, and
+exchanges them back on exit.  ``ema_state_dict`` / ``load_ema_state_dict`` carry the average under the model's ``state_dict`` keys,
+``num_ema_updates`` is the one integer that goes with them; ``state_dict()`` stays torch's.
 """
 from __future__ import annotations
 
+import contextlib
+
 import torch
 
-from . import _lib
+from . import _lib, ops
 from .functions import shadows_of
 
 HYPER_HEADER, GROUP_WORDS, DESC_WORDS = 8, 8, 10
 HYPER_STEP, HYPER_SKIP_FLAG, HYPER_SKIPPED = 0, 1, 2
+HYPER_EMA_DECAY, HYPER_EMA_WARMUP, HYPER_EMA_COUNT = 3, 4, 5
+
+
+def _checked_ema_decay(value, who):
+    if value is None:
+        return None
+    value = float(value)
+    if not 0.0 <= value < 1.0:
+        raise ValueError(f'{who}: ema_decay must lie in [0, 1), got {value}')
+    return value
 
 
 class _FlatOptimizer(torch.optim.Optimizer):
@@ -31,11 +51,18 @@ class _FlatOptimizer(torch.optim.Optimizer):
     _state_names = ()
     _state_at_bind = True              # install state[p] views when bound (AdamW) or after the first update (SGD, as torch does)
 
-    def __init__(self, params, defaults, model=None, skip_nonfinite=False):
+    def __init__(self, params, defaults, model=None, skip_nonfinite=False, ema_decay=None, ema_warmup=False):
+        ema_decay = _checked_ema_decay(ema_decay, type(self).__name__)      # before anything is built
         super().__init__(params, defaults)
         self.flat = None
         self._model = model
         self.skip_nonfinite = bool(skip_nonfinite)
+        self._ema_decay, self.ema_warmup = ema_decay, bool(ema_warmup)
+        self._ema = None               # the flat fp32 average, laid out like the gradient buffer (allocated at the first bind)
+        self._ema_seen = None          # the EMA words sync_hyperparameters uploaded last
+        self._ema_loaded = None        # {id(p): tensor} of a load_ema_state_dict before bind_flat
+        self._ema_loaded_count = None  # ... and its num_ema_updates
+        self._swapped = False          # inside ``with swap_ema():``
         self._bufs = None              # {state name: flat fp32 buffer laid out like the gradient buffer}
         self._desc = self._desc_key = None
         self._hyper = self._hyper_seen = None
@@ -53,7 +80,11 @@ class _FlatOptimizer(torch.optim.Optimizer):
         dev = flat.flat.device
         if dev.type != 'cuda':
             raise RuntimeError(f'{name} runs on the MI355X HIP kernel only (no CPU path); use torch.optim for CPU parameters')
+        if self._swapped:
+            raise RuntimeError(f'{name}.bind_flat: not inside `with swap_ema():` (parameters and averages are exchanged)')
         rebind = self.flat is flat and self._bufs is not None and all(b.numel() == flat.flat.numel() for b in self._bufs.values())
+        # the averages of an earlier binding to another buffer go along, like the counters in the hyper header
+        ema_before = None if rebind or self._ema is None else {id(p): self.ema_of(p).clone() for p in self.flat.params}
         self.flat = flat
         if model is not None:
             self._model = model
@@ -71,8 +102,11 @@ class _FlatOptimizer(torch.optim.Optimizer):
             self._norm = torch.zeros(1, dtype=torch.float32, device=dev)
             self._ws = torch.empty(_lib.load().vited_adamw_workspace_bytes() // 4, dtype=torch.float32, device=dev)
             self._desc = self._desc_key = None
+            self._ema = None
         self._hyper[HYPER_SKIP_FLAG: HYPER_SKIP_FLAG + 1].fill_(1.0 if self.skip_nonfinite else 0.0)
-        self._hyper_seen = None
+        self._hyper_seen = self._ema_seen = None
+        if self._ema_decay is not None:
+            self._bind_ema(ema_before)
         for p, off in zip(flat.params, flat.offsets):
             st = self.state[p] if (self._state_at_bind or p in self.state) else {}
             for n in self._state_names:
@@ -91,6 +125,153 @@ class _FlatOptimizer(torch.optim.Optimizer):
     def _state_view(self, name, p):
         off = self.flat.offsets[next(i for i, q in enumerate(self.flat.params) if q is p)]
         return self._bufs[name][off: off + p.numel()].view_as(p)
+
+    # -- the moving average of the parameters ----------------------------------------------------
+    def _bind_ema(self, before=None):
+        """The flat average exists from here on: allocated ONCE per binding (a captured update graph bakes its address in) and equal
+        to the parameters bit for bit, unless an earlier binding (``before``) or a ``load_ema_state_dict`` says otherwise."""
+        fresh = self._ema is None
+        if fresh:
+            self._ema = torch.zeros_like(self.flat.flat)
+        with torch.no_grad():
+            for p in self.flat.params:
+                src = (self._ema_loaded or {}).get(id(p))
+                if src is None and fresh:
+                    src = p if before is None or id(p) not in before else before[id(p)]
+                if src is not None:
+                    self.ema_of(p).copy_(src)
+        if self._ema_loaded_count is not None:
+            self._hyper[HYPER_EMA_COUNT] = float(self._ema_loaded_count)
+        elif fresh and before is None:
+            self._hyper[HYPER_EMA_COUNT] = 0.0
+        self._ema_loaded = self._ema_loaded_count = None
+
+    @property
+    def ema_decay(self):
+        """The decay ``d`` of the average (None: no average is kept).  Assigning a number between two steps reaches the device through
+        ``sync_hyperparameters``, so a replayed update follows it without a recapture; assigning one to an optimizer that kept no
+        average starts one from the present parameters, and None drops it (either changes what a captured update graph bakes in:
+        ``shadow_signature`` tells ``engine.TrainStep`` to capture again)."""
+        return self._ema_decay
+
+    @ema_decay.setter
+    def ema_decay(self, value):
+        value = _checked_ema_decay(value, type(self).__name__)
+        if (value is None) != (self._ema_decay is None):
+            if self._swapped or torch.cuda.is_current_stream_capturing():
+                raise RuntimeError(f'{type(self).__name__}: the average cannot be switched on or off inside `with swap_ema():` or during '
+                                   f'graph capture')
+            self._ema_decay = value
+            if value is None:
+                self._ema = self._ema_seen = None
+            elif self.flat is not None:
+                self._bind_ema()
+            return
+        self._ema_decay = value
+
+    @property
+    def ema(self):
+        """The flat fp32 average (None before ``bind_flat`` or without ``ema_decay``); inside ``with swap_ema():`` it holds the raw
+        parameters."""
+        return self._ema
+
+    def ema_of(self, p):
+        """The average of parameter ``p``: a view of ``ema`` shaped like ``p``."""
+        if self._ema is None:
+            raise RuntimeError(f'{type(self).__name__}.ema_of: no average is kept (build the optimizer with ema_decay=... and bind it)')
+        off = self.flat.offsets[next(i for i, q in enumerate(self.flat.params) if q is p)]
+        return self._ema[off: off + p.numel()].view_as(p)
+
+    @property
+    def num_ema_updates(self) -> int:
+        """EMA updates done, the ``n`` of the warmup (one host read once bound); a skipped update does not count."""
+        if self._ema_loaded_count is not None:
+            return int(self._ema_loaded_count)
+        return int(self._hyper[HYPER_EMA_COUNT].item()) if self._hyper is not None and self._ema_decay is not None else 0
+
+    @property
+    def ema_swapped(self) -> bool:
+        """Inside ``with swap_ema():``."""
+        return self._swapped
+
+    def _exchange_ema(self):
+        desc = self._descriptors()
+        ops.ema_swap(desc, self._tiles, self._ema, self.flat.flat)
+        _FlatOptimizer._publish_update(self)         # p and the table's shadows were raw-written, exactly as by an update
+
+    @contextlib.contextmanager
+    def swap_ema(self):
+        """Inside the block the parameters and their bf16 shadows hold the averaged weights, at unchanged addresses - the model, its
+        pair caches and any captured forward graph evaluate on them as they are - and ``ema`` holds the raw parameters; on exit
+        every bit is back.  One launch each way."""
+        name = type(self).__name__
+        if self._ema_decay is None:
+            raise RuntimeError(f'{name}.swap_ema: no average is kept (build the optimizer with ema_decay=...)')
+        if self._swapped:
+            raise RuntimeError(f'{name}.swap_ema: already inside `with swap_ema():` (nested use would exchange the weights back)')
+        if self._ema is None:
+            raise RuntimeError(f'{name}.swap_ema: call bind_flat(FlatGradients) first (engine.TrainStep does)')
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f'{name}.swap_ema: not during graph capture (the exchange back on exit would be captured with it)')
+        self._exchange_ema()
+        self._swapped = True
+        try:
+            yield self
+        finally:
+            self._swapped = False
+            self._exchange_ema()
+
+    def _trainable_ids(self):
+        return {id(p) for g in self.param_groups for p in g['params'] if p.requires_grad}
+
+    @torch.no_grad()
+    def ema_state_dict(self, model):
+        """{name: tensor} under ``model.state_dict()``'s keys: clones of the averages; a parameter that is not trainable and a buffer
+        contribute their own value.  ``num_ema_updates`` is the one integer to save beside it."""
+        mine, named = self._trainable_ids(), dict(model.named_parameters())
+        out = {}
+        for key, value in model.state_dict().items():
+            p = named.get(key)
+            if p is None or id(p) not in mine:
+                out[key] = value.detach().clone()
+            elif self._swapped:
+                out[key] = p.detach().clone()            # inside the block the parameter holds the average
+            elif self._ema is not None:
+                out[key] = self.ema_of(p).clone()
+            else:                                        # not bound yet: what was loaded, else e == p
+                out[key] = (self._ema_loaded or {}).get(id(p), p).detach().clone()
+        return out
+
+    @torch.no_grad()
+    def load_ema_state_dict(self, state_dict, model, num_ema_updates=None):
+        """Load what ``ema_state_dict`` gave, before or after ``bind_flat``: once bound the values are copied INTO the existing flat
+        buffer, so a captured update graph stays valid.  ``num_ema_updates`` (None: keep the counter) sets the ``n`` of the warmup."""
+        name = type(self).__name__
+        if self._ema_decay is None:
+            raise RuntimeError(f'{name}.load_ema_state_dict: no average is kept (build the optimizer with ema_decay=...)')
+        if self._swapped:
+            raise RuntimeError(f'{name}.load_ema_state_dict: not inside `with swap_ema():`')
+        mine = self._trainable_ids()
+        loaded = {}
+        for key, p in model.named_parameters():
+            if id(p) not in mine:
+                continue
+            if key not in state_dict:
+                raise KeyError(f'{name}.load_ema_state_dict: {key} is missing')
+            value = state_dict[key]
+            if value.shape != p.shape:
+                raise ValueError(f'{name}.load_ema_state_dict: {key} has shape {tuple(value.shape)}, the parameter {tuple(p.shape)}')
+            loaded[id(p)] = value.detach().to(device=p.device, dtype=torch.float32)
+        if num_ema_updates is not None and int(num_ema_updates) < 0:
+            raise ValueError(f'{name}.load_ema_state_dict: num_ema_updates must not be negative, got {num_ema_updates}')
+        if self._ema is None:
+            self._ema_loaded = {k: v.clone() for k, v in loaded.items()}
+            self._ema_loaded_count = None if num_ema_updates is None else int(num_ema_updates)
+            return
+        for p in self.flat.params:
+            self.ema_of(p).copy_(loaded[id(p)])
+        if num_ema_updates is not None:
+            self._hyper[HYPER_EMA_COUNT] = float(int(num_ema_updates))
 
     @property
     def num_updates(self) -> int:
@@ -118,6 +299,12 @@ class _FlatOptimizer(torch.optim.Optimizer):
             self._hyper[HYPER_HEADER:].copy_(torch.tensor(vals, dtype=torch.float32))
             self._hyper_seen = vals
             self.hyper_uploads += 1
+        if self._ema_decay is not None:
+            words = [self._ema_decay, 1.0 if self.ema_warmup else 0.0]       # hyper[3..4]; hyper[5], the counter, is the kernel's
+            if words != self._ema_seen:
+                self._hyper[HYPER_EMA_DECAY: HYPER_EMA_WARMUP + 1].copy_(torch.tensor(words, dtype=torch.float32))
+                self._ema_seen = words
+                self.hyper_uploads += 1
 
     @staticmethod
     def hyper_lr_words():
@@ -164,20 +351,27 @@ class _FlatOptimizer(torch.optim.Optimizer):
         """clip(max_norm) + update + shadow refresh (+ zero the gradients).  Returns the pre-clip gradient norm (device scalar)."""
         if self.flat is None:
             raise RuntimeError(f'{type(self).__name__}.step_flat: call bind_flat(FlatGradients) first (engine.TrainStep does)')
+        if self._swapped:
+            raise RuntimeError(f'{type(self).__name__}.step_flat: not inside `with swap_ema():` (the update would act on the averaged '
+                               f'weights and average the raw ones)')
         capturing = torch.cuda.is_current_stream_capturing()
         if not capturing:
             self.sync_hyperparameters()
         desc = self._descriptors()
-        _lib.call(self._entry, desc.data_ptr(), desc.shape[0], self._tiles, self.flat.flat.data_ptr(), self.flat.flat.numel(),
+        # with an average the *_ema entry, which takes the flat average behind the workspace; without, the entry as it always was
+        entry, ema = (self._entry, ()) if self._ema_decay is None else (self._entry + '_ema', (self._ema.data_ptr(), self._ema.numel()))
+        _lib.call(entry, desc.data_ptr(), desc.shape[0], self._tiles, self.flat.flat.data_ptr(), self.flat.flat.numel(),
                   self._hyper.data_ptr(), float(max_norm) if max_norm else 0.0, int(zero_grad), self._norm.data_ptr(), self._ws.data_ptr(),
-                  self._ws.numel() * 4, torch.cuda.current_stream().cuda_stream)
+                  self._ws.numel() * 4, *ema, torch.cuda.current_stream().cuda_stream)
         if not capturing:
             self._publish_update()
         return self._norm[0]
 
     def shadow_signature(self):
-        """What a captured update graph baked in besides this optimizer's own buffers: the set of weight-shadow buffers."""
-        return tuple(sorted(item for cache in shadows_of(self._model) for item in cache.signature()))
+        """What a captured update graph baked in besides this optimizer's state buffers: the set of weight-shadow buffers and, where
+        an average is kept, its buffer (which also tells the entry that was captured)."""
+        shadows = tuple(sorted(item for cache in shadows_of(self._model) for item in cache.signature()))
+        return shadows if self._ema is None else shadows + (('ema', self._ema.data_ptr()),)
 
     def _publish_update(self):
         """The kernel raw-wrote the fp32 parameters (and the shadows listed in its descriptor table).  Bump every
@@ -221,11 +415,13 @@ class FlatAdamW(_FlatOptimizer):
     _entry = 'vited_adamw_step'
     _state_names = ('exp_avg', 'exp_avg_sq')
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, model=None, skip_nonfinite=False):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, model=None, skip_nonfinite=False,
+                 ema_decay=None, ema_warmup=False):
         """``model`` (the HIP ViT-ED whose parameters these are) lets the kernel refresh the model's bf16 weight shadows in the
         same pass; without it the parameters' version counters are bumped after every update instead, so the model recasts its
         shadows on the next forward (correct, one extra launch per weight)."""
-        super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay), model, skip_nonfinite)
+        super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay), model, skip_nonfinite, ema_decay,
+                         ema_warmup)
         self._loaded_step = None       # step count of a state_dict loaded before bind_flat (the reference's resume order)
 
     exp_avg = property(lambda self: self._bufs['exp_avg'] if self._bufs else None)
@@ -274,7 +470,8 @@ class FlatSGD(_FlatOptimizer):
     _state_names = ('momentum_buffer',)
     _state_at_bind = False
 
-    def __init__(self, params, lr=1e-3, momentum=0., dampening=0, weight_decay=0., nesterov=False, model=None, skip_nonfinite=False):
+    def __init__(self, params, lr=1e-3, momentum=0., dampening=0, weight_decay=0., nesterov=False, model=None, skip_nonfinite=False,
+                 ema_decay=None, ema_warmup=False):
         if lr < 0.0:
             raise ValueError(f'Invalid learning rate: {lr}')
         if momentum < 0.0:
@@ -286,7 +483,7 @@ class FlatSGD(_FlatOptimizer):
         # torch.optim.SGD's group keys, so that a state_dict moves between the two in both directions
         defaults = dict(lr=lr, momentum=momentum, dampening=0, weight_decay=weight_decay, nesterov=bool(nesterov), maximize=False,
                         foreach=None, differentiable=False, fused=None)
-        super().__init__(params, defaults, model, skip_nonfinite)
+        super().__init__(params, defaults, model, skip_nonfinite, ema_decay, ema_warmup)
         for g in self.param_groups:
             self._check_group(g)
         self._state_installed = False
