@@ -618,6 +618,31 @@ int vited_sgd_step_ema(const int64_t* desc, int count, int64_t total_tiles, cons
  * VITED_ERR_BAD_ARG before the launch: a null desc, ema_flat or grad_flat, ema_flat not 16-byte aligned, count or total_tiles < 1. */
 int vited_ema_swap(const int64_t* desc, int count, int64_t total_tiles, float* ema_flat, const float* grad_flat, void* stream);
 
+/* LAMB (You et al. 2020, Algorithm 2, with timm's Lamb conventions: bias correction, gradient averaging, weight decay inside the update,
+ * the trust ratio only where it applies) in place of AdamW: same arguments, same descriptor row (exp_avg, exp_avg_sq), same hyper header
+ * (skipping and the EMA words included).  The rule is csrc/optim_update.h's (lamb_u, lamb_ratio); with c the clip coefficient and t =
+ * hyper[0] after the decision, per element and per tensor (= descriptor row)
+ *     g' = g c;  m = m + (g' - m)(1 - beta1);  v = beta2 v + (1 - beta2) g' g'
+ *     u  = (m / (1 - beta1^t)) / (sqrt(v) / sqrt(1 - beta2^t) + eps) + weight_decay p
+ *     r  = (weight_decay == 0 and always_adapt == 0) ? 1 : ((|p| > 0 and |u| > 0) ? |p| / |u| : 1);  trust_clip != 0: r = min(r, 1)
+ *     p  = p - lr r u
+ * |.| is the 2-norm over the tensor, from fp32 sums of squares taken in a fixed order (no atomics: bits do not depend on scheduling).
+ *   group words {lr, beta1, beta2, eps, weight_decay, always_adapt (0 / 1), trust_clip (0 / 1), 0}
+ *   workspace   >= vited_lamb_workspace_bytes(total_tiles, count) (0 for arguments the step entries refuse): the words of
+ *               vited_adamw_workspace_bytes(), then ratio[count] - r of every row as of the latest applied update, word 1028 + row -
+ *               then {sum p^2, sum u^2} per tile
+ * Five launches: sum of squares, decision, moments and per-tile sums, one wave per row for r, the apply pass (p, both shadows, the
+ * average, g zeroed).  g is read by the third launch only and written by the last only, so zero_grad == 0 leaves its bits alone.  A
+ * skipped update leaves p, m, v, the shadows, the average and ratio alone and still zeroes g when zero_grad is set.  The clip is the
+ * step's own max_norm; there is no second max_grad_norm. */
+int64_t vited_lamb_workspace_bytes(int64_t total_tiles, int count);
+int vited_lamb_step(const int64_t* desc, int count, int64_t total_tiles, const float* grad_flat, int64_t grad_numel,
+                    float* hyper, float max_norm, int zero_grad, float* norm_out, float* workspace,
+                    int64_t workspace_bytes, void* stream);
+int vited_lamb_step_ema(const int64_t* desc, int count, int64_t total_tiles, const float* grad_flat, int64_t grad_numel,
+                        float* hyper, float max_norm, int zero_grad, float* norm_out, float* workspace,
+                        int64_t workspace_bytes, float* ema_flat, int64_t ema_numel, void* stream);
+
 /* One step of a per-iteration learning-rate schedule on the device (misc/lr_scheduler.py through misc/engine.py:228; the rules are
  * csrc/lr_schedule.h, in fp64): one launch of one workgroup, queued behind the update it follows.
  *   t = *counter;  for g < groups: dst[first + stride * g] = (float)(lr_schedule_value(table, base[g], t) * scale[g]);  *counter = t + 1

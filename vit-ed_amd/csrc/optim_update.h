@@ -1,7 +1,7 @@
-// The per-element update bodies of the fused optimizer kernels (optimizer.hip): torch.optim.AdamW's and torch.optim.SGD's rules
-// on four consecutive elements of one parameter row, and the decision whether an update is applied at all.  Plain C++ (one call =
-// one 4-element piece, the unit a thread of the update kernel handles), so that the same text runs inside the HIP kernels and in a
-// host program under the sanitizers (tools/optim_host_check.cpp, tools/ema_host_check.cpp).  The exponential moving average of the
+// The per-element update bodies of the fused optimizer kernels (optimizer.hip): torch.optim.AdamW's and torch.optim.SGD's rules and
+// LAMB's on four consecutive elements of one parameter row, and the decision whether an update is applied at all.  Plain C++ (one call
+// = one 4-element piece, the unit a thread of the update kernel handles), so that the same text runs inside the HIP kernels and in a
+// host program under the sanitizers (tools/optim_host_check.cpp, tools/ema_host_check.cpp, tools/lamb_host_check.cpp).  The exponential moving average of the
 // parameters (the *_ema entries, vited_ema_swap) is stated here as well: ema_decay_at / ema_blend are THE rule.
 #pragma once
 #include <stdint.h>
@@ -153,6 +153,108 @@ OPTIM_FN void sgd_piece(float* p, float* g, float* buf, int64_t o, int n, bool w
 #pragma unroll
         for (int e = 0; e < 4; ++e)
             if (e < n) { p[o + e] = pn[e]; if (mom) buf[o + e] = bv[e]; if (zero_grad) g[o + e] = 0.f; }
+    }
+}
+
+// ---- LAMB (You et al. 2020, Algorithm 2, with timm's Lamb conventions) ----------------------------------------------------------------
+// Group words {lr, b1, b2, eps, wd, always_adapt, trust_clip, -}; c the clip coefficient, t the count of applied updates:
+//     g' = g c;  m = m + (g' - m) (1 - b1);  v = b2 v + (1 - b2) g' g'                       (the moments as adamw_piece forms them)
+//     u  = (m / (1 - b1^t)) / (sqrt(v) / sqrt(1 - b2^t) + eps) + wd p                        (lamb_u: THE statement of u)
+//     r  = (wd == 0 and not always_adapt) ? 1 : ((|p| > 0 and |u| > 0) ? |p| / |u| : 1),  with trust_clip min(r, 1)      (lamb_ratio)
+//     p  = p - lr r u
+// |.| is the 2-norm over the whole tensor.  Three passes (optimizer.hip): lamb_moments_piece writes m, v and returns the piece's sums
+// of p^2 and u^2; lamb_ratio turns a tensor's sums into r; lamb_apply_piece forms u again from the m, v it reads and the old p -
+// through lamb_u, whose two multiply-adds are fmaf by name, so that both passes get the same bits whatever the compiler may contract.
+struct LambCoef { float lr, b1, b2, eps, wd, bc1, inv_sqrt_bc2; int adapt, trust_clip; };
+
+OPTIM_FN LambCoef lamb_coef(const float* hg, float step) {
+    LambCoef k;
+    k.lr = hg[0]; k.b1 = hg[1]; k.b2 = hg[2]; k.eps = hg[3]; k.wd = hg[4];
+    k.adapt = hg[4] != 0.f || hg[5] != 0.f; k.trust_clip = hg[6] != 0.f;
+    // the bias corrections in fp64, once per workgroup: in fp32, 1 - b2^t cancels (b2 = 0.999, t = 2: 2^-24 of 0.998 is 1.5e-5 of
+    // 0.002), which every element of u and with them the trust ratio would inherit as one common error
+    k.bc1 = (float)(1.0 - pow((double)k.b1, (double)step));
+    k.inv_sqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow((double)k.b2, (double)step)));
+    return k;
+}
+
+OPTIM_FN float lamb_u(float m, float v, float p, const LambCoef& k) {
+    const float denom = fmaf(sqrtf(v), k.inv_sqrt_bc2, k.eps);
+    return fmaf(k.wd, p, (m / k.bc1) / denom);
+}
+
+// sum_p, sum_u: the tensor's sums of p^2 and u^2.
+OPTIM_FN float lamb_ratio(float sum_p, float sum_u, const LambCoef& k) {
+    if (!k.adapt) return 1.0f;
+    const float pn = sqrtf(sum_p), un = sqrtf(sum_u);
+    float r = (pn > 0.f && un > 0.f) ? pn / un : 1.0f;
+    if (k.trust_clip) r = r < 1.0f ? r : 1.0f;
+    return r;
+}
+
+// Pass 1 on elements [o, o + n) (n, wide as adamw_piece): new m and v are written, p and g only read; *sp and *su are advanced by the
+// piece's p^2 and u^2, element after element.
+OPTIM_FN void lamb_moments_piece(const float* p, const float* g, float* m, float* v, int64_t o, int n, bool wide, const LambCoef& k,
+                                 float clip, float* sp, float* su) {
+    float gv[4], pv[4], mv[4], vv[4];
+    if (wide) {
+        const OptimVec4 qg = *(const OptimVec4*)(g + o), qp = *(const OptimVec4*)(p + o), qm = *(const OptimVec4*)(m + o),
+                        qv = *(const OptimVec4*)(v + o);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { gv[e] = qg.v[e]; pv[e] = qp.v[e]; mv[e] = qm.v[e]; vv[e] = qv.v[e]; }
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const bool in = e < n;
+            gv[e] = in ? g[o + e] : 0.f; pv[e] = in ? p[o + e] : 0.f; mv[e] = in ? m[o + e] : 0.f; vv[e] = in ? v[o + e] : 0.f;
+        }
+    }
+    float s_p = *sp, s_u = *su;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const float ge = gv[e] * clip;
+        mv[e] = mv[e] + (ge - mv[e]) * (1.0f - k.b1);
+        vv[e] = vv[e] * k.b2 + (1.0f - k.b2) * ge * ge;
+        const float u = e < n ? lamb_u(mv[e], vv[e], pv[e], k) : 0.f;
+        s_p += pv[e] * pv[e];
+        s_u += u * u;
+    }
+    *sp = s_p; *su = s_u;
+    if (wide) {
+        *(OptimVec4*)(m + o) = OptimVec4{{mv[0], mv[1], mv[2], mv[3]}};
+        *(OptimVec4*)(v + o) = OptimVec4{{vv[0], vv[1], vv[2], vv[3]}};
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            if (e < n) { m[o + e] = mv[e]; v[o + e] = vv[e]; }
+    }
+}
+
+// Pass 3: p = p - step_size u with step_size = lr r, u from the moments pass 1 wrote and the p it read; m and v are only read, g is
+// only zeroed.  pn as adamw_piece.
+OPTIM_FN void lamb_apply_piece(float* p, float* g, const float* m, const float* v, int64_t o, int n, bool wide, const LambCoef& k,
+                               float step_size, int zero_grad, float* pn) {
+    float pv[4], mv[4], vv[4];
+    if (wide) {
+        const OptimVec4 qp = *(const OptimVec4*)(p + o), qm = *(const OptimVec4*)(m + o), qv = *(const OptimVec4*)(v + o);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { pv[e] = qp.v[e]; mv[e] = qm.v[e]; vv[e] = qv.v[e]; }
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const bool in = e < n;
+            pv[e] = in ? p[o + e] : 0.f; mv[e] = in ? m[o + e] : 0.f; vv[e] = in ? v[o + e] : 0.f;
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) pn[e] = pv[e] - step_size * lamb_u(mv[e], vv[e], pv[e], k);
+    if (wide) {
+        *(OptimVec4*)(p + o) = OptimVec4{{pn[0], pn[1], pn[2], pn[3]}};
+        if (zero_grad) *(OptimVec4*)(g + o) = OptimVec4{{0.f, 0.f, 0.f, 0.f}};
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            if (e < n) { p[o + e] = pn[e]; if (zero_grad) g[o + e] = 0.f; }
     }
 }
 

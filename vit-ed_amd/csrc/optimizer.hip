@@ -31,6 +31,9 @@
 // fresh p it holds in registers); launch 2 advances the EMA counter hyper[5] beside hyper[0].  vited_ema_swap: the OPT_SWAP instance
 // of that body, p <-> e and both shadows rewritten from the value now in p.  The entries without _ema launch optim_update_kernel,
 // which instantiates the body without any of it.
+//
+// vited_lamb_step / vited_lamb_step_ema: LAMB, whose trust ratio needs the norms of a whole tensor before any of its elements may
+// move - launches 1 and 2, then three more (at the end of this file), the last one the OPT_LAMB instance of the same tile body.
 #include "common.h"
 #include "optim_update.h"
 
@@ -39,7 +42,7 @@
 #define AD_GROUP_WORDS 8   // AdamW {lr, beta1, beta2, eps, weight_decay, -, -, -}; SGD {lr, momentum, nesterov, -, weight_decay, -, -, -}
 #define AD_PARTIALS 1024
 #define AD_RESULT_WORDS 4  // behind the partials: {norm, clip, applied, step count}
-enum { OPT_ADAMW = 0, OPT_SGD = 1, OPT_SWAP = 2 };
+enum { OPT_ADAMW = 0, OPT_SGD = 1, OPT_SWAP = 2, OPT_LAMB = 3 };
 
 __device__ __forceinline__ float block_sum_256(float v, float* red) {
     v = wave_sum(v);
@@ -93,11 +96,11 @@ optim_decide_kernel(float* __restrict__ ws, float* __restrict__ hyper, float max
 
 // One 64 x 64 tile of one parameter.  OPT_ADAMW / OPT_SGD: the update; EMA adds e' = ema_blend(d_t, e, p') on the row's slice of
 // ema_flat (at the offset of its g in grad_flat).  OPT_SWAP: p <-> e and the shadows rewritten from the value now in p (vited_ema_swap;
-// res, hyper and zero_grad unused).
+// res, hyper and zero_grad unused).  OPT_LAMB: LAMB's third launch (below), p -= lr r u with r = ratio[row], m and v only read.
 template <int OPT, bool EMA>
 __device__ __forceinline__ void
 optim_update_tile(const int64_t* __restrict__ desc, int count, const float* __restrict__ res, const float* __restrict__ hyper,
-                  int zero_grad, float* __restrict__ ema_flat, const float* grad_flat) {
+                  int zero_grad, float* __restrict__ ema_flat, const float* grad_flat, const float* __restrict__ ratio = nullptr) {
     __shared__ bf16 tile[64][66];
     float clip = 1.0f, step = 0.f;
     bool applied = true;
@@ -123,10 +126,14 @@ optim_update_tile(const int64_t* __restrict__ desc, int count, const float* __re
     const int64_t rows = d[6], cols = d[7];
     AdamWCoef ka = {};
     SgdCoef ks = {};
+    LambCoef kl = {};
+    float lamb_step = 0.f;                      // LAMB: lr * r of this row
     if constexpr (OPT != OPT_SWAP) {
         const float* hg = hyper + AD_HYPER_HEADER + d[9] * AD_GROUP_WORDS;
         if constexpr (OPT == OPT_ADAMW) ka = adamw_coef(hg, step);
-        else ks = sgd_coef(hg);
+        else if constexpr (OPT == OPT_LAMB) {
+            if (applied) { kl = lamb_coef(hg, step); lamb_step = kl.lr * ratio[lo]; }
+        } else ks = sgd_coef(hg);
     }
     float* e = nullptr;                         // the row's slice of the average
     float dt = 0.f;
@@ -137,7 +144,7 @@ optim_update_tile(const int64_t* __restrict__ desc, int count, const float* __re
     const int64_t r0 = (t / tiles_c) << 6, c0 = (t % tiles_c) << 6;
     const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;   // 16 x 16: 4 columns x 4 rows per thread
     uintptr_t ptrs = (uintptr_t)p | (uintptr_t)g;
-    if constexpr (OPT == OPT_ADAMW) ptrs |= (uintptr_t)m | (uintptr_t)v;
+    if constexpr (OPT == OPT_ADAMW || OPT == OPT_LAMB) ptrs |= (uintptr_t)m | (uintptr_t)v;
     else if (OPT == OPT_SGD && ks.momentum != 0.f) ptrs |= (uintptr_t)m;
     if constexpr (EMA) ptrs |= (uintptr_t)e;
     const bool vec = (cols & 3) == 0 && (ptrs & 15) == 0;
@@ -161,6 +168,7 @@ optim_update_tile(const int64_t* __restrict__ desc, int count, const float* __re
             const int n = cols - c < 4 ? (int)(cols - c) : 4;
             if constexpr (OPT == OPT_ADAMW) adamw_piece(p, g, m, v, r * cols + c, n, vec && n == 4, ka, clip, zero_grad, pn);
             else if constexpr (OPT == OPT_SGD) sgd_piece(p, g, m, r * cols + c, n, vec && n == 4, ks, clip, zero_grad, pn);
+            else if constexpr (OPT == OPT_LAMB) lamb_apply_piece(p, g, m, v, r * cols + c, n, vec && n == 4, kl, lamb_step, zero_grad, pn);
             else swap_piece(p, e, r * cols + c, n, vec && n == 4, pn);
             if constexpr (EMA && OPT != OPT_SWAP) ema_piece(e, r * cols + c, n, vec && n == 4, dt, pn);
         }
@@ -269,6 +277,127 @@ extern "C" int vited_sgd_step_ema(const int64_t* desc, int count, int64_t total_
     if (!ema_buffer_ok(ema_flat, ema_numel, grad_numel)) return VITED_ERR_BAD_ARG;
     return optim_step<OPT_SGD>(desc, count, total_tiles, grad_flat, grad_numel, hyper, max_norm, zero_grad, norm_out, workspace,
                                workspace_bytes, ema_flat, stream);
+}
+
+// ---- LAMB (vited_lamb_step / vited_lamb_step_ema; the rule is optim_update.h's) ----------------------------------------------------------
+// No element of a tensor may move before the 2-norms of the whole tensor's p and u are known, so the update takes three launches behind
+// the sum of squares and the decision:
+//   launch 3  lamb_moments_kernel: one workgroup per 64 x 64 tile (the table and tiling of optim_update_tile); reads g, p, m, v, writes
+//                                  m, v, forms u in registers and leaves the tile's {sum p^2, sum u^2} in tile_sums[2 * tile ..].  Order:
+//                                  a thread adds its 16 elements one after the other, then block_sum_256 (wave butterfly, 4 wave sums).
+//   launch 4  lamb_ratio_kernel  : one wave per tensor; lane l adds the tensor's tiles l, l + 64, .. in ascending order, wave_sum, lane
+//                                  0 writes r to ratio[row].  No atomics: the sums do not depend on scheduling.
+//   launch 5  optim_update_kernel<OPT_LAMB> (or its EMA instance): the tile body above; u again through lamb_u from the m, v just
+//                                  written and the old p, p -= lr r u, both shadows, the average, g zeroed.  g is never read here and
+//                                  never used as scratch, so zero_grad == 0 leaves its bits alone.
+// A skipped update returns at once from launches 3 and 4 (m, v, tile_sums and ratio keep their bits) and zeroes g in launch 5.
+// HBM traffic per element: 28 B read (g, p, m, v; then p, m, v) + 16 B written (m, v; then p, g) + 4 B of shadows.
+// Workspace (floats): [0, 1024) partials, 4 result words, ratio[count], tile_sums[2 * total_tiles].
+#define LAMB_RATIO_AT (AD_PARTIALS + AD_RESULT_WORDS)
+
+__global__ void __launch_bounds__(256)
+lamb_moments_kernel(const int64_t* __restrict__ desc, int count, const float* __restrict__ res, const float* __restrict__ hyper,
+                    float* __restrict__ tile_sums) {
+    __shared__ float red[4];
+    if (res[2] == 0.f) return;                  // skipped: the same word in every workgroup
+    const float clip = res[1], step = res[3];
+    const int64_t blk = blockIdx.x;
+    int lo = 0, hi = count - 1;     // last descriptor whose first_tile <= blk
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (desc[(int64_t)mid * AD_DESC_WORDS + 8] <= blk) lo = mid; else hi = mid - 1;
+    }
+    const int64_t* d = desc + (int64_t)lo * AD_DESC_WORDS;
+    const float* p = (const float*)d[0];
+    const float* g = (const float*)d[1];
+    float* m = (float*)d[2];
+    float* v = (float*)d[3];
+    const int64_t rows = d[6], cols = d[7];
+    const LambCoef k = lamb_coef(hyper + AD_HYPER_HEADER + d[9] * AD_GROUP_WORDS, step);
+    const int64_t t = blk - d[8], tiles_c = (cols + 63) >> 6;
+    const int64_t r0 = (t / tiles_c) << 6, c0 = (t % tiles_c) << 6;
+    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;   // 16 x 16: 4 columns x 4 rows per thread
+    const bool vec = (cols & 3) == 0 && (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0;
+    float sp = 0.f, su = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int64_t r = r0 + ty + 16 * j, c = c0 + tx * 4;
+        if (r < rows && c < cols) {
+            const int n = cols - c < 4 ? (int)(cols - c) : 4;
+            lamb_moments_piece(p, g, m, v, r * cols + c, n, vec && n == 4, k, clip, &sp, &su);
+        }
+    }
+    sp = block_sum_256(sp, red);
+    su = block_sum_256(su, red);
+    if (threadIdx.x == 0) { tile_sums[2 * blk] = sp; tile_sums[2 * blk + 1] = su; }
+}
+
+__global__ void __launch_bounds__(64)
+lamb_ratio_kernel(const int64_t* __restrict__ desc, const float* __restrict__ res, const float* __restrict__ hyper,
+                  const float* __restrict__ tile_sums, float* __restrict__ ratio) {
+    if (res[2] == 0.f) return;
+    const int64_t* d = desc + (int64_t)blockIdx.x * AD_DESC_WORDS;
+    const int64_t tiles = ((d[6] + 63) >> 6) * ((d[7] + 63) >> 6);
+    const float* sums = tile_sums + 2 * d[8];
+    float sp = 0.f, su = 0.f;
+    for (int64_t t = threadIdx.x; t < tiles; t += 64) { sp += sums[2 * t]; su += sums[2 * t + 1]; }
+    sp = wave_sum(sp);
+    su = wave_sum(su);
+    if (threadIdx.x == 0) ratio[blockIdx.x] = lamb_ratio(sp, su, lamb_coef(hyper + AD_HYPER_HEADER + d[9] * AD_GROUP_WORDS, res[3]));
+}
+
+__global__ void __launch_bounds__(256)
+lamb_apply_kernel(const int64_t* __restrict__ desc, int count, const float* __restrict__ res, const float* __restrict__ hyper,
+                  int zero_grad, const float* __restrict__ ratio) {
+    optim_update_tile<OPT_LAMB, false>(desc, count, res, hyper, zero_grad, nullptr, nullptr, ratio);
+}
+
+__global__ void __launch_bounds__(256)
+lamb_apply_ema_kernel(const int64_t* __restrict__ desc, int count, const float* __restrict__ res, const float* __restrict__ hyper,
+                      int zero_grad, float* __restrict__ ema_flat, const float* grad_flat, const float* __restrict__ ratio) {
+    optim_update_tile<OPT_LAMB, true>(desc, count, res, hyper, zero_grad, ema_flat, grad_flat, ratio);
+}
+
+extern "C" int64_t vited_lamb_workspace_bytes(int64_t total_tiles, int count) {
+    if (total_tiles <= 0 || total_tiles > 0x7fffffff || count <= 0) return 0;
+    return (int64_t)(LAMB_RATIO_AT + (int64_t)count + 2 * total_tiles) * sizeof(float);
+}
+
+static int lamb_step(const int64_t* desc, int count, int64_t total_tiles, const float* grad_flat, int64_t grad_numel, float* hyper,
+                     float max_norm, int zero_grad, float* norm_out, float* workspace, int64_t workspace_bytes, float* ema_flat,
+                     void* stream) {
+    if (!desc || !grad_flat || !hyper || !workspace || count <= 0 || grad_numel <= 0 || total_tiles <= 0 || total_tiles > 0x7fffffff)
+        return VITED_ERR_BAD_ARG;
+    if (workspace_bytes < vited_lamb_workspace_bytes(total_tiles, count)) return VITED_ERR_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    const float* res = workspace + AD_PARTIALS;
+    float* ratio = workspace + LAMB_RATIO_AT;
+    float* tile_sums = ratio + count;
+    hipLaunchKernelGGL(optim_sumsq_kernel, dim3(AD_PARTIALS), dim3(256), 0, s, grad_flat, grad_numel, workspace);
+    hipLaunchKernelGGL(optim_decide_kernel, dim3(1), dim3(256), 0, s, workspace, hyper, max_norm, norm_out, ema_flat ? 1 : 0);
+    hipLaunchKernelGGL(lamb_moments_kernel, dim3((unsigned)total_tiles), dim3(256), 0, s, desc, count, res, hyper, tile_sums);
+    hipLaunchKernelGGL(lamb_ratio_kernel, dim3((unsigned)count), dim3(64), 0, s, desc, res, hyper, tile_sums, ratio);
+    if (ema_flat)
+        hipLaunchKernelGGL(lamb_apply_ema_kernel, dim3((unsigned)total_tiles), dim3(256), 0, s, desc, count, res, hyper, zero_grad,
+                           ema_flat, grad_flat, ratio);
+    else
+        hipLaunchKernelGGL(lamb_apply_kernel, dim3((unsigned)total_tiles), dim3(256), 0, s, desc, count, res, hyper, zero_grad, ratio);
+    return vited_check_launch();
+}
+
+extern "C" int vited_lamb_step(const int64_t* desc, int count, int64_t total_tiles, const float* grad_flat, int64_t grad_numel,
+                               float* hyper, float max_norm, int zero_grad, float* norm_out, float* workspace,
+                               int64_t workspace_bytes, void* stream) {
+    return lamb_step(desc, count, total_tiles, grad_flat, grad_numel, hyper, max_norm, zero_grad, norm_out, workspace, workspace_bytes,
+                     nullptr, stream);
+}
+
+extern "C" int vited_lamb_step_ema(const int64_t* desc, int count, int64_t total_tiles, const float* grad_flat, int64_t grad_numel,
+                                   float* hyper, float max_norm, int zero_grad, float* norm_out, float* workspace,
+                                   int64_t workspace_bytes, float* ema_flat, int64_t ema_numel, void* stream) {
+    if (!ema_buffer_ok(ema_flat, ema_numel, grad_numel)) return VITED_ERR_BAD_ARG;
+    return lamb_step(desc, count, total_tiles, grad_flat, grad_numel, hyper, max_norm, zero_grad, norm_out, workspace, workspace_bytes,
+                     ema_flat, stream);
 }
 
 extern "C" int vited_ema_swap(const int64_t* desc, int count, int64_t total_tiles, float* ema_flat, const float* grad_flat,

@@ -27,7 +27,7 @@ class LRFinderResult(NamedTuple):
 
 
 class LRRangeTest:
-    """One range test on a bound ``optim.FlatAdamW`` / ``optim.FlatSGD``: iteration i of group g runs at
+    """One range test on a bound fused optimizer (``optim.FlatAdamW`` / ``FlatSGD`` / ``FlatLAMB``): iteration i of group g runs at
     ``start_g * (end_g / start_g) ** (i / num_iter)``.  A scalar ``start_lr`` / ``end_lr`` gives ``value * lr_scale`` of every group, as
     ``TrainStep.set_lr`` does; a sequence gives one value per group.
 
@@ -42,8 +42,8 @@ class LRRangeTest:
     def __init__(self, optimizer, num_iter, start_lr=1e-7, end_lr=1e-2, smooth_f=0.05, diverge_th=5.0):
         name = type(self).__name__
         if not (hasattr(optimizer, 'hyper_lr_words') and hasattr(optimizer, 'mark_lr_on_device')):
-            raise NotImplementedError(f'{name}: the rates are written on the device into the hyper-parameter array of optim.FlatAdamW / '
-                                      f'optim.FlatSGD; {type(optimizer).__name__} has none (engine.build_optimizer gives the HIP optimizers '
+            raise NotImplementedError(f'{name}: the rates are written on the device into the hyper-parameter array of a fused optimizer - '
+                                      f'optim.FlatLAMB / optim.FlatAdamW / optim.FlatSGD; {type(optimizer).__name__} has none (engine.build_optimizer gives the HIP optimizers '
                                       f'for a GPU model)')
         if getattr(optimizer, '_hyper', None) is None:
             raise RuntimeError(f'{name}: the optimizer has no device hyper-parameter array yet (bind_flat first; engine.TrainStep does)')
@@ -125,6 +125,7 @@ class _Snapshot:
         self.bufs = {n: b.clone() for n, b in opt._bufs.items()}
         self.hyper = opt._hyper.clone()                   # the EMA counter hyper[5] with it
         self.ema = None if opt.ema is None else opt.ema.clone()
+        self.workspace = opt._ws.clone()                  # scratch, but for FlatLAMB.trust_ratios, which reads its ratio table
         self.seen = None if opt._hyper_seen is None else list(opt._hyper_seen)
         self.rates = [g['lr'] for g in opt.param_groups]
         self.state_keys = {id(p): set(opt.state[p]) if p in opt.state else None for g in opt.param_groups for p in g['params']}
@@ -143,6 +144,7 @@ class _Snapshot:
         opt._hyper.copy_(self.hyper)
         if self.ema is not None:
             opt.ema.copy_(self.ema)
+        opt._ws.copy_(self.workspace)
         opt._hyper_seen = self.seen
         for g, lr in zip(opt.param_groups, self.rates):
             g['lr'] = lr
@@ -166,8 +168,8 @@ class _Snapshot:
 
 def find_lr(step, loader, num_iter=None, start_lr=1e-7, end_lr=1e-2, smooth_f=0.05, diverge_th=5.0, restore=True, poll_every=16,
             group=None) -> LRFinderResult:
-    """``lr_finder.py``'s range test over ``step`` - an ``engine.TrainStep`` or ``TwoStageTrainStep`` on ``optim.FlatAdamW`` /
-    ``optim.FlatSGD``, built without an ``lr_scheduler`` and with ``accumulation_steps == 1``, ``use_graph`` either way - and ``loader``,
+    """``lr_finder.py``'s range test over ``step`` - an ``engine.TrainStep`` or ``TwoStageTrainStep`` on one of ``optim.py``'s fused
+    optimizers, built without an ``lr_scheduler`` and with ``accumulation_steps == 1``, ``use_graph`` either way - and ``loader``,
     anything that yields ``(x, y)``; ``num_iter=None`` takes ``len(loader)``.  Per iteration: ``loss = step.step(x, y)``, then
     ``LRRangeTest.record(loss)``, and nothing else - the rate of the next iteration, the smoothed and the best loss, the stop and the
     history are the kernel's.  The halt state is read every ``poll_every`` iterations (0: only at the end) and the loop ends at the
@@ -189,8 +191,8 @@ def find_lr(step, loader, num_iter=None, start_lr=1e-7, end_lr=1e-2, smooth_f=0.
     if step.accum != 1:
         raise ValueError(f'find_lr: the step was built with accumulation_steps {step.accum}: the sweep sets a rate per call, build it with 1')
     if not step.hip_opt:
-        raise NotImplementedError(f'find_lr: the rates are written on the device into the hyper-parameter array of optim.FlatAdamW / '
-                                  f'optim.FlatSGD; {type(step.optimizer).__name__} has none')
+        raise NotImplementedError(f'find_lr: the rates are written on the device into the hyper-parameter array of a fused optimizer - '
+                                  f'optim.FlatLAMB / optim.FlatAdamW / optim.FlatSGD; {type(step.optimizer).__name__} has none')
     if num_iter is None:
         num_iter = len(loader)
     poll_every = int(poll_every)

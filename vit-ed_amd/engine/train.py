@@ -35,13 +35,19 @@ def build_optimizer(config, model, capturable: bool = False, fused_hip: bool | N
     captured into a hipGraph must be built with capturable=True, and TrainStep keeps its learning rate in a device tensor).
     ``skip_nonfinite=True`` (HIP optimizers only) leaves out an update whose gradient norm is inf or NaN, which is what
     ``GradScaler.step`` does in the reference's loop (misc/utils.py:206-226).  ``ema_decay`` / ``ema_warmup`` (HIP optimizers only)
-    keep timm's ``--model-ema`` average of the parameters inside the update launch (optim.py); None keeps none."""
+    keep timm's ``--model-ema`` average of the parameters inside the update launch (optim.py); None keeps none.
+
+    ``'lamb'`` (or ``'fused_lamb'``, the spelling of the reference drivers' ``--optim`` help) is ``optim.FlatLAMB`` with EPS, BETAS,
+    BASE_LR, WEIGHT_DECAY and the no-decay group as for AdamW.  It exists as a HIP optimizer only: on a CPU model, or with
+    ``fused_hip=False``, the name is unknown."""
     name = config.TRAIN.OPTIMIZER.NAME.lower()
     groups = param_groups_no_decay_1d(model)
     on_gpu = all(p.is_cuda for g in groups for p in g['params'])
     hip = on_gpu and (fused_hip is None or fused_hip)
-    if name not in ('adamw', 'sgd'):
-        raise ValueError(f'unknown optimizer {name}')
+    lamb = name in ('lamb', 'fused_lamb')
+    if name not in ('adamw', 'sgd') and not (lamb and hip):
+        raise ValueError(f'unknown optimizer {name}' + (' (LAMB exists as a HIP optimizer only: a GPU model and fused_hip in (None, True))'
+                                                         if lamb else ''))
     if skip_nonfinite and not hip:
         raise ValueError('skip_nonfinite=True needs the HIP optimizers (a GPU model and fused_hip in (None, True)): the torch '
                          'optimizers have no such check')
@@ -49,9 +55,12 @@ def build_optimizer(config, model, capturable: bool = False, fused_hip: bool | N
         raise ValueError('ema_decay needs the HIP optimizers (a GPU model and fused_hip in (None, True)): the average is kept by their '
                          'update kernel')
     ema = dict(ema_decay=ema_decay, ema_warmup=ema_warmup)
-    if name == 'adamw':
+    if name == 'adamw' or lamb:
         kw = dict(eps=config.TRAIN.OPTIMIZER.EPS, betas=tuple(config.TRAIN.OPTIMIZER.BETAS), lr=config.TRAIN.BASE_LR,
                   weight_decay=config.TRAIN.WEIGHT_DECAY)
+        if lamb:
+            from ..optim import FlatLAMB
+            return FlatLAMB(groups, model=model, skip_nonfinite=skip_nonfinite, **ema, **kw)
         if hip:
             from ..optim import FlatAdamW     # here, not at the top: optim imports this package (FlatGradients)
             # the model's bf16 weight shadows are refreshed by the update kernel

@@ -18,6 +18,10 @@ with ``n`` the EMA updates done so far; a skipped update leaves the average and 
 exchanges parameters and averages in place (``vited_ema_swap``, shadows included) for an evaluation on the averaged weights, and
 exchanges them back on exit.  ``ema_state_dict`` / ``load_ema_state_dict`` carry the average under the model's ``state_dict`` keys,
 ``num_ema_updates`` is the one integer that goes with them; ``state_dict()`` stays torch's.
+
+``FlatLAMB`` is LAMB (You et al. 2020, with timm's ``Lamb`` conventions) on the same base - ``vited_lamb_step``: five launches, because
+every tensor's trust ratio needs two norms over the whole tensor before any element moves - with ``FlatAdamW``'s state and
+``state_dict``; ``trust_ratios()`` reads the ratios of the latest applied update.
 """
 from __future__ import annotations
 
@@ -100,7 +104,7 @@ class _FlatOptimizer(torch.optim.Optimizer):
                 hyper[:HYPER_HEADER].copy_(self._hyper[:HYPER_HEADER])
             self._hyper = hyper
             self._norm = torch.zeros(1, dtype=torch.float32, device=dev)
-            self._ws = torch.empty(_lib.load().vited_adamw_workspace_bytes() // 4, dtype=torch.float32, device=dev)
+            self._ws = self._new_workspace(flat, dev)
             self._desc = self._desc_key = None
             self._ema = None
         self._hyper[HYPER_SKIP_FLAG: HYPER_SKIP_FLAG + 1].fill_(1.0 if self.skip_nonfinite else 0.0)
@@ -121,6 +125,10 @@ class _FlatOptimizer(torch.optim.Optimizer):
 
     def _after_bind(self):
         pass
+
+    def _new_workspace(self, flat, dev):
+        """The workspace of ``_entry`` for ``flat``, allocated by ``bind_flat`` before the descriptor table exists."""
+        return torch.empty(_lib.load().vited_adamw_workspace_bytes() // 4, dtype=torch.float32, device=dev)
 
     def _state_view(self, name, p):
         off = self.flat.offsets[next(i for i, q in enumerate(self.flat.params) if q is p)]
@@ -411,17 +419,12 @@ class _FlatOptimizer(torch.optim.Optimizer):
             super().zero_grad(set_to_none=set_to_none)
 
 
-class FlatAdamW(_FlatOptimizer):
-    _entry = 'vited_adamw_step'
+class _FlatAdamMoments(_FlatOptimizer):
+    """What ``FlatAdamW`` and ``FlatLAMB`` share: the two moments, one step count, and torch.optim.AdamW's ``state_dict`` layout."""
     _state_names = ('exp_avg', 'exp_avg_sq')
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, model=None, skip_nonfinite=False,
-                 ema_decay=None, ema_warmup=False):
-        """``model`` (the HIP ViT-ED whose parameters these are) lets the kernel refresh the model's bf16 weight shadows in the
-        same pass; without it the parameters' version counters are bumped after every update instead, so the model recasts its
-        shadows on the next forward (correct, one extra launch per weight)."""
-        super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay), model, skip_nonfinite, ema_decay,
-                         ema_warmup)
+    def __init__(self, params, defaults, model=None, skip_nonfinite=False, ema_decay=None, ema_warmup=False):
+        super().__init__(params, defaults, model, skip_nonfinite, ema_decay, ema_warmup)
         self._loaded_step = None       # step count of a state_dict loaded before bind_flat (the reference's resume order)
 
     exp_avg = property(lambda self: self._bufs['exp_avg'] if self._bufs else None)
@@ -438,9 +441,6 @@ class FlatAdamW(_FlatOptimizer):
         if self._hyper is not None:
             return int(self._hyper[HYPER_STEP].item())
         return int(self._loaded_step or 0)
-
-    def _group_words(self, g):
-        return [float(g['lr']), float(g['betas'][0]), float(g['betas'][1]), float(g['eps']), float(g['weight_decay']), 0., 0., 0.]
 
     # -- checkpoint compatibility with torch.optim.AdamW (misc/utils.py:130-142 saves optimizer.state_dict()) ----
     def state_dict(self):
@@ -460,6 +460,90 @@ class FlatAdamW(_FlatOptimizer):
         self._loaded_step = max(steps) if steps else None
         if flat is not None:
             self.bind_flat(flat)                 # copies the loaded moments into the flat buffers and applies the step count
+
+
+class FlatAdamW(_FlatAdamMoments):
+    _entry = 'vited_adamw_step'
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, model=None, skip_nonfinite=False,
+                 ema_decay=None, ema_warmup=False):
+        """``model`` (the HIP ViT-ED whose parameters these are) lets the kernel refresh the model's bf16 weight shadows in the
+        same pass; without it the parameters' version counters are bumped after every update instead, so the model recasts its
+        shadows on the next forward (correct, one extra launch per weight)."""
+        super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay), model, skip_nonfinite, ema_decay,
+                         ema_warmup)
+
+    def _group_words(self, g):
+        return [float(g['lr']), float(g['betas'][0]), float(g['betas'][1]), float(g['eps']), float(g['weight_decay']), 0., 0., 0.]
+
+
+LAMB_RATIO_AT = 1028               # the first word of ratio[count] in vited_lamb_step's workspace (include/vited.h)
+
+
+class FlatLAMB(_FlatAdamMoments):
+    """LAMB (You et al. 2020, Algorithm 2) with timm's ``Lamb`` conventions - bias correction, gradient averaging, the weight decay
+    inside the update (L2 in ``u``, not AdamW's decoupled decay), the trust ratio only where it applies - in the fused update:
+    ``vited_lamb_step`` / ``vited_lamb_step_ema``, the rule is csrc/optim_update.h's.  Per parameter tensor, with ``c`` the step's clip
+    coefficient and ``t`` the updates applied::
+
+        g' = g c;  m = m + (g' - m)(1 - b1);  v = b2 v + (1 - b2) g' g'
+        u  = (m / (1 - b1^t)) / (sqrt(v) / sqrt(1 - b2^t) + eps) + wd p
+        r  = 1 if wd == 0 and not always_adapt else (|p| / |u| if |p| > 0 and |u| > 0 else 1);   trust_clip: r = min(r, 1)
+        p  = p - lr r u
+
+    The gradient clip is the step's own (``step_flat(max_norm)``, ``TRAIN.CLIP_GRAD``): there is no second ``max_grad_norm``.  State
+    and ``state_dict`` are ``FlatAdamW``'s (``exp_avg``, ``exp_avg_sq``, one step count), so a checkpoint of either loads into the other.
+    Everything else - shadows, graph replay, device-stepped rates, skipped updates, the parameter average - is ``_FlatOptimizer``'s."""
+    _entry = 'vited_lamb_step'
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.01, always_adapt=False, trust_clip=False,
+                 model=None, skip_nonfinite=False, ema_decay=None, ema_warmup=False):
+        if not 0.0 <= lr:
+            raise ValueError(f'Invalid learning rate: {lr}')
+        if not 0.0 <= eps:
+            raise ValueError(f'Invalid epsilon value: {eps}')
+        betas = tuple(betas)
+        if len(betas) != 2 or not all(0.0 <= b < 1.0 for b in betas):
+            raise ValueError(f'Invalid beta parameters: {betas}')
+        if not 0.0 <= weight_decay:
+            raise ValueError(f'Invalid weight_decay value: {weight_decay}')
+        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, always_adapt=bool(always_adapt),
+                        trust_clip=bool(trust_clip))
+        super().__init__(params, defaults, model, skip_nonfinite, ema_decay, ema_warmup)
+
+    def _group_words(self, g):
+        return [float(g['lr']), float(g['betas'][0]), float(g['betas'][1]), float(g['eps']), float(g['weight_decay']),
+                1.0 if g['always_adapt'] else 0.0, 1.0 if g['trust_clip'] else 0.0, 0.]
+
+    def _new_workspace(self, flat, dev):
+        # the tile count depends on the parameters' shapes alone (``_descriptors`` counts the same way), so the workspace - ratio[count]
+        # and two sums per tile behind AdamW's words - can be sized, once per binding, before the table exists
+        tiles = 0
+        for p in flat.params:
+            r = p.shape[0] if p.dim() >= 2 else 1
+            tiles += ((r + 63) // 64) * ((p.numel() // r + 63) // 64)
+        nbytes = _lib.load().vited_lamb_workspace_bytes(tiles, len(flat.params))
+        if nbytes <= 0:
+            raise ValueError(f'FlatLAMB: no workspace for {len(flat.params)} parameters in {tiles} tiles')
+        return torch.zeros(nbytes // 4, dtype=torch.float32, device=dev)
+
+    def load_state_dict(self, state_dict):
+        """As ``FlatAdamW.load_state_dict``; groups saved by ``FlatAdamW`` (or torch.optim.AdamW) carry no ``always_adapt`` /
+        ``trust_clip`` and take this optimizer's defaults."""
+        super().load_state_dict(state_dict)
+        for g in self.param_groups:
+            for key in ('always_adapt', 'trust_clip'):
+                g.setdefault(key, self.defaults[key])
+
+    def trust_ratios(self):
+        """{parameter name, or its index in ``state_dict()`` where the optimizer has no ``model`` that names it: r} of the latest applied
+        update of this binding (0.0 before the first): one host read of the ratio table."""
+        if self.flat is None:
+            raise RuntimeError('FlatLAMB.trust_ratios: call bind_flat(FlatGradients) first (engine.TrainStep does)')
+        names = {id(p): n for n, p in self._model.named_parameters()} if hasattr(self._model, 'named_parameters') else {}
+        index = {id(p): i for i, p in enumerate(p for g in self.param_groups for p in g['params'])}
+        values = self._ws[LAMB_RATIO_AT: LAMB_RATIO_AT + len(self.flat.params)].tolist()
+        return {names.get(id(p), index[id(p)]): r for p, r in zip(self.flat.params, values)}
 
 
 class FlatSGD(_FlatOptimizer):
