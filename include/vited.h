@@ -643,6 +643,24 @@ int vited_lamb_step_ema(const int64_t* desc, int count, int64_t total_tiles, con
                         float* hyper, float max_norm, int zero_grad, float* norm_out, float* workspace,
                         int64_t workspace_bytes, float* ema_flat, int64_t ema_numel, void* stream);
 
+/* Lion (Chen et al. 2023, "Symbolic Discovery of Optimization Algorithms", with timm's Lion conventions) in place of AdamW: same
+ * arguments and argument checks, same three launches, same hyper header (skipping and the EMA words included), same workspace
+ * (vited_adamw_workspace_bytes).  One moment, no step count in the rule (hyper[0] still counts the applied updates), no bias correction.
+ *   desc row    {p, g, exp_avg, 0, shadow, shadow_t, rows, cols, first_tile, group}
+ *   group words {lr, beta1, beta2, 0, weight_decay, 0, 0, 0}
+ * The rule is csrc/optim_update.h's (lion_piece); with c the clip coefficient, per element
+ *     g' = g c;  pe = p (1 - lr weight_decay);  s = sign(beta1 m + (1 - beta1) g')      +1, -1, 0 for 0, NaN for NaN
+ *     p  = pe - lr s;  m = m + (g' - m)(1 - beta2)
+ * Every product is rounded on its own, never contracted into an fma: the sign is decided by rounding where the two terms nearly
+ * cancel, and so the kernel gives the bits of the same rule in separate fp32 operations.  12 B read and 12 B written per element, and
+ * 4 B of shadows.  vited_lion_step_ema keeps the average as vited_adamw_step_ema does (same further arguments and checks). */
+int vited_lion_step(const int64_t* desc, int count, int64_t total_tiles, const float* grad_flat, int64_t grad_numel,
+                    float* hyper, float max_norm, int zero_grad, float* norm_out, float* workspace,
+                    int64_t workspace_bytes, void* stream);
+int vited_lion_step_ema(const int64_t* desc, int count, int64_t total_tiles, const float* grad_flat, int64_t grad_numel,
+                        float* hyper, float max_norm, int zero_grad, float* norm_out, float* workspace,
+                        int64_t workspace_bytes, float* ema_flat, int64_t ema_numel, void* stream);
+
 /* One step of a per-iteration learning-rate schedule on the device (misc/lr_scheduler.py through misc/engine.py:228; the rules are
  * csrc/lr_schedule.h, in fp64): one launch of one workgroup, queued behind the update it follows.
  *   t = *counter;  for g < groups: dst[first + stride * g] = (float)(lr_schedule_value(table, base[g], t) * scale[g]);  *counter = t + 1

@@ -1,7 +1,8 @@
 // The per-element update bodies of the fused optimizer kernels (optimizer.hip): torch.optim.AdamW's and torch.optim.SGD's rules and
-// LAMB's on four consecutive elements of one parameter row, and the decision whether an update is applied at all.  Plain C++ (one call
-// = one 4-element piece, the unit a thread of the update kernel handles), so that the same text runs inside the HIP kernels and in a
-// host program under the sanitizers (tools/optim_host_check.cpp, tools/ema_host_check.cpp, tools/lamb_host_check.cpp).  The exponential moving average of the
+// LAMB's and Lion's on four consecutive elements of one parameter row, and the decision whether an update is applied at all.  Plain C++
+// (one call = one 4-element piece, the unit a thread of the update kernel handles), so that the same text runs inside the HIP kernels
+// and in a host program under the sanitizers (tools/optim_host_check.cpp, tools/ema_host_check.cpp, tools/lamb_host_check.cpp,
+// tools/lion_host_check.cpp).  The exponential moving average of the
 // parameters (the *_ema entries, vited_ema_swap) is stated here as well: ema_decay_at / ema_blend are THE rule.
 #pragma once
 #include <stdint.h>
@@ -255,6 +256,76 @@ OPTIM_FN void lamb_apply_piece(float* p, float* g, const float* m, const float* 
 #pragma unroll
         for (int e = 0; e < 4; ++e)
             if (e < n) { p[o + e] = pn[e]; if (zero_grad) g[o + e] = 0.f; }
+    }
+}
+
+// ---- Lion (Chen et al. 2023, "Symbolic Discovery of Optimization Algorithms", with timm's Lion conventions) ----------------------------
+// Group words {lr, b1, b2, -, wd, -, -, -}; c the clip coefficient.  One moment, no step count, no bias correction:
+//     g' = g c
+//     pe = p (1 - lr wd)                       decoupled decay (timm: p.mul_(1 - lr * wd))
+//     cc = b1 m + (1 - b1) g'                  (timm: exp_avg.mul(b1).add_(grad, alpha=1 - b1))
+//     s  = sign(cc)                            +1, -1, 0 for cc == 0, NaN for NaN
+//     p' = pe - lr s
+//     m' = m + (g' - m)(1 - b2)                (timm: exp_avg.lerp_(grad, 1 - b2))
+// Every product - g c, lr wd, p (1 - lr wd), b1 m, (1 - b1) g', (g' - m)(1 - b2) - is rounded on its own (lion_product), never
+// contracted into an fma with the sum or difference that follows: sign(cc) is decided by rounding exactly where the two terms nearly
+// cancel, and with the rule pinned the kernel, the host build and an fp32 restatement in separate torch ops give the same bits.
+struct LionCoef { float lr, b1, b2, omb1, omb2, decay; };
+
+OPTIM_FN float lion_product(float a, float b) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    float r = OPTIM_MUL_RN(a, b);
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("" : "+v"(r));                          // the value barrier of ema_blend: the product is a value of its own
+#endif
+    return r;
+}
+
+OPTIM_FN LionCoef lion_coef(const float* hg) {
+    LionCoef k;
+    k.lr = hg[0]; k.b1 = hg[1]; k.b2 = hg[2];
+    k.omb1 = 1.0f - k.b1; k.omb2 = 1.0f - k.b2;
+    k.decay = 1.0f - lion_product(k.lr, hg[4]);
+    return k;
+}
+
+OPTIM_FN float lion_sign(float c) {
+    return c > 0.f ? 1.0f : (c < 0.f ? -1.0f : (c == 0.f ? 0.f : c));
+}
+
+// n, wide, pn as adamw_piece.
+OPTIM_FN void lion_piece(float* p, float* g, float* m, int64_t o, int n, bool wide, const LionCoef& k, float clip, int zero_grad,
+                         float* pn) {
+    float gv[4], pv[4], mv[4];
+    if (wide) {
+        const OptimVec4 qg = *(const OptimVec4*)(g + o), qp = *(const OptimVec4*)(p + o), qm = *(const OptimVec4*)(m + o);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { gv[e] = qg.v[e]; pv[e] = qp.v[e]; mv[e] = qm.v[e]; }
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const bool in = e < n;
+            gv[e] = in ? g[o + e] : 0.f; pv[e] = in ? p[o + e] : 0.f; mv[e] = in ? m[o + e] : 0.f;
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const float ge = lion_product(gv[e], clip);
+        const float pe = lion_product(pv[e], k.decay);
+        const float cc = lion_product(k.b1, mv[e]) + lion_product(k.omb1, ge);
+        pn[e] = pe - k.lr * lion_sign(cc);      // lr s is exact (+lr, -lr, 0): an fma here changes no bit
+        mv[e] = mv[e] + lion_product(ge - mv[e], k.omb2);
+    }
+    if (wide) {
+        *(OptimVec4*)(p + o) = OptimVec4{{pn[0], pn[1], pn[2], pn[3]}};
+        *(OptimVec4*)(m + o) = OptimVec4{{mv[0], mv[1], mv[2], mv[3]}};
+        if (zero_grad) *(OptimVec4*)(g + o) = OptimVec4{{0.f, 0.f, 0.f, 0.f}};
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            if (e < n) { p[o + e] = pn[e]; m[o + e] = mv[e]; if (zero_grad) g[o + e] = 0.f; }
     }
 }
 

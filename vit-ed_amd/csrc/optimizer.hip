@@ -34,15 +34,19 @@
 //
 // vited_lamb_step / vited_lamb_step_ema: LAMB, whose trust ratio needs the norms of a whole tensor before any of its elements may
 // move - launches 1 and 2, then three more (at the end of this file), the last one the OPT_LAMB instance of the same tile body.
+//
+// vited_lion_step / vited_lion_step_ema: Lion (lion_piece), the OPT_LION instance of the tile body behind the same launches 1 and 2.
+// One moment (descriptor word 2; word 3 is 0, as for SGD):  pe = p (1 - lr wd);  p' = pe - lr sign(b1 m + (1 - b1) g');
+// m' = m + (g' - m)(1 - b2), every product rounded on its own.  12 B read (g, p, m) + 12 B written + 4 B of shadows per element.
 #include "common.h"
 #include "optim_update.h"
 
 #define AD_DESC_WORDS 10   // {p, g, m, v, shadow, shadow_t, rows, cols, first_tile, group}
 #define AD_HYPER_HEADER 8  // hyper[0] = updates applied (float), [1] = skip-non-finite flag, [2] = updates skipped, [3..5] = EMA decay, warmup flag, EMA updates (the *_ema entries only), [6..7] reserved; then 8 floats per group
-#define AD_GROUP_WORDS 8   // AdamW {lr, beta1, beta2, eps, weight_decay, -, -, -}; SGD {lr, momentum, nesterov, -, weight_decay, -, -, -}
+#define AD_GROUP_WORDS 8   // AdamW {lr, beta1, beta2, eps, weight_decay, -, -, -}; SGD {lr, momentum, nesterov, -, weight_decay, -, -, -}; Lion {lr, beta1, beta2, -, weight_decay, -, -, -}
 #define AD_PARTIALS 1024
 #define AD_RESULT_WORDS 4  // behind the partials: {norm, clip, applied, step count}
-enum { OPT_ADAMW = 0, OPT_SGD = 1, OPT_SWAP = 2, OPT_LAMB = 3 };
+enum { OPT_ADAMW = 0, OPT_SGD = 1, OPT_SWAP = 2, OPT_LAMB = 3, OPT_LION = 4 };
 
 __device__ __forceinline__ float block_sum_256(float v, float* red) {
     v = wave_sum(v);
@@ -97,6 +101,7 @@ optim_decide_kernel(float* __restrict__ ws, float* __restrict__ hyper, float max
 // One 64 x 64 tile of one parameter.  OPT_ADAMW / OPT_SGD: the update; EMA adds e' = ema_blend(d_t, e, p') on the row's slice of
 // ema_flat (at the offset of its g in grad_flat).  OPT_SWAP: p <-> e and the shadows rewritten from the value now in p (vited_ema_swap;
 // res, hyper and zero_grad unused).  OPT_LAMB: LAMB's third launch (below), p -= lr r u with r = ratio[row], m and v only read.
+// OPT_LION: Lion's update; m is its one moment, v unused (0).
 template <int OPT, bool EMA>
 __device__ __forceinline__ void
 optim_update_tile(const int64_t* __restrict__ desc, int count, const float* __restrict__ res, const float* __restrict__ hyper,
@@ -119,21 +124,23 @@ optim_update_tile(const int64_t* __restrict__ desc, int count, const float* __re
     const int64_t* d = desc + (int64_t)lo * AD_DESC_WORDS;
     float* p = (float*)d[0];
     float* g = (float*)d[1];
-    float* m = (float*)d[2];                    // SGD: the momentum buffer
-    float* v = (float*)d[3];                    // SGD: unused (0)
+    float* m = (float*)d[2];                    // SGD: the momentum buffer; Lion: exp_avg
+    float* v = (float*)d[3];                    // SGD, Lion: unused (0)
     bf16* __restrict__ dst = (bf16*)d[4];
     bf16* __restrict__ dst_t = (bf16*)d[5];
     const int64_t rows = d[6], cols = d[7];
     AdamWCoef ka = {};
     SgdCoef ks = {};
     LambCoef kl = {};
+    LionCoef kn = {};
     float lamb_step = 0.f;                      // LAMB: lr * r of this row
     if constexpr (OPT != OPT_SWAP) {
         const float* hg = hyper + AD_HYPER_HEADER + d[9] * AD_GROUP_WORDS;
         if constexpr (OPT == OPT_ADAMW) ka = adamw_coef(hg, step);
         else if constexpr (OPT == OPT_LAMB) {
             if (applied) { kl = lamb_coef(hg, step); lamb_step = kl.lr * ratio[lo]; }
-        } else ks = sgd_coef(hg);
+        } else if constexpr (OPT == OPT_LION) kn = lion_coef(hg);
+        else ks = sgd_coef(hg);
     }
     float* e = nullptr;                         // the row's slice of the average
     float dt = 0.f;
@@ -145,6 +152,7 @@ optim_update_tile(const int64_t* __restrict__ desc, int count, const float* __re
     const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;   // 16 x 16: 4 columns x 4 rows per thread
     uintptr_t ptrs = (uintptr_t)p | (uintptr_t)g;
     if constexpr (OPT == OPT_ADAMW || OPT == OPT_LAMB) ptrs |= (uintptr_t)m | (uintptr_t)v;
+    else if constexpr (OPT == OPT_LION) ptrs |= (uintptr_t)m;
     else if (OPT == OPT_SGD && ks.momentum != 0.f) ptrs |= (uintptr_t)m;
     if constexpr (EMA) ptrs |= (uintptr_t)e;
     const bool vec = (cols & 3) == 0 && (ptrs & 15) == 0;
@@ -168,6 +176,7 @@ optim_update_tile(const int64_t* __restrict__ desc, int count, const float* __re
             const int n = cols - c < 4 ? (int)(cols - c) : 4;
             if constexpr (OPT == OPT_ADAMW) adamw_piece(p, g, m, v, r * cols + c, n, vec && n == 4, ka, clip, zero_grad, pn);
             else if constexpr (OPT == OPT_SGD) sgd_piece(p, g, m, r * cols + c, n, vec && n == 4, ks, clip, zero_grad, pn);
+            else if constexpr (OPT == OPT_LION) lion_piece(p, g, m, r * cols + c, n, vec && n == 4, kn, clip, zero_grad, pn);
             else if constexpr (OPT == OPT_LAMB) lamb_apply_piece(p, g, m, v, r * cols + c, n, vec && n == 4, kl, lamb_step, zero_grad, pn);
             else swap_piece(p, e, r * cols + c, n, vec && n == 4, pn);
             if constexpr (EMA && OPT != OPT_SWAP) ema_piece(e, r * cols + c, n, vec && n == 4, dt, pn);
@@ -277,6 +286,21 @@ extern "C" int vited_sgd_step_ema(const int64_t* desc, int count, int64_t total_
     if (!ema_buffer_ok(ema_flat, ema_numel, grad_numel)) return VITED_ERR_BAD_ARG;
     return optim_step<OPT_SGD>(desc, count, total_tiles, grad_flat, grad_numel, hyper, max_norm, zero_grad, norm_out, workspace,
                                workspace_bytes, ema_flat, stream);
+}
+
+extern "C" int vited_lion_step(const int64_t* desc, int count, int64_t total_tiles, const float* grad_flat, int64_t grad_numel,
+                               float* hyper, float max_norm, int zero_grad, float* norm_out, float* workspace,
+                               int64_t workspace_bytes, void* stream) {
+    return optim_step<OPT_LION>(desc, count, total_tiles, grad_flat, grad_numel, hyper, max_norm, zero_grad, norm_out, workspace,
+                                workspace_bytes, nullptr, stream);
+}
+
+extern "C" int vited_lion_step_ema(const int64_t* desc, int count, int64_t total_tiles, const float* grad_flat, int64_t grad_numel,
+                                   float* hyper, float max_norm, int zero_grad, float* norm_out, float* workspace,
+                                   int64_t workspace_bytes, float* ema_flat, int64_t ema_numel, void* stream) {
+    if (!ema_buffer_ok(ema_flat, ema_numel, grad_numel)) return VITED_ERR_BAD_ARG;
+    return optim_step<OPT_LION>(desc, count, total_tiles, grad_flat, grad_numel, hyper, max_norm, zero_grad, norm_out, workspace,
+                                workspace_bytes, ema_flat, stream);
 }
 
 // ---- LAMB (vited_lamb_step / vited_lamb_step_ema; the rule is optim_update.h's) ----------------------------------------------------------

@@ -39,15 +39,18 @@ def build_optimizer(config, model, capturable: bool = False, fused_hip: bool | N
 
     ``'lamb'`` (or ``'fused_lamb'``, the spelling of the reference drivers' ``--optim`` help) is ``optim.FlatLAMB`` with EPS, BETAS,
     BASE_LR, WEIGHT_DECAY and the no-decay group as for AdamW.  It exists as a HIP optimizer only: on a CPU model, or with
-    ``fused_hip=False``, the name is unknown."""
+    ``fused_hip=False``, the name is unknown.
+
+    ``'lion'`` is ``optim.FlatLion`` with BASE_LR, BETAS, WEIGHT_DECAY and the no-decay group (EPS is unused), HIP only in the same
+    way.  The config's values are passed as they are: Lion wants a rate 3-10x smaller and a decay 3-10x larger than AdamW's."""
     name = config.TRAIN.OPTIMIZER.NAME.lower()
     groups = param_groups_no_decay_1d(model)
     on_gpu = all(p.is_cuda for g in groups for p in g['params'])
     hip = on_gpu and (fused_hip is None or fused_hip)
-    lamb = name in ('lamb', 'fused_lamb')
-    if name not in ('adamw', 'sgd') and not (lamb and hip):
-        raise ValueError(f'unknown optimizer {name}' + (' (LAMB exists as a HIP optimizer only: a GPU model and fused_hip in (None, True))'
-                                                         if lamb else ''))
+    lamb, lion = name in ('lamb', 'fused_lamb'), name == 'lion'
+    if name not in ('adamw', 'sgd') and not ((lamb or lion) and hip):
+        raise ValueError(f'unknown optimizer {name}' + (f' ({"LAMB" if lamb else "Lion"} exists as a HIP optimizer only: a GPU model and '
+                                                         f'fused_hip in (None, True))' if lamb or lion else ''))
     if skip_nonfinite and not hip:
         raise ValueError('skip_nonfinite=True needs the HIP optimizers (a GPU model and fused_hip in (None, True)): the torch '
                          'optimizers have no such check')
@@ -55,6 +58,10 @@ def build_optimizer(config, model, capturable: bool = False, fused_hip: bool | N
         raise ValueError('ema_decay needs the HIP optimizers (a GPU model and fused_hip in (None, True)): the average is kept by their '
                          'update kernel')
     ema = dict(ema_decay=ema_decay, ema_warmup=ema_warmup)
+    if lion:
+        from ..optim import FlatLion
+        return FlatLion(groups, lr=config.TRAIN.BASE_LR, betas=tuple(config.TRAIN.OPTIMIZER.BETAS), weight_decay=config.TRAIN.WEIGHT_DECAY,
+                        model=model, skip_nonfinite=skip_nonfinite, **ema)
     if name == 'adamw' or lamb:
         kw = dict(eps=config.TRAIN.OPTIMIZER.EPS, betas=tuple(config.TRAIN.OPTIMIZER.BETAS), lr=config.TRAIN.BASE_LR,
                   weight_decay=config.TRAIN.WEIGHT_DECAY)

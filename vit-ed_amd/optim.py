@@ -22,6 +22,9 @@ exchanges them back on exit.  ``ema_state_dict`` / ``load_ema_state_dict`` carry
 ``FlatLAMB`` is LAMB (You et al. 2020, with timm's ``Lamb`` conventions) on the same base - ``vited_lamb_step``: five launches, because
 every tensor's trust ratio needs two norms over the whole tensor before any element moves - with ``FlatAdamW``'s state and
 ``state_dict``; ``trust_ratios()`` reads the ratios of the latest applied update.
+
+``FlatLion`` is Lion (Chen et al. 2023, with timm's ``Lion`` conventions) on the same base - ``vited_lion_step``: the three launches of
+``FlatAdamW`` with one moment, ``p -= lr sign(b1 m + (1 - b1) g)`` after the decoupled decay, every product rounded on its own.
 """
 from __future__ import annotations
 
@@ -544,6 +547,73 @@ class FlatLAMB(_FlatAdamMoments):
         index = {id(p): i for i, p in enumerate(p for g in self.param_groups for p in g['params'])}
         values = self._ws[LAMB_RATIO_AT: LAMB_RATIO_AT + len(self.flat.params)].tolist()
         return {names.get(id(p), index[id(p)]): r for p, r in zip(self.flat.params, values)}
+
+
+class FlatLion(_FlatOptimizer):
+    """Lion (Chen et al. 2023, "Symbolic Discovery of Optimization Algorithms") with timm's ``Lion`` conventions in the fused update:
+    ``vited_lion_step`` / ``vited_lion_step_ema``, the rule is csrc/optim_update.h's.  Per element, with ``c`` the step's clip
+    coefficient::
+
+        g' = g c;  pe = p (1 - lr wd);  s = sign(b1 m + (1 - b1) g')
+        p  = pe - lr s;  m = m + (g' - m)(1 - b2)
+
+    One moment (4 B of state per parameter instead of AdamW's 8), no step count in the rule, no bias correction; every product is
+    rounded on its own, so the kernel gives the bits of the rule written as separate fp32 operations.  The step has the same size for
+    every element, so Lion wants a rate 3-10x smaller and a decay 3-10x larger than AdamW's.  ``state_dict()`` has timm Lion's layout
+    (``exp_avg`` per parameter, no ``step``); ``load_state_dict`` also takes a ``FlatAdamW`` / ``FlatLAMB`` / ``torch.optim.AdamW``
+    checkpoint, of which ``exp_avg`` is kept.  Everything else - shadows, graph replay, device-stepped rates, skipped updates, the
+    parameter average - is ``_FlatOptimizer``'s."""
+    _entry = 'vited_lion_step'
+    _state_names = ('exp_avg',)
+
+    def __init__(self, params, lr=1e-4, betas=(0.9, 0.99), weight_decay=0.0, model=None, skip_nonfinite=False, ema_decay=None,
+                 ema_warmup=False):
+        if not 0.0 <= lr:
+            raise ValueError(f'Invalid learning rate: {lr}')
+        betas = tuple(betas)
+        if len(betas) != 2:
+            raise ValueError(f'Invalid beta parameters: {betas}')
+        for i, b in enumerate(betas):
+            if not 0.0 <= b < 1.0:
+                raise ValueError(f'Invalid beta parameter at index {i}: {b}')
+        if not 0.0 <= weight_decay:
+            raise ValueError(f'Invalid weight_decay value: {weight_decay}')
+        # timm Lion's group keys, so that a state_dict moves between the two
+        defaults = dict(lr=lr, betas=betas, weight_decay=weight_decay, foreach=None, maximize=False)
+        super().__init__(params, defaults, model, skip_nonfinite, ema_decay, ema_warmup)
+        for g in self.param_groups:
+            self._check_group(g)
+
+    exp_avg = property(lambda self: self._bufs['exp_avg'] if self._bufs else None)
+
+    @staticmethod
+    def _check_group(g):
+        if g.get('maximize'):
+            raise ValueError('FlatLion does not support maximize=True')
+
+    def _group_words(self, g):
+        self._check_group(g)
+        return [float(g['lr']), float(g['betas'][0]), float(g['betas'][1]), 0., float(g['weight_decay']), 0., 0., 0.]
+
+    def load_state_dict(self, state_dict):
+        """Accepts timm ``Lion``'s state and that of ``FlatAdamW`` / ``FlatLAMB`` / ``torch.optim.AdamW`` (``exp_avg`` is taken,
+        ``exp_avg_sq`` and ``step`` are dropped), before or after ``bind_flat``; a parameter without a loaded ``exp_avg`` starts from
+        zero.  Once bound the loaded moments are copied INTO the existing flat buffer, so a captured update graph stays valid."""
+        flat = self.flat
+        super().load_state_dict(state_dict)
+        for g in self.param_groups:
+            for key in ('foreach', 'maximize'):
+                g.setdefault(key, self.defaults[key])
+            self._check_group(g)
+        for st in self.state.values():
+            for key in [k for k in st if k != 'exp_avg']:
+                del st[key]
+        if flat is not None:
+            for st in self.state.values():       # a loaded moment may be a view of the flat buffer itself (our own state_dict)
+                if st.get('exp_avg') is not None:
+                    st['exp_avg'] = st['exp_avg'].clone()
+            self._bufs['exp_avg'].zero_()
+            self.bind_flat(flat)
 
 
 class FlatSGD(_FlatOptimizer):
