@@ -413,6 +413,24 @@ int vited_gemm_scaled(const void* A, int64_t lda, const void* B, int64_t ldb, in
                       int64_t K, const float* bias, const float* residual, const float* row_scale, float* out, int64_t ldo,
                       void* stream);
 
+/* Several 384-column NT products of ONE bf16 A [M, 384] (row stride lda) in one launch, the weights held in registers
+ * (csrc/gemm_nt_wreg.hip):  out_g = bf16(A . W[g * 384 : (g + 1) * 384, 0 : 384]^T + bias[g * 384 : (g + 1) * 384]),  g < groups,
+ * W bf16 [groups * 384, 384] (row stride ldw), bias fp32 [groups * 384] or null.  Group g is written as an [M, 384] block with row
+ * stride ldo at  out + (g / groups_inner) * group_stride + (g % groups_inner) * 384  (elements): groups = 1 is VITED_EPI_STORE of
+ * vited_gemm at N = K = 384; groups = 2 L, groups_inner = 2, ldo = 768, group_stride = M * 768 writes the keys / values of L
+ * decoder blocks as L dense [M, 768] tensors.  Every element is bit-identical to vited_gemm's on the same operands.
+ * `workgroups`: 0 = one per CU; a small positive count makes long per-workgroup shares out of few rows (tests).  The launch has
+ * max(1, workgroups / groups) * groups workgroups.  Errors: VITED_ERR_UNSUPPORTED where vited_gemm_nt_wreg_supported (host-only,
+ * 1 / 0) refuses the strides, M or the group counts; VITED_ERR_BAD_ARG for null or misaligned (16 bytes) pointers.  Reports GEMM
+ * path 2.
+ *   vited_gemm_nt_wreg_select  mode 0 = automatic (the default): vited_gemm itself hands the shapes its dispatch names to this
+ *                              kernel; 1 = vited_gemm never does.  Process-wide; returns the previous mode, or VITED_ERR_BAD_ARG
+ *                              for any other mode.  Test/diagnostic use: one process can run both kernels on the same data. */
+int vited_gemm_nt_wreg_supported(int64_t lda, int64_t ldw, int64_t ldo, int64_t M, int groups, int groups_inner, int64_t group_stride);
+int vited_gemm_nt_wreg(const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias, void* out, int64_t ldo, int64_t M,
+                       int groups, int groups_inner, int64_t group_stride, int workgroups, void* stream);
+int vited_gemm_nt_wreg_select(int mode);
+
 /* dW[n, k] = sum_m dY[m, n] * X[m, k] (fp32 [N, K]) and, if dbias != null, dbias[n] = sum_m dY[m, n];
  * overwritten, or added onto their current content when `accumulate` != 0.  dY / X are `dtype`.
  * workspace >= *_workspace_bytes. */

@@ -85,6 +85,25 @@ extern "C" int vited_gemm_scaled(const void* A, int64_t lda, const void* B, int6
                      row_scale, stream);
 }
 
+// ---- 384-column groups with the weights in registers (gemm_nt_wreg.hip) -------------------------------------------------
+static int g_nt_wreg_select = 0;
+bool gemm_nt_wreg_auto() { return __atomic_load_n(&g_nt_wreg_select, __ATOMIC_RELAXED) == 0; }
+extern "C" int vited_gemm_nt_wreg_select(int mode) {
+    if (mode != 0 && mode != 1) return VITED_ERR_BAD_ARG;
+    return __atomic_exchange_n(&g_nt_wreg_select, mode, __ATOMIC_RELAXED);
+}
+extern "C" int vited_gemm_nt_wreg_supported(int64_t lda, int64_t ldw, int64_t ldo, int64_t M, int groups, int groups_inner,
+                                            int64_t group_stride) {
+    return gemm_nt_wreg_supported(lda, ldw, ldo, M, groups, groups_inner, group_stride) ? 1 : 0;
+}
+extern "C" int vited_gemm_nt_wreg(const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias, void* out, int64_t ldo,
+                                  int64_t M, int groups, int groups_inner, int64_t group_stride, int workgroups, void* stream) {
+    if (!A || !W || !out || workgroups < 0) return VITED_ERR_BAD_ARG;
+    const int rc = gemm_nt_wreg(A, lda, W, ldw, bias, out, ldo, M, groups, groups_inner, group_stride, workgroups, (hipStream_t)stream);
+    if (rc == VITED_OK) g_last_gemm_path = 2;
+    return rc;
+}
+
 static inline int64_t tn_portable_splits(int64_t M, int64_t N, int64_t K) {
     const int64_t tiles = ceil_div64(N, 64) * ceil_div64(K, 64);
     int64_t s = ceil_div64(1024, tiles);

@@ -24,6 +24,12 @@ int gemm_nt_mfma(const void* A, int64_t lda, const void* B, int64_t ldb, int64_t
 bool gemm_nt_areg_supported(int64_t ldw, int64_t M, int64_t N, int64_t K, int epilogue);
 int gemm_nt_areg(const void* A, int64_t lda, const void* W, int64_t ldw, int64_t M, int64_t N, int epilogue, int waves,
                  const EpiParams& ep, hipStream_t s);
+// K = 384, 384-column groups with the weights in registers, A streamed once (gemm_nt_wreg.hip); plain-store epilogue only.
+// gemm_nt_wreg_auto: whether dispatch_nt may hand shapes to it (vited_gemm_nt_wreg_select, gemm.hip)
+bool gemm_nt_wreg_supported(int64_t lda, int64_t ldw, int64_t ldo, int64_t M, int groups, int groups_inner, int64_t group_stride);
+int gemm_nt_wreg(const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias, void* out, int64_t ldo, int64_t M,
+                 int groups, int groups_inner, int64_t group_stride, int workgroups, hipStream_t s);
+bool gemm_nt_wreg_auto();
 bool gemm_tn_mfma_supported(const void* dY, int64_t lddy, const void* X, int64_t ldx, int64_t M, int64_t N, int64_t K);
 int64_t gemm_tn_mfma_splits(int64_t M, int64_t N, int64_t K);
 int gemm_tn_mfma(const void* dY, int64_t lddy, const void* X, int64_t ldx, int64_t M, int64_t N, int64_t K, int64_t splits,

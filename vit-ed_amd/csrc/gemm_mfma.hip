@@ -248,13 +248,42 @@ template <int EPI> static inline int nt_areg_waves(int64_t ldb, int64_t M, int64
     if (const char* force = getenv("VITED_NT_AREG")) return atoi(force);
 #endif
     if (EPI == VITED_EPI_MUL) return 8;
-    if (EPI == VITED_EPI_STORE && N >= 1152 && M >= 65536) return 4;
+    if (EPI == VITED_EPI_STORE && N >= 1152 && M >= 65536) return 4;   // N = 1152 itself: dispatch_nt asks nt_wreg_groups first
     return 0;
+}
+
+// Plain-store K = 384 products that take the weights-in-registers kernel (gemm_nt_wreg.hip): 0 = none, else its number of
+// 384-column groups.  That kernel's time is a fixed ~12 us (the launch, 288 KB of W per workgroup before the first MFMA) + A read
+// once and the output at 5.2 TB/s, cached or not; the tile kernels need their operands in the last-level cache to be faster, and in
+// the step they are not.  Measured (profiles/wreg_probe.py, cold operands; in the step: DESIGN.md section 5.0.2):
+//  * N = 384 (do = dy . W_proj of the attention backward, the cross-attention q projection), one group: 36.0 -> 34.5 us at 65,536
+//    rows, 38.6 -> 34.9 at 66,560, 43.5 -> 37.9 at 73,800, but 20.8 -> 22.4 at 24,576 rows (three tiles per workgroup behind the W
+//    load), so it starts between the two row counts the workloads have; the cls tail's 1,024 rows keep the tile kernel;
+//  * N = 1152 (qkv), three groups on 255 workgroups, where gemm_nt_areg_kernel<0, 4> ran before, i.e. from 65,536 rows: 75.3 -> 68.1 us
+//    at 65,536 rows, 83.6 -> 69.0 at 66,560, 92.3 -> 74.6 at 73,800; A-train step 23.06 -> 22.92 ms.  Below that row count qkv
+//    keeps the tile kernel (24,576 rows: level warm, and the A-in-registers rule it replaces starts at 65,536 as well).
+// Experiment builds move the thresholds: make VARIANT=x EXTRA="-DNT_WREG_MIN_M=... -DNT_WREG_QKV_MIN_M=..." (0 = never for qkv).
+#ifndef NT_WREG_MIN_M
+#define NT_WREG_MIN_M 32768
+#endif
+#ifndef NT_WREG_QKV_MIN_M
+#define NT_WREG_QKV_MIN_M 65536
+#endif
+static inline int nt_wreg_groups(int64_t lda, int64_t ldb, int64_t M, int64_t N, int64_t K, const EpiParams& ep) {
+    if (K != 384 || !gemm_nt_wreg_auto()) return 0;
+    int groups = 0;
+    if (N == 384 && M >= (int64_t)NT_WREG_MIN_M) groups = 1;
+    if (N == 1152 && NT_WREG_QKV_MIN_M > 0 && M >= (int64_t)NT_WREG_QKV_MIN_M) groups = 3;
+    return groups && gemm_nt_wreg_supported(lda, ldb, ep.ldo, M, groups, groups, 0) ? groups : 0;
 }
 
 template <int EPI>
 static int dispatch_nt(const bf16* a, int64_t lda, const bf16* b, int64_t ldb, int64_t M, int64_t N, int64_t K, const EpiParams& ep,
                        hipStream_t s) {
+    if constexpr (EPI == VITED_EPI_STORE) {
+        if (const int groups = nt_wreg_groups(lda, ldb, M, N, K, ep))
+            return gemm_nt_wreg(a, lda, b, ldb, ep.bias, ep.out, ep.ldo, M, groups, groups, 0, 0, s);
+    }
     if (const int waves = nt_areg_waves<EPI>(ldb, M, N, K)) return gemm_nt_areg(a, lda, b, ldb, M, N, EPI, waves, ep, s);
     // BK = 32 (4 workgroups / CU) pays only when the grid is large: at N = 384 (1,536 tiles) BK = 64 is 9-14 % faster
     bool shallow = K <= 512 && N >= 768;

@@ -126,6 +126,10 @@ class Runtime:
         self.dw_queue = None        # inside a block's backward: [(dy, x, dW target, dbias target | None, accumulate)]
         self.ln_queue = None        # inside a Function's backward: deferred LayerNorm column sums (ops.layernorm_bwd_finish)
         self.fold_context = os.environ.get('VITED_FOLD_CONTEXT', '1') != '0'   # norm_context + kv of all decoder blocks as one GEMM
+        # ... in ONE launch of ops.gemm_nt_wreg instead of one GEMM per block: the same bits, 426 -> 305 us for the eight of config A, but
+        # 0.04 - 0.17 ms of the 23.4 ms step in four A / B sessions, inside the parent's run-to-run range in three of them: off by default
+        # 
+        self.kv_one_launch = os.environ.get('VITED_KV_ONE_LAUNCH', '0') != '0'
         self._fold_bufs = None      # (folded W [L 2D, D], its transpose, folded bias): refreshed in place every forward
         self._unit_ln = None        # (ones, zeros) for the affine-free LayerNorm of the features
         self.tap = None             # test/diagnostic: a dict that receives clones of per-block activations and gradients
@@ -1070,6 +1074,12 @@ def _context_kv_folded(rt, ctxf, blocks):
     n2 = 2 * rt.dim
     kv_all = torch.empty((len(blocks), ctxf.shape[0], n2), dtype=rt.act_dtype, device=dev)
     wf, wft, bf = bufs
+    # rt.kv_one_launch, 384-wide models: all 2 L key / value groups in one launch of the weights-in-registers kernel, which holds a
+    # group's weights for the whole launch (nothing to fall out of L2) and addresses kv_all[l]'s dense rows itself; the same bits as the loop
+    if (rt.kv_one_launch and rt.dim == ops.WREG_WIDTH and xhat.dtype == torch.bfloat16
+            and ops.gemm_nt_wreg_supported(xhat.shape[0], 2 * len(blocks), 2, lda=xhat.stride(0), ldw=wf.stride(0))):
+        ops.gemm_nt_wreg(xhat, wf, bf, kv_all, groups=2 * len(blocks))
+        return FoldSaved(kv_all, xhat, mean, rstd, wt=wft)
     for l in range(len(blocks)):
         ops.gemm(xhat, wf[l * n2:(l + 1) * n2], bias=bf[l * n2:(l + 1) * n2], out=kv_all[l])
     return FoldSaved(kv_all, xhat, mean, rstd, wt=wft)

@@ -1371,3 +1371,6 @@ from .ops_ema import ema_swap  # noqa: E402,F401
 
 # matrix-core fp32 attention: predicate, per-thread record and kernel selection (csrc/attention_f32_mfma.hip); ops_f32attn.py
 from .ops_f32attn import fp32_attention_kernels, fp32_attention_supported, last_fp32_attention_kernel  # noqa: E402,F401
+
+# ---- 384-column NT products with the weights in registers: the wrapper of vited_gemm_nt_wreg (csrc/gemm_nt_wreg.hip); ops_wreg.py
+from .ops_wreg import WREG_WIDTH, gemm_nt_wreg, gemm_nt_wreg_dispatch, gemm_nt_wreg_supported  # noqa: E402,F401
