@@ -5,12 +5,21 @@
     last block, keys / values computed ahead) and for the plain, q/k-norm and pooled-head trees;
   * completeness: the stages between them own every parameter of the state_dict, once;
   * the bf16 bound (2 x the rounding model's statistic + 2^-8) lets a second, differently rounding bf16 implementation through ...
-  * ... and catches each of five planted glue defects.
+  * ... and catches each of five planted glue defects;
+  * the same four properties with the options of training in the stages - stochastic-depth scales, patch dropout's keep tables,
+    position dropout's masks, the gathered and the pair-indexed two-stage forms: the restarts reproduce droppath_cases' /
+    patchdrop_cases' / posdrop_cases' compositions and oracle(feats[i], imgs[j]) to 1e-10, the second rounding model is admitted in
+    every case the GPU test runs, whose fp64 references need no small-gradient exemption, and five defects planted in the
+    implementation that records (a scale missing from a branch's gradient, the neighbouring branch's scales, d(pos_embed) one row
+    off, the position mask missing from the gradient, a pair missing from an image's sum) fail at exactly the labels they touch.
 """
 import pytest
 import torch
 
 import block_restart_cases as br
+import droppath_cases as droppath
+import patchdrop_cases as patchdrop
+import posdrop_cases as posdrop
 from oracle import vited_oracle as vo
 
 SMALL = vo.ViTEDShape(img_size=32, patch_size=8, embed_dim=64, num_heads=2, depth=2, c_depth=3)      # 16 / 17 tokens
@@ -96,6 +105,240 @@ def test_the_bf16_bound_admits_a_second_rounding_model(geometry, kind, cls_rows,
     rows = br.compare(br.observed(taps, grads, s), ref, br.restart_all(m, taps, br.MODEL))
     print(br.table(rows))
     assert br.failures(rows) == []
+
+
+# ----------------------------------------------------------------------------------------------------------------------------
+# the stages with the training options: drop path, patch dropout, position dropout, the two-stage forms
+# ----------------------------------------------------------------------------------------------------------------------------
+#         form        tree     what the options are made of                          two calls
+FORMS = {'droppath':  ('plain', dict(drop_path=0.2),                                  None),
+         'patchdrop': ('plain', dict(patch_drop=0.25),                                None),
+         'posdrop':   ('plain', dict(pos_drop=0.1),                                   None),
+         'all-qk':    ('qk',    dict(drop_path=0.2, patch_drop=0.25, pos_drop=0.1),   None),
+         'gathered':  ('plain', dict(),                                               'gathered'),
+         'indexed':   ('plain', dict(),                                               'indexed')}
+
+
+def _small_case(form, ops):
+    """(tree fp64, x1, x2, y, Options, images or None for a one-shot form) of ``form`` at SMALL: 16 / 17 tokens (11 + 1 / 12 + 1 kept)."""
+    kind, what, calls = FORMS[form]
+    m = br.build_tree(SMALL, kind, seed=3).double()
+    if calls is None:
+        x, y = br.inputs(SMALL, 3, seed=3)
+        return m, x[:, 0].double(), x[:, 1].double(), y.double(), br.make_options(SMALL, 3, ops=ops, **what), None
+    images, index, x2_index = br.PAIRS_A
+    imgs, y = br.pair_inputs(SMALL, images, len(index), seed=3)
+    opt = br.make_options(SMALL, images, len(index), ops=ops, index=index, x2_index=x2_index, indexed=calls == 'indexed', **what)
+    return m, imgs.double(), imgs[opt.x2_index].double(), y.double(), opt, imgs.double()
+
+
+def _straight_composition(m, x1, x2, y, opt, imgs, ops):
+    """The whole network as the option's own case module composes it, untouched by the restart code: logits and parameter gradients."""
+    x = torch.stack((x1, x2), 1) if imgs is None else None
+    enc, dec = (None, None) if opt.enc is None else (opt.enc.double(), opt.dec.double())
+    m.zero_grad(set_to_none=True)
+    if imgs is not None:
+        logits = m(m(imgs, forward_first_part=True)[opt.index], imgs[opt.x2_index])      # oracle(feats[i], imgs[j]), the encoder on the images
+    elif opt.mult1 is not None:
+        mask1, mask2, scale = posdrop.masks_of(ops, opt.seeds, opt.pos_rate, x1.shape[0], x2.shape[0], SMALL)
+        logits = posdrop.forward_dropped(m, x, mask1, mask2, scale, opt.keep1, opt.keep2, enc, dec)
+    elif opt.keep1 is not None:
+        logits = patchdrop.forward_kept(m, x, opt.keep1, opt.keep2)
+    else:
+        logits = droppath.forward_scaled(m, x, enc, dec)
+    _, grads = droppath.loss_and_grads(m, logits, y)
+    m.zero_grad(set_to_none=True)
+    return logits.detach(), grads
+
+
+@pytest.mark.parametrize('cls_rows,fold', [(False, False), (True, True)])
+@pytest.mark.parametrize('form', list(FORMS))
+def test_restarts_under_the_options_reproduce_the_fp64_composition(vited, form, cls_rows, fold):
+    m, x1, x2, y, opt, imgs = _small_case(form, vited.ops)
+    logits0, grads0 = _straight_composition(m, x1, x2, y, opt, imgs, vited.ops)
+    taps, grads = br.network_taps(m, (x1, x2), y, br.EXACT, cls_rows=cls_rows, fold=fold, opt=opt)
+    # the tapped run IS the composition's forward + backward
+    assert _rel(taps['logits'], logits0) < 1e-12
+    assert set(grads) == set(grads0) == {n for n, _ in m.named_parameters()}
+    for n in grads0:
+        if not n.endswith('k_norm.bias'):        # zero in exact arithmetic (block_restart_cases.scale_of): two runs' rounding noise
+            assert _rel(grads[n], grads0[n]) < 1e-10, n
+    assert br.layout_of(taps, SMALL) == (cls_rows, fold)
+    if opt.keep1 is not None:
+        assert taps['enc.in'].shape[1] == 12 and taps['dec.in'].shape[1] == 13      # 1 + 11 of 16 and 1 + 12 of 17 tokens
+    ref = br.restart_all(m, taps, br.EXACT, opt)
+    got = br.observed(taps, grads0, SMALL)
+    assert set(got) == set(ref)
+    assert br.checked_parameters(ref) == set(m.state_dict())       # the stages still own every parameter, once (_take_grads)
+    for label, (whole, rowmax), _ in br.compare(got, ref):
+        assert whole < 1e-10 and (rowmax is None or rowmax < 1e-10), (label, whole, rowmax)
+    # what the encoder received is the decoder's d(features): summed over the pairs by autograd, or per image already
+    assert _rel(taps[f'enc.dx.{SMALL.depth}'], br.features_gradient(taps, SMALL, opt, dtype=torch.float64)) < 1e-14
+    if opt.index is not None:
+        items = 5 if opt.indexed else 12
+        assert ref['context.dfeats'].shape[0] == ref[f'dec1.{"dkv" if fold else "dctx"}'].shape[0] == items
+    if opt.indexed:
+        unread = sorted(set(range(5)) - set(opt.index.tolist()))
+        assert unread == [2] and torch.bincount(opt.index).tolist() == [3, 2, 0, 5, 2]
+        assert not bool(ref['context.dfeats'][2].any()) and bool(ref['context.dfeats'][[0, 1, 3, 4]].flatten(1).any(1).all())
+
+
+#          every case of the GPU test's option table in the layout its bf16 run has ...
+ADMITTED = [(c[0], c[4].get('cls_tail', True), c[4].get('fold_context', True)) for c in br.OPTION_CASES]
+#          ... and each kind of option once more with every row of the last block live and the d(context) terms per block (the fp32 runs' layout)
+ADMITTED += [(name, False, False) for name in ('droppath', 'patchdrop', 'posdrop', 'all-qk_norm', 'two-stage', 'indexed')]
+
+
+@pytest.mark.parametrize('name,cls_rows,fold', ADMITTED)
+def test_the_bf16_bound_admits_a_second_rounding_model_under_the_options(vited, name, cls_rows, fold):
+    """Every case of tests/test_gpu_block_restart.py's option table at its own geometry, with MODEL2 as the implementation: inside
+    2 x MODEL + 2^-8 on every tensor.  And the fp64 reference needs no small-gradient exemption."""
+    kind, s, images, pairs, switches, opt, (x1, x2, y) = br.option_case(name, vited.ops)
+    m = br.build_tree(s, kind).double()
+    taps, grads = br.network_taps(m, (x1.double(), x2.double()), y.double(), br.MODEL2, cls_rows=cls_rows, fold=fold, opt=opt)
+    ref = br.restart_all(m, taps, br.EXACT, opt)
+    assert br.exempt_labels(ref) == []
+    rows = br.compare(br.observed(taps, grads, s), ref, br.restart_all(m, taps, br.MODEL, opt))
+    print(br.table(rows))
+    assert br.failures(rows) == []
+
+
+class _ForwardOnly(torch.autograd.Function):
+    """t * mult in the forward; the gradient comes back multiplied by ``back`` instead."""
+
+    @staticmethod
+    def forward(ctx, t, mult, back):
+        ctx.back = back
+        return t * mult
+
+    @staticmethod
+    def backward(ctx, g):
+        return g * ctx.back, None, None
+
+
+class _GatherLosingAPair(torch.autograd.Function):
+    """kv[index]; the backward's per-image sum leaves pair ``skip`` out."""
+
+    @staticmethod
+    def forward(ctx, kv, index, skip):
+        ctx.index, ctx.skip, ctx.items = index, skip, kv.shape[0]
+        return kv[index]
+
+    @staticmethod
+    def backward(ctx, g):
+        g = g.clone()
+        g[ctx.skip] = 0
+        return torch.zeros((ctx.items,) + tuple(g.shape[1:]), dtype=g.dtype).index_add_(0, ctx.index, g), None, None
+
+
+def _failing(vited, name, stages=None, alter=None, cls_rows=False, fold=False):
+    """The labels at which MODEL, run as the implementation of option case ``name`` with a defect planted in it (``stages(m, opt)``:
+    replacement stages; ``alter(taps, grads, opt)``: what it recorded, rewritten), misses the bound - after the same implementation
+    without the defect has passed everywhere.  Returns (labels, the failure lines)."""
+    kind, s, images, pairs, _, opt, (x1, x2, y) = br.option_case(name, vited.ops)
+    m = br.build_tree(s, kind).double()
+    out = []
+    for defect in (False, True):
+        taps, grads = br.network_taps(m, (x1.double(), x2.double()), y.double(), br.MODEL, cls_rows=cls_rows, fold=fold, opt=opt,
+                                      stages=stages(m, opt) if defect and stages else None)
+        if defect and alter:
+            alter(taps, grads, opt)
+        rows = br.compare(br.observed(taps, grads, s), br.restart_all(m, taps, br.EXACT, opt), br.restart_all(m, taps, br.MODEL, opt))
+        out.append(br.failures(rows))
+    assert out[0] == []
+    print('\n'.join(out[1]))
+    return {line.split(': ', 1)[0] for line in out[1]}, out[1]
+
+
+def _params(prefix, *names):
+    return {f'g:{prefix}.{n}.{p}' for n in names for p in ('weight', 'bias')}
+
+
+def test_planted_scale_missing_from_a_branch_gradient(vited):
+    """Encoder block 1's attention branch scaled in the forward, its incoming gradient not: that block's dx and that branch's parameters
+    (the MLP branch runs first in the backward and saw the right gradient)."""
+    def stages(m, opt):
+        def block(R, blk, x, nh, scales=None):
+            if blk is not m.blocks[1]:
+                return br.encoder_block(R, blk, x, nh, scales)
+            a = R.branch(br.self_attention(R, blk.attn, R.ln(vo._ln(blk.norm1, x)), nh))
+            x = x + _ForwardOnly.apply(a, scales[0].view(-1, 1, 1), 1.0)
+            return br._add(R, x, br._mlp(R, blk.mlp, R.ln(vo._ln(blk.norm2, x))), scales, 1)
+        return dict(encoder_block=block)
+
+    labels, _ = _failing(vited, 'droppath', stages)
+    assert labels == {'enc1.dx'} | _params('blocks.1', 'norm1', 'attn.qkv', 'attn.proj')
+
+
+def test_planted_scales_of_the_neighbouring_branch(vited):
+    """Decoder block 1's cross-attention branch scaled with its self-attention branch's scales: that block - its output, its dx, its
+    d(kv), and the parameters of all three branches, since the MLP ran on a wrong input and the self-attention received a wrong
+    gradient - and nothing else: every other stage saw what block 1 really produced (keys / values computed ahead, so d(features)
+    restarts from the block's own d(kv))."""
+    def stages(m, opt):
+        assert not torch.equal(opt.dec[1, 0], opt.dec[1, 1])
+
+        def block(R, blk, x, c, nh, store=None, scales=None, index=None):
+            if blk is m.cross_blocks[1]:
+                scales = torch.stack((scales[0], scales[0], scales[2]))
+            return br.decoder_block(R, blk, x, c, nh, store, scales, index)
+        return dict(decoder_block=block)
+
+    labels, _ = _failing(vited, 'droppath', stages, cls_rows=True, fold=True)
+    own = {'dec1.y', 'dec1.dx', 'dec1.dkv'} | _params('cross_blocks.1', 'norm1', 'attn.qkv', 'attn.proj', 'norm_cross', 'cross_attn.q',
+                                                      'cross_attn.proj', 'norm2', 'mlp.fc1', 'mlp.fc2')
+    # every tensor of the block but one: d fc2.bias is the column sum of s_mlp dy, which no other branch enters
+    assert labels == own - {'g:cross_blocks.1.mlp.fc2.bias'}
+
+
+def test_planted_position_gradient_one_row_off(vited):
+    """d(pos_embed) of the image-2 stream scattered to row keep instead of 1 + keep (the prefix slot forgotten): pos_embed alone."""
+    def alter(taps, grads, opt):
+        dx = taps['dec.dx.0'][:, 1:]
+        rows = torch.zeros_like(grads['pos_embed'][0])
+        for b in range(dx.shape[0]):
+            rows.index_add_(0, opt.keep2[b], dx[b])
+            rows.index_add_(0, 1 + opt.keep2[b], -dx[b])
+        grads['pos_embed'] = grads['pos_embed'] + rows[None]
+
+    labels, lines = _failing(vited, 'patchdrop', alter=alter)
+    assert labels == {'g:pos_embed'} and any('rowmax' in line for line in lines)
+
+
+def test_planted_position_mask_missing_from_the_gradient(vited):
+    """The streams multiplied by mask * scale, their gradients by the scale alone: the embed stage's four parameters."""
+    def stages(m, opt):
+        def embed(R, m_, img, with_cls, keep=None, mult=None):
+            return _ForwardOnly.apply(br.embed(R, m_, img, with_cls, keep), mult, float(mult.max()))
+        return dict(embed=embed)
+
+    labels, _ = _failing(vited, 'posdrop', stages)
+    assert labels == {'g:pos_embed', 'g:cls_token', 'g:patch_embed.proj.weight', 'g:patch_embed.proj.bias'}
+
+
+@pytest.mark.parametrize('fold', [False, True])
+def test_planted_pair_missing_from_an_image_sum(vited, fold):
+    """The last of image 3's five pairs left out of decoder block 1's per-image sum.  Keys / values per block (the running d(context)):
+    that block's term, the total - by their worst rows - and the block's own norm_context / kv gradients, which the same sum feeds.
+    Keys / values computed ahead: the block's d(kv output) alone - the context stage restarts from what the block really handed it."""
+    def stages(m, opt):
+        skip = max(p for p, i in enumerate(opt.index.tolist()) if i == 3)
+        assert skip == 10
+
+        def lossy(R, kv, index):
+            return _GatherLosingAPair.apply(R.seg(kv), index, skip)
+
+        def block(R, blk, x, c, nh, store=None, scales=None, index=None):
+            return br.decoder_block(R, blk, x, c, nh, store, scales, index, gather=lossy if blk is m.cross_blocks[1] else br.gather_kv)
+        return dict(decoder_block=block)
+
+    labels, lines = _failing(vited, 'indexed', stages, fold=fold)
+    if fold:
+        assert labels == {'dec1.dkv'}
+    else:
+        assert labels == {'dec1.dctx', 'context.dfeats'} | _params('cross_blocks.1', 'norm_context', 'cross_attn.kv')
+    for label in labels - _params('cross_blocks.1', 'norm_context', 'cross_attn.kv'):
+        assert any(line.startswith(label + ': rowmax') for line in lines), label
 
 
 @pytest.fixture(scope='module')
