@@ -213,6 +213,28 @@ int vited_michigan_windows_u8(const uint8_t* store, const int64_t* img_off, cons
 int vited_michigan_blur_gray_u8(const uint8_t* in, const int* flags, const int* weights, uint8_t* out, int64_t batch, int img_size,
                                 void* stream);
 
+/* Pillow's Image.resize((Rw, Rh), BILINEAR) for 8-bit RGB at any scale, antialiased where it shrinks, from images that stay on the
+ * device (csrc/resample_u8.hip, the rule in csrc/resample_u8.h): what transforms.Resize does in
+ * TwoImgSyncEval.normalize (pajigsaw.py, evaluation.py) and in michigan.py's evaluation transform.  All arrays are DEVICE memory.
+ *   store / img_off / img_hw / image   as for vited_div2k_regions_u8 (indices are clamped)
+ *   windows   int32 [batch, 4] = (top, left, h, w) in image coordinates, or null: the whole image.  A window may reach outside the
+ *             image (top, left may be negative); pixels outside it are `fill` (0..255) in all three channels
+ *   xtab      int32 [ncx, Rw, 2 + ksx]: per class of window width and per output column (first tap in window coordinates, tap count,
+ *             ksx 22-bit fixed-point weights, unused ones 0) - Pillow's precompute_coeffs + normalize_coeffs_8bpc for w -> Rw, computed
+ *             in fp64 by the caller; xcls int32 [batch] names each sample's class (clamped).  ytab / ycls / ncy / ksy likewise for
+ *             h -> Rh.  max_h, max_w: the largest window the tables were made for; they size the LDS band and bound the ratio
+ *   T(x, r) = clip8((2^21 + sum_j kx[x][j] Wd(first_x[x] + j, r)) >> 22),  R(x, y) = clip8((2^21 + sum_j ky[y][j] T(x, first_y[y] + j)) >> 22)
+ *   out       uint8: sample b's planes [3, S, S] at out + b * out_bs bytes, R at (x + crop_left, y + crop_top); every byte of them is
+ *             written on every call, nothing else is
+ * No allocation, copy or synchronisation.  A first tap or count outside its range is clamped or skipped, never followed.
+ * VITED_ERR_BAD_ARG: a null pointer other than windows, a misaligned table, batch outside 1..65535, a non-positive size, fill outside
+ * 0..255, a crop that leaves the resized image, out_bs < 3 S^2 with batch > 1 (samples would overlap), ksx / ksy below
+ * 2 ceil(max(max_len / out_len, 1)) + 1.  VITED_ERR_UNSUPPORTED: Rh or Rw above 1024, max_h > 8 Rh or max_w > 8 Rw, ksx or ksy above 17. */
+int vited_resample_u8(const uint8_t* store, const int64_t* img_off, const int* img_hw, int n_images, const int* image, const int* windows,
+                      int fill, const int* xtab, const int* xcls, int ncx, int ksx, const int* ytab, const int* ycls, int ncy, int ksy,
+                      int max_h, int max_w, int Rh, int Rw, int crop_top, int crop_left, int img_size, uint8_t* out, int64_t out_bs,
+                      int64_t batch, void* stream);
+
 /* out[b, r] = (out_dtype) in[b, row_offset + r] for r < rows: drops the cls row of a token-gradient
  * tensor before the patch-embed weight gradient. in is fp32 [batch, in_rows, dim]. */
 int vited_slice_rows_cast(const float* in, void* out, int out_dtype, int64_t batch, int64_t in_rows,

@@ -4,15 +4,17 @@ instead of c10d's 25 MB DDP buckets, bf16 autocast instead of fp16 + GradScaler,
 and the input pipelines and evaluation paths on the device; loading from disk, logging and checkpoints stay in the reference.
 
 One concern per module: ``distributed`` (process group, flat gradient exchange), ``train`` (optimizer, ``TrainStep``, meters),
-``feeds`` (prefetcher; DIV2K, HisFrag and Michigan device loaders), ``mining`` (pair mining and its loss), ``similarity`` (the
+``feeds`` (prefetcher; DIV2K, HisFrag, Michigan and Pajigsaw device loaders, evaluation sources), ``mining`` (pair mining and its loss), ``similarity`` (the
 streamed similarity matrix), ``metrics`` (retrieval, group mAP / Pr@k, geshaem, classifier validation), ``puzzle`` (with ``puzzle_mixed``), ``relevancy``,
 ``lr_finder`` (the learning-rate range test).
 Every public name is re-exported here, so callers write ``engine.TrainStep``.  State that is rebound at run time is not: read
 and set ``engine.train._CAPTURE_MODE`` there."""
 from .distributed import FlatGradients, broadcast_parameters, configure_ddp  # noqa: F401
-from .feeds import (HISFRAG_PLAN_COLUMNS, MICHIGAN_MAX_HOLES, MICHIGAN_PLAN_COLUMNS, DevicePrefetcher, Div2kDeviceLoader,  # noqa: F401
-                    Div2kImageStore, HisfragDeviceLoader, HisfragPlan, MichiganDeviceLoader, MichiganPlan, assemble_pairs,
-                    div2k_augment_plan, div2k_pair_plan, hisfrag_augment_plan, hisfrag_feed, michigan_augment_plan, michigan_feed)
+from .feeds import (HISFRAG_PLAN_COLUMNS, MICHIGAN_MAX_HOLES, MICHIGAN_PLAN_COLUMNS, CenterCropSource, DevicePrefetcher,  # noqa: F401
+                    Div2kDeviceLoader, Div2kImageStore, HisfragDeviceLoader, HisfragPlan, MichiganDeviceLoader, MichiganEvalSource,
+                    MichiganPlan, PajigsawDeviceLoader, PajigsawIndex, assemble_pairs, div2k_augment_plan, div2k_pair_plan,
+                    hisfrag_augment_plan, hisfrag_feed, michigan_augment_plan, michigan_feed, pajigsaw_index, pajigsaw_pair_plan,
+                    pajigsaw_pieces, resize_images)
 from .lr_finder import LR_FINDER_MAX_ITER, LRFinderResult, LRRangeTest, find_lr  # noqa: F401
 from .metrics import (ClassificationMeters, GeshaemMetrics, MeterValue, PairScoreAggregator, PairScoreStats, RetrievalCurves,  # noqa: F401
                       RetrievalLists, ValidationResult, class_members, geshaem_pair_metrics, group_relations,

@@ -1,6 +1,7 @@
 """Input pipelines: the host prefetcher, and the DIV2K, HisFrag and Michigan pipelines on the device
 (DESIGN.md sections 16-18) - resident images, the per-batch random plans (pinned bit for bit against Pillow, cv2 and torchvision)
-and the loaders that drive the feed kernels."""
+and the loaders that drive the feed kernels - and, on Pillow's resize at any scale, the Pajigsaw loader and
+the evaluation sources of michigan.py and hisfrag.py."""
 from __future__ import annotations
 
 import collections
@@ -561,3 +562,256 @@ class MichiganDeviceLoader(HisfragDeviceLoader):
     (images uint8 [B, 3, S, S], targets int64 [B]) for ``hisfrag_prepare_data``.  Images smaller than the window are padded with
     255.  The reference runs 20 passes over the set per epoch (michigan.py:110-112): that is the caller's ``repeat``."""
     plan_columns, augment_plan, feed = MICHIGAN_PLAN_COLUMNS, staticmethod(michigan_augment_plan), staticmethod(michigan_feed)
+
+
+# ---- Pillow-exact resize from the store: the Pajigsaw loader and the evaluation feeds (pajigsaw.py, michigan.py:90-96,
+# hisfrag.py:163-211; DESIGN.md section 42)
+def _half(n: int) -> int:
+    """torchvision's crop origin int(round(n / 2.0)): Python's round, half to even."""
+    return int(round(n / 2.0))
+
+
+def _square_tables(store: Div2kImageStore, size: int):
+    """``ops.resample_tables`` of the sides of the store's square images -> ``size``, made once per (store, size)."""
+    cache = store.__dict__.setdefault('_square_tables', {})
+    if size not in cache:
+        square = store.sizes[store.sizes[:, 0] == store.sizes[:, 1]]
+        if square.shape[0] == 0:
+            raise ValueError(f'resize_images: none of the {len(store)} stored images is square')
+        cache[size] = ops.resample_tables(square[:, 0].tolist(), size, store.device)
+    return cache[size]
+
+
+def _require_square(store: Div2kImageStore, image, size: int, names=None):
+    """Resize(S) takes the shorter side to S and keeps the aspect ratio; the model takes S x S only.  ``image``: the indices that
+    will be read where the host knows them (a list or a CPU tensor), else None: then every stored image must be square."""
+    sizes = store.sizes if image is None else store.sizes[torch.as_tensor(image, dtype=torch.int64).reshape(-1).clamp(0, len(store) - 1)]
+    bad = (sizes[:, 0] != sizes[:, 1]).nonzero().flatten().tolist()
+    if bad:
+        k = bad[0] if image is None else int(torch.as_tensor(image).reshape(-1)[bad[0]])
+        name = f'image {k}' if names is None else f'{names[k]!r} (image {k})'
+        raise ValueError(f'{name} is {int(store.sizes[k, 0])} x {int(store.sizes[k, 1])}: Resize({size}) keeps its aspect ratio, and the model '
+                         f'takes square {size} x {size} images only ({len(bad)} such image(s))')
+
+
+def resize_images(store: Div2kImageStore, image, img_size: int, out: torch.Tensor | None = None) -> torch.Tensor:
+    """``TwoImgSyncEval.normalize``'s ``Resize(img_size)`` (data/transforms.py:14-18) of the stored images ``image`` (indices [n]: a
+    list, or an integer tensor on any device) -> uint8 [n, 3, S, S] on the store's device, Pillow's 8-bit bilinear resize bit for
+    bit at any scale up to 8x down (``ops.resample_u8``); ToTensor + Normalize are folded into the patch-embedding kernel.  The
+    shorter side goes to S, so a square image gives S x S; a non-square one is refused by name (indices that live on the device are
+    not read back: then every stored image must be square).  ``out``: a destination view,
+    ``pairs[:, 0]`` of a [B, 2, 3, S, S] tensor for one."""
+    S = int(img_size)
+    on_host = not torch.is_tensor(image) or not image.is_cuda
+    _require_square(store, image if on_host else None, S)
+    tables = _square_tables(store, S)
+    idx = torch.as_tensor(image).reshape(-1).to(device=store.device, dtype=torch.int32).contiguous()
+    return ops.resample_u8(store.data, store.offsets_dev, store.sizes_dev, idx, None, 0, tables, tables, S, S, 0, 0, S, out=out)
+
+
+def pajigsaw_pieces(store: Div2kImageStore, img_size: int) -> torch.Tensor:
+    """The pre-cut pieces of one puzzle (``PajigsawPieces``, one stored image per piece) at the model's size, uint8 [n, 3, S, S]:
+    what ``engine.puzzle_distances`` takes in pajigsaw.py's validation.  The reference's pieces make an 8-bit BGR -> LAB -> RGB
+    round trip through cv2 on the way; that is not reproduced: the pieces are resized as stored."""
+    return resize_images(store, list(range(len(store))), img_size)
+
+
+class PajigsawIndex(NamedTuple):
+    """``Pajigsaw.__init__``'s tables (data/datasets/pajigsaw_dataset.py:39-81) over fragment numbers: fragment f is the f-th
+    fragment with ``degree == 0`` in the file's order, which is the order a store of the fragments has.  CSR tables are a pointer
+    vector [rows + 1] and an index vector; all tensors int64."""
+    im_path: list                # [F] the fragments' files, in store order
+    im_names: list               # [m] sorted names of the images that have samples
+    fragment: torch.Tensor       # [F, 3] (image: position in im_names or -1, row, col)
+    samples: torch.Tensor        # [n] the fragments with a positive, stably sorted by (col, row)
+    pos_ptr: torch.Tensor        # [F + 1] positives of every fragment, in the reference's order
+    pos_idx: torch.Tensor
+    neg_ptr: torch.Tensor        # [F + 1] in-image negatives
+    neg_idx: torch.Tensor
+    ent_ptr: torch.Tensor        # [m + 1] ``entries`` of every image of im_names
+    ent_idx: torch.Tensor
+
+    def to(self, device):
+        return self._replace(**{k: v.to(device) for k, v in self._asdict().items() if torch.is_tensor(v)})
+
+
+def _csr(rows):
+    ptr = [0]
+    for r in rows:
+        ptr.append(ptr[-1] + len(r))
+    return torch.tensor(ptr, dtype=torch.int64), torch.tensor([v for r in rows for v in r], dtype=torch.int64)
+
+
+def pajigsaw_index(dataset: dict) -> PajigsawIndex:
+    """The parsed ``{split}.json`` of the Pajigsaw data set -> ``PajigsawIndex``, in plain Python on the host: the fragments with
+    ``degree == 0``; per fragment its positives (row or column neighbours at distance 1) and in-image negatives, skipping a second
+    fragment with ``white_percentage > 0.85`` or the same ``im_path``; the samples are the fragments with at least one positive."""
+    frags, per_image = [], {}
+    for name in dataset:
+        per_image[name] = []
+        for frag in dataset[name]['Fragment1v1Rotate90']:
+            if frag['degree'] == 0:
+                per_image[name].append(len(frags))
+                frags.append((name, frag))
+    pos, neg = [[] for _ in frags], [[] for _ in frags]
+    entries, samples = {}, []
+    for name, members in per_image.items():
+        for f in members:
+            first = frags[f][1]
+            for g in members:
+                second = frags[g][1]
+                if second['white_percentage'] > 0.85 or first['im_path'] == second['im_path']:
+                    continue
+                if first['col'] == second['col'] and abs(first['row'] - second['row']) == 1:
+                    pos[f].append(g)
+                elif first['row'] == second['row'] and abs(first['col'] - second['col']) == 1:
+                    pos[f].append(g)
+                else:
+                    neg[f].append(g)
+            if pos[f]:
+                entries.setdefault(name, []).append(f)
+                samples.append(f)
+    im_names = sorted(entries)
+    number = {name: k for k, name in enumerate(im_names)}
+    samples = sorted(samples, key=lambda f: (frags[f][1]['col'], frags[f][1]['row']))          # stable, as the reference's sort
+    fragment = torch.tensor([[number.get(name, -1), frag['row'], frag['col']] for name, frag in frags], dtype=torch.int64).reshape(-1, 3)
+    return PajigsawIndex([frag['im_path'] for _, frag in frags], im_names, fragment, torch.tensor(samples, dtype=torch.int64),
+                         *_csr(pos), *_csr(neg), *_csr([entries[name] for name in im_names]))
+
+
+def _csr_choice(ptr: torch.Tensor, idx: torch.Tensor, row: torch.Tensor, t: torch.Tensor) -> torch.Tensor:
+    """random.choice(row's list) from uniforms ``t``: element min(floor(t len), len - 1); an empty list gives some valid element of
+    ``idx`` (the caller discards it)."""
+    start, length = ptr[row], ptr[row + 1] - ptr[row]
+    pick = torch.minimum(torch.floor(t * length).to(torch.int64), length - 1).clamp_(min=0)
+    return idx[(start + pick).clamp_(max=max(idx.numel() - 1, 0))] if idx.numel() else torch.zeros_like(row)
+
+
+def pajigsaw_pair_plan(u: torch.Tensor, sample: torch.Tensor, index: PajigsawIndex):
+    """The random choices of ``Pajigsaw.__getitem__`` (pajigsaw_dataset.py:87-131) for a whole batch at once, from uniform numbers
+    ``u`` [B, 4] in [0, 1) (columns: positive draw, negative draw, the choice within the list, the other image) and the sample
+    numbers ``sample`` [B] (positions in ``index.samples``): (first int64 [B], second int64 [B], labels fp32 [B, 4]), fragments by
+    number.  Positive iff u0 < 0.75: second = positive[min(floor(u2 len), len - 1)], the label the side of ``first`` that ``second``
+    lies on (same column, first above: [0, 1, 0, 0], below: [0, 0, 0, 1]; same row, first left: [1, 0, 0, 0], right: [0, 0, 1, 0]).
+    Otherwise the label is zero and second is negative[...] by u2 if u1 < 0.5 and the fragment has negatives, else a fragment of
+    another image: image k = min(floor(u3 (m - 1)), m - 2) of the m images, stepping over the sample's own, and entries[image][...]
+    by u2 (the reference redraws until the image differs: one draw of the same distribution).  Torch operations on the device of
+    ``u``; ``index`` must live there (``index.to``)."""
+    m = len(index.im_names)
+    if m < 2:
+        raise ValueError(f'pajigsaw_pair_plan: {m} image(s) with samples: a negative pair from another image needs two (the reference '
+                         f'would draw for ever)')
+    u = u.double()
+    first = index.samples[sample.to(device=u.device, dtype=torch.int64)]
+    positive = u[:, 0] < 0.75
+    in_image = (u[:, 1] < 0.5) & (index.neg_ptr[first + 1] > index.neg_ptr[first])
+    own = index.fragment[first, 0]
+    k = torch.minimum(torch.floor(u[:, 3] * (m - 1)).to(torch.int64), torch.full_like(own, m - 2))
+    other = k + (k >= own).to(torch.int64)
+    second = torch.where(positive, _csr_choice(index.pos_ptr, index.pos_idx, first, u[:, 2]),
+                         torch.where(in_image, _csr_choice(index.neg_ptr, index.neg_idx, first, u[:, 2]),
+                                     _csr_choice(index.ent_ptr, index.ent_idx, other, u[:, 2])))
+    r1, c1, r2, c2 = index.fragment[first, 1], index.fragment[first, 2], index.fragment[second, 1], index.fragment[second, 2]
+    bin_ = torch.where(c1 == c2, torch.where(r1 < r2, 1, 3), torch.where(c1 < c2, 0, 2))
+    labels = torch.nn.functional.one_hot(bin_, 4).float() * positive.float().unsqueeze(1)
+    return first, second, labels
+
+
+class PajigsawDeviceLoader(_DeviceLoader):
+    """pajigsaw.py's training loader on the device: what ``get_dataloader('train')`` over ``Pajigsaw`` delivers, from a
+    ``Div2kImageStore`` of the fragments in ``index.im_path``'s order, without a host copy or a sync per batch.  An epoch is a
+    permutation (drawn on the device, the same on every rank) of the sample numbers, of which rank r takes every ``world``-th from
+    r on; the last incomplete batch is dropped.  Each batch: uniforms -> ``pajigsaw_pair_plan`` -> ``ops.resample_u8`` of the first
+    fragments into ``pairs[:, 0]`` and of the second ones into ``pairs[:, 1]``; it yields (pairs uint8 [B, 2, 3, S, S], labels fp32
+    [B, 4]) for ``TrainStep.step``.  The transform is ``TwoImgSyncEval.normalize`` on each fragment (the reference hands the
+    two-image transform to a one-image call, which raises; that is what it means)."""
+
+    def __init__(self, store: Div2kImageStore, index: PajigsawIndex, batch_size: int, img_size: int, rank: int = 0, world: int = 1,
+                 seed: int = 0):
+        if len(index.im_path) != len(store):
+            raise ValueError(f'the index names {len(index.im_path)} fragments, the store holds {len(store)} images')
+        if len(index.im_names) < 2:
+            raise ValueError(f'{len(index.im_names)} image(s) with samples: every sample can draw a fragment of another image, which needs '
+                             f'two (the reference would draw for ever)')
+        self.index, self.img_size = index.to(store.device), int(img_size)
+        super().__init__(store, batch_size, 1, rank, world, seed)
+        _require_square(store, None, self.img_size, index.im_path)
+        self.tables = _square_tables(store, self.img_size)
+
+    def __len__(self):
+        return self.index.samples.numel() // self.world // self.batch_size
+
+    def epoch_order(self) -> torch.Tensor:
+        """The epoch's permutation of the sample numbers (int64 on the store's device), before sharding."""
+        return torch.randperm(self.index.samples.numel(), generator=self._generator(0), device=self.store.device)
+
+    def rank_indices(self) -> torch.Tensor:
+        """[len(self), batch_size]: the sample number of every sample this rank sees in the epoch."""
+        per_rank = self.index.samples.numel() // self.world
+        mine = self.epoch_order()[self.rank::self.world][:per_rank]
+        return mine[: len(self) * self.batch_size].view(len(self), self.batch_size)
+
+    def plan(self, sample: torch.Tensor, generator: torch.Generator):
+        """One batch's draws: the three tensors of ``pajigsaw_pair_plan``."""
+        u = torch.rand(sample.numel(), 4, generator=generator, device=self.store.device)
+        return pajigsaw_pair_plan(u, sample, self.index)
+
+    def feed(self, first: torch.Tensor, second: torch.Tensor) -> torch.Tensor:
+        """Fragment numbers [B], [B] -> uint8 pairs [B, 2, 3, S, S]: two resize launches, each into its half of the pairs."""
+        S, st, t = self.img_size, self.store, self.tables
+        pairs = torch.empty(first.numel(), 2, 3, S, S, dtype=torch.uint8, device=st.device)
+        for half, frag in enumerate((first, second)):
+            ops.resample_u8(st.data, st.offsets_dev, st.sizes_dev, frag.to(torch.int32), None, 0, t, t, S, S, 0, 0, S, out=pairs[:, half])
+        return pairs
+
+    def __iter__(self):
+        g = self._generator(1 + self.rank)
+        for sample in self.rank_indices():
+            first, second, labels = self.plan(sample, g)
+            yield self.feed(first, second), labels
+
+
+class _WindowSource:
+    """An image source of ``engine.pairwise_similarity`` that serves device tensors straight from a store: a callable
+    ``(lo, hi) -> uint8 [hi - lo, 3, S, S]`` with ``__len__``; a subclass sets the per-image windows, the fill and the resize."""
+    fill = 0
+
+    def __init__(self, store: Div2kImageStore, img_size: int, resized: int, windows):
+        self.store, self.img_size, self.resized = store, int(img_size), int(resized)
+        self.crop = _half(self.resized - self.img_size)
+        self.windows = torch.tensor(windows, dtype=torch.int32).reshape(-1, 4).to(store.device)
+        self.tables = ops.resample_tables([self.img_size], self.resized, store.device)
+
+    def __len__(self):
+        return len(self.store)
+
+    def __call__(self, lo: int, hi: int) -> torch.Tensor:
+        lo, hi = int(lo), int(hi)
+        if not 0 <= lo < hi <= len(self):
+            raise IndexError(f'images {lo}..{hi} of {len(self)}')
+        st, t = self.store, self.tables
+        image = torch.arange(lo, hi, dtype=torch.int32, device=st.device)
+        return ops.resample_u8(st.data, st.offsets_dev, st.sizes_dev, image, self.windows[lo:hi], self.fill, t, t, self.resized,
+                               self.resized, self.crop, self.crop, self.img_size)
+
+
+class CenterCropSource(_WindowSource):
+    """HisFrag's evaluation transform (hisfrag.py:83-93) from the store: torchvision's ``CenterCrop(S)`` - an axis shorter than S is
+    padded with 0, (S - len) // 2 in front and (S - len + 1) // 2 behind; otherwise the crop starts at int(round((len - S) / 2.0))."""
+
+    def __init__(self, store: Div2kImageStore, img_size: int):
+        S = int(img_size)
+        origin = lambda n: -((S - n) // 2) if n < S else _half(n - S)
+        super().__init__(store, S, S, [[origin(h), origin(w), S, S] for h, w in store.sizes.tolist()])
+
+
+class MichiganEvalSource(_WindowSource):
+    """michigan.py's evaluation transform (michigan.py:90-96) from the store: ``PadCenterCrop(S, pad_if_needed, fill 255)`` - an axis
+    shorter than S is padded by S - len on both sides, then torchvision's centre crop - then ``Resize(R = int(1.15 S))`` and
+    ``CenterCrop(S)`` at int(round((R - S) / 2.0)); only the cropped region of the resized image is computed."""
+    fill = 255
+
+    def __init__(self, store: Div2kImageStore, img_size: int):
+        S = int(img_size)
+        origin = lambda n: _half(S - n) - (S - n) if n < S else _half(n - S)
+        super().__init__(store, S, int(S * 1.15), [[origin(h), origin(w), S, S] for h, w in store.sizes.tolist()])

@@ -1374,3 +1374,7 @@ from .ops_f32attn import fp32_attention_kernels, fp32_attention_supported, last_
 
 # ---- 384-column NT products with the weights in registers: the wrapper of vited_gemm_nt_wreg (csrc/gemm_nt_wreg.hip); ops_wreg.py
 from .ops_wreg import WREG_WIDTH, gemm_nt_wreg, gemm_nt_wreg_dispatch, gemm_nt_wreg_supported  # noqa: E402,F401
+
+# ---- Pillow-exact resize at any scale: the wrapper of csrc/resample_u8.hip, its tap tables and the rule in numpy live in ops_resample.py
+from .ops_resample import (RESAMPLE_MAX_OUT, RESAMPLE_MAX_RATIO, RESAMPLE_MAX_TAPS, ResampleTables, resample_image,  # noqa: E402,F401
+                           resample_ksize, resample_tables, resample_taps, resample_u8, window_image)
