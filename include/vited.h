@@ -701,6 +701,56 @@ int vited_lion_step_ema(const int64_t* desc, int count, int64_t total_tiles, con
                         float* hyper, float max_norm, int zero_grad, float* norm_out, float* workspace,
                         int64_t workspace_bytes, float* ema_flat, int64_t ema_numel, void* stream);
 
+/* Muon (Jordan et al. 2024, with torch.optim.Muon's conventions) for the 2-D tensors of the Muon groups and vited_adamw_step's rule, bit
+ * for bit from the same tile body, for every tensor of another group (all 1-D parameters, cls_token, pos_embed, the patch projection,
+ * the head): one optimizer, one flat buffer.  The rule is csrc/muon_update.h's; with c the clip coefficient, per Muon tensor [rows, cols]
+ *     g'  = g c;  buf = buf + (g' - buf)(1 - momentum);  u = nesterov ? g' + (buf - g') momentum : buf
+ *     X   = bf16(u / max(|u|_F, eps)), stored transposed when rows > cols, so that X is [m, n] with m <= n
+ *     ns_steps times:  A = bf16(X X^T);  B = bf16(ns_b A + ns_c A A);  X = bf16(ns_a X + B X)
+ *     p   = p (1 - lr weight_decay) - lr adj O,   O = X transposed back,
+ *     adj = sqrt(max(1, rows / cols)) (adjust == 0) or 0.2 sqrt(max(rows, cols)) (adjust == 1, torch's 'match_rms_adamw')
+ * bf16 operands and fp32 accumulation on the matrix cores; the only roundings to bf16 are at the three stores; the fp32 expressions of
+ * the two epilogues are separate rounded operations, never an fma.  |u|_F comes from fp32 sums in a fixed order; there are no atomics,
+ * so two runs give the same bits.
+ *   desc row     the family's; word 2 is momentum_buffer on a Muon tensor and exp_avg on an aux tensor, word 3 exp_avg_sq on an aux
+ *                tensor and unused on a Muon tensor
+ *   group words  Muon group {lr, momentum, nesterov (0 / 1), eps, weight_decay, adjust (0 / 1), kind = 1, 0}; aux group AdamW's words
+ *                with kind = 0 in word 6.  Word 0 is the rate in both.
+ * The arguments of vited_lamb_step (vited_lamb_step_ema) come first, then
+ *   tensor_tab   DEVICE int64 [count x 4]: {base of the tensor's region in the bf16 scratch in elements, or -1 for an aux tensor; mp; np;
+ *                tall (rows > cols)} with m = min(rows, cols), n = max(rows, cols), mp and np these padded up to multiples of 64.  A
+ *                region holds X0 [mp, np], X1, XT0 [np, mp], XT1, A [mp, mp], B [mp, mp]: 4 mp np + 2 mp mp elements, regions in table
+ *                order without gaps.  This table decides which rule a tensor takes.
+ *   tiles_sq     DEVICE int64 [n_sq x 8]: one row {tensor, tile row, tile column, base, mp, np, tall, 0} per 64 x 64 tile of every Muon
+ *                tensor's A (and B): n_sq = sum of (mp / 64)^2
+ *   tiles_x      DEVICE int64 [n_x x 8]: the same row per 64 x 64 tile of every Muon tensor's X: n_x = sum of (mp / 64)(np / 64)
+ *   host_meta    HOST int64 [count x 5]: {rows, cols, ndim, is_muon, group} of every row of desc, from which the entries check the
+ *                counts, the workspace and the refusals below before any launch
+ *   host_kinds   HOST int64 [groups]: the kind word of every group as hyper holds it (1 Muon, 0 aux); a tensor whose is_muon disagrees
+ *                with the kind of its group is refused, so no kernel reads one rule's group words as the other's
+ *   ns_steps, ns_a, ns_b, ns_c   the Newton-Schulz steps (1..16) and coefficients, by value: a captured update bakes them in
+ *   workspace    >= vited_muon_workspace_bytes(count, rows, cols, is_muon) (HOST int64 arrays; host-only; 0 for arguments the entries
+ *                refuse): 1028 + count + total_tiles floats padded to a multiple of 64 floats, then the bf16 scratch
+ * 6 + 3 ns_steps launches: sum of squares, decision, moments (aux tensors are finished here), one wave per tensor for |u|_F, pack, three
+ * grouped GEMM launches per step over all Muon tensors at once, apply (p, both shadows, the average, g zeroed).  g is written by a
+ * tensor's last pass only, so zero_grad == 0 leaves its bits alone.  A skipped update leaves p, buf, the moments, the shadows and the
+ * average alone and still zeroes g when zero_grad is set.
+ * VITED_ERR_BAD_ARG before any launch: a null or misaligned pointer, a Muon tensor whose ndim is not 2, ns_steps < 1 or > 16, table
+ * counts that do not follow from host_meta, a tensor whose is_muon and whose group's kind disagree, and whatever vited_lamb_step refuses.  VITED_ERR_UNSUPPORTED: a Muon tensor whose short
+ * side exceeds 1024. */
+int64_t vited_muon_workspace_bytes(int count, const int64_t* rows, const int64_t* cols, const int64_t* is_muon);
+int vited_muon_step(const int64_t* desc, int count, int64_t total_tiles, const float* grad_flat, int64_t grad_numel,
+                    float* hyper, float max_norm, int zero_grad, float* norm_out, float* workspace,
+                    int64_t workspace_bytes, void* stream, const int64_t* tiles_sq, int64_t n_sq, const int64_t* tiles_x,
+                    int64_t n_x, const int64_t* tensor_tab, const int64_t* host_meta, const int64_t* host_kinds, int groups,
+                    int ns_steps, float ns_a, float ns_b, float ns_c);
+int vited_muon_step_ema(const int64_t* desc, int count, int64_t total_tiles, const float* grad_flat, int64_t grad_numel,
+                        float* hyper, float max_norm, int zero_grad, float* norm_out, float* workspace,
+                        int64_t workspace_bytes, float* ema_flat, int64_t ema_numel, void* stream, const int64_t* tiles_sq,
+                        int64_t n_sq, const int64_t* tiles_x, int64_t n_x, const int64_t* tensor_tab,
+                        const int64_t* host_meta, const int64_t* host_kinds, int groups, int ns_steps, float ns_a, float ns_b,
+                        float ns_c);
+
 /* One step of a per-iteration learning-rate schedule on the device (misc/lr_scheduler.py through misc/engine.py:228; the rules are
  * csrc/lr_schedule.h, in fp64): one launch of one workgroup, queued behind the update it follows.
  *   t = *counter;  for g < groups: dst[first + stride * g] = (float)(lr_schedule_value(table, base[g], t) * scale[g]);  *counter = t + 1

@@ -38,15 +38,23 @@
 // vited_lion_step / vited_lion_step_ema: Lion (lion_piece), the OPT_LION instance of the tile body behind the same launches 1 and 2.
 // One moment (descriptor word 2; word 3 is 0, as for SGD):  pe = p (1 - lr wd);  p' = pe - lr sign(b1 m + (1 - b1) g');
 // m' = m + (g' - m)(1 - b2), every product rounded on its own.  12 B read (g, p, m) + 12 B written + 4 B of shadows per element.
+//
+// vited_muon_step / vited_muon_step_ema (muon.hip) launch two kernels of this file, at its end: the moments pass, whose aux tiles are the
+// OPT_ADAMW instance of the tile body, and the apply pass, its OPT_MUON instance.
 #include "common.h"
 #include "optim_update.h"
+#include "muon_update.h"
 
 #define AD_DESC_WORDS 10   // {p, g, m, v, shadow, shadow_t, rows, cols, first_tile, group}
 #define AD_HYPER_HEADER 8  // hyper[0] = updates applied (float), [1] = skip-non-finite flag, [2] = updates skipped, [3..5] = EMA decay, warmup flag, EMA updates (the *_ema entries only), [6..7] reserved; then 8 floats per group
 #define AD_GROUP_WORDS 8   // AdamW {lr, beta1, beta2, eps, weight_decay, -, -, -}; SGD {lr, momentum, nesterov, -, weight_decay, -, -, -}; Lion {lr, beta1, beta2, -, weight_decay, -, -, -}
 #define AD_PARTIALS 1024
 #define AD_RESULT_WORDS 4  // behind the partials: {norm, clip, applied, step count}
-enum { OPT_ADAMW = 0, OPT_SGD = 1, OPT_SWAP = 2, OPT_LAMB = 3, OPT_LION = 4 };
+enum { OPT_ADAMW = 0, OPT_SGD = 1, OPT_SWAP = 2, OPT_LAMB = 3, OPT_LION = 4, OPT_MUON = 5 };
+
+// What the OPT_MUON instance of the tile body needs beside the family's arguments (muon.hip): the tensor table, the bf16 scratch and
+// which of the two X images holds the result of the last Newton-Schulz step.
+struct MuonApplyArgs { const int64_t* tensor_tab; const uint16_t* scratch; int final_img; };
 
 __device__ __forceinline__ float block_sum_256(float v, float* red) {
     v = wave_sum(v);
@@ -101,11 +109,13 @@ optim_decide_kernel(float* __restrict__ ws, float* __restrict__ hyper, float max
 // One 64 x 64 tile of one parameter.  OPT_ADAMW / OPT_SGD: the update; EMA adds e' = ema_blend(d_t, e, p') on the row's slice of
 // ema_flat (at the offset of its g in grad_flat).  OPT_SWAP: p <-> e and the shadows rewritten from the value now in p (vited_ema_swap;
 // res, hyper and zero_grad unused).  OPT_LAMB: LAMB's third launch (below), p -= lr r u with r = ratio[row], m and v only read.
-// OPT_LION: Lion's update; m is its one moment, v unused (0).
+// OPT_LION: Lion's update; m is its one moment, v unused (0).  OPT_MUON: Muon's apply pass on the Muon tensors of the table (an aux
+// tensor was finished by the moments pass: its workgroups return at once), p = p (1 - lr wd) - lr adj O with O read from the scratch.
 template <int OPT, bool EMA>
 __device__ __forceinline__ void
 optim_update_tile(const int64_t* __restrict__ desc, int count, const float* __restrict__ res, const float* __restrict__ hyper,
-                  int zero_grad, float* __restrict__ ema_flat, const float* grad_flat, const float* __restrict__ ratio = nullptr) {
+                  int zero_grad, float* __restrict__ ema_flat, const float* grad_flat, const float* __restrict__ ratio = nullptr,
+                  MuonApplyArgs mu = MuonApplyArgs{}) {
     __shared__ bf16 tile[64][66];
     float clip = 1.0f, step = 0.f;
     bool applied = true;
@@ -129,6 +139,16 @@ optim_update_tile(const int64_t* __restrict__ desc, int count, const float* __re
     bf16* __restrict__ dst = (bf16*)d[4];
     bf16* __restrict__ dst_t = (bf16*)d[5];
     const int64_t rows = d[6], cols = d[7];
+    MuonCoef km = {};
+    const uint16_t* o_img = nullptr;            // Muon: the image of O in the orientation of p, leading dimension o_ld
+    int64_t o_ld = 0;
+    if constexpr (OPT == OPT_MUON) {
+        const int64_t* tt = mu.tensor_tab + (int64_t)lo * MUON_TENSOR_WORDS;
+        if (tt[0] < 0) return;                  // an aux tensor: the same decision in every thread of the workgroup
+        // wide: O is X [mp, np] itself; tall: X is O transposed, so O is the XT image [np, mp] - either way [pad(rows), pad(cols)]
+        o_img = mu.scratch + tt[0] + ((tt[3] ? 2 : 0) + mu.final_img) * tt[1] * tt[2];
+        o_ld = muon_pad(cols);
+    }
     AdamWCoef ka = {};
     SgdCoef ks = {};
     LambCoef kl = {};
@@ -140,6 +160,7 @@ optim_update_tile(const int64_t* __restrict__ desc, int count, const float* __re
         else if constexpr (OPT == OPT_LAMB) {
             if (applied) { kl = lamb_coef(hg, step); lamb_step = kl.lr * ratio[lo]; }
         } else if constexpr (OPT == OPT_LION) kn = lion_coef(hg);
+        else if constexpr (OPT == OPT_MUON) km = muon_coef(hg, rows, cols);
         else ks = sgd_coef(hg);
     }
     float* e = nullptr;                         // the row's slice of the average
@@ -178,6 +199,12 @@ optim_update_tile(const int64_t* __restrict__ desc, int count, const float* __re
             else if constexpr (OPT == OPT_SGD) sgd_piece(p, g, m, r * cols + c, n, vec && n == 4, ks, clip, zero_grad, pn);
             else if constexpr (OPT == OPT_LION) lion_piece(p, g, m, r * cols + c, n, vec && n == 4, kn, clip, zero_grad, pn);
             else if constexpr (OPT == OPT_LAMB) lamb_apply_piece(p, g, m, v, r * cols + c, n, vec && n == 4, kl, lamb_step, zero_grad, pn);
+            else if constexpr (OPT == OPT_MUON) {
+                // four padded columns of one padded row: 8-byte aligned (o_ld and c are multiples of 4) and inside the image
+                uint16_t ob[4];
+                memcpy(ob, o_img + r * o_ld + c, 8);
+                muon_apply_piece(p, g, ob, r * cols + c, n, vec && n == 4, km, zero_grad, pn);
+            }
             else swap_piece(p, e, r * cols + c, n, vec && n == 4, pn);
             if constexpr (EMA && OPT != OPT_SWAP) ema_piece(e, r * cols + c, n, vec && n == 4, dt, pn);
         }
@@ -431,3 +458,90 @@ extern "C" int vited_ema_swap(const int64_t* desc, int count, int64_t total_tile
     hipLaunchKernelGGL(ema_swap_kernel, dim3((unsigned)total_tiles), dim3(256), 0, (hipStream_t)stream, desc, count, ema_flat, grad_flat);
     return vited_check_launch();
 }
+
+// ---- Muon's two elementwise launches that share the tile body (the entries, the Newton-Schulz kernels and the rest are muon.hip's) ------
+//   muon_moments_kernel: one workgroup per 64 x 64 tile.  A tile of an aux tensor (tensor table base < 0) IS vited_adamw_step's third
+//                        launch - the OPT_ADAMW instance of optim_update_tile, skipped update and average included - so an aux tensor
+//                        gets AdamW's bits.  A tile of a Muon tensor reads g and buf, writes buf and leaves its sum of u^2 in
+//                        tile_sums[tile] (a thread adds its 16 elements one after the other, then block_sum_256); skipped: nothing.
+//   muon_apply_kernel  : the OPT_MUON instance of the tile body; aux tiles return at once.
+template <bool EMA>
+__global__ void __launch_bounds__(256)
+muon_moments_kernel(const int64_t* __restrict__ desc, int count, const float* __restrict__ res, const float* __restrict__ hyper,
+                    int zero_grad, float* __restrict__ ema_flat, const float* grad_flat, const int64_t* __restrict__ tensor_tab,
+                    float* __restrict__ tile_sums) {
+    __shared__ float red[4];
+    const int64_t blk = blockIdx.x;
+    int lo = 0, hi = count - 1;     // last descriptor whose first_tile <= blk
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (desc[(int64_t)mid * AD_DESC_WORDS + 8] <= blk) lo = mid; else hi = mid - 1;
+    }
+    if (tensor_tab[(int64_t)lo * MUON_TENSOR_WORDS] < 0) {      // aux: the same word in every thread of the workgroup
+        optim_update_tile<OPT_ADAMW, EMA>(desc, count, res, hyper, zero_grad, ema_flat, grad_flat);
+        return;
+    }
+    if (res[2] == 0.f) return;                  // skipped
+    const float clip = res[1];
+    const int64_t* d = desc + (int64_t)lo * AD_DESC_WORDS;
+    const float* g = (const float*)d[1];
+    float* buf = (float*)d[2];
+    const int64_t rows = d[6], cols = d[7];
+    const MuonCoef k = muon_coef(hyper + AD_HYPER_HEADER + d[9] * AD_GROUP_WORDS, rows, cols);
+    const int64_t t = blk - d[8], tiles_c = (cols + 63) >> 6;
+    const int64_t r0 = (t / tiles_c) << 6, c0 = (t % tiles_c) << 6;
+    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;   // 16 x 16: 4 columns x 4 rows per thread
+    const bool vec = (cols & 3) == 0 && (((uintptr_t)g | (uintptr_t)buf) & 15) == 0;
+    float su = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int64_t r = r0 + ty + 16 * j, c = c0 + tx * 4;
+        if (r < rows && c < cols) {
+            const int n = cols - c < 4 ? (int)(cols - c) : 4;
+            muon_moments_piece(g, buf, r * cols + c, n, vec && n == 4, k, clip, &su);
+        }
+    }
+    su = block_sum_256(su, red);
+    if (threadIdx.x == 0) tile_sums[blk] = su;
+}
+
+__global__ void __launch_bounds__(256)
+muon_apply_kernel(const int64_t* __restrict__ desc, int count, const float* __restrict__ res, const float* __restrict__ hyper,
+                  int zero_grad, MuonApplyArgs mu) {
+    optim_update_tile<OPT_MUON, false>(desc, count, res, hyper, zero_grad, nullptr, nullptr, nullptr, mu);
+}
+
+__global__ void __launch_bounds__(256)
+muon_apply_ema_kernel(const int64_t* __restrict__ desc, int count, const float* __restrict__ res, const float* __restrict__ hyper,
+                      int zero_grad, float* __restrict__ ema_flat, const float* grad_flat, MuonApplyArgs mu) {
+    optim_update_tile<OPT_MUON, true>(desc, count, res, hyper, zero_grad, ema_flat, grad_flat, nullptr, mu);
+}
+
+void muon_launch_head(const float* grad_flat, int64_t grad_numel, float* hyper, float max_norm, float* norm_out, float* workspace,
+                      int ema, hipStream_t s) {
+    hipLaunchKernelGGL(optim_sumsq_kernel, dim3(AD_PARTIALS), dim3(256), 0, s, grad_flat, grad_numel, workspace);
+    hipLaunchKernelGGL(optim_decide_kernel, dim3(1), dim3(256), 0, s, workspace, hyper, max_norm, norm_out, ema);
+}
+
+void muon_launch_moments(const int64_t* desc, int count, int64_t total_tiles, const float* res, const float* hyper, int zero_grad,
+                         float* ema_flat, const float* grad_flat, const int64_t* tensor_tab, float* tile_sums, hipStream_t s) {
+    if (ema_flat)
+        hipLaunchKernelGGL(muon_moments_kernel<true>, dim3((unsigned)total_tiles), dim3(256), 0, s, desc, count, res, hyper, zero_grad,
+                           ema_flat, grad_flat, tensor_tab, tile_sums);
+    else
+        hipLaunchKernelGGL(muon_moments_kernel<false>, dim3((unsigned)total_tiles), dim3(256), 0, s, desc, count, res, hyper, zero_grad,
+                           (float*)nullptr, (const float*)nullptr, tensor_tab, tile_sums);
+}
+
+void muon_launch_apply(const int64_t* desc, int count, int64_t total_tiles, const float* res, const float* hyper, int zero_grad,
+                       float* ema_flat, const float* grad_flat, const int64_t* tensor_tab, const uint16_t* scratch, int final_img,
+                       hipStream_t s) {
+    const MuonApplyArgs mu = {tensor_tab, scratch, final_img};
+    if (ema_flat)
+        hipLaunchKernelGGL(muon_apply_ema_kernel, dim3((unsigned)total_tiles), dim3(256), 0, s, desc, count, res, hyper, zero_grad,
+                           ema_flat, grad_flat, mu);
+    else
+        hipLaunchKernelGGL(muon_apply_kernel, dim3((unsigned)total_tiles), dim3(256), 0, s, desc, count, res, hyper, zero_grad, mu);
+}
+
+bool muon_ema_buffer_ok(const float* ema_flat, int64_t ema_numel, int64_t grad_numel) { return ema_buffer_ok(ema_flat, ema_numel, grad_numel); }

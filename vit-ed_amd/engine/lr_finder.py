@@ -27,7 +27,7 @@ class LRFinderResult(NamedTuple):
 
 
 class LRRangeTest:
-    """One range test on a bound fused optimizer (``optim.FlatAdamW`` / ``FlatSGD`` / ``FlatLAMB``): iteration i of group g runs at
+    """One range test on a bound fused optimizer (``optim.FlatAdamW`` / ``FlatSGD`` / ``FlatLAMB`` / ``FlatLion`` / ``FlatMuon``): iteration i of group g runs at
     ``start_g * (end_g / start_g) ** (i / num_iter)``.  A scalar ``start_lr`` / ``end_lr`` gives ``value * lr_scale`` of every group, as
     ``TrainStep.set_lr`` does; a sequence gives one value per group.
 
@@ -43,7 +43,7 @@ class LRRangeTest:
         name = type(self).__name__
         if not (hasattr(optimizer, 'hyper_lr_words') and hasattr(optimizer, 'mark_lr_on_device')):
             raise NotImplementedError(f'{name}: the rates are written on the device into the hyper-parameter array of a fused optimizer - '
-                                      f'optim.FlatLAMB / optim.FlatAdamW / optim.FlatSGD; {type(optimizer).__name__} has none (engine.build_optimizer gives the HIP optimizers '
+                                      f'optim.FlatMuon / optim.FlatLion / optim.FlatLAMB / optim.FlatAdamW / optim.FlatSGD; {type(optimizer).__name__} has none (engine.build_optimizer gives the HIP optimizers '
                                       f'for a GPU model)')
         if getattr(optimizer, '_hyper', None) is None:
             raise RuntimeError(f'{name}: the optimizer has no device hyper-parameter array yet (bind_flat first; engine.TrainStep does)')
@@ -192,7 +192,7 @@ def find_lr(step, loader, num_iter=None, start_lr=1e-7, end_lr=1e-2, smooth_f=0.
         raise ValueError(f'find_lr: the step was built with accumulation_steps {step.accum}: the sweep sets a rate per call, build it with 1')
     if not step.hip_opt:
         raise NotImplementedError(f'find_lr: the rates are written on the device into the hyper-parameter array of a fused optimizer - '
-                                  f'optim.FlatLAMB / optim.FlatAdamW / optim.FlatSGD; {type(step.optimizer).__name__} has none')
+                                  f'optim.FlatMuon / optim.FlatLion / optim.FlatLAMB / optim.FlatAdamW / optim.FlatSGD; {type(step.optimizer).__name__} has none')
     if num_iter is None:
         num_iter = len(loader)
     poll_every = int(poll_every)

@@ -42,15 +42,21 @@ def build_optimizer(config, model, capturable: bool = False, fused_hip: bool | N
     ``fused_hip=False``, the name is unknown.
 
     ``'lion'`` is ``optim.FlatLion`` with BASE_LR, BETAS, WEIGHT_DECAY and the no-decay group (EPS is unused), HIP only in the same
-    way.  The config's values are passed as they are: Lion wants a rate 3-10x smaller and a decay 3-10x larger than AdamW's."""
+    way.  The config's values are passed as they are: Lion wants a rate 3-10x smaller and a decay 3-10x larger than AdamW's.
+
+    ``'muon'`` is ``optim.FlatMuon``, HIP only in the same way, with three groups: the 2-D weights under ``blocks.*`` and
+    ``cross_blocks.*`` as the Muon group (BASE_LR, WEIGHT_DECAY, Muon's own momentum of 0.95 - OPTIMIZER.MOMENTUM is SGD's key - and
+    ``adjust_lr_fn='match_rms_adamw'``, so that the rates the configs hold for AdamW carry over); everything else that is decayed (the
+    head, the patch projection, ``pos_embed``, ``cls_token``) as an aux AdamW group with BETAS and EPS; the no-decay group as the second
+    aux group."""
     name = config.TRAIN.OPTIMIZER.NAME.lower()
     groups = param_groups_no_decay_1d(model)
     on_gpu = all(p.is_cuda for g in groups for p in g['params'])
     hip = on_gpu and (fused_hip is None or fused_hip)
-    lamb, lion = name in ('lamb', 'fused_lamb'), name == 'lion'
-    if name not in ('adamw', 'sgd') and not ((lamb or lion) and hip):
-        raise ValueError(f'unknown optimizer {name}' + (f' ({"LAMB" if lamb else "Lion"} exists as a HIP optimizer only: a GPU model and '
-                                                         f'fused_hip in (None, True))' if lamb or lion else ''))
+    lamb, lion, muon = name in ('lamb', 'fused_lamb'), name == 'lion', name == 'muon'
+    if name not in ('adamw', 'sgd') and not ((lamb or lion or muon) and hip):
+        raise ValueError(f'unknown optimizer {name}' + (f' ({"LAMB" if lamb else "Lion" if lion else "Muon"} exists as a HIP optimizer only: a GPU model and '
+                                                         f'fused_hip in (None, True))' if lamb or lion or muon else ''))
     if skip_nonfinite and not hip:
         raise ValueError('skip_nonfinite=True needs the HIP optimizers (a GPU model and fused_hip in (None, True)): the torch '
                          'optimizers have no such check')
@@ -58,6 +64,19 @@ def build_optimizer(config, model, capturable: bool = False, fused_hip: bool | N
         raise ValueError('ema_decay needs the HIP optimizers (a GPU model and fused_hip in (None, True)): the average is kept by their '
                          'update kernel')
     ema = dict(ema_decay=ema_decay, ema_warmup=ema_warmup)
+    if muon:
+        from ..optim import FlatMuon
+        decay, no_decay = (set(map(id, g['params'])) for g in groups)
+        in_blocks = {id(p) for n, p in model.named_parameters() if n.startswith(('blocks.', 'cross_blocks.'))}
+        params = [p for g in groups for p in g['params']]
+        pick = lambda keep: [p for p in params if keep(p)]
+        muon_ids = {id(p) for p in params if id(p) in decay and id(p) in in_blocks and p.ndim == 2}
+        return FlatMuon([{'params': pick(lambda p: id(p) in muon_ids), 'use_muon': True},
+                         {'params': pick(lambda p: id(p) in decay and id(p) not in muon_ids)},
+                         {'params': pick(lambda p: id(p) in no_decay), 'weight_decay': 0.}],
+                        lr=config.TRAIN.BASE_LR, momentum=0.95, nesterov=True, weight_decay=config.TRAIN.WEIGHT_DECAY,
+                        adjust_lr_fn='match_rms_adamw', betas=tuple(config.TRAIN.OPTIMIZER.BETAS), adam_eps=config.TRAIN.OPTIMIZER.EPS,
+                        model=model, skip_nonfinite=skip_nonfinite, **ema)
     if lion:
         from ..optim import FlatLion
         return FlatLion(groups, lr=config.TRAIN.BASE_LR, betas=tuple(config.TRAIN.OPTIMIZER.BETAS), weight_decay=config.TRAIN.WEIGHT_DECAY,

@@ -25,6 +25,10 @@ every tensor's trust ratio needs two norms over the whole tensor before any elem
 
 ``FlatLion`` is Lion (Chen et al. 2023, with timm's ``Lion`` conventions) on the same base - ``vited_lion_step``: the three launches of
 ``FlatAdamW`` with one moment, ``p -= lr sign(b1 m + (1 - b1) g)`` after the decoupled decay, every product rounded on its own.
+
+``FlatMuon`` is Muon (Jordan et al. 2024, with ``torch.optim.Muon``'s conventions) on the same base - ``vited_muon_step``: the momentum of
+every 2-D tensor of a ``use_muon=True`` group is orthogonalised by Newton-Schulz steps on the matrix cores, all tensors sharing every
+launch; every other group takes ``FlatAdamW``'s rule in the same update.
 """
 from __future__ import annotations
 
@@ -116,18 +120,27 @@ class _FlatOptimizer(torch.optim.Optimizer):
             self._bind_ema(ema_before)
         for p, off in zip(flat.params, flat.offsets):
             st = self.state[p] if (self._state_at_bind or p in self.state) else {}
-            for n in self._state_names:
-                old = st.get(n)
+            for key, n in self._state_keys(p):
+                old = st.get(key)
                 if old is None and not self._state_at_bind:
                     continue                                 # no state yet (or a loaded None): the zero the buffer holds
                 new = self._bufs[n][off: off + p.numel()].view_as(p)
                 if old is not None and old.data_ptr() != new.data_ptr():
                     new.copy_(old)
-                st[n] = new
+                st[key] = new
         self._after_bind()
 
     def _after_bind(self):
         pass
+
+    def _state_keys(self, p):
+        """((key in ``state[p]``, name of the flat buffer it views), ...) of parameter ``p``: the same for every parameter, unless a
+        subclass keeps different state on different tensors (``FlatMuon``)."""
+        return tuple((n, n) for n in self._state_names)
+
+    def _entry_extras(self):
+        """What ``_entry`` takes behind the stream (``FlatMuon``: the tile tables, the steps and the coefficients)."""
+        return ()
 
     def _new_workspace(self, flat, dev):
         """The workspace of ``_entry`` for ``flat``, allocated by ``bind_flat`` before the descriptor table exists."""
@@ -373,7 +386,7 @@ class _FlatOptimizer(torch.optim.Optimizer):
         entry, ema = (self._entry, ()) if self._ema_decay is None else (self._entry + '_ema', (self._ema.data_ptr(), self._ema.numel()))
         _lib.call(entry, desc.data_ptr(), desc.shape[0], self._tiles, self.flat.flat.data_ptr(), self.flat.flat.numel(),
                   self._hyper.data_ptr(), float(max_norm) if max_norm else 0.0, int(zero_grad), self._norm.data_ptr(), self._ws.data_ptr(),
-                  self._ws.numel() * 4, *ema, torch.cuda.current_stream().cuda_stream)
+                  self._ws.numel() * 4, *ema, torch.cuda.current_stream().cuda_stream, *self._entry_extras())
         if not capturing:
             self._publish_update()
         return self._norm[0]
@@ -613,6 +626,275 @@ class FlatLion(_FlatOptimizer):
                 if st.get('exp_avg') is not None:
                     st['exp_avg'] = st['exp_avg'].clone()
             self._bufs['exp_avg'].zero_()
+            self.bind_flat(flat)
+
+
+MUON_GRANULE, MUON_MAX_SHORT_SIDE, MUON_TILE_WORDS = 64, 1024, 8
+
+
+def muon_layout(shapes, is_muon, group_of=None):
+    """The workspace layout and the host side of ``vited_muon_step``'s tables for parameters of ``shapes`` (in flat-buffer order), of
+    which ``is_muon[i]`` says whether tensor ``i`` belongs to a Muon group and ``group_of[i]`` (default: 0 everywhere) names its group.  A Muon tensor ``[rows, cols]`` has ``m = min``, ``n = max``
+    of the two, padded up to the GEMM granule of 64 as ``mp``, ``np``; its region of the bf16 scratch holds ``X0 [mp, np]``, ``X1``,
+    ``XT0 [np, mp]``, ``XT1``, ``A [mp, mp]``, ``B [mp, mp]``.  Returns a dict:
+
+    ``meta``        ``[rows, cols, ndim, is_muon, group]`` per tensor (the HOST table the entry checks)
+    ``tensor_tab``  ``[base, mp, np, tall]`` per tensor, ``base`` in bf16 elements from the start of the scratch, -1 for an aux tensor
+    ``tiles_sq``    ``[tensor, tile row, tile column, base, mp, np, tall, 0]`` per 64 x 64 tile of every Muon tensor's ``A``
+    ``tiles_x``     the same row per 64 x 64 tile of every Muon tensor's ``X``
+    ``total_tiles`` the update's 64 x 64 tiles over all tensors; ``float_words``: the fp32 words in front of the scratch;
+    ``scratch_elems``: the bf16 elements of the scratch; ``nbytes``: what ``vited_muon_workspace_bytes`` returns."""
+    meta, tensor_tab, tiles_sq, tiles_x, total, base = [], [], [], [], 0, 0
+    group_of = [0] * len(is_muon) if group_of is None else list(group_of)
+    for i, (shape, mu) in enumerate(zip(shapes, is_muon)):
+        shape = tuple(int(d) for d in shape)
+        rows = shape[0] if len(shape) >= 2 else 1
+        numel = 1
+        for d in shape:
+            numel *= d
+        cols = numel // rows
+        meta.append([rows, cols, len(shape), 1 if mu else 0, int(group_of[i])])
+        total += ((rows + 63) // 64) * ((cols + 63) // 64)
+        if not mu:
+            tensor_tab.append([-1, 0, 0, 0])
+            continue
+        if len(shape) != 2:
+            raise ValueError(f'Muon takes 2-D tensors only: tensor {i} has the shape {shape}')
+        m, n, tall = min(rows, cols), max(rows, cols), int(rows > cols)
+        if m > MUON_MAX_SHORT_SIDE:
+            raise ValueError(f'Muon: tensor {i} of shape {shape} has a short side above {MUON_MAX_SHORT_SIDE}, the limit of the scratch layout')
+        mp, np_ = -(-m // MUON_GRANULE) * MUON_GRANULE, -(-n // MUON_GRANULE) * MUON_GRANULE
+        tensor_tab.append([base, mp, np_, tall])
+        tiles_sq += [[i, ti, tj, base, mp, np_, tall, 0] for ti in range(mp // 64) for tj in range(mp // 64)]
+        tiles_x += [[i, ti, tj, base, mp, np_, tall, 0] for ti in range(mp // 64) for tj in range(np_ // 64)]
+        base += 4 * mp * np_ + 2 * mp * mp
+    words = -(-(1028 + len(meta) + total) // 64) * 64
+    return dict(meta=meta, tensor_tab=tensor_tab, tiles_sq=tiles_sq, tiles_x=tiles_x, total_tiles=total, float_words=words,
+                scratch_elems=base, nbytes=4 * words + 2 * base)
+
+
+class FlatMuon(_FlatAdamMoments):
+    """Muon (Jordan et al. 2024) with ``torch.optim.Muon``'s conventions in the fused update - ``vited_muon_step`` /
+    ``vited_muon_step_ema``, the rule is csrc/muon_update.h's.  A param group with ``use_muon=True`` is a Muon group and takes 2-D tensors
+    only; with ``c`` the step's clip coefficient and ``(a, b, cc) = ns_coefficients``, per tensor ``[rows, cols]``::
+
+        g'  = g c;  buf = buf + (g' - buf)(1 - momentum);  u = g' + (buf - g') momentum if nesterov else buf
+        X   = bf16(u / max(|u|_F, eps))                      transposed when rows > cols
+        ns_steps times:  A = bf16(X X^T);  B = bf16(b A + cc A A);  X = bf16(a X + B X)
+        p   = p (1 - lr wd) - lr adj X                       adj = sqrt(max(1, rows / cols)), or 0.2 sqrt(max(rows, cols)) with
+                                                             adjust_lr_fn='match_rms_adamw'
+
+    Every other group is an aux group and takes ``FlatAdamW``'s rule, bit for bit, with ``betas`` and ``adam_eps`` - all 1-D parameters,
+    ``cls_token``, ``pos_embed``, the patch projection, the head: Jordan's ``MuonWithAuxAdam`` in one optimizer and one flat buffer.  The
+    products of all Muon tensors share ``3 ns_steps`` launches.  ``ns_steps`` and ``ns_coefficients`` are fixed at construction (a
+    captured update bakes the launch count in); every group value can change between updates without a recapture.
+
+    ``state_dict()``: a Muon tensor carries ``momentum_buffer`` (``torch.optim.Muon``'s key), an aux tensor ``step``, ``exp_avg``,
+    ``exp_avg_sq``.  ``load_state_dict`` also takes a ``FlatAdamW`` / ``FlatLAMB`` / ``FlatLion`` checkpoint over the same groups of
+    parameters - on a Muon tensor its ``exp_avg``, the same kind of average of the gradients, becomes ``momentum_buffer`` - and a
+    ``torch.optim.Muon`` state.  A checkpoint written under ``build_optimizer('adamw' | 'lamb' | 'lion')``, which has two groups where
+    ``build_optimizer('muon')`` has three, is regrouped by the parameters' order in ``model`` (``_regrouped``), so a run may switch to
+    Muon on resume.  Both flat state buffers span all parameters: ``exp_avg_sq`` is
+    allocated over the Muon tensors too and never touched there (4 B per Muon parameter, 85 MB on config A's).  Everything else - shadows, graph replay, device-stepped rates, skipped updates, the parameter average -
+    is ``_FlatOptimizer``'s."""
+    _entry = 'vited_muon_step'
+    _ADJUST = {None: 0.0, 'original': 0.0, 'match_rms_adamw': 1.0}
+
+    def __init__(self, params, lr=1e-3, momentum=0.95, nesterov=True, weight_decay=0.1, ns_steps=5,
+                 ns_coefficients=(3.4445, -4.7750, 2.0315), eps=1e-7, adjust_lr_fn=None, betas=(0.9, 0.999), adam_eps=1e-8, model=None,
+                 skip_nonfinite=False, ema_decay=None, ema_warmup=False):
+        if not 0.0 <= lr:
+            raise ValueError(f'Invalid learning rate: {lr}')
+        if not 0.0 <= momentum < 1.0:
+            raise ValueError(f'Invalid momentum value: {momentum}')
+        if not 0.0 <= weight_decay:
+            raise ValueError(f'Invalid weight_decay value: {weight_decay}')
+        if not 0.0 <= eps or not 0.0 <= adam_eps:
+            raise ValueError(f'Invalid epsilon value: {eps if not 0.0 <= eps else adam_eps}')
+        if isinstance(ns_steps, bool) or int(ns_steps) != ns_steps or not 1 <= ns_steps <= 16:
+            raise ValueError(f'Invalid ns_steps: {ns_steps} (an integer in [1, 16])')
+        ns_coefficients = tuple(float(v) for v in ns_coefficients)
+        if len(ns_coefficients) != 3:
+            raise ValueError(f'Invalid ns_coefficients: {ns_coefficients} (exactly 3 values)')
+        if adjust_lr_fn not in self._ADJUST:
+            raise ValueError(f'Invalid adjust_lr_fn: {adjust_lr_fn!r} (None, \'original\' or \'match_rms_adamw\')')
+        betas = tuple(betas)
+        if len(betas) != 2 or not all(0.0 <= b < 1.0 for b in betas):
+            raise ValueError(f'Invalid beta parameters: {betas}')
+        defaults = dict(lr=lr, momentum=momentum, nesterov=bool(nesterov), weight_decay=weight_decay, eps=eps, adjust_lr_fn=adjust_lr_fn,
+                        betas=betas, adam_eps=adam_eps, use_muon=False)
+        super().__init__(params, defaults, model, skip_nonfinite, ema_decay, ema_warmup)
+        self._ns_steps, self._ns_coefficients = int(ns_steps), ns_coefficients
+        self._mu = None                # the device tables and the host tables of the current binding
+        self._muon_set = None          # ids of the Muon groups' parameters, gathered once per binding and per load
+        names = {id(p): n for n, p in model.named_parameters()} if hasattr(model, 'named_parameters') else {}
+        for gi, g in enumerate(self.param_groups):
+            self._check_group(g)
+            if g['use_muon']:
+                for i, p in enumerate(g['params']):
+                    if p.ndim != 2:
+                        raise ValueError(f'FlatMuon: {names.get(id(p), f"parameter {i} of group {gi}")} has the shape {tuple(p.shape)}; a '
+                                         f'Muon group (use_muon=True) takes 2-D tensors only - put it into an aux group')
+
+    ns_steps = property(lambda self: self._ns_steps)
+    ns_coefficients = property(lambda self: self._ns_coefficients)
+
+    @classmethod
+    def _check_group(cls, g):
+        if g['adjust_lr_fn'] not in cls._ADJUST:
+            raise ValueError(f'Invalid adjust_lr_fn: {g["adjust_lr_fn"]!r} (None, \'original\' or \'match_rms_adamw\')')
+        if not 0.0 <= g['momentum'] < 1.0:
+            raise ValueError(f'Invalid momentum value: {g["momentum"]}')
+
+    def _group_words(self, g):
+        self._check_group(g)
+        if g['use_muon']:
+            return [float(g['lr']), float(g['momentum']), 1.0 if g['nesterov'] else 0.0, float(g['eps']), float(g['weight_decay']),
+                    self._ADJUST[g['adjust_lr_fn']], 1.0, 0.]
+        return [float(g['lr']), float(g['betas'][0]), float(g['betas'][1]), float(g['adam_eps']), float(g['weight_decay']), 0., 0., 0.]
+
+    def _muon_ids(self):
+        return {id(p) for g in self.param_groups if g['use_muon'] for p in g['params']}
+
+    def _after_bind(self):
+        super()._after_bind()
+        self._muon_set = None          # the next binding gathers the ids again (add_param_group may have come between)
+
+    def _state_keys(self, p):
+        if self._muon_set is None:
+            self._muon_set = self._muon_ids()
+        if id(p) in self._muon_set:
+            return (('momentum_buffer', 'exp_avg'),)
+        return (('exp_avg', 'exp_avg'), ('exp_avg_sq', 'exp_avg_sq'))
+
+    def _new_workspace(self, flat, dev):
+        # the tables depend on the parameters' shapes and groups alone, so they are built, and uploaded, once per binding, with the
+        # workspace they describe
+        mine = self._muon_ids()
+        group_of = {id(p): gi for gi, g in enumerate(self.param_groups) for p in g['params']}
+        lay = muon_layout([p.shape for p in flat.params], [id(p) in mine for p in flat.params], [group_of[id(p)] for p in flat.params])
+        meta = torch.tensor(lay['meta'], dtype=torch.int64)
+        kinds = torch.tensor([1 if g['use_muon'] else 0 for g in self.param_groups], dtype=torch.int64)     # word 6 of _group_words
+        rows, cols, kind = (meta[:, j].contiguous() for j in (0, 1, 3))         # alive across the call that reads them
+        nbytes = _lib.load().vited_muon_workspace_bytes(len(lay['meta']), rows.data_ptr(), cols.data_ptr(), kind.data_ptr())
+        if nbytes != lay['nbytes']:
+            raise RuntimeError(f'FlatMuon: the library sizes the workspace at {nbytes} bytes, the layout at {lay["nbytes"]}')
+        table = lambda rows, width: torch.tensor(rows, dtype=torch.int64).reshape(-1, width).to(dev)
+        self._mu = dict(meta=meta, kinds=kinds, float_words=lay['float_words'], tensor_tab=table(lay['tensor_tab'], 4), tiles_sq=table(lay['tiles_sq'], MUON_TILE_WORDS),
+                        tiles_x=table(lay['tiles_x'], MUON_TILE_WORDS))
+        return torch.zeros(nbytes // 4, dtype=torch.float32, device=dev)
+
+    def orthogonalized(self, p):
+        """O of Muon tensor ``p`` as the latest applied update of this binding left it in the scratch: a bf16 copy shaped like ``p``
+        (one device copy; what the apply pass read)."""
+        if self.flat is None:
+            raise RuntimeError('FlatMuon.orthogonalized: call bind_flat(FlatGradients) first (engine.TrainStep does)')
+        i = next(k for k, q in enumerate(self.flat.params) if q is p)
+        base, mp, np_, tall = self._mu['tensor_tab'][i].tolist()
+        if base < 0:
+            raise ValueError('FlatMuon.orthogonalized: not a tensor of a Muon group')
+        rp, cp = (np_, mp) if tall else (mp, np_)
+        at = base + ((2 if tall else 0) + (self._ns_steps & 1)) * mp * np_
+        scratch = self._ws[self._mu['float_words']:].view(torch.bfloat16)
+        return scratch[at: at + rp * cp].view(rp, cp)[: p.shape[0], : p.shape[1]].clone()
+
+    def _entry_extras(self):
+        mu = self._mu
+        return (mu['tiles_sq'].data_ptr(), mu['tiles_sq'].shape[0], mu['tiles_x'].data_ptr(), mu['tiles_x'].shape[0],
+                mu['tensor_tab'].data_ptr(), mu['meta'].data_ptr(), mu['kinds'].data_ptr(), mu['kinds'].numel(), self._ns_steps, *self._ns_coefficients)
+
+    def state_dict(self):
+        sd = torch.optim.Optimizer.state_dict(self)
+        n = self.num_updates
+        for st in sd['state'].values():
+            if 'momentum_buffer' not in st:
+                st['step'] = torch.tensor(float(n))
+        return sd
+
+    def _regrouped(self, state_dict):
+        """``state_dict`` of an optimizer that held the same parameters in fewer groups, each of them a union of whole groups of this
+        one with its parameters in the model's order (what ``engine.build_optimizer`` builds under every other name: the decayed group
+        is the Muon group and the decayed aux group together), rewritten over this optimizer's groups.  Which groups were united is
+        found from the group sizes and the shapes of the state tensors; none or several fits are a ``ValueError``."""
+        import itertools
+        name = type(self).__name__
+        if not hasattr(self._model, 'named_parameters'):
+            raise ValueError(f'{name}.load_state_dict: the checkpoint has {len(state_dict["param_groups"])} parameter groups, this optimizer '
+                             f'{len(self.param_groups)}; regrouping it needs the order of the parameters (build the optimizer with model=...)')
+        rank = {id(p): k for k, (_, p) in enumerate(self._model.named_parameters())}
+        theirs, state = state_dict['param_groups'], state_dict['state']
+        fits = []
+        for assign in itertools.product(range(len(theirs)), repeat=len(self.param_groups)):
+            index, ok = {}, True
+            for j, g in enumerate(theirs):
+                members = sorted((p for gi, mg in enumerate(self.param_groups) if assign[gi] == j for p in mg['params']), key=lambda p: rank.get(id(p), -1))
+                if len(members) != len(g['params']) or any(id(p) not in rank for p in members):
+                    ok = False
+                    break
+                for p, k in zip(members, g['params']):
+                    shapes = [tuple(v.shape) for v in state.get(k, {}).values() if torch.is_tensor(v) and v.dim() > 0]
+                    ok = ok and all(s == tuple(p.shape) for s in shapes)
+                    index[id(p)] = k
+            if ok:
+                fits.append((assign, index))
+        if len(fits) != 1:
+            raise ValueError(f'{name}.load_state_dict: the checkpoint\'s {len(theirs)} groups of {[len(g["params"]) for g in theirs]} parameters '
+                             f'can be spread over this optimizer\'s groups of {[len(g["params"]) for g in self.param_groups]} in {len(fits)} ways '
+                             f'(exactly one is needed)')
+        assign, index = fits[0]
+        groups, new_state, at = [], {}, 0
+        for gi, mg in enumerate(self.param_groups):
+            ids = list(range(at, at + len(mg['params'])))
+            at += len(ids)
+            groups.append({**{k: v for k, v in theirs[assign[gi]].items() if k != 'params'}, 'params': ids})
+            for p, k in zip(mg['params'], ids):
+                if index[id(p)] in state:
+                    new_state[k] = state[index[id(p)]]
+        return {'state': new_state, 'param_groups': groups}
+
+    def load_state_dict(self, state_dict):
+        """Accepts this class's state, that of ``FlatAdamW`` / ``FlatLAMB`` / ``FlatLion`` / ``torch.optim.AdamW`` over the same groups of
+        parameters (on a Muon tensor ``exp_avg`` becomes ``momentum_buffer``; ``exp_avg_sq`` and ``step`` are dropped there) and that of
+        ``torch.optim.Muon``, before or after ``bind_flat``.  Groups of a foreign checkpoint give their rate and decay (and, where they
+        have them, the momentum words on a Muon group and ``betas`` / ``eps`` on an aux group); which group is a Muon group is never
+        loaded.  A checkpoint with FEWER groups than this optimizer - ``build_optimizer('adamw' | 'lamb' | 'lion')`` writes two, ``'muon'``
+        has three - is regrouped first (``_regrouped``), which needs the ``model`` for the order of the parameters.  Once bound the
+        loaded state is copied INTO the existing flat buffers, so a captured update graph stays valid."""
+        flat = self.flat
+        before = [{k: v for k, v in g.items() if k != 'params'} for g in self.param_groups]
+        if len(state_dict['param_groups']) < len(self.param_groups):
+            state_dict = self._regrouped(state_dict)
+        torch.optim.Optimizer.load_state_dict(self, state_dict)
+        for g, old in zip(self.param_groups, before):
+            loaded = {k: v for k, v in g.items() if k != 'params'}
+            if 'use_muon' not in loaded:                 # a foreign checkpoint
+                keep = {'lr', 'weight_decay'} | ({'momentum', 'nesterov', 'eps', 'adjust_lr_fn'} if old['use_muon'] and 'momentum' in loaded
+                                                  else set())
+                take = {k: loaded[k] for k in keep if k in loaded}
+                if not old['use_muon'] and 'betas' in loaded:
+                    take['betas'] = tuple(loaded['betas'])
+                    if 'eps' in loaded:
+                        take['adam_eps'] = loaded['eps']
+                for k in loaded:
+                    del g[k]
+                g.update({**old, **take})
+            g['use_muon'] = old['use_muon']
+            for k, v in old.items():
+                g.setdefault(k, v)
+            self._check_group(g)
+        mine, steps = self._muon_ids(), []
+        for p, st in list(self.state.items()):
+            if 'step' in st:
+                steps.append(float(st['step']))
+            if id(p) in mine:
+                buf = st.get('momentum_buffer', st.get('exp_avg'))
+                self.state[p] = {} if buf is None else {'momentum_buffer': buf.clone()}
+            else:
+                self.state[p] = {k: st[k].clone() for k in ('exp_avg', 'exp_avg_sq') if st.get(k) is not None}
+        self._loaded_step = max(steps) if steps else None
+        if flat is not None:
+            for b in self._bufs.values():
+                b.zero_()
             self.bind_flat(flat)
 
 
